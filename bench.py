@@ -1,10 +1,23 @@
 #!/usr/bin/env python3
 """bench.py -- images/sec of N-step Natural Inference on MI355X (BASELINE.json metric).
 
-    python bench.py --gpus N --steps K --warmup W [--workload cifar10|sd3|fid50k|validate]
+    python bench.py --gpus N --steps K --warmup W [--workload cifar10|sd3|fid50k|validate] [--full] [--dump-outputs DIR]
 
 The JSON line carries NUMBERS and short identifiers only (the whole line stays under 3 KB so that it survives any log tail);
 what every field means is written HERE.
+
+A plain run of the default workload does only what the headline needs: set-up, W untimed steps, the K timed steps, the
+outputs (``--dump-outputs``) and the line (metric, value, unit, n_gpus, steps, warmup, ms_per_step, higher_is_better, scaling,
+vs_baseline, dtype, data, config).  ``--full`` adds everything else below: single_stream, pipeline, the roofline objects,
+cpu_baseline, accuracy and the sd3 / sd3_fp8 / fid50k / validate objects (the ``--no-*`` switches still leave parts of it out).
+The ``--workload sd3 | fid50k | validate`` lines are as described below with or without ``--full``.
+
+``--dump-outputs DIR``: after the timed steps, what the timed path computed in its LAST step, as ``DIR/<name>.npy`` (float32
+unless noted; rank 0; at most 64 MB in all -- a larger array is cut to a fixed, seeded sample of its leading axis).  Inputs
+(synthetic weights, noise) are seeded, so the same arguments give the same inputs on every run.  cifar10: ``x_final``
+[batch, 3, 32, 32] (the final x of the last step's batch); sd3: ``latents`` [4, 16, 128, 128] (the 28th step's mean);
+validate: ``latents`` [8, 4, 32, 32] (what natural_inference returns); fid50k: ``images_<matrix>`` [n, 32, 32, 3] (uint8
+values) and ``fid`` [2] (float64, against the synthetic (0, I) statistics when the downloads are absent).
 
 Top level (default workload = BASELINE config 2).  One "step" = one pass of the hot path over one batch: 15-step Natural
 Inference with ``weights/step_15_weight_173.npz`` on 512 CIFAR10-shaped samples = 15 NCSN++ forwards in the HIP engine (bf16
@@ -73,7 +86,7 @@ Multi-GPU: generation batches are independent, so rank r runs its own batches (w
 fid50k: one all-reduce of statistics at the end); timing is barrier + synchronize on both sides and the max over ranks.  One process
 per GPU: under ``torch.distributed.run`` (WORLD_SIZE set) this process IS a rank; a bare ``python bench.py --gpus N`` starts the N
 ranks itself (``launch_ranks``, before this process touches a GPU) and relays rank 0's line.  With N > 1 only rank 0 runs the
-instrumented replica / CPU legs, and the SD3 / validate sub-objects are left to ``--workload`` runs (the line then carries fid50k).
+instrumented replica / CPU legs, and the SD3 / validate sub-objects are left to ``--workload`` runs (a ``--full`` line then carries fid50k).
 """
 import argparse
 import json
@@ -125,6 +138,23 @@ def profiled_traffic(match, exclude=None):
         if n:
             return r4(sum(v["hbm_bytes_per_launch"] * v["launches"] for v in rows) / n)
     return None
+
+
+def write_outputs(dirpath, arrays, cap_bytes=64 << 20):
+    """``--dump-outputs``: one DIR/<name>.npy per array, float64 kept, everything else as float32.  The arrays share
+    ``cap_bytes`` equally; one over its share is cut to a fixed, seeded sample of its leading axis (sorted indices), so two
+    runs with the same arguments write the same elements."""
+    import numpy as np
+    out = Path(dirpath)
+    out.mkdir(parents=True, exist_ok=True)
+    share = cap_bytes // max(1, len(arrays))
+    for name, a in arrays.items():
+        a = np.asarray(a)
+        a = a.astype(np.float64 if a.dtype == np.float64 else np.float32, copy=False)
+        if a.nbytes > share and a.ndim > 0 and a.shape[0] > 1:
+            keep = max(1, share // (a.nbytes // a.shape[0]))
+            a = a[np.sort(np.random.default_rng(0).choice(a.shape[0], keep, replace=False))]
+        np.save(out / f"{name}.npy", np.ascontiguousarray(a))
 
 
 def launch_ranks(args):
@@ -187,7 +217,7 @@ def main():
     ap.add_argument("--steps", type=int, default=None, help="timed steps (default: 8 for cifar10, 2 for sd3, 1 for fid50k, 3 for validate)")
     ap.add_argument("--warmup", type=int, default=None, help="untimed steps before them (default 1; 0 for fid50k)")
     ap.add_argument("--no-single-stream", dest="single_stream_extra", action="store_false", help="skip the extra one-stream timing of the CIFAR10 workload")
-    ap.add_argument("--streams", type=int, default=3, help="CIFAR10 / fid50k: HIP streams (lanes) the consecutive batches rotate over (default 3 since round 6: +1 % over 2 in same-box A/Bs, profiles/r06/streams_ab.txt; 1 = one batch after the other)")
+    ap.add_argument("--streams", type=int, default=3, help="CIFAR10 / fid50k: HIP streams (lanes) the consecutive batches rotate over (default 3 since round 6: +1 %% over 2 in same-box A/Bs, profiles/r06/streams_ab.txt; 1 = one batch after the other)")
     ap.add_argument("--batch", type=int, default=512)
     ap.add_argument("--weights", default=str(ROOT / "weights" / "step_15_weight_173.npz"))
     ap.add_argument("--workload", choices=["cifar10", "sd3", "fid50k", "validate", "selftest"], default="cifar10",
@@ -209,6 +239,11 @@ def main():
     ap.add_argument("--selftest-fail-rank", type=int, default=-1, help="selftest: this rank exits non-zero (launcher error-path test)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-roofline", action="store_true", help="skip the event-instrumented replica (for rocprof runs)")
+    ap.add_argument("--full", action="store_true",
+                    help="default workload: also the one-stream timing, the production pipeline, the roofline replica, the CPU baseline + accuracy and the "
+                         "sd3 / sd3_fp8 / fid50k / validate objects (a plain run times the headline alone)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed to DIR/<name>.npy (float32 / float64, at most 64 MB in all)")
     args = ap.parse_args()
     dflt = {"cifar10": (8, 1), "sd3": (2, 1), "fid50k": (1, 0), "validate": (3, 1), "selftest": (8, 1)}[args.workload]
     args.steps = dflt[0] if args.steps is None else args.steps
@@ -252,14 +287,15 @@ def main():
     def release():
         gc.collect(); torch.cuda.empty_cache()
 
+    outputs = {} if args.dump_outputs and rank == 0 else None
     if args.workload == "sd3":
-        line = bench_sd3(args, world, rank, dev, fp8=args.fp8, steps=args.steps, warmup=args.warmup)
+        line = bench_sd3(args, world, rank, dev, fp8=args.fp8, steps=args.steps, warmup=args.warmup, outputs=outputs)
     elif args.workload == "fid50k":
-        line = bench_fid50k(args, world, rank, dev, steps=args.steps, warmup=args.warmup)
+        line = bench_fid50k(args, world, rank, dev, steps=args.steps, warmup=args.warmup, outputs=outputs)
     elif args.workload == "validate":
-        line = bench_validate(args, world, rank, dev, steps=args.steps, warmup=args.warmup)
+        line = bench_validate(args, world, rank, dev, steps=args.steps, warmup=args.warmup, outputs=outputs)
     else:
-        line = bench_cifar(args, world, rank, dev)
+        line = bench_cifar(args, world, rank, dev, outputs=outputs)
         tail = {k: line.pop(k) for k in list(line) if k.startswith(("config", "roofline", "cpu_baseline", "accuracy"))}
         strip = ("metric", "unit", "n_gpus", "higher_is_better", "scaling", "vs_baseline", "data", "config", "warmup", "steps")
         drop = ("bound", "peak", "unit", "traffic", "flops_per_launch", "launches", "flop_share", "sample", "kind", "where")       # constants of the sub-objects: in the docstring
@@ -267,7 +303,7 @@ def main():
         def slim(o):
             return {k: slim(v) for k, v in o.items() if k not in drop} if isinstance(o, dict) else o
         release()
-        if not args.no_sd3 and world == 1:
+        if args.full and not args.no_sd3 and world == 1:
             # configs 4 / 5 in the same line (one GPU: with N > 1 they are `--workload sd3 [--fp8]` runs -- every rank would repeat them)
             from naturaldiffusion_amd.mmdit import SD3_MEDIUM
             from naturaldiffusion_amd.synth import synthetic_mmdit_flat
@@ -277,17 +313,19 @@ def main():
                 line[key] = slim({k: v for k, v in sub.items() if k not in strip and k != "dtype" and not (fp8 and k == "acc")})      # (acc carries both precisions: once, in "sd3")
                 release()
             del flat
-        if not args.no_fid50k:
+        if args.full and not args.no_fid50k:
             sub = bench_fid50k(args, world, rank, dev, steps=1, warmup=0)
             line["fid50k"] = slim({k: v for k, v in sub.items() if k not in strip and k not in ("dtype", "cpu_baseline", "batches", "last_batch", "frechet_vs_synthetic_ref", "ms_per_step")})
             release()
-        if not args.no_validate and world == 1:
+        if args.full and not args.no_validate and world == 1:
             sub = bench_validate(args, world, rank, dev, steps=3, warmup=1)
             line["validate"] = slim({k: v for k, v in sub.items() if k not in strip and k not in ("dtype", "cpu_baseline", "dit_forwards")})
             release()
         line.update(tail)
     if grouped:
         line.setdefault("config", {})["process_group"] = f"{dist.get_backend()} x{world}"
+    if outputs is not None:
+        write_outputs(args.dump_outputs, outputs)
     if rank == 0:
         print(json.dumps(line, separators=(",", ":")), flush=True)
     if grouped:
@@ -326,7 +364,7 @@ def bench_selftest(args, world, rank):
         dist.destroy_process_group()
 
 
-def bench_cifar(args, world, rank, dev):
+def bench_cifar(args, world, rank, dev, outputs=None):
     import numpy as np
     import torch
     import torch.distributed as dist
@@ -369,7 +407,7 @@ def bench_cifar(args, world, rank, dev):
             e_(noises[0], torch.full((Bz,), 500.0, device=dev))
     torch.cuda.synchronize()
     dt1 = None
-    if n_str == 1 or args.single_stream_extra:
+    if n_str == 1 or (args.full and args.single_stream_extra):
         dt1, outs = timed_region(one_step, args.steps, args.warmup, world, torch.cuda.synchronize, dist, dev)
         assert all(torch.isfinite(o).all() for o in outs)
     if n_str > 1:
@@ -378,6 +416,8 @@ def bench_cifar(args, world, rank, dev):
         assert all(torch.isfinite(o).all() for o in outs)                  # the last step of EVERY lane
     else:
         dt = dt1
+    if outputs is not None:                                                # before anything below reuses a lane's buffers
+        outputs["x_final"] = outs[-1].float().cpu().numpy()
     imgs = world * Bz * args.steps
     line = {
         "metric": "images/sec at 15-step Natural Inference (CIFAR10 32x32, NCSN++)" + (f", {n_str}-stream throughput" if n_str > 1 else ""),
@@ -387,7 +427,7 @@ def bench_cifar(args, world, rank, dev):
     }
     if n_str > 1 and dt1 is not None:
         line["single_stream"] = {"value": round(imgs / dt1, 2), "ms_per_step": round(dt1 / args.steps * 1e3, 3)}
-    if rank == 0 and n_str > 1:
+    if rank == 0 and n_str > 1 and args.full:
         # the same K batches through the PRODUCTION pipeline (generate_sharded: Philox noise by global index drawn on the lane's stream, 15 steps, to_pixel, uint8
         # images to the host once at the end) -- what the reference's per-batch loop contains beyond the timed region above (:290 noise, :308-309 to_pixel + copy)
         from naturaldiffusion_amd.CIFAR10NaturalInference import generate_sharded
@@ -400,7 +440,7 @@ def bench_cifar(args, world, rank, dev):
     line["config"] = {"workload": f"CIFAR10 NI 15-step {os.path.basename(args.weights)} B={Bz}/GPU NCSN++ 61.8M bf16, ni_step fp64 history",
                       "nfe": n_step, "batch_per_gpu": Bz, "streams": n_str, "sharding": f"batch x{world}, no collective"}
 
-    if rank == 0 and not args.no_roofline:
+    if rank == 0 and args.full and not args.no_roofline:
         # ---- instrumented replica of the timed region: HIP events around every engine launch group and every ni_step launch (same stream)
         engine.profile(True)
         ev = []
@@ -457,7 +497,7 @@ def bench_cifar(args, world, rank, dev):
                                     "frac": r4(ach_gbs / HBM_PEAK_GBS), "traffic": profiled_traffic("k_step_f64hist"),
                                     "mean_launch_ms": r4(tot_ms / len(ev)), "bytes_per_launch": r4(tot_bytes / len(ev))}
 
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if rank == 0 and world == 1 and args.full and not args.no_cpu_baseline:
         # ---- CPU baseline: the oracle (eager-PyTorch restatement of the reference path, fp32 NCSN++ +
         # ---- fp64 recurrence) on this host's cores; two bounded points
         from oracle import ni_oracle as O, ncsnpp_oracle as N
@@ -557,7 +597,7 @@ def sd3_reduced_depth_accuracy(dev, weights_csv="sd3_step_28_weight_sharp.csv", 
     return out
 
 
-def bench_sd3(args, world, rank, dev, fp8=False, steps=2, warmup=1, flat=None):
+def bench_sd3(args, world, rank, dev, fp8=False, steps=2, warmup=1, flat=None, outputs=None):
     """BASELINE config 4 / 5 (see the module docstring)."""
     import numpy as np
     import torch
@@ -597,6 +637,8 @@ def bench_sd3(args, world, rank, dev, fp8=False, steps=2, warmup=1, flat=None):
 
     dt, outs = timed_region(lambda i: one_step(), steps, warmup, world, torch.cuda.synchronize, dist, dev)
     assert torch.isfinite(outs[-1].float()).all()
+    if outputs is not None:
+        outputs["latents"] = outs[-1].float().reshape(n, 16, 128, 128).cpu().numpy()
     D, L, tx = 1536, 24, 4096
     T = tx + tc
     flops_fwd_seq = L * (2.0 * T * 3 * D * D + 4.0 * T * T * D + 2.0 * T * D * D + 2.0 * T * 8 * D * D) - 2.0 * tc * 9 * D * D + 2.0 * tc * 4096 * D
@@ -707,7 +749,7 @@ def bench_sd3(args, world, rank, dev, fp8=False, steps=2, warmup=1, flat=None):
     return line
 
 
-def bench_fid50k(args, world, rank, dev, steps=1, warmup=0):
+def bench_fid50k(args, world, rank, dev, steps=1, warmup=0, outputs=None):
     """BASELINE config 3 (see the module docstring): generate_sharded + Inception pool3 engine + calc_fid_sharded, both matrices."""
     import numpy as np
     import torch
@@ -764,6 +806,10 @@ def bench_fid50k(args, world, rank, dev, steps=1, warmup=0):
         return res
 
     dt, _ = timed_region(one_step, steps, warmup, world, torch.cuda.synchronize, dist, dev)
+    if outputs is not None:
+        for name, _ in mats:
+            outputs[f"images_{name}"] = res[name]["imgs"].cpu().numpy()
+        outputs["fid"] = np.array([float(res[name]["fid"]) for name, _ in mats], dtype=np.float64)
     n_local = res[mats[0][0]]["images_local"]
     n_all = res[mats[0][0]]["images_all"]
     runs = steps + warmup
@@ -813,7 +859,7 @@ def bench_fid50k(args, world, rank, dev, steps=1, warmup=0):
     return line
 
 
-def bench_validate(args, world, rank, dev, steps=3, warmup=1):
+def bench_validate(args, world, rank, dev, steps=3, warmup=1, outputs=None):
     """SURVEY 8f N2 + N4 (see the module docstring): ValidateNaturalInference.natural_inference("ddim", 24) on the DiT-XL/2 engine + VAE decode."""
     import tempfile
     import torch
@@ -853,6 +899,8 @@ def bench_validate(args, world, rank, dev, steps=3, warmup=1):
     finally:
         V.denoiser_factory = V.decoder_factory = None
     assert torch.isfinite(outs[-1]).all()
+    if outputs is not None:
+        outputs["latents"] = outs[-1].float().cpu().numpy()
     dit_ms = sum(a.elapsed_time(b) for a, b in t_acc["ev"]) / len(t_acc["ev"])
     vae_ms = sum(a.elapsed_time(b) for a, b in t_acc["evv"]) / len(t_acc["evv"])
     dit_fl = XL2["depth"] * 256 * (24 * XL2["hidden"] ** 2 + 4 * 256 * XL2["hidden"]) * 2 * n        # 2*MAC per forward of 16 samples (tools/bench_dit.py)

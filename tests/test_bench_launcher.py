@@ -54,3 +54,24 @@ def test_force_pg_runs_the_collectives_through_a_group_of_one_rank():
     assert p.returncode == 0, p.stderr[-2000:]
     line = json.loads(p.stdout.strip().splitlines()[-1])
     assert line["n_gpus"] == 1 and line["config"]["process_group"] == "gloo x1" and line["config"]["rank_sum"] == 1.0
+
+
+def test_dump_outputs_writer_keeps_the_cap_with_a_fixed_sample(tmp_path):
+    """--dump-outputs: float64 stays float64, everything else is written as float32; an array over its share of the cap is cut to a
+    fixed, seeded sample of whole rows, the same on every call."""
+    import importlib.util
+    import numpy as np
+    spec = importlib.util.spec_from_file_location("bench_under_test", ROOT / "bench.py")
+    bench = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(bench)
+    big = np.arange(100 * 8, dtype=np.float32).reshape(100, 8)
+    arrays = {"big": big, "f64": np.arange(3, dtype=np.float64), "u8": np.arange(10, dtype=np.uint8).reshape(5, 2)}
+    for d in ("a", "b"):
+        bench.write_outputs(tmp_path / d, arrays, cap_bytes=3000)
+    a, b = (np.load(tmp_path / d / "big.npy") for d in ("a", "b"))
+    assert a.dtype == np.float32 and a.shape == (31, 8) and np.array_equal(a, b)
+    rows = a[:, 0].astype(int) // 8
+    assert np.all(np.diff(rows) > 0) and np.array_equal(a, big[rows])
+    f64, u8 = np.load(tmp_path / "a" / "f64.npy"), np.load(tmp_path / "a" / "u8.npy")
+    assert f64.dtype == np.float64 and np.array_equal(f64, arrays["f64"])
+    assert u8.dtype == np.float32 and np.array_equal(u8, arrays["u8"].astype(np.float32))

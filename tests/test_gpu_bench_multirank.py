@@ -20,7 +20,7 @@ def test_two_ranks_self_launched_on_the_gpu():
         pytest.skip("needs a GPU")
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT")}
     p = subprocess.run([sys.executable, str(ROOT / "bench.py"), "--gpus", "2", "--backend", "gloo", "--same-device", "--batch", "64", "--steps", "1",
-                        "--warmup", "1", "--fid-samples", "600", "--no-cpu-baseline", "--no-roofline"], env=env, stdout=subprocess.PIPE, stderr=subprocess.PIPE,
+                        "--warmup", "1", "--fid-samples", "600", "--full", "--no-cpu-baseline", "--no-roofline"], env=env, stdout=subprocess.PIPE, stderr=subprocess.PIPE,
                        text=True, timeout=900)
     assert p.returncode == 0, p.stderr[-3000:]
     lines = [ln for ln in p.stdout.splitlines() if ln.strip()]

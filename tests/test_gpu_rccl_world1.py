@@ -25,7 +25,7 @@ def _env():
 def test_bench_line_through_an_rccl_group_of_one_rank():
     if not torch.cuda.is_available():
         pytest.skip("needs a GPU")
-    p = subprocess.run([sys.executable, str(ROOT / "bench.py"), "--gpus", "1", "--force-pg", "--backend", "nccl", "--batch", "64", "--steps", "1", "--warmup", "1",
+    p = subprocess.run([sys.executable, str(ROOT / "bench.py"), "--gpus", "1", "--force-pg", "--backend", "nccl", "--batch", "64", "--steps", "1", "--warmup", "1", "--full",
                         "--fid-samples", "600", "--fid-share-of", "1", "--no-sd3", "--no-validate", "--no-cpu-baseline", "--no-roofline"],
                        env=_env(), stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, timeout=900)
     assert p.returncode == 0, p.stderr[-3000:]
