@@ -75,6 +75,34 @@ int natinf_step_f32hist(const float* x_k, const float* model_out, const float* n
                         int k, float alpha, float sigma, float std_f32, float b0_f32,
                         int64_t E, natinf_stream_t stream);
 
+/* The same step for a STOCHASTIC matrix, one whose noise matrix B has entries beyond column 0 (SDE Euler-Maruyama,
+ * DDPM ancestral / DDIM-eta: x_{k+1} = sum_j C[k,j] x0_j + sum_j B[k,j] eps_j, eps_0 the initial noise, eps_j the noise
+ * injected after step j-1).  Replaces the reference's general loop, src/ValidateNaturalInference.py:349-366 (seq_eps +
+ * weighted_sum(past_eps_coeff[kk], ...)), on the CIFAR10 form's fp64 history:
+ *
+ *   x0_k, acc   as natinf_step_f64hist (hist[k] <- x0_k)
+ *   nacc   = sum over terms t (ascending idx_b[t]) of (double)(eps_{idx_b[t]} * val_b[t])   (fp32 product, fp64 add;
+ *            src/ValidateNaturalInference.py:198-204)
+ *   x_next = (float)acc + (float)nacc                     (fp32)
+ *
+ * eps_0 is read from `noise`; eps_j, j >= 1, is NOT read from memory: it is generated in registers as
+ * natinf_randn_philox_col_f32(..., seed, column = j) would return it (same Philox4x32-10 counter, same Box-Muller,
+ * bit for bit).  Element e of image i (i = e / elems_per_image within the call) draws counter = (global index lo,
+ * global index hi, quad (e % elems_per_image) / 4, j), key = (seed lo, seed hi); the global index is image_index[i]
+ * (device int64 array) or, when image_index is NULL, first_index + i*index_stride.  An image's noise is therefore a
+ * function of (seed, global index, column) only, whatever the batch split or GPU count.
+ * A row whose only entry is column 0 (val_b[0] = b0_f32) gives exactly natinf_step_f64hist's x_next.
+ * idx_b / val_b (fp32 values): the sparse row of B, columns <= k+1.  E % elems_per_image == 0, elems_per_image % 4 == 0
+ * and elems_per_image / 4 < 2^32 (counter word 3 carries the column), otherwise NATINF_EINVAL.
+ */
+int natinf_step_f64hist_noise(const float* x_k, const float* model_out, const float* noise,
+                              double* hist, float* x_next,
+                              const int32_t* idx, const double* val, int n_terms, double c_diag,
+                              const int32_t* idx_b, const float* val_b, int n_b,
+                              int k, double alpha, double sigma, float std_f32,
+                              uint64_t seed, const int64_t* image_index, int64_t first_index, int64_t index_stride,
+                              int64_t elems_per_image, int64_t E, natinf_stream_t stream);
+
 /* src/CIFAR10NaturalInference.py:233-238 on its own: out = (float) sum_t hist[idx[t]]*val[t]. */
 int natinf_weighted_sum_f64(const double* hist, float* out,
                             const int32_t* idx, const double* val, int n_terms,
@@ -88,6 +116,14 @@ int natinf_weighted_sum_f64(const double* hist, float* out,
  * elems_per_image % 4 == 0. */
 int natinf_randn_philox_f32(float* out, int64_t n_images, int64_t elems_per_image, const int64_t* image_index,
                             int64_t first_index, int64_t index_stride, uint64_t seed, natinf_stream_t stream);
+
+/* natinf_randn_philox_f32 for noise column `column` of a stochastic matrix: counter = (global image index lo, hi,
+ * e/4, column).  Column 0 is natinf_randn_philox_f32 itself (word 3 = (e/4) >> 32), bit for bit; for column > 0 the
+ * quad must fit word 2 (elems_per_image / 4 < 2^32, else NATINF_EINVAL).  These are exactly the eps_j that
+ * natinf_step_f64hist_noise injects. */
+int natinf_randn_philox_col_f32(float* out, int64_t n_images, int64_t elems_per_image, const int64_t* image_index,
+                                int64_t first_index, int64_t index_stride, uint64_t seed, uint32_t column,
+                                natinf_stream_t stream);
 
 /* src/CIFAR10NaturalInference.py:212-216 (to_pixel): x [B,C,H,W] fp32 -> uint8 [B,H,W,C] =
  * trunc(clip(x*255, 0, 255)); with centered != 0 the inverse scaler of datasets.py:32-38,

@@ -74,22 +74,25 @@ def weighted_sum(past_x0_coeff: Sequence[float], seq_x0: Sequence[torch.Tensor])
 
 @torch.no_grad()
 def natural_inference(model_fn: Callable, noise: torch.Tensor, weight_path, dense: bool = False,
-                      fast_f32: bool = False, return_all: bool = False, stds=None):
-    """The loop body of ``natural_inference_tx`` (:292-304) for one batch of initial noise."""
+                      fast_f32: bool = False, return_all: bool = False, stds=None, seed: int = 888, first_index: int = 0):
+    """The loop body of ``natural_inference_tx`` (:292-304) for one batch of initial noise.  A stochastic matrix
+    (``coeff.is_stochastic``) also injects the noise of every later column of B: image i of the batch draws column j >= 1
+    from Philox(``seed``, global index ``first_index + i``, j) -- ``philox_noise(..., column=j)``."""
     C, B, node = load_coeff_npz(weight_path)
-    ni = CifarNI(C, B, node, noise.numel(), device=noise.device, dense=dense, fast_f32=fast_f32, stds=stds)
-    return ni.run(model_fn, noise, return_all=return_all)
+    ni = CifarNI(C, B, node, noise.numel(), device=noise.device, dense=dense, fast_f32=fast_f32, stds=stds, seed=seed)
+    return ni.run(model_fn, noise, return_all=return_all, index=int(first_index))
 
 
-def philox_noise(indices, shape_per_image, seed: int, device="cuda:0") -> torch.Tensor:
+def philox_noise(indices, shape_per_image, seed: int, device="cuda:0", column: int = 0) -> torch.Tensor:
     """[len(indices), *shape_per_image] fp32 N(0,1), image i keyed by its GLOBAL index (include/natinf.h,
-    natinf_randn_philox_f32): identical for any GPU count / batch split."""
+    natinf_randn_philox_col_f32): identical for any GPU count / batch split.  ``column`` j >= 1 gives the noise a
+    stochastic matrix injects after step j-1 (what the fused CIFAR10 step generates for column j of B)."""
     _lib.require_gpu()
     idx = torch.as_tensor(list(indices), dtype=torch.int64, device=device)
     per = int(np.prod(shape_per_image))
     out = torch.empty((idx.numel(),) + tuple(shape_per_image), dtype=torch.float32, device=device)
-    check(lib.natinf_randn_philox_f32(ptr(out), idx.numel(), per, ptr(idx), 0, 0, int(seed) & (2 ** 64 - 1), stream_ptr()),
-          "natinf_randn_philox_f32")
+    check(lib.natinf_randn_philox_col_f32(ptr(out), idx.numel(), per, ptr(idx), 0, 0, int(seed) & (2 ** 64 - 1), int(column),
+                                          stream_ptr()), "natinf_randn_philox_col_f32")
     return out
 
 
@@ -98,9 +101,10 @@ class BatchLanes:
     trajectories (reference loop :287-309), so consecutive batches go to ``len(models)`` lanes -- one HIP stream, one denoiser handle and
     one set of history slabs each -- and the under-occupied launches of one batch run under the other's convolutions.
     A batch is enqueued end to end (noise, 15-18 forwards + ni_step launches, ``to_pixel``) without the host waiting for the GPU; the uint8
-    images stay on the device until ``finish``; at most ``depth`` batches per lane are enqueued ahead of the GPU."""
+    images stay on the device until ``finish``; at most ``depth`` batches per lane are enqueued ahead of the GPU.  ``seed`` keys the noise a
+    stochastic matrix injects after each step (``CifarNI``), per image by the global indices ``submit`` gets."""
 
-    def __init__(self, models, C, B, node, device, depth: int = 2):
+    def __init__(self, models, C, B, node, device, depth: int = 2, seed: Optional[int] = None):
         _lib.require_gpu()
         self.device = torch.device(device)
         self.coeff = (C, B, node)
@@ -110,18 +114,21 @@ class BatchLanes:
         self.samplers = [dict() for _ in self.models]                   # per lane: batch size -> CifarNI (a ragged last batch gets its own slabs)
         self.pending = [[] for _ in self.models]
         self.depth = int(depth)
+        self.seed = seed
         self.count = 0
         self.out = []
         self.joined = [False] * len(self.models)                       # lane k has been ordered behind the caller's stream
 
     def _sampler(self, k: int, n: int) -> CifarNI:
         if n not in self.samplers[k]:
-            self.samplers[k][n] = CifarNI(*self.coeff, n * 3 * 32 * 32, device=self.device)
+            self.samplers[k][n] = CifarNI(*self.coeff, n * 3 * 32 * 32, device=self.device, seed=self.seed, elems_per_image=3 * 32 * 32)
         return self.samplers[k][n]
 
-    def submit(self, n: int, noise=None, noise_fn=None) -> torch.Tensor:
+    def submit(self, n: int, noise=None, noise_fn=None, index=None) -> torch.Tensor:
         """One batch of ``n`` images: ``noise`` (drawn on the CALLER's current stream) or ``noise_fn()`` (called on the lane's stream).
-        Returns the uint8 [n, 32, 32, 3] DEVICE tensor the lane will fill."""
+        ``index``: the images' global indices, which key the noise a stochastic matrix injects -- an int64 device tensor made on the
+        caller's stream, the int index of the first image, or ``(first, stride)`` (``CifarNI.step``).  Returns the uint8 [n, 32, 32, 3] DEVICE tensor the lane will fill."""
+        idx_t = isinstance(index, torch.Tensor)
         k = self.count % len(self.models)
         self.count += 1
         st = self.streams[k]
@@ -131,15 +138,17 @@ class BatchLanes:
             # A lane's first launch is ordered behind everything the caller's stream has queued: the engine's workspace and packed weights (and
             # the blocks clone() got from the caching allocator, which may be recycled ones with work pending) were allocated THERE, and a
             # still-queued forward of lane 0's engine on the caller's stream would otherwise race with the lane's.  With `noise` every submit waits.
-            if st is not None and (noise is not None or not self.joined[k]):
+            if st is not None and (noise is not None or idx_t or not self.joined[k]):
                 st.wait_stream(torch.cuda.current_stream())
                 self.joined[k] = True
             if st is not None and noise is not None:
                 noise.record_stream(st)
+            if st is not None and idx_t:
+                index.record_stream(st)
             with torch.cuda.stream(st):
                 ni = self._sampler(k, n)                                # (first use allocates on the lane's stream)
                 z = noise if noise is not None else noise_fn()
-                pix = _to_pixel(ni.run(self.models[k], z), 1, to_cpu=False)
+                pix = _to_pixel(ni.run(self.models[k], z, index=index), 1, to_cpu=False)
                 ev = torch.cuda.Event()
                 ev.record()
         self.pending[k].append(ev)
@@ -182,7 +191,8 @@ def generate_sharded(model_fn, weight_path, sample_count: int, batch_size: int, 
     of ``natural_inference_tx`` (``BatchLanes``): Philox noise keyed by the GLOBAL image index drawn on the lane's own stream, uint8 images
     kept on the device, one copy to the host at the end (none with ``to_cpu=False``: ``calc_fid_sharded`` scores device tensors).
     ``model_fn``: an ``NCSNppEngine`` (cloned per lane), a sequence of callables (one lane each) or one callable (one lane).
-    ``coeff``: (C, B, node_coeff) instead of a file (matrices from ``coeffgen``).
+    ``coeff``: (C, B, node_coeff) instead of a file (matrices from ``coeffgen``).  A stochastic matrix draws the noise it injects after each
+    step from the same (seed, global index) key, column j of B as counter word 3: an image's whole noise is Philox(seed, global index, column).
     Returns (uint8 images [n_local, 32, 32, 3], their global indices [n_local] int64 on the CPU)."""
     from .shard import rank_batches
     C, B, node = coeff if coeff is not None else load_coeff_npz(weight_path)
@@ -190,9 +200,9 @@ def generate_sharded(model_fn, weight_path, sample_count: int, batch_size: int, 
     dev = torch.device(device)
     if not batches:
         return torch.empty((0, 32, 32, 3), dtype=torch.uint8, device="cpu" if to_cpu else dev), torch.empty(0, dtype=torch.int64)
-    lanes = BatchLanes(_lane_models(model_fn, streams, len(batches)), C, B, node, dev)
+    lanes = BatchLanes(_lane_models(model_fn, streams, len(batches)), C, B, node, dev, seed=seed)
     for batch in batches:
-        lanes.submit(len(batch), noise_fn=lambda b=batch: philox_noise(b, (3, 32, 32), seed, dev))
+        lanes.submit(len(batch), noise_fn=lambda b=batch: philox_noise(b, (3, 32, 32), seed, dev), index=(batch[0], world))   # = batch
     imgs = torch.cat(lanes.finish())
     idxs = torch.cat([torch.tensor(b, dtype=torch.int64) for b in batches])
     return (imgs.cpu() if to_cpu else imgs), idxs
@@ -394,13 +404,13 @@ def natural_inference_tx(batch_size: int = 500,
     bz = batch_size
     num = int(np.ceil(sample_count / bz))
     engine = NCSNppEngine(flat_params, max_batch=batch_size, device=device)
-    lanes = BatchLanes(_lane_models(engine, streams, num), C, B, node, device)       # the second lane shares the first's packed weights
+    lanes = BatchLanes(_lane_models(engine, streams, num), C, B, node, device, seed=seed)   # the second lane shares the first's packed weights
     torch.cuda.synchronize(torch.device(device))
     torch.manual_seed(seed)
     for ii in range(num):
         print("processing", ii)
         noise = torch.randn(bz, 3, 32, 32, dtype=torch.float32, device=device)      # the reference's stream of normals, in its order (:290)
-        lanes.submit(bz, noise=noise)
+        lanes.submit(bz, noise=noise, index=ii * bz)                                  # (stochastic matrices: image b of batch ii is ii*bz + b)
     all_batch = torch.concatenate(lanes.finish()).cpu()                                # ONE copy to the host, after the last batch
     if not compute_fid:
         return all_batch

@@ -28,6 +28,13 @@ def load_coeff_npz(path) -> Tuple[np.ndarray, np.ndarray, np.ndarray]:
     return C, B, node
 
 
+def is_stochastic(B: np.ndarray) -> bool:
+    """True when the noise matrix injects noise after some step (any B[k, j >= 1] != 0): SDE Euler-Maruyama, DDPM
+    ancestral, DDIM-eta.  Column 0 alone (the initial noise) is every deterministic sampler."""
+    B = np.asarray(B, dtype=np.float64)
+    return bool(B.ndim == 2 and B.shape[1] > 1 and np.any(B[:, 1:] != 0.0))
+
+
 def load_sd3_csv(path) -> np.ndarray:
     with open(path, newline="") as fh:
         rows = list(csv.reader(fh))

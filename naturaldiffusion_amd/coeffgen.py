@@ -14,7 +14,8 @@ here (SURVEY.md section 8f N1, and the DDIM matrix BASELINE config 3 needs on th
 * :func:`ddim_discrete`       -- DDIM on the 1000-step linear-beta DDPM schedule, strided (reproduces the shipped
                                  ``results/ddim/ddim_0NN.npz``),
 * :func:`ddim_vp_continuous`  -- DDIM == DPM-Solver-1 on a continuous VP time grid (``a = sigma_t/sigma_s``,
-                                 ``b = alpha_t - alpha_s*sigma_t/sigma_s``, cf. deps/dpm_solver_pytorch.py:547-592),
+                                 ``b = alpha_t - alpha_s*sigma_t/sigma_s``, cf. deps/dpm_solver_pytorch.py:547-592);
+                                 with ``eta > 0`` DDIM-eta / DDPM ancestral sampling on the same grid (stochastic B),
 * :func:`save_coeff_matrix`   -- the reference's ``.npz`` layout (src/Utils.py:49),
 * :class:`LinearTrace` and, built on it, every other sampler family the reference ships matrices for:
   :func:`dpmsolver_singlestep` (DPM-Solver-2/-3, DPM-Solver++(2S)/(3S); src/AnalyzeDPMSolver.py),
@@ -81,15 +82,31 @@ def quadratic_time_grid(num_step: int, t_start: float = 1.0, t_end: float = 1e-3
     return (np.sqrt(t_start) + i * (np.sqrt(t_end) - np.sqrt(t_start))) ** 2
 
 
-def ddim_vp_continuous(ts: Sequence[float]):
-    """DDIM / DPM-Solver-1 on the continuous VP SDE over the decreasing time grid ``ts`` (N+1 nodes)."""
+def ddim_vp_continuous(ts: Sequence[float], eta: float = 0.0):
+    """DDIM / DPM-Solver-1 on the continuous VP SDE over the decreasing time grid ``ts`` (N+1 nodes).
+
+    ``eta > 0``: DDIM-eta (eta = 1 is DDPM ancestral sampling on this grid), a stochastic matrix (column j >= 1 of B is the
+    noise injected after step j-1): with y the predicted x0 and c = eta (sigma_{i+1}/sigma_i) sqrt(1 - alpha_i^2/alpha_{i+1}^2),
+    x_{i+1} = alpha_{i+1} y + sqrt(sigma_{i+1}^2 - c^2) (x - alpha_i y)/sigma_i + c eps_{i+1}.  ``eta = 0`` keeps the closed form
+    (the same recurrence through ``LinearTrace`` differs from it by ~1e-16)."""
     ts = np.asarray(ts, np.float64)
     al, sg = vp_alpha_sigma(ts)
-    a = sg[1:] / sg[:-1]
-    b = al[1:] - al[:-1] * a
-    C, B = first_order_matrices(a, b)
-    node = np.stack([ts, al, sg], axis=1)
-    return C, B, node
+    if eta == 0.0:
+        a = sg[1:] / sg[:-1]
+        b = al[1:] - al[:-1] * a
+        C, B = first_order_matrices(a, b)
+        node = np.stack([ts, al, sg], axis=1)
+        return C, B, node
+    n = len(ts) - 1
+    tr = LinearTrace(n)
+    x = tr.new_eps()
+    tr.record(ts[0], al[0], sg[0], x)
+    for i in range(n):
+        y = tr.new_y()
+        c = eta * (sg[i + 1] / sg[i]) * np.sqrt(1.0 - al[i] ** 2 / al[i + 1] ** 2)
+        x = al[i + 1] * y + np.sqrt(sg[i + 1] ** 2 - c ** 2) * (x - al[i] * y) / sg[i] + c * tr.new_eps()
+        tr.record(ts[i + 1], al[i + 1], sg[i + 1], x)
+    return tr.matrices()
 
 
 def save_coeff_matrix(path, C, B, node) -> None:

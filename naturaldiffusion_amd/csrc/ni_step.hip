@@ -368,27 +368,97 @@ __device__ __forceinline__ void philox4x32_10(uint32_t c0, uint32_t c1, uint32_t
     o[0] = c0; o[1] = c1; o[2] = c2; o[3] = c3;
 }
 
+// The four normals of one element quad: Philox4x32-10 of counter (gi lo, gi hi, quad lo, word3), then Box-Muller on the
+// two pairs.  word3 is quad >> 32 for the initial noise (column 0) and the column j for the noise injected after step
+// j-1 (quad < 2^32 then): k_randn_philox and k_step_noise_f64 both call this, so the fused step injects exactly the
+// normals natinf_randn_philox_col_f32 returns.
+__device__ __forceinline__ float4 philox_normals(uint64_t gi, uint64_t q, uint32_t word3, uint32_t k0, uint32_t k1)
+{
+    uint32_t r[4];
+    philox4x32_10((uint32_t)gi, (uint32_t)(gi >> 32), (uint32_t)q, word3, k0, k1, r);
+    float z[4];
+#pragma unroll
+    for (int h = 0; h < 2; ++h) {
+        const float u1 = ((float)(r[2 * h] >> 8) + 0.5f) * (1.0f / 16777216.0f);       // (0, 1), 24 bits
+        const float u2 = ((float)(r[2 * h + 1] >> 8) + 0.5f) * (1.0f / 16777216.0f);
+        const float rad = sqrtf(-2.0f * logf(u1));
+        float sn, cs;
+        sincosf(6.28318530717958647692f * u2, &sn, &cs);
+        z[2 * h] = rad * cs; z[2 * h + 1] = rad * sn;
+    }
+    return make_float4(z[0], z[1], z[2], z[3]);
+}
+
 __global__ __launch_bounds__(kBlock) void k_randn_philox(
     float4* __restrict__ out, const int64_t* __restrict__ index, int64_t first_index, int64_t index_stride,
-    int64_t quads_per_image, int64_t total_quads, uint32_t k0, uint32_t k1)
+    int64_t quads_per_image, int64_t total_quads, uint32_t column, uint32_t k0, uint32_t k1)
 {
     const int64_t stride = (int64_t)gridDim.x * kBlock;
     for (int64_t v = (int64_t)blockIdx.x * kBlock + threadIdx.x; v < total_quads; v += stride) {
         const int64_t img = v / quads_per_image, q = v - img * quads_per_image;
         const uint64_t gi = (uint64_t)(index ? index[img] : first_index + img * index_stride);
-        uint32_t r[4];
-        philox4x32_10((uint32_t)gi, (uint32_t)(gi >> 32), (uint32_t)q, (uint32_t)(q >> 32), k0, k1, r);
-        float z[4];
+        out[v] = philox_normals(gi, (uint64_t)q, column ? column : (uint32_t)((uint64_t)q >> 32), k0, k1);
+    }
+}
+
+// ------------------------------------------------------------------------------------------
+// CIFAR10 form with per-step noise (stochastic matrices: B[k, j >= 1] != 0).  x0_k and the signal sum exactly as
+// k_step_f64hist; the noise row sum_t val_b[t] * eps_{idx_b[t]} in the Validate form's arithmetic
+// (src/ValidateNaturalInference.py:198-204: fp32 product, fp64 accumulate in ascending column order, one cast), then
+// x_next = (float)acc_x0 + (float)acc_eps.  eps_0 is the caller's noise; eps_j, j >= 1, is generated in registers
+// (philox_normals with word3 = j): no noise slab, and every image's noise is a function of (seed, global index, column).
+// A row whose only entry is column 0 gives (float)acc + b0*noise, the bits of k_step_f64hist.
+// ------------------------------------------------------------------------------------------
+__global__ __launch_bounds__(kBlock) void k_step_noise_f64(
+    const float4* __restrict__ x_k, const float4* __restrict__ mout, const float4* __restrict__ noise,
+    double* __restrict__ hist, float4* __restrict__ x_next,
+    const int32_t* __restrict__ idx, const double* __restrict__ val, int n_terms, double c_diag,
+    const int32_t* __restrict__ idx_b, const float* __restrict__ val_b, int n_b,
+    const int64_t* __restrict__ index, int64_t first_index, int64_t index_stride, int64_t quads_per_image,
+    uint32_t k0, uint32_t k1, int k, double alpha, double sigma2, float stdv, int64_t nvec, int64_t E)
+{
+    // one element quad per thread, no grid-stride loop: with the loop's carried scalars the 20 Philox round keys the
+    // compiler hoists into SGPRs spill (10-35 SGPRs); without it the kernel needs 57 SGPRs and spills nothing
+    const int64_t v = (int64_t)blockIdx.x * kBlock + threadIdx.x;
+    if (v < nvec) {
+        const float4 xv = x_k[v], ov = mout[v];
+        const float xs[4] = {xv.x, xv.y, xv.z, xv.w};
+        const float os[4] = {ov.x, ov.y, ov.z, ov.w};
+        double x0[4];
 #pragma unroll
-        for (int h = 0; h < 2; ++h) {
-            const float u1 = ((float)(r[2 * h] >> 8) + 0.5f) * (1.0f / 16777216.0f);       // (0, 1), 24 bits
-            const float u2 = ((float)(r[2 * h + 1] >> 8) + 0.5f) * (1.0f / 16777216.0f);
-            const float rad = sqrtf(-2.0f * logf(u1));
-            float sn, cs;
-            sincosf(6.28318530717958647692f * u2, &sn, &cs);
-            z[2 * h] = rad * cs; z[2 * h + 1] = rad * sn;
+        for (int i = 0; i < 4; ++i) {
+            const float s = (-os[i]) / stdv;                          // score, fp32
+            x0[i] = ((double)s * sigma2 + (double)xs[i]) / alpha;     // fp64, three roundings
         }
-        out[v] = make_float4(z[0], z[1], z[2], z[3]);
+        d2* hk = reinterpret_cast<d2*>(hist + (int64_t)k * E) + 2 * v;
+        hk[0] = d2{x0[0], x0[1]};
+        hk[1] = d2{x0[2], x0[3]};
+
+        double acc[4] = {0.0, 0.0, 0.0, 0.0};
+#pragma unroll 4
+        for (int t = 0; t < n_terms; ++t) {
+            const double c = val[t];
+            const d2* hj = reinterpret_cast<const d2*>(hist + (int64_t)idx[t] * E) + 2 * v;
+            const d2 a = hj[0], b = hj[1];
+            acc[0] = acc[0] + a.x * c; acc[1] = acc[1] + a.y * c;
+            acc[2] = acc[2] + b.x * c; acc[3] = acc[3] + b.y * c;
+        }
+#pragma unroll
+        for (int i = 0; i < 4; ++i) acc[i] = acc[i] + x0[i] * c_diag;
+
+        const int64_t img = v / quads_per_image, q = v - img * quads_per_image;
+        const uint64_t gi = (uint64_t)(index ? index[img] : first_index + img * index_stride);
+        double nacc[4] = {0.0, 0.0, 0.0, 0.0};
+        for (int t = 0; t < n_b; ++t) {                               // wave-uniform column: one Philox call per quad and term
+            const float c = val_b[t];
+            const uint32_t j = (uint32_t)idx_b[t];
+            const float4 e = j == 0 ? noise[v] : philox_normals(gi, (uint64_t)q, j, k0, k1);
+            const float p0 = e.x * c, p1 = e.y * c, p2 = e.z * c, p3 = e.w * c;
+            nacc[0] = nacc[0] + (double)p0; nacc[1] = nacc[1] + (double)p1;
+            nacc[2] = nacc[2] + (double)p2; nacc[3] = nacc[3] + (double)p3;
+        }
+        x_next[v] = make_float4((float)acc[0] + (float)nacc[0], (float)acc[1] + (float)nacc[1],
+                                (float)acc[2] + (float)nacc[2], (float)acc[3] + (float)nacc[3]);
     }
 }
 
@@ -453,13 +523,43 @@ int natinf_step_f32hist(const float* x_k, const float* model_out, const float* n
     return launched();
 }
 
-int natinf_randn_philox_f32(float* out, int64_t n_images, int64_t elems_per_image, const int64_t* image_index,
-                            int64_t first_index, int64_t index_stride, uint64_t seed, natinf_stream_t stream)
+int natinf_randn_philox_col_f32(float* out, int64_t n_images, int64_t elems_per_image, const int64_t* image_index,
+                                int64_t first_index, int64_t index_stride, uint64_t seed, uint32_t column,
+                                natinf_stream_t stream)
 {
     if (!out || n_images <= 0 || elems_per_image <= 0 || (elems_per_image & 3)) return NATINF_EINVAL;
     const int64_t qpi = elems_per_image / 4, total = qpi * n_images;
+    if (column && (qpi >> 32)) return NATINF_EINVAL;               // counter word 3 carries the column: the quad must fit word 2
     hipLaunchKernelGGL(k_randn_philox, dim3(grid_for(total)), dim3(kBlock), 0, (hipStream_t)stream, (float4*)out,
-                       image_index, first_index, index_stride, qpi, total, (uint32_t)seed, (uint32_t)(seed >> 32));
+                       image_index, first_index, index_stride, qpi, total, column, (uint32_t)seed, (uint32_t)(seed >> 32));
+    return launched();
+}
+
+int natinf_randn_philox_f32(float* out, int64_t n_images, int64_t elems_per_image, const int64_t* image_index,
+                            int64_t first_index, int64_t index_stride, uint64_t seed, natinf_stream_t stream)
+{
+    return natinf_randn_philox_col_f32(out, n_images, elems_per_image, image_index, first_index, index_stride, seed, 0, stream);
+}
+
+int natinf_step_f64hist_noise(const float* x_k, const float* model_out, const float* noise,
+                              double* hist, float* x_next,
+                              const int32_t* idx, const double* val, int n_terms, double c_diag,
+                              const int32_t* idx_b, const float* val_b, int n_b,
+                              int k, double alpha, double sigma, float std_f32,
+                              uint64_t seed, const int64_t* image_index, int64_t first_index, int64_t index_stride,
+                              int64_t elems_per_image, int64_t E, natinf_stream_t stream)
+{
+    if (!x_k || !model_out || !noise || !hist || !x_next || !terms_ok(idx, val, n_terms) || !terms_ok(idx_b, val_b, n_b) ||
+        k < 0 || E <= 0 || (E & 3) || elems_per_image <= 0 || (elems_per_image & 3) || (E % elems_per_image) ||
+        ((elems_per_image / 4) >> 32))
+        return NATINF_EINVAL;
+    const int64_t nvec = E / 4, blocks = (nvec + kBlock - 1) / kBlock;
+    if (blocks > INT32_MAX) return NATINF_EINVAL;                      // one quad per thread (k_step_noise_f64)
+    hipLaunchKernelGGL(k_step_noise_f64, dim3((unsigned)blocks), dim3(kBlock), 0, (hipStream_t)stream,
+                       (const float4*)x_k, (const float4*)model_out, (const float4*)noise, hist, (float4*)x_next,
+                       idx, val, n_terms, c_diag, idx_b, val_b, n_b, image_index, first_index, index_stride,
+                       elems_per_image / 4, (uint32_t)seed, (uint32_t)(seed >> 32), k, alpha, sigma * sigma, std_f32,
+                       nvec, E);
     return launched();
 }
 

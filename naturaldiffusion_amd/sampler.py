@@ -19,7 +19,7 @@ import torch
 
 from . import _lib
 from ._lib import lib, check, ptr, stream_ptr
-from .coeff import SparseRows
+from .coeff import SparseRows, is_stochastic
 
 
 def vp_std_f32(t: float, beta_0: float = 0.1, beta_1: float = 20.0) -> float:
@@ -31,10 +31,16 @@ def vp_std_f32(t: float, beta_0: float = 0.1, beta_1: float = 20.0) -> float:
 
 
 class CifarNI:
-    """x_{k+1} = fp32(sum_j C[k,j]*x0_j) + fp32(B[k,0])*noise with x0_k = ((-out/std)*sigma^2 + x_k)/alpha."""
+    """x_{k+1} = fp32(sum_j C[k,j]*x0_j) + fp32(B[k,0])*noise with x0_k = ((-out/std)*sigma^2 + x_k)/alpha.
+
+    A stochastic matrix (``coeff.is_stochastic``: some B[k, j >= 1] != 0) adds the noise injected after each step,
+    fp32(sum_j fp32(B[k,j]*eps_j)) in fp64 accumulation, eps_0 = ``noise`` and eps_j (j >= 1) drawn in the kernel from
+    Philox(``seed``, global image index, column j) (include/natinf.h, natinf_step_f64hist_noise).  It needs ``seed``;
+    ``elems_per_image`` defaults to the per-image size of the noise ``run`` gets; the fp32 fast mode does not take it."""
 
     def __init__(self, C: np.ndarray, B: np.ndarray, node: np.ndarray, n_elem: int, device="cuda:0",
-                 dense: bool = False, fast_f32: bool = False, stds=None):
+                 dense: bool = False, fast_f32: bool = False, stds=None, *, seed: Optional[int] = None,
+                 elems_per_image: Optional[int] = None):
         _lib.require_gpu()
         if n_elem % 4:
             raise ValueError("element count must be a multiple of 4")
@@ -45,6 +51,18 @@ class CifarNI:
         self.E = int(n_elem)
         self.device = torch.device(device)
         self.fast = bool(fast_f32)
+        self.stochastic = is_stochastic(self.B)
+        if self.stochastic:
+            if seed is None:
+                raise ValueError("stochastic NI matrix (B[k, j >= 1] != 0): the injected noise needs a seed")
+            if self.fast:
+                raise ValueError("stochastic NI matrix: fast_f32 mode only covers column 0 of B")
+            if elems_per_image is not None and (elems_per_image <= 0 or elems_per_image % 4 or self.E % elems_per_image):
+                raise ValueError("elems_per_image must be a positive multiple of 4 dividing the element count")
+            self.rows_b = SparseRows(self.B, lambda k: min(k + 2, self.B.shape[1]), torch.float32, self.device,
+                                     diag=False, dense=dense)
+        self.seed = None if seed is None else int(seed) & (2 ** 64 - 1)
+        self.epi = None if elems_per_image is None else int(elems_per_image)
         hdt = torch.float32 if self.fast else torch.float64
         self.rows = SparseRows(self.C, lambda k: k + 1, hdt, self.device, dense=dense)
         self.hist = torch.empty((self.n_step, self.E), dtype=hdt, device=self.device)
@@ -55,7 +73,11 @@ class CifarNI:
         self.labels = [float(np.float32(self.node[k, 0]) * np.float32(999)) for k in range(self.n_step)]
 
     def step(self, k: int, x_k: torch.Tensor, model_out: torch.Tensor, noise: torch.Tensor,
-             x_next: Optional[torch.Tensor] = None) -> torch.Tensor:
+             x_next: Optional[torch.Tensor] = None, index=None, elems_per_image: Optional[int] = None) -> torch.Tensor:
+        """``index`` (stochastic matrices): the batch's global image indices -- an int64 device tensor with one entry per
+        image, an int ``first`` (image i is ``first + i``) or a pair ``(first, stride)`` (image i is ``first + i*stride``);
+        None = 0.  ``elems_per_image`` overrides the constructor's value for this call."""
+        epi = self.epi if elems_per_image is None else int(elems_per_image)
         if x_next is None:
             x_next = self._x[k & 1]
             if x_next.data_ptr() == x_k.data_ptr():
@@ -66,21 +88,47 @@ class CifarNI:
         idx, val, n = self.rows.ptrs(k)
         r = self.rows.rows[k]
         a, s = float(self.node[k, 1]), float(self.node[k, 2])
+        if self.stochastic:
+            if epi is None:
+                raise ValueError("stochastic NI matrix: elems_per_image is needed to key the injected noise")
+            ib, vb, nb = self.rows_b.ptrs(k)
+            index, first, stride = self._index(index, epi, x_k.device)
+            check(lib.natinf_step_f64hist_noise(ptr(x_k), ptr(model_out), ptr(noise), ptr(self.hist), ptr(x_next), idx, val, n,
+                                                r.diag, ib, vb, nb, k, a, s, self.std[k], self.seed, ptr(index), first, stride,
+                                                epi, self.E, stream_ptr()), "natinf_step_f64hist_noise")
+            return x_next
         b0 = float(np.float32(self.B[k, 0]))
         fn = lib.natinf_step_f32hist if self.fast else lib.natinf_step_f64hist
         check(fn(ptr(x_k), ptr(model_out), ptr(noise), ptr(self.hist), ptr(x_next), idx, val, n, r.diag, k,
                  a, s, self.std[k], b0, self.E, stream_ptr()), "natinf_step_f64hist")
         return x_next
 
-    def run(self, model_fn: Callable, noise: torch.Tensor, return_all: bool = False):
-        """``model_fn(x [B,...] fp32, labels [B] fp32) -> out`` (raw network output)."""
+    def _index(self, index, epi, device):
+        """-> (index tensor or None, first index, index stride)"""
+        if index is None:
+            return None, 0, 1
+        if isinstance(index, torch.Tensor):
+            if (index.dtype != torch.int64 or index.device != device or not index.is_contiguous()
+                    or index.numel() != self.E // epi):
+                raise ValueError("index must be a contiguous int64 tensor on the sampler's device, one entry per image")
+            return index, 0, 0
+        if isinstance(index, (tuple, list)):
+            return None, int(index[0]), int(index[1])
+        return None, int(index), 1
+
+    def run(self, model_fn: Callable, noise: torch.Tensor, return_all: bool = False, index=None):
+        """``model_fn(x [B,...] fp32, labels [B] fp32) -> out`` (raw network output).  ``index``: see ``step``."""
         shape, B = noise.shape, noise.shape[0]
         noise = noise.contiguous()
+        epi = self.epi if self.epi is not None else noise.numel() // B
         x, xs = noise, [noise]
         for k in range(self.n_step):
             labels = torch.full((B,), self.labels[k], dtype=torch.float32, device=self.device)
             out = model_fn(x.view(shape), labels)
-            x = self.step(k, x.reshape(-1), out.contiguous().reshape(-1), noise.reshape(-1))
+            args = (k, x.reshape(-1), out.contiguous().reshape(-1), noise.reshape(-1))
+            # every step goes through self.step (callers wrap it per instance, e.g. bench.py's timed replica); a column-0
+            # matrix gets exactly the four positional arguments it always got
+            x = self.step(*args, index=index, elems_per_image=epi) if self.stochastic else self.step(*args)
             if return_all:
                 x = x.clone()
                 xs.append(x.view(shape))
