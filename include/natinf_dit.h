@@ -4,8 +4,9 @@
  * Replaces `model.forward(zt, timesteps, classlabels)` of src/ValidateNaturalInference.py:190-191, i.e.
  * DiT.forward (deps/DiT/models.py:237-253) with its blocks (:105-146), embedders (:27-99), fixed sin-cos position
  * embedding (:279-326) and unpatchify (:222-235); `timm`'s PatchEmbed / Attention / Mlp (models.py:16) follow their
- * published definitions.  Input size 32, patch 2, 4 input channels, 1000 classes (+1 null), learn_sigma (8 output
- * channels); depth / hidden size / head count are create-time parameters (DiT-XL/2 = 28 / 1152 / 16).
+ * published definitions.  Input size S = 32 (256x256 images, 256 tokens) or 64 (512x512 images, 1,024 tokens), patch 2,
+ * 4 input channels, 1000 classes (+1 null), learn_sigma (8 output channels); depth / hidden size / head count and the
+ * input size are create-time parameters (DiT-XL/2 = 28 / 1152 / 16).
  *
  * Arithmetic: bf16 operands on the matrix cores, fp32 accumulation, fp32 residual stream, LayerNorm / softmax /
  * modulation in fp32.  Same conventions as natinf.h (device pointers, explicit stream, int return codes, caller-owned
@@ -23,18 +24,22 @@ extern "C" {
 
 typedef struct natinf_dit* natinf_dit_t;
 
-/* Attention runs as one fused launch per block when head_dim <= 96; this flag selects the per-head GEMM / softmax /
+/* Attention runs as one fused launch per block when head_dim <= 96 (256 tokens: all keys of a head resident in LDS;
+ * 1,024 tokens: keys streamed through LDS, natinf_dit_attention_bf16); this flag selects the per-head GEMM / softmax /
  * GEMM path instead (the one used for larger heads), for testing one against the other. */
 #define NATINF_DIT_UNFUSED_ATTENTION 1
 
-/* hidden % 64 == 0, hidden <= 1536, hidden % heads == 0, (hidden / heads) % 8 == 0 */
+/* hidden % 64 == 0, hidden <= 1536, hidden % heads == 0, (hidden / heads) % 8 == 0; input size 32 */
 int natinf_dit_create(natinf_dit_t* out, int depth, int hidden, int heads, int flags);
-/* 1 (read when an engine is CREATED): the residual stream x [256 tokens][hidden] is kept in IEEE half instead of fp32; every update
+/* the same at input size 32 or 64 (the latent side S: 256 or 1,024 tokens; anything else is NATINF_EINVAL) */
+int natinf_dit_create_sized(natinf_dit_t* out, int depth, int hidden, int heads, int input_size, int flags);
+int natinf_dit_input_size(natinf_dit_t h);
+/* 1 (read when an engine is CREATED): the residual stream x [tokens][hidden] is kept in IEEE half instead of fp32; every update
  * x += gate * (W h + b) is computed in fp32 from the half row and rounded to half once (the MMDiT engine's natinf_set_mmdit_stream16,
  * include/natinf_mmdit.h).  0: fp32; a negative value: the library's default (1 since round 6). */
 int natinf_set_dit_stream16(int on);
 int natinf_dit_destroy(natinf_dit_t h);
-int64_t natinf_dit_param_count(natinf_dit_t h);           /* incl. the frozen pos_embed */
+int64_t natinf_dit_param_count(natinf_dit_t h);           /* incl. the frozen pos_embed (tokens x hidden) */
 int64_t natinf_dit_packed_bytes(natinf_dit_t h);
 int64_t natinf_dit_workspace_bytes(natinf_dit_t h, int max_batch);
 
@@ -47,10 +52,20 @@ int64_t natinf_dit_workspace_bytes(natinf_dit_t h, int max_batch);
 int natinf_dit_load(natinf_dit_t h, const float* params_f32, int64_t n_params, void* packed, int64_t packed_bytes,
                     natinf_stream_t stream);
 
-/* out = model.forward(z, t, y): z [B,4,32,32] fp32 NCHW, t [B] fp32 timesteps, y [B] int32 class labels (1000 = null),
- * out [B,8,32,32] fp32 NCHW. */
+/* out = model.forward(z, t, y): z [B,4,S,S] fp32 NCHW (S = the engine's input size), t [B] fp32 timesteps, y [B] int32
+ * class labels (1000 = null), out [B,8,S,S] fp32 NCHW. */
 int natinf_dit_forward(natinf_dit_t h, const float* z, const float* t, const int32_t* y, float* out, int B,
                        void* workspace, int64_t workspace_bytes, natinf_stream_t stream);
+
+/* The engine's attention alone (tests and measurement): o = softmax(q k^T * hd^-0.5) v per (sample, head), bf16 in and out.
+ * q, k, v: [B*T][ld] (head h at columns h*hd .. h*hd+hd-1; the engine passes its one q | k | v buffer, ld = 3 * hidden),
+ * o: [B*T][ld_o].  Keys stream through LDS in tiles of 64 (the kernel of 1,024-token engines).  T a multiple of 128 in
+ * [256, 4096], hd a multiple of 8 in [8, 96], ld % 8 == 0, ld_o % 4 == 0, q / k / v 16-byte aligned; else NATINF_EINVAL.
+ * flags NATINF_DIT_ATTN_RESIDENT: the 256-token kernel instead (all keys of a head in LDS; T must be 256, k addressed
+ * as q + (k - q)). */
+#define NATINF_DIT_ATTN_RESIDENT 1
+int natinf_dit_attention_bf16(const void* q, const void* k, const void* v, int ld, void* o, int ld_o, int B, int T, int H,
+                              int hd, int flags, natinf_stream_t stream);
 
 #ifdef __cplusplus
 }

@@ -161,13 +161,30 @@ _engine_cache = {}
 
 def load_dit_engine(path, max_batch=16):
     """Reference :150-154 (``DiT_models['DiT-XL/2'](input_size=32, num_classes=1000)`` + ``load_state_dict``) on the
-    gfx950 engine: the checkpoint's tensors go straight into ``natinf_dit_load``; one engine per checkpoint path."""
-    from .dit import DiTEngine, flatten_state_dict, XL2
-    key = (str(path), max_batch)
-    if key not in _engine_cache:
+    gfx950 engine: the checkpoint's tensors go straight into ``natinf_dit_load``; one engine per checkpoint path and
+    input size.  The input size is the checkpoint's own (``pos_embed``): 32 for ``DiT-XL-2-256x256.pt``, 64 for
+    ``DiT-XL-2-512x512.pt``."""
+    from .dit import DiTEngine, flatten_state_dict, input_size_of, XL2
+    sd = None
+    size = _engine_sizes.get(str(path))
+    if size is None:
         sd = torch.load(path, map_location="cpu", weights_only=True)
-        _engine_cache[key] = DiTEngine(flatten_state_dict(sd, XL2["depth"], XL2["hidden"]), max_batch, device=device, **XL2)
+        size = _engine_sizes[str(path)] = input_size_of(sd)
+    key = (str(path), max_batch, size)
+    if key not in _engine_cache:
+        if sd is None:
+            sd = torch.load(path, map_location="cpu", weights_only=True)
+        _engine_cache[key] = DiTEngine(flatten_state_dict(sd, XL2["depth"], XL2["hidden"], size), max_batch, device=device,
+                                       input_size=size, **XL2)
     return _engine_cache[key]
+
+
+_engine_sizes = {}
+
+
+def latent_size(model) -> int:
+    """Latent side S of the denoiser in use: the engine's ``input_size``; 32 for a denoiser that declares none."""
+    return int(getattr(model, "input_size", 32))
 
 
 def _setup(seed):
@@ -184,11 +201,12 @@ def _setup(seed):
     return model, labels, len(labels)
 
 
-def load_vae_decoder(path, max_batch=8):
+def load_vae_decoder(path, max_batch=8, latent_res=32):
     """Reference :212-214 (``AutoencoderKL.from_pretrained(vae_path)``) on the gfx950 decoder engine (include/natinf_vae.h):
-    ``path`` is the model directory (``diffusion_pytorch_model.safetensors`` / ``.bin``) or a weights file."""
+    ``path`` is the model directory (``diffusion_pytorch_model.safetensors`` / ``.bin``) or a weights file; one engine
+    per latent resolution (32: 256x256 images, 64: 512x512)."""
     from .vae import VAEDecoder, flatten_state_dict
-    key = ("vae", str(path), max_batch)
+    key = ("vae", str(path), max_batch, latent_res)
     if key not in _engine_cache:
         p = Path(path)
         if p.is_dir():
@@ -199,7 +217,7 @@ def load_vae_decoder(path, max_batch=8):
             sd = load_file(str(p))
         else:
             sd = torch.load(p, map_location="cpu", weights_only=True)
-        _engine_cache[key] = VAEDecoder(flatten_state_dict(sd, 4, prefix="decoder."), max_batch, latent_ch=4, latent_res=32, device=device)
+        _engine_cache[key] = VAEDecoder(flatten_state_dict(sd, 4, prefix="decoder."), max_batch, latent_ch=4, latent_res=latent_res, device=device)
     return _engine_cache[key]
 
 
@@ -268,10 +286,13 @@ def save_image_grid(images: torch.Tensor, path, nrow: int = 8) -> None:
 def _finish(input_z, name):
     global last_latents
     last_latents = input_z
+    S = input_z.shape[-1]
+    if S != 32:                                              # (256x256 keeps the reference's names; other sizes must not overwrite them)
+        name = name[:-4] + "__%dx%d.png" % (8 * S, 8 * S)
     if decoder_factory is not None:
         decoder_factory()(input_z / 0.18215, make_path(root_path / ("results/validation/" + name)))
     elif vae_path is not None:                               # reference :231-236: decode the latents, write the 1x8 image row
-        images = load_vae_decoder(vae_path)(input_z / 0.18215)
+        images = load_vae_decoder(vae_path, latent_res=S)(input_z / 0.18215)
         save_image_grid(images, make_path(root_path / ("results/validation/" + name)))
     return input_z
 
@@ -283,7 +304,8 @@ def _original(num_step, stochastic, seed=0):
     tb = [torch.from_numpy(e).to(device=device, dtype=torch.float32) for e in tables]
     log_var = tb[2] if stochastic else None
     coeff = tuple(tb[3:7]) if stochastic else tuple(tb[2:6])
-    input_z = torch.randn(n, 4, 32, 32, device=device)
+    S = latent_size(model)
+    input_z = torch.randn(n, 4, S, S, device=device)
     for ii in list(range(0, num_step))[::-1]:
         timesteps = torch.ones(n, dtype=torch.int32, device=device) * skip_idxs[ii]
         _, _, fuse_eps = forward_cfg(model, input_z, timesteps, labels, 4.0, 1000)
@@ -317,19 +339,20 @@ def natural_inference(alg_name="ddpm", num_step=24):
     tables, _ = skip_ddim_coeff(create_ddim_coeff(), num_step)
     c1 = np.asarray(tables[2])[::-1]
     c2 = np.asarray(tables[3])[::-1]
-    E = n * 4 * 32 * 32
+    S = latent_size(model)
+    E = n * 4 * S * S
     ni = ValidateNI(C, B, node, c1.astype(np.float32), c2.astype(np.float32), E, device=device)
-    noise = torch.randn(n, 4, 32, 32, device=device)
+    noise = torch.randn(n, 4, S, S, device=device)
     ni.hist_eps[0].copy_(noise.reshape(-1))
     input_z = noise.clone()
     classnulls = torch.full((n,), 1000, dtype=labels.dtype, device=device)             # (reference :352 builds it per step from a host list: a blocking copy each time)
     for kk in range(num_step):
         timesteps = torch.full((n,), int(node[kk, 0]), dtype=torch.int32, device=device)
-        cond, uncond = _cond_uncond(model, input_z, timesteps, labels, classnulls)      # [n, 8, 32, 32] each; first 4 channels used
+        cond, uncond = _cond_uncond(model, input_z, timesteps, labels, classnulls)      # [n, 8, S, S] each; first 4 channels used
         ni.hist_eps[kk + 1].copy_(torch.randn_like(input_z, dtype=torch.float32, device=device).reshape(-1))
-        per, stride = 4 * 32 * 32, cond.shape[1] * 32 * 32
+        per, stride = 4 * S * S, cond.shape[1] * S * S
         z = ni.step(kk, input_z.reshape(-1), cond.contiguous(), uncond.contiguous(), 4.0, per, stride)
-        input_z = z.view(n, 4, 32, 32)
+        input_z = z.view(n, 4, S, S)
     weight_name = os.path.basename(weight_path)[:-4]
     return _finish(input_z.clone(), "%s__seed_%d__natural.png" % (weight_name, 0))
 

@@ -97,6 +97,9 @@ SIGNATURES = {
     "natinf_debug_gemm_fp8": (C.c_int, [_i32, _i32, _i32, _p, _p, _p, _p, _p, _p, _p, _p, _i32, _i32, _p]),
     # include/natinf_dit.h
     "natinf_dit_create": (C.c_int, [C.POINTER(_p), _i32, _i32, _i32, _i32]),
+    "natinf_dit_create_sized": (C.c_int, [C.POINTER(_p), _i32, _i32, _i32, _i32, _i32]),
+    "natinf_dit_input_size": (C.c_int, [_p]),
+    "natinf_dit_attention_bf16": (C.c_int, [_p, _p, _p, _i32, _p, _i32, _i32, _i32, _i32, _i32, _i32, _p]),
     "natinf_dit_destroy": (C.c_int, [_p]),
     "natinf_dit_param_count": (C.c_int64, [_p]),
     "natinf_dit_packed_bytes": (C.c_int64, [_p]),

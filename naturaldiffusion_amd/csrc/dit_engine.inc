@@ -245,6 +245,30 @@ __global__ void k_unpatchify(const float* __restrict__ tok, float* __restrict__ 
     const int S = 2 * g, xw = (int)(i % S), yh = (int)((i / S) % S), c = (int)((i / ((int64_t)S * S)) % OC); const int64_t n = i / ((int64_t)S * S * OC);
     out[i] = tok[(n * g * g + (yh >> 1) * g + (xw >> 1)) * (4 * OC) + ((yh & 1) * 2 + (xw & 1)) * OC + c];
 }
+// k_softmax_rows for the per-head attention path at more than 256 keys (DiT at input 64: 1,024): one wave per row, T % 64 == 0, T <= 1024
+__global__ __launch_bounds__(256) void k_softmax_rows_1k(const float* __restrict__ S, bf16* __restrict__ P, int T, int64_t rows)
+{
+    const int lane = threadIdx.x & 63;
+    const int64_t row = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (row >= rows) return;
+    const float* s = S + row * T;
+    const int n = T >> 6;
+    float v[16];
+    float mx = -INFINITY;
+#pragma unroll
+    for (int i = 0; i < 16; ++i) { v[i] = i < n ? s[lane + 64 * i] : -INFINITY; mx = fmaxf(mx, v[i]); }
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) mx = fmaxf(mx, __shfl_xor(mx, o));
+    float sum = 0.f;
+#pragma unroll
+    for (int i = 0; i < 16; ++i) { v[i] = i < n ? __expf(v[i] - mx) : 0.f; sum += v[i]; }
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) sum += __shfl_xor(sum, o);
+    const float inv = 1.0f / sum;
+#pragma unroll
+    for (int i = 0; i < 16; ++i)
+        if (i < n) P[row * T + lane + 64 * i] = (bf16)(v[i] * inv);
+}
 __global__ void k_f32_to_bf16(const float* __restrict__ src, bf16* __restrict__ dst, int64_t n)
 {
     const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
@@ -287,6 +311,7 @@ struct EngineCore {                      // what a transformer engine is: a laun
 
 struct natinf_dit : EngineCore {
     int depth = 0, D = 0, heads = 0, hd = 0, nmod = 0;
+    int input_size = 32, T = 256;        // latent side S and tokens (S / 2)^2: natinf_dit_create_sized
     const int32_t* y = nullptr;          // per-forward
     bool unfused_attention = false;      // NATINF_DIT_UNFUSED_ATTENTION: per-head GEMM / softmax / GEMM (also used when head_dim > 96)
     bool stream16 = false;               // natinf_set_dit_stream16 (read when the plan is BUILT): the residual stream x [T][D] in IEEE half, not fp32 (as the MMDiT engine's image stream)
@@ -294,11 +319,11 @@ struct natinf_dit : EngineCore {
 
 namespace {
 
-constexpr int DIT_T = 256;
 constexpr int DIT_STREAM16_DEFAULT = 1;          // (round 6: DiT-XL/2 forward of 16 6.53 -> 6.28 ms; profiles/r06/dit_stream16_ab.txt)
 int g_dit_stream16 = DIT_STREAM16_DEFAULT;      // natinf_set_dit_stream16
 
-// qkv: [B*256][3 D] (q | k | v columns, one GEMM); v is transposed inside the attention kernel on its way into LDS (k_attn_fused<., ., false, true>)
+// qkv: [B*256][3 D] (q | k | v columns, one GEMM); v is transposed inside the attention kernel on its way into LDS (k_attn_fused<., ., false, true>).
+// More than 256 tokens: the streaming kernel of dit_flash.h on the same buffer (launch_dit_flash).
 template <int NQK, int ND>
 void launch_attn(const bf16* qkv, bf16* o, int B, int D, int H, int hd, hipStream_t s) {
     using Cfg = AttnCfg<NQK, ND>;
@@ -363,7 +388,8 @@ struct DitBuilder : PlanBuilder {
     natinf_dit& E;
     explicit DitBuilder(natinf_dit& e) : PlanBuilder(e), E(e) {}
     void build() {
-        const int D = E.D, H = E.heads, hd = E.hd, T = DIT_T, depth = E.depth;
+        const int D = E.D, H = E.heads, hd = E.hd, T = E.T, depth = E.depth, gs = E.input_size / 2;       // gs: tokens per latent side
+        const int log_T = T == 256 ? 8 : 10;                        // rows per sample of the gated epilogues (256 or 1,024 tokens)
         const int nmod = (6 * depth + 2) * D;
         E.nmod = nmod;
         // ---- parameters (order documented in natinf_dit.h)
@@ -393,9 +419,9 @@ struct DitBuilder : PlanBuilder {
         op([=](const Ctx& c) {                                      // embeddings and conditioning
             const int64_t prow = (int64_t)c.B * T;
             if (s16) hipLaunchKernelGGL(k_patch_embed<true>, dim3((unsigned)((D + 255) / 256), (unsigned)((prow + PE_TOK - 1) / PE_TOK)), dim3(256), 0, c.stream, c.x,
-                                        c.w<float>(w_pw), c.w<float>(w_pb), c.w<float>(w_pos), c.at<float>(x), 4, 16, D, prow);
+                                        c.w<float>(w_pw), c.w<float>(w_pb), c.w<float>(w_pos), c.at<float>(x), 4, gs, D, prow);
             else hipLaunchKernelGGL(k_patch_embed<false>, dim3((unsigned)((D + 255) / 256), (unsigned)((prow + PE_TOK - 1) / PE_TOK)), dim3(256), 0, c.stream, c.x,
-                                    c.w<float>(w_pw), c.w<float>(w_pb), c.w<float>(w_pos), c.at<float>(x), 4, 16, D, prow);
+                                    c.w<float>(w_pw), c.w<float>(w_pb), c.w<float>(w_pos), c.at<float>(x), 4, gs, D, prow);
             hipLaunchKernelGGL(k_dit_time_freq, dim3(grid1d((int64_t)c.B * 256)), dim3(256), 0, c.stream, c.labels, c.at<bf16>(tf), c.B);
             GemmArgs g = gemm_defaults();                           // SiLU(Linear_0(t_freq))
             g.a0 = c.at<bf16>(tf); g.a0_ld = 256; g.a0_C = 256; g.M = c.B; g.N = D; g.b = c.w<bf16>(w_t0); g.b_ld = 256;
@@ -439,7 +465,10 @@ struct DitBuilder : PlanBuilder {
                 g.a0 = c.at<bf16>(h); g.a0_ld = D; g.a0_C = D; g.M = c.B * T; g.N = QL; g.b = c.w<bf16>(w_qk); g.b_ld = D;
                 g.bias_n = c.w<float>(b_qk); g.c = c.at<bf16>(qk); g.c_ld = QL;
                 launch_gemm(g, c.stream);
-                if (fused_attn) {                                   // softmax(q k^T / sqrt(hd)) v, all heads, one launch
+                if (fused_attn && T != 256) {                       // keys streamed through LDS (dit_flash.h)
+                    const bf16* qkv = c.at<bf16>(qk);
+                    launch_dit_flash(qkv, qkv + D, qkv + 2 * D, 3 * D, c.at<bf16>(o), D, c.B, H, T, hd, c.stream);
+                } else if (fused_attn) {                            // softmax(q k^T / sqrt(hd)) v, all heads, one launch
                     if (hd <= 64) launch_attn<2, 4>(c.at<bf16>(qk), c.at<bf16>(o), c.B, D, H, hd, c.stream);
                     else if (hd <= 80) launch_attn<3, 5>(c.at<bf16>(qk), c.at<bf16>(o), c.B, D, H, hd, c.stream);
                     else launch_attn<3, 6>(c.at<bf16>(qk), c.at<bf16>(o), c.B, D, H, hd, c.stream);
@@ -458,7 +487,8 @@ struct DitBuilder : PlanBuilder {
                     launch_gemm(g, c.stream);
                 }
                 const int64_t rows = (int64_t)c.B * H * T;
-                hipLaunchKernelGGL(k_softmax_rows, dim3((unsigned)((rows + 3) / 4)), dim3(256), 0, c.stream, c.at<float>(S), c.at<bf16>(P), T, rows);
+                if (T == 256) hipLaunchKernelGGL(k_softmax_rows, dim3((unsigned)((rows + 3) / 4)), dim3(256), 0, c.stream, c.at<float>(S), c.at<bf16>(P), T, rows);
+                else hipLaunchKernelGGL(k_softmax_rows_1k, dim3((unsigned)((rows + 3) / 4)), dim3(256), 0, c.stream, c.at<float>(S), c.at<bf16>(P), T, rows);
                 for (int hh = 0; hh < H; ++hh) {                    // o[b][:, hh*hd : (hh+1)*hd] = P V
                     g = gemm_defaults();
                     g.a0 = c.at<bf16>(P) + (int64_t)hh * T * T; g.a0_ld = T; g.a0_C = T; g.a_bs = (int64_t)H * T * T; g.M = T; g.N = hd;
@@ -469,7 +499,7 @@ struct DitBuilder : PlanBuilder {
                 }
                 g = gemm_defaults();                                // x += gate_msa * (o Wproj + b)
                 g.a0 = c.at<bf16>(o); g.a0_ld = D; g.a0_C = D; g.M = c.B * T; g.N = D; g.b = c.w<bf16>(w_pr); g.b_ld = D;
-                g.bias_n = c.w<float>(b_pr); g.gate = c.at<float>(mod) + m0 + 2 * D; g.gate_ld = nmod; g.log_rows_per_sample = 8;
+                g.bias_n = c.w<float>(b_pr); g.gate = c.at<float>(mod) + m0 + 2 * D; g.gate_ld = nmod; g.log_rows_per_sample = log_T;
                 g.resid_f32 = c.at<float>(x); g.resid_f32_ld = D; g.c = c.at<float>(x); g.c_ld = D; g.c_mode = OUT_F32; g.stream_f16 = s16;
                 launch_gemm(g, c.stream);
             });
@@ -481,7 +511,7 @@ struct DitBuilder : PlanBuilder {
                 launch_gemm(g, c.stream);
                 g = gemm_defaults();                                // x += gate_mlp * fc2
                 g.a0 = c.at<bf16>(f); g.a0_ld = 4 * D; g.a0_C = 4 * D; g.M = c.B * T; g.N = D; g.b = c.w<bf16>(w_f2); g.b_ld = 4 * D;
-                g.bias_n = c.w<float>(b_f2); g.gate = c.at<float>(mod) + m0 + 5 * D; g.gate_ld = nmod; g.log_rows_per_sample = 8;
+                g.bias_n = c.w<float>(b_f2); g.gate = c.at<float>(mod) + m0 + 5 * D; g.gate_ld = nmod; g.log_rows_per_sample = log_T;
                 g.resid_f32 = c.at<float>(x); g.resid_f32_ld = D; g.c = c.at<float>(x); g.c_ld = D; g.c_mode = OUT_F32; g.stream_f16 = s16;
                 g.splitk_ws = c.at<float>(skw); g.splitk_max = SK_MAX;
                 launch_gemm(g, c.stream);
@@ -499,8 +529,8 @@ struct DitBuilder : PlanBuilder {
             g.a0 = c.at<bf16>(h); g.a0_ld = D; g.a0_C = D; g.M = c.B * T; g.N = 32; g.b = c.w<bf16>(w_f); g.b_ld = D;
             g.bias_n = c.w<float>(b_f); g.c = c.at<float>(tok); g.c_ld = 32; g.c_mode = OUT_F32;
             launch_gemm(g, c.stream);
-            const int64_t tot = (int64_t)c.B * 8 * 32 * 32;
-            hipLaunchKernelGGL(k_unpatchify, dim3(grid1d(tot, 256, 1 << 30)), dim3(256), 0, c.stream, c.at<float>(tok), c.out, 8, 16, tot);
+            const int64_t tot = (int64_t)c.B * 8 * (2 * gs) * (2 * gs);
+            hipLaunchKernelGGL(k_unpatchify, dim3(grid1d(tot, 256, 1 << 30)), dim3(256), 0, c.stream, c.at<float>(tok), c.out, 8, gs, tot);
         });
         finish();
     }
@@ -511,10 +541,15 @@ struct DitBuilder : PlanBuilder {
 extern "C" {
 
 int natinf_dit_create(natinf_dit_t* out, int depth, int hidden, int heads, int flags) {
+    return natinf_dit_create_sized(out, depth, hidden, heads, 32, flags);
+}
+int natinf_dit_create_sized(natinf_dit_t* out, int depth, int hidden, int heads, int input_size, int flags) {
     if (!out || (flags & ~NATINF_DIT_UNFUSED_ATTENTION) || depth <= 0 || hidden <= 0 || heads <= 0 || hidden % 64 || hidden % heads || (hidden / heads) % 8 || hidden > 1536)
         return NATINF_EINVAL;
+    if (input_size != 32 && input_size != 64) return NATINF_EINVAL;
     natinf_dit* e = new natinf_dit();
     e->depth = depth; e->D = hidden; e->heads = heads; e->hd = hidden / heads;
+    e->input_size = input_size; e->T = (input_size / 2) * (input_size / 2);
     e->unfused_attention = (flags & NATINF_DIT_UNFUSED_ATTENTION) != 0;
     e->stream16 = g_dit_stream16 != 0;
     DitBuilder b(*e);
@@ -523,6 +558,7 @@ int natinf_dit_create(natinf_dit_t* out, int depth, int hidden, int heads, int f
     return NATINF_OK;
 }
 int natinf_set_dit_stream16(int on) { g_dit_stream16 = on < 0 ? DIT_STREAM16_DEFAULT : (on != 0); return NATINF_OK; }
+int natinf_dit_input_size(natinf_dit_t h) { return h ? h->input_size : NATINF_EINVAL; }
 int natinf_dit_destroy(natinf_dit_t h) { if (!h) return NATINF_EINVAL; delete h; return NATINF_OK; }
 int64_t natinf_dit_param_count(natinf_dit_t h) { return h ? h->n_params : NATINF_EINVAL; }
 int64_t natinf_dit_packed_bytes(natinf_dit_t h) { return h ? h->packed_bytes : NATINF_EINVAL; }
@@ -537,6 +573,32 @@ int natinf_dit_forward(natinf_dit_t h, const float* z, const float* t, const int
     if (!h || !y) return NATINF_EINVAL;
     h->y = y;
     return h->run(z, t, out, B, workspace, workspace_bytes, (hipStream_t)stream);
+}
+
+int natinf_dit_attention_bf16(const void* q, const void* k, const void* v, int ld, void* o, int ld_o, int B, int T, int H, int hd, int flags,
+                              natinf_stream_t stream) {
+    if (!q || !k || !v || !o || B <= 0 || H <= 0 || hd < 8 || hd > 96 || hd % 8 || ld % 8 || ld < H * hd || ld_o % 4 || ld_o < H * hd) return NATINF_EINVAL;
+    if ((reinterpret_cast<uintptr_t>(q) | reinterpret_cast<uintptr_t>(k) | reinterpret_cast<uintptr_t>(v)) % 16 || reinterpret_cast<uintptr_t>(o) % 8) return NATINF_EINVAL;
+    if (flags & ~NATINF_DIT_ATTN_RESIDENT) return NATINF_EINVAL;
+    const bool resident = (flags & NATINF_DIT_ATTN_RESIDENT) != 0;
+    if (resident ? T != 256 : (T < 256 || T > 4096 || T % 128)) return NATINF_EINVAL;
+    if (!configure_gemm_kernels()) return NATINF_ENODEV;
+    if (resident) {                                      // k_attn_fused addresses k as q + k_off
+        const int64_t k_off = (int64_t)(reinterpret_cast<intptr_t>(k) - reinterpret_cast<intptr_t>(q)) / 2;
+        if (k_off > INT32_MAX || k_off < INT32_MIN) return NATINF_EINVAL;
+        const bf16* qb = (const bf16*)q;
+        const bf16* vb = (const bf16*)v;
+        bf16* ob = (bf16*)o;
+        const float sc = 1.0f / sqrtf((float)hd);
+        const hipStream_t s = (hipStream_t)stream;
+        auto run = [&](auto kern, int lds) { hipLaunchKernelGGL(kern, dim3((unsigned)(B * H)), dim3(512), lds, s, qb, ld, (int)k_off, vb, ob, ld_o, H, hd, sc); };
+        if (hd <= 64) run(&k_attn_fused<2, 4, false, true>, AttnCfg<2, 4>::LDS_BYTES);
+        else if (hd <= 80) run(&k_attn_fused<3, 5, false, true>, AttnCfg<3, 5>::LDS_BYTES);
+        else run(&k_attn_fused<3, 6, false, true>, AttnCfg<3, 6>::LDS_BYTES);
+    } else {
+        launch_dit_flash((const bf16*)q, (const bf16*)k, (const bf16*)v, ld, (bf16*)o, ld_o, B, H, T, hd, (hipStream_t)stream);
+    }
+    return hipGetLastError() == hipSuccess ? NATINF_OK : NATINF_ELAUNCH;
 }
 
 }  // extern "C"

@@ -44,6 +44,7 @@
 #include "attn_qkv.h"
 #include "attn_blk256.h"
 #include "flash_attn.h"
+#include "dit_flash.h"
 
 using namespace ncsn;
 

@@ -1,7 +1,7 @@
 """Host wrapper of the gfx950 DiT denoiser engine (include/natinf_dit.h).
 
 ``DiTEngine`` stands where ``DiT_models['DiT-XL/2'](input_size=32, num_classes=1000)`` + ``load_state_dict``
-stand in the reference (src/ValidateNaturalInference.py:150-154); ``engine(z, t, y)`` replaces
+(or ``input_size=64`` for the 512x512 checkpoint) stand in the reference (src/ValidateNaturalInference.py:150-154); ``engine(z, t, y)`` replaces
 ``model.forward(z, t, y)`` (deps/DiT/models.py:237-253).  PyTorch only provides device memory and the stream.
 """
 from __future__ import annotations
@@ -16,13 +16,21 @@ from ._lib import lib, check, ptr, stream_ptr
 
 UNFUSED_ATTENTION = 1
 XL2 = dict(depth=28, hidden=1152, heads=16)          # deps/DiT/models.py:333-334
+INPUT_SIZES = (32, 64)                               # latent side of the 256x256 / 512x512 checkpoints (patch 2: 256 / 1,024 tokens)
 
 
-def param_layout(depth: int, hidden: int) -> List[Tuple[str, Tuple[int, ...]]]:
+def _check_input_size(input_size: int) -> int:
+    if input_size not in INPUT_SIZES:
+        raise ValueError(f"input_size must be one of {INPUT_SIZES}, got {input_size}")
+    return int(input_size)
+
+
+def param_layout(depth: int, hidden: int, input_size: int = 32) -> List[Tuple[str, Tuple[int, ...]]]:
     """Flat parameter order of ``natinf_dit_load`` with the reference's state-dict names and shapes."""
     D = hidden
+    T = (_check_input_size(input_size) // 2) ** 2
     out: List[Tuple[str, Tuple[int, ...]]] = [
-        ("pos_embed", (1, 256, D)), ("x_embedder.proj.weight", (D, 4, 2, 2)), ("x_embedder.proj.bias", (D,)),
+        ("pos_embed", (1, T, D)), ("x_embedder.proj.weight", (D, 4, 2, 2)), ("x_embedder.proj.bias", (D,)),
         ("t_embedder.mlp.0.weight", (D, 256)), ("t_embedder.mlp.0.bias", (D,)),
         ("t_embedder.mlp.2.weight", (D, D)), ("t_embedder.mlp.2.bias", (D,)),
         ("y_embedder.embedding_table.weight", (1001, D))]
@@ -38,10 +46,22 @@ def param_layout(depth: int, hidden: int) -> List[Tuple[str, Tuple[int, ...]]]:
     return out
 
 
-def flatten_state_dict(sd: Dict[str, torch.Tensor], depth: int, hidden: int) -> torch.Tensor:
-    """state_dict of the reference's DiT (e.g. ``DiT-XL-2-256x256.pt``) -> the flat fp32 vector of ``natinf_dit_load``."""
+def input_size_of(sd: Dict[str, torch.Tensor]) -> int:
+    """The latent side a state dict was trained at, from its ``pos_embed`` (1, T, D): 32 for 256 tokens, 64 for 1,024."""
+    T = int(sd["pos_embed"].shape[-2])
+    for s in INPUT_SIZES:
+        if (s // 2) ** 2 == T:
+            return s
+    raise ValueError(f"pos_embed has {T} tokens; supported are {[(s // 2) ** 2 for s in INPUT_SIZES]} (input sizes {INPUT_SIZES})")
+
+
+def flatten_state_dict(sd: Dict[str, torch.Tensor], depth: int, hidden: int, input_size: int = None) -> torch.Tensor:
+    """state_dict of the reference's DiT (``DiT-XL-2-256x256.pt`` or ``DiT-XL-2-512x512.pt``) -> the flat fp32 vector of
+    ``natinf_dit_load``.  ``input_size`` None: taken from ``pos_embed``; given, the dict must match it."""
+    if input_size is None:
+        input_size = input_size_of(sd)
     parts = []
-    for name, shape in param_layout(depth, hidden):
+    for name, shape in param_layout(depth, hidden, input_size):
         t = sd[name]
         if tuple(t.shape) != shape:
             raise ValueError(f"{name}: expected shape {shape}, got {tuple(t.shape)}")
@@ -51,7 +71,8 @@ def flatten_state_dict(sd: Dict[str, torch.Tensor], depth: int, hidden: int) -> 
 
 class DiTEngine:
     def __init__(self, flat_params: torch.Tensor, max_batch: int, depth: int = 28, hidden: int = 1152, heads: int = 16,
-                 device="cuda:0", unfused_attention: bool = False, stream16=None):
+                 device="cuda:0", unfused_attention: bool = False, stream16=None, input_size: int = 32):
+        self.input_size = _check_input_size(input_size)
         _lib.require_gpu()
         if depth <= 0 or hidden <= 0 or heads <= 0 or hidden % 64 or hidden > 1536 or hidden % heads or (hidden // heads) % 8:
             raise ValueError("hidden must be a multiple of 64 (<= 1536) and of heads, head_dim a multiple of 8")
@@ -66,7 +87,8 @@ class DiTEngine:
         if stream16 is not None:
             check(lib.natinf_set_dit_stream16(int(bool(stream16))), "natinf_set_dit_stream16")
         try:
-            check(lib.natinf_dit_create(C.byref(self._h), depth, hidden, heads, UNFUSED_ATTENTION if unfused_attention else 0), "natinf_dit_create")
+            check(lib.natinf_dit_create_sized(C.byref(self._h), depth, hidden, heads, self.input_size, UNFUSED_ATTENTION if unfused_attention else 0),
+                  "natinf_dit_create_sized")
         finally:
             if stream16 is not None:
                 lib.natinf_set_dit_stream16(-1)
@@ -83,8 +105,9 @@ class DiTEngine:
             self._ws = torch.empty(self.workspace_bytes, dtype=torch.uint8, device=self.device)
 
     def __call__(self, z: torch.Tensor, t: torch.Tensor, y: torch.Tensor, out: torch.Tensor = None) -> torch.Tensor:
-        if z.dtype != torch.float32 or z.dim() != 4 or tuple(z.shape[1:]) != (4, 32, 32) or not z.is_cuda:
-            raise ValueError("z must be a CUDA fp32 tensor of shape [B,4,32,32]")
+        S = self.input_size
+        if z.dtype != torch.float32 or z.dim() != 4 or tuple(z.shape[1:]) != (4, S, S) or not z.is_cuda:
+            raise ValueError(f"z must be a CUDA fp32 tensor of shape [B,4,{S},{S}]")
         B = z.shape[0]
         if B > self.max_batch:
             raise ValueError(f"batch {B} exceeds max_batch {self.max_batch}")
@@ -94,7 +117,7 @@ class DiTEngine:
         if t.numel() != B or y.numel() != B:
             raise ValueError("t and y must have one entry per sample")
         if out is None:
-            out = torch.empty((B, 8, 32, 32), dtype=torch.float32, device=z.device)
+            out = torch.empty((B, 8, S, S), dtype=torch.float32, device=z.device)
         check(lib.natinf_dit_forward(self._h, ptr(z), ptr(t), ptr(y), ptr(out), B, ptr(self._ws), self._ws.numel(),
                                      stream_ptr()), "natinf_dit_forward")
         return out

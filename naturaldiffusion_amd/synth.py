@@ -45,15 +45,16 @@ def dit_pos_embed(dim: int, grid: int = 16) -> torch.Tensor:
     return torch.from_numpy(np.concatenate([one(dim // 2, gw), one(dim // 2, gh)], axis=1)).float()
 
 
-def synthetic_dit_state_dict(depth: int = 28, hidden: int = 1152, seed: int = 0) -> Dict[str, torch.Tensor]:
-    """Synthetic DiT weights (``DiT-XL-2-256x256.pt`` is a download the image lacks): xavier-uniform matrices --
-    including the adaLN / output layers the reference zero-initialises --, N(0, 0.02) embeddings and biases."""
+def synthetic_dit_state_dict(depth: int = 28, hidden: int = 1152, seed: int = 0, input_size: int = 32) -> Dict[str, torch.Tensor]:
+    """Synthetic DiT weights (``DiT-XL-2-256x256.pt`` / ``-512x512.pt`` are downloads the image lacks): xavier-uniform
+    matrices -- including the adaLN / output layers the reference zero-initialises --, N(0, 0.02) embeddings and biases;
+    the position table of the ``input_size // 2`` token grid."""
     from .dit import param_layout as dit_layout
     g = torch.Generator().manual_seed(seed)
     out: Dict[str, torch.Tensor] = {}
-    for name, shp in dit_layout(depth, hidden):
+    for name, shp in dit_layout(depth, hidden, input_size):
         if name == "pos_embed":
-            out[name] = dit_pos_embed(hidden).unsqueeze(0)
+            out[name] = dit_pos_embed(hidden, input_size // 2).unsqueeze(0)
         elif len(shp) >= 2 and "embedding_table" not in name:
             lim = math.sqrt(6.0 / (int(np.prod(shp[1:])) + shp[0]))
             out[name] = (torch.rand(shp, generator=g) * 2 - 1) * lim
