@@ -80,11 +80,12 @@ int natinf_ncsnpp_forward(natinf_ncsnpp_t h, const float* x, const float* labels
 int natinf_ncsnpp_describe_gemms(natinf_ncsnpp_t h, int B, char* buf, int cap);
 
 /* Tuning hooks.  natinf_debug_gemm runs `iters` launches of one GEMM-kernel variant on caller-supplied operands
- * (A [batch][M][K0/taps channels] bf16 -- zero-bordered [B][H+2][W+2][C] when taps == 9, W = 1 << logW --,
+ * (A [batch][M][K0/taps channels] bf16 -- zero-bordered [B][H+2][W+2][C] when taps == 9, W = H = 1 << logW --,
  * optional 1x1 segment a1 [M][K1], B [N][K0+K1] bf16 in the engine's K order, optional fp32 bias, C [M][N] bf16 or
  * fp32).  Variants: 0 auto, 1 generic, 2/3/4 two-stage DMA 256x256 / 256x128 / 128x128, 5/6/7/8 ring
- * 256x256 / 256x128 / 128x128 / 64x128.  natinf_set_gemm_variant forces a variant for every DMA-eligible launch of
- * subsequent forwards (0 = automatic). */
+ * 256x256 / 256x128 / 128x128 / 64x128.  NATINF_EINVAL (nothing launched) unless K0 % taps == 0, N % 8 == 0 and a1 is
+ * given exactly when K1 > 0; taps == 9 also needs C % 64 == 0, M a multiple of the image size and batch == 1.
+ * natinf_set_gemm_variant forces a variant for every DMA-eligible launch of subsequent forwards (0 = automatic). */
 int natinf_debug_gemm(int variant, int M, int N, int K0, int K1, int taps, int logW, int batch,
                       const void* a0, const void* a1, const void* b, const float* bias_n, void* c, int c_f32, float scale,
                       int iters, natinf_stream_t stream);
@@ -99,10 +100,15 @@ int natinf_debug_quant_fp8_rows(const float* w, void* q, float* row_scale, int r
 /* One plain GEMM C[M][N] = A[M][K] B[N][K]^T (bf16 operands) with the fused epilogue terms, any of which may be NULL: column bias,
  * row bias, per-sample row vector and gate ([samples][N], sample = row >> log_rows_per_sample), bf16 / fp32 residual [M][N], scale,
  * activation (0 none, 1 SiLU, 2 tanh-GELU); output bf16 or fp32 [M][N]; gn_part (optional) receives (sum, sum of squares) per
- * block tile of *bm_out rows and 4-column quad.  fp32_slab = 1 forces the general fp32-slab epilogue.  N % 8 == 0. */
+ * block tile of *bm_out rows and 4-column quad.  fp32_slab = 1 forces the general fp32-slab epilogue.  N % 8 == 0 (row-major outputs). */
 int natinf_debug_gemm_fused(int variant, int M, int N, int K, const void* a, const void* b, const float* bias_n, const float* bias_m,
                             const float* rowvec, const float* gate, int log_rows_per_sample, const void* resid_bf16, const float* resid_f32,
                             float scale, int act, void* c, int c_f32, float* gn_part, int* bm_out, int fp32_slab, natinf_stream_t stream);
+/* Test hook: the NEXT natinf_debug_gemm_fused call (and only that one, whatever its outcome) is a 3x3 implicit convolution:
+ * `a` is the zero-bordered [M / HW][H+2][W+2][K / 9] operand (W = H = 1 << logW, HW = W * H, K / 9 % 64 == 0, M % HW == 0), a1 the
+ * optional 1x1 segment [M][c1] (c1 % 64 == 0) and b [N][K + c1] in the engine's K order.  With it, c_f32 = 2 writes fp32 NCHW
+ * [M / HW][N][H][W] (bias_n and scale only, any N: the VAE's output head).  logW = 0 clears it. */
+int natinf_debug_set_conv_operand(int logW, const void* a1, int c1);
 int natinf_debug_gemm_fp8(int M, int N, int K, const void* a8, const float* a_scale, const void* a_mx, const void* b8, const float* b_scale,
                           const float* bias_n, void* c, void* c_mx, int c_mode, int iters, natinf_stream_t stream);
 /* Test hook for the up-sampling fetch paths of k_conv_gn2 (the up-sampling res-blocks, natinf_set_fuse_up): bit 0 = the following

@@ -89,6 +89,7 @@ SIGNATURES = {
     "natinf_set_conv_gn8_tile": (C.c_int, [_i32]),
     "natinf_set_gemm_splitk": (C.c_int, [_i32]),
     "natinf_debug_set_splitk_workspace": (C.c_int, [_p, _i32]),
+    "natinf_debug_set_conv_operand": (C.c_int, [_i32, _p, _i32]),
     "natinf_debug_conv_gn": (C.c_int, [_i32, _i32, _i32, _i32, _i32, _p, _p, _p, _p, _p, _p, _p, _p, _f32, _p, _p, _i32, _p]),
     "natinf_debug_conv_gn_up": (C.c_int, [_i32]),
     "natinf_ncsnpp_profile": (C.c_int, [_p, _i32]),

@@ -677,6 +677,15 @@ int launch_gemm_run(const GemmArgs& g0, hipStream_t s) {
     }
     const GemmArgs& g = g0;
     const int v = choose_variant(g);
+    if (g.taps == 9 && v != V_CONV_GN && g.a0_C % BK) {
+        // (the packed weight rows of a 3x3 launch hold ((c / 64) * 9 + tap) * 64 + c % 64 columns: with a0_C % 64 != 0 no kernel has a defined K order)
+        if (g_record) {
+            char line[160];
+            snprintf(line, sizeof(line), "%d %d %d %d %d %d invalid_conv3x3/e0\n", g.M, g.N, g.taps * g.a0_C, g.a1 ? g.a1_C : 0, g.taps, g.batch);
+            *g_record += line;
+        } else g_launch_error = 1;
+        return 256;
+    }
     if (v == V_CONV_GN && !conv_gn_ok(g)) {
         if (g_record) {                 // description pass: say so in the table instead of dropping the row
             char line[160];
@@ -1741,7 +1750,11 @@ int natinf_ncsnpp_describe_gemms(natinf_ncsnpp_t h, int B, char* buf, int cap) {
 int natinf_debug_gemm(int variant, int M, int N, int K0, int K1, int taps, int logW, int batch,
                       const void* a0, const void* a1, const void* b, const float* bias_n, void* c, int c_f32, float scale,
                       int iters, natinf_stream_t stream) {
-    if (variant < 0 || variant >= V_COUNT || !a0 || !b || !c || M <= 0 || N <= 0 || iters <= 0 || (taps != 1 && taps != 9)) return NATINF_EINVAL;
+    if (variant < 0 || variant >= V_COUNT || !a0 || !b || !c || M <= 0 || N <= 0 || K0 <= 0 || K1 < 0 || iters <= 0 || (taps != 1 && taps != 9)) return NATINF_EINVAL;
+    // the row-major epilogues store 8 columns at a time (only n < N is checked); 3x3: 64-channel chunks (the packed K order), whole
+    // zero-bordered images, one batch index (a_bs would have to be the padded image size, and a1 shares it)
+    if (K0 % taps || N % 8 || (a1 != nullptr) != (K1 > 0)) return NATINF_EINVAL;
+    if (taps == 9 && ((K0 / 9) % BK || logW < 1 || logW > 12 || M % (1 << (2 * logW)) || batch != 1)) return NATINF_EINVAL;
     if (!variant_shipped(variant) || variant == V_CONV_GN || variant == V_FP8_256x256) return NATINF_ESTATE;      // superseded / ablation variants: -DNATINF_DEV builds
 #ifndef NATINF_DEV
     if (c_f32 >= 2) return NATINF_ESTATE;      // timing experiments: -DNATINF_DEV builds
@@ -1758,9 +1771,19 @@ int natinf_debug_gemm(int variant, int M, int N, int K0, int K1, int taps, int l
     g.splitk_ws = g_dbg_splitk_ws; g.splitk_max = g_dbg_splitk_max;
     const int saved = g_force_variant;
     g_force_variant = variant;
+    g_launch_error = 0;
     for (int i = 0; i < iters; ++i) launch_gemm(g, (hipStream_t)stream);
     g_force_variant = saved;
+    if (g_launch_error) { g_launch_error = 0; return NATINF_EINVAL; }
     return hipGetLastError() == hipSuccess ? NATINF_OK : NATINF_ELAUNCH;
+}
+
+// natinf_debug_set_conv_operand: the next natinf_debug_gemm_fused call is a 3x3 implicit convolution (taps == 9) -- see include/natinf_ncsnpp.h
+int g_dbg_conv_logW = 0; const void* g_dbg_conv_a1 = nullptr; int g_dbg_conv_c1 = 0;
+int natinf_debug_set_conv_operand(int logW, const void* a1, int c1) {
+    if (logW < 0 || logW > 12 || c1 < 0 || c1 % BK || (c1 > 0) != (a1 != nullptr) || (logW == 0 && a1)) return NATINF_EINVAL;
+    g_dbg_conv_logW = logW; g_dbg_conv_a1 = a1; g_dbg_conv_c1 = c1;
+    return NATINF_OK;
 }
 
 // One plain GEMM C = A B^T with the fused epilogue terms of GemmArgs (tests/test_gpu_gemm_epilogue.py): every pointer but a / b / c
@@ -1769,22 +1792,35 @@ int natinf_debug_gemm(int variant, int M, int N, int K0, int K1, int taps, int l
 int natinf_debug_gemm_fused(int variant, int M, int N, int K, const void* a, const void* b, const float* bias_n, const float* bias_m,
                             const float* rowvec, const float* gate, int log_rows_per_sample, const void* resid_bf16, const float* resid_f32,
                             float scale, int act, void* c, int c_f32, float* gn_part, int* bm_out, int fp32_slab, natinf_stream_t stream) {
-    if (variant < 0 || variant >= V_COUNT || !a || !b || !c || M <= 0 || N <= 0 || K <= 0 || N % 8) return NATINF_EINVAL;
+    const int logW = g_dbg_conv_logW, c1 = g_dbg_conv_c1;              // natinf_debug_set_conv_operand: consumed by this call, whatever its outcome
+    const void* a1 = g_dbg_conv_a1;
+    g_dbg_conv_logW = 0; g_dbg_conv_a1 = nullptr; g_dbg_conv_c1 = 0;
+    if (variant < 0 || variant >= V_COUNT || !a || !b || !c || M <= 0 || N <= 0 || K <= 0 || c_f32 < 0 || c_f32 > 2) return NATINF_EINVAL;
+    if (c_f32 == 2) {                          // NCHW fp32 (the VAE's output head): bias and scale only, whole images
+        if (!logW || bias_m || rowvec || gate || resid_bf16 || resid_f32 || gn_part || act != ACT_NONE) return NATINF_EINVAL;
+    } else if (N % 8) return NATINF_EINVAL;
+    if (logW && (K % 9 || (K / 9) % BK || M % (1 << (2 * logW)))) return NATINF_EINVAL;
     if (!variant_shipped(variant) || variant == V_CONV_GN || variant == V_FP8_256x256) return NATINF_ESTATE;
     if (!configure_gemm_kernels()) return NATINF_ENODEV;
     GemmArgs g = gemm_defaults();
     g.a0 = (const bf16*)a; g.a0_C = K; g.a0_ld = K; g.M = M; g.N = N; g.b = (const bf16*)b; g.b_ld = K;
+    if (logW) {
+        g.taps = 9; g.a0_C = g.a0_ld = K / 9; g.logW = logW; g.logHW = 2 * logW; g.a0_padded = 1; g.b_ld = K + c1;
+        if (a1) { g.a1 = (const bf16*)a1; g.a1_C = g.a1_ld = c1; }
+    }
     g.bias_n = bias_n; g.bias_m = bias_m; g.rowvec = rowvec; g.rowvec_ld = N; g.gate = gate; g.gate_ld = N; g.log_rows_per_sample = log_rows_per_sample;
     g.resid = (const bf16*)resid_bf16; g.resid_ld = N; g.resid_f32 = resid_f32; g.resid_f32_ld = N;
-    g.scale = scale; g.act = act; g.c = c; g.c_ld = N; g.c_mode = c_f32 ? OUT_F32 : OUT_BF16;
+    g.scale = scale; g.act = act; g.c = c; g.c_ld = N; g.c_mode = c_f32 == 2 ? OUT_F32_NCHW : (c_f32 ? OUT_F32 : OUT_BF16);
     g.gn_part = gn_part; g.gn_quads = N / 4; g.epi_fp32_slab = fp32_slab != 0;
     g.splitk_ws = g_dbg_splitk_ws; g.splitk_max = g_dbg_splitk_max;
     g.dbg_ts = g_dbg_ts;
     const int saved = g_force_variant;
     g_force_variant = variant;
+    g_launch_error = 0;
     const int bm = launch_gemm(g, (hipStream_t)stream);
     g_force_variant = saved;
     if (bm_out) *bm_out = bm;
+    if (g_launch_error) { g_launch_error = 0; return NATINF_EINVAL; }
     return hipGetLastError() == hipSuccess ? NATINF_OK : NATINF_ELAUNCH;
 }
 

@@ -70,7 +70,7 @@ struct GemmArgs {
     const bf16* a0; int a0_ld; int a0_C;
     const bf16* a1; int a1_ld; int a1_C;
     int taps; int logW; int logHW;                    // spatial decode of m for taps == 9 (power-of-two H, W)
-    int a0_padded;                                    // taps == 9: a0 is [B][H+2][W+2][C] with a zero border (k_gemm_bf16_dma only)
+    int a0_padded;                                    // taps == 9: a0 is [B][H+2][W+2][C] with a zero border (every kernel but k_conv_gn*; 0: unpadded [B][H][W][C], k_gemm_bf16 only)
     int M, N;
     const bf16* b; int b_ld;                          // [N][K0+K1], K contiguous
     int64_t a_bs, b_bs, c_bs; int batch;              // per-batch element strides (blockIdx.z)
@@ -384,13 +384,14 @@ __global__ __launch_bounds__(256, 2) void k_gemm_bf16(const GemmArgs g)
     int64_t a_off0[4], a_off1[4], b_off[4];
     bool a_ok[4], b_ok[4];
     const int Wd = 1 << g.logW, Hd = 1 << (g.logHW - g.logW);
+    const int Wa = g.a0_padded ? Wd + 2 : Wd;      // row pitch of a0 in pixels: zero-bordered [B][H+2][W+2][C] or plain [B][H][W][C]
 #pragma unroll
     for (int i = 0; i < 4; ++i) {
         const int m = m0 + row0 + 32 * i;
         a_ok[i] = m < g.M;
         const int p = m & ((1 << g.logHW) - 1);
         a_y[i] = p >> g.logW; a_x[i] = p & (Wd - 1);
-        a_off0[i] = (int64_t)m * g.a0_ld;
+        a_off0[i] = g.a0_padded ? ((int64_t)((m >> g.logHW) * (Hd + 2) + a_y[i] + 1) * Wa + a_x[i] + 1) * g.a0_ld : (int64_t)m * g.a0_ld;
         a_off1[i] = (int64_t)m * g.a1_ld;
         const int n = n0 + row0 + 32 * i;
         b_ok[i] = n < g.N;
@@ -406,7 +407,7 @@ __global__ __launch_bounds__(256, 2) void k_gemm_bf16(const GemmArgs g)
             const int dy = g.taps == 9 ? tap / 3 - 1 : 0, dx = g.taps == 9 ? tap % 3 - 1 : 0;
             const int cc = c0 + colc * 8;
             const bool kin = cc < (g.taps == 9 ? g.a0_C : K0);
-            const int64_t shift = (int64_t)(dy * Wd + dx) * g.a0_ld + cc;
+            const int64_t shift = (int64_t)(dy * Wa + dx) * g.a0_ld + cc;
 #pragma unroll
             for (int i = 0; i < 4; ++i) {
                 const bool ok = a_ok[i] && kin && (unsigned)(a_y[i] + dy) < (unsigned)Hd && (unsigned)(a_x[i] + dx) < (unsigned)Wd;
