@@ -83,7 +83,7 @@ int natinf_attention_profile(int enable);
  * softmax, the running maximum updated every key tile; rounds 1-3), 3 (default) = k_flash_attn64_v2<1, 64>: q pre-multiplied by scale * log2 e,
  * scores leave the matrix pipe as exponents relative to a reference that is only moved when a score exceeds it by more than 2^8 (no per-score fma, no
  * cross-lane step on the common path), row sums on the matrix pipe, 64-key tiles (three to four waves per SIMD).  1 / 2 = intermediate forms of it
- * (vector-pipe row sums / 128-key tiles): -DNATINF_DEV builds only, NATINF_ESTATE elsewhere.  Same function up to rounding; NATINF_EINVAL outside 0..3. */
+ * (vector-pipe row sums / 128-key tiles): retired, NATINF_ESTATE.  Same function up to rounding; NATINF_EINVAL outside 0..3. */
 int natinf_set_flash_mode(int mode);
 /* 1 (default): a forward puts the text stream's launches (M = ctx_tokens rows per sequence: small GEMMs that fill a fraction of the chip) on a HIP stream of the
  * engine's own, forked from and joined to the caller's stream by events -- in front of the joint attention of every block and behind it, and at both ends of the

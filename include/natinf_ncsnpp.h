@@ -82,8 +82,8 @@ int natinf_ncsnpp_describe_gemms(natinf_ncsnpp_t h, int B, char* buf, int cap);
 /* Tuning hooks.  natinf_debug_gemm runs `iters` launches of one GEMM-kernel variant on caller-supplied operands
  * (A [batch][M][K0/taps channels] bf16 -- zero-bordered [B][H+2][W+2][C] when taps == 9, W = H = 1 << logW --,
  * optional 1x1 segment a1 [M][K1], B [N][K0+K1] bf16 in the engine's K order, optional fp32 bias, C [M][N] bf16 or
- * fp32).  Variants: 0 auto, 1 generic, 2/3/4 two-stage DMA 256x256 / 256x128 / 128x128, 5/6/7/8 ring
- * 256x256 / 256x128 / 128x128 / 64x128.  NATINF_EINVAL (nothing launched) unless K0 % taps == 0, N % 8 == 0 and a1 is
+ * fp32).  Variants (ids 0..32; the retired ones -- 2-7, 10-16, 18-22, 24, 25, 30-32 -- answer NATINF_ESTATE): 0 auto, 1 generic, 8 ring 64x128,
+ * 9 ring 256x128 (4 waves), 17 two-stage 128x128 (hand pipeline), 26 / 27 256x256 / 512x128 (one issuing wave per SIMD), 29 k_gemm_w128.  NATINF_EINVAL (nothing launched) unless K0 % taps == 0, N % 8 == 0 and a1 is
  * given exactly when K1 > 0; taps == 9 also needs C % 64 == 0, M a multiple of the image size and batch == 1.
  * natinf_set_gemm_variant forces a variant for every DMA-eligible launch of subsequent forwards (0 = automatic). */
 int natinf_debug_gemm(int variant, int M, int N, int K0, int K1, int taps, int logW, int batch,
@@ -115,7 +115,7 @@ int natinf_debug_gemm_fp8(int M, int N, int K, const void* a8, const float* a_sc
  * natinf_debug_conv_gn calls take x at HALF the resolution ([B][res/2][res/2][cin]) and up-sample it (nearest, 2x) inside the patch fetch,
  * bit 1 = the same for the 1x1 shortcut operand a1.  0 restores the plain fetch. */
 int natinf_debug_conv_gn_up(int flags);
-/* The fused GroupNorm-apply + SiLU + 3x3 convolution kernel (csrc/conv_gn.h) on caller-supplied operands:
+/* The fused GroupNorm-apply + SiLU + 3x3 convolution kernel (csrc/conv_gn2.h) on caller-supplied operands:
  *   out[m, n] = (sum_{tap, c} silu(x[pixel(m) + tap, c] * scale[b, c] + shift[b, c]) * w[n, c, tap] + sum_c a1[m, c] * w1[n, c]
  *                + bias_n[n] + resid[m, n]) * out_scale,  zero padding applied after the activation (layerspp.py:242-274).
  * x: bf16 [B][res][res][cin] (res 32 or 16, cin % 64 == 0); w_packed: bf16 [N][9*cin + c1], K order ((c/64)*9 + tap)*64 + c%64
@@ -125,9 +125,9 @@ int natinf_debug_conv_gn_up(int flags);
  * Operands are taken in the kernel's FOLDED form: `scale` and `shift` must be the GroupNorm scale / shift multiplied by -log2(e)
  * and the 3x3 columns of w_packed multiplied by -ln 2 (the shortcut columns are plain); the kernel evaluates t / (1 + exp2(t)),
  * t = x*scale + shift = -log2(e) v, i.e. -log2(e) silu(v) -- the same function with two vector instructions fewer per element.
- * w_frag: NULL -> k_conv_gn (weights through an LDS ring); else a buffer of N * (9*cin + c1) bf16 that receives the fragment-major
- * copy of w_packed (k_pack_frag) and k_conv_gn2 runs (weights streamed through registers, csrc/conv_gn2.h) when N is a multiple of
- * its column tile (128; 256 for the 128-row tile) and natinf_set_conv_gn_regw is 1 (default). */
+ * w_frag: a buffer of N * (9*cin + c1) bf16 that receives the fragment-major copy of w_packed (k_pack_frag); k_conv_gn2 runs (weights
+ * streamed through registers, csrc/conv_gn2.h) when N is a multiple of its column tile (128; 256 for the 128-row tile).  NULL (k_conv_gn,
+ * weights through an LDS ring: retired) or a ragged N: NATINF_EINVAL. */
 int natinf_debug_conv_gn(int res, int B, int N, int cin, int c1, const void* x, const float* scale, const float* shift, const void* w_packed, void* w_frag,
                          const void* a1, const float* bias_n, const void* resid, float out_scale, void* out, float* gn_part, int iters,
                          natinf_stream_t stream);
@@ -137,7 +137,7 @@ int natinf_set_gemm_variant(int variant);
 int natinf_set_gemm_epilogue(int fp32_slab);
 /* A/B switch for tuning: 0 = N <= 128 layers on the 4-wave 256x128 ring tile, 1 (default) = on the 512x128 hand-pipelined tile. */
 int natinf_set_gemm_pref512(int on);
-/* A/B switch for tuning: 1 (default) = in the 256x256 / 512x128 kernels one wave per SIMD issues all LDS-DMA pieces, 0 = every wave its own. */
+/* 1 (default): in the 256x256 / 512x128 kernels one wave per SIMD issues all LDS-DMA pieces; 0 (every wave its own): retired, NATINF_ESTATE. */
 int natinf_set_gemm_half_issue(int on);
 /* A/B switch for tuning: 1 (default) = small-M plain GEMMs (fewer than two rounds of 256 x 256 tiles) choose between 256 x 256 and 128 x 128 tiles by the number of
  * ROUNDS of blocks each needs (128 x 128: two blocks per CU; a 256 x 256 round costs 1.5 of a 128 x 128 one, 1.3 on the four-wave tile of csrc/gemm_w128.h),
@@ -163,6 +163,7 @@ int natinf_set_conv_gn_w128(int mask);
 /* Smallest K (9 * cin + shortcut channels) at which a launch of shape 0 (32x32, 512 x 128 tiles), 1 (32x32, 256 x 256) or 2 (16x16, 256 x 256) takes k_conv_gn3
  * (defaults 2304 / 0 / 2304: with one block per CU a tile's prologue and epilogue are exposed, so short-K launches stay on k_conv_gn2); 0 = every K (tests, A/B runs). */
 int natinf_set_conv_gn_w128_min_k(int shape, int k);
+/* 1 (default): k_conv_gn2, weights streamed through registers; 0 (k_conv_gn, weights through an LDS ring): retired, NATINF_ESTATE. */
 int natinf_set_conv_gn_regw(int on);
 /* 1 (default; read when a plan is built): the up-sampling blocks at 16x16 / 32x32 read their half-resolution input inside the fused
  * convolution (nearest up-sampling in the patch fetch and in the residual fetch); 0: through the separate GroupNorm-apply + up-sample pass. */
@@ -188,8 +189,8 @@ int natinf_set_fuse_fin(int on);
  * weights are cold).  NATINF_EINVAL outside 0..15. */
 int natinf_set_conv_gn_warm(int mask);
 /* 1 (default): the 16x16 attention (256 tokens, one head of 256 channels) runs as k_attn256 -- K and V^T streamed through a two-stage LDS ring by
- * LDS-DMA, two blocks per CU; 0: k_attn_fused<8,16,true> (whole K, then whole V^T, resident in LDS; one block per CU) -- a -DNATINF_DEV kernel:
- * NATINF_ESTATE in the shipped library. */
+ * LDS-DMA, two blocks per CU; 0: k_attn_fused<8,16,true> (whole K, then whole V^T, resident in LDS; one block per CU) -- retired:
+ * NATINF_ESTATE. */
 int natinf_set_attn256(int on);
 /* 1 (default; read when a plan is built): k_attn256 also applies the attention block's output projection, skip connection and rescale and writes the
  * GroupNorm partials of the block's output (the O tensor is never stored); 0: a separate GEMM launch for the projection. */
@@ -207,8 +208,7 @@ int natinf_set_attn_waves8(int on);
 int natinf_set_attn_block(int on);
 int natinf_set_attn_qkv(int on);
 /* Tile of the fused kernel on the 8x8 level: 1 (default) = 64 pixels x 256 channels (one image per tile, wave tile 64 x 64, two blocks per CU at
- * B = 512), 0 = 128 x 256 (two images per tile, one block per CU; 0.6 % slower per forward: a -DNATINF_DEV kernel -- NATINF_ESTATE in the shipped
- * library). */
+ * B = 512), 0 = 128 x 256 (two images per tile, one block per CU; 0.6 % slower per forward: retired -- NATINF_ESTATE). */
 int natinf_set_conv_gn8_tile(int one_image);
 /* 1 (default): small-M, long-K launches (the 8x8 and 4x4 levels) run as 128 x 128 tiles x 2..4 K slices + a reduce pass; 0: never. */
 int natinf_set_gemm_splitk(int on);

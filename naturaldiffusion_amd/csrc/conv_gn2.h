@@ -1,5 +1,28 @@
-// conv_gn2.h -- k_conv_gn2: the fused GroupNorm-apply + SiLU + 3x3 convolution of conv_gn.h with the WEIGHTS STREAMED THROUGH
-// REGISTERS instead of an LDS ring.
+// conv_gn2.h -- k_conv_gn2: 3x3 convolution with GroupNorm-apply + SiLU fused into its operand path, the WEIGHTS STREAMED THROUGH REGISTERS.
+//
+// Reference arithmetic: ResnetBlockBigGANpp.forward, layerspp.py:242-274:  h = Conv(act(GroupNorm(x))).
+// Round 1 ran  act(GroupNorm(.))  as its own HBM pass (k_gn_apply: read the raw tensor, write a normalised, zero-bordered copy;
+// 20 % of the device time of a sampling step) and the convolution as a tap-by-tap implicit GEMM that re-fetches its A tile from
+// L2 for each of the nine taps.  Round 2's k_conv_gn (weights through an LDS ring; retired, in git history before the commit that
+// removed it) read the RAW tensor instead, and k_conv_gn2 keeps that design:
+//   * the K loop walks 32-channel HALF-CHUNKS.  Per half-chunk the block DMAs the PATCH of its pixels -- the pixels plus a one-pixel
+//     halo -- into LDS ONCE (64-byte rows), normalises it IN PLACE (x * scale[b,c] + shift[b,c], SiLU; halo pixels outside the image
+//     -> 0) and all nine taps read their A fragments from it: the A-side fill drops 9x and the separate pass disappears;
+//   * the 1x1 shortcut segment (a1: Conv_2 of the res-block, raw input, no normalisation) runs after the half-chunks as plain
+//     32-wide K-tiles through the same buffers.
+// K order: the packed weights keep round 1's order (64-channel chunk, tap, channel); K-tile (chunk c, half h, tap t) reads
+// columns (c*9 + t)*64 + h*32 -- only the accumulation order differs from the unfused kernels.
+// Folded form (GemmArgs::gn_folded, the only one the kernel implements): scale / shift carry -log2(e), so t = x*scale + shift = -log2(e) v,
+// exp2(t) = exp(-v) and t / (1 + exp2(t)) = -log2(e) silu(v); the 3x3 weights carry -ln 2.
+// LDS swizzle of k_conv_gn (64-byte rows, four 16-byte slots; the derivation the patch geometry below builds on): chunk k of row p sat at
+// slot k ^ ((p >> 1) & 2).  That is conflict-free for ds_read_b128 on ANY window of 16 consecutive rows (the taps shift the window): a lane
+// group holds the 16 rows once each, rows 0-3 / 12-15 with k-chunk q and rows 4-11 with q ^ 1; rows of equal p & 3 share a 64-byte quarter
+// of a bank line, there are four of them in a window -- p0, p0+4, p0+8, p0+12 with chunks q, q^1, q^1, q -- and bit 2 of p alternates
+// along them, so their slots q ^ 2b, q ^ 1 ^ 2(1-b), q ^ 1 ^ 2b, q ^ 2(1-b) are the four distinct ones.
+// Why the K loop is inline asm: (i) with a builtin LDS-DMA in flight hipcc puts `s_waitcnt vmcnt(0)` in front of any LDS access IT can see
+// (a pending LDS write to it), which drains the weight stream at every tap; (ii) the builtin takes a 64-bit per-lane address: a dozen VALU
+// ops per 1-KiB piece, or -- hoisted -- two registers per piece.  A piece is `global_load_lds_dwordx4 voffset, sbase` here: a 32-bit per-lane
+// byte offset and a scalar base that carries everything that changes from tap to tap.
 //
 // What bounded k_conv_gn (tools/conv_gn_timeline.py, profiles/r02): its only per-tap stream was the 128 x 64 B weight tile, but that
 // stream put an `s_waitcnt + s_barrier` in front of every 32-wide K step (nine per half-chunk) and two LDS-DMA instructions per wave
@@ -14,7 +37,7 @@
 //     and everyone is done reading the buffer of h-1".
 // Both tile shapes use the same wave tile (128 pixels x 64 channels: eight A row-tiles stream past four resident weight fragments):
 // 256 x 128 = 2 x 2 waves, 128 x 256 (N = 256 layers at 16x16) = 1 x 4 waves, all four reading the same A fragments.
-// Arithmetic (folded SiLU form, K order, swizzle, epilogues): as conv_gn.h.
+// Arithmetic (folded SiLU form, K order, epilogues): as above.
 // Measured on top of this form and not kept (same-box A/B, tools/bench_conv_gn.py; DESIGN.md section 4 has the numbers):
 //   * the taps as ONE software pipeline (A fragments of tap t+1 requested in the last two steps of tap t, the four weight loads and the
 //     request items of tap 0 spread one per MFMA group): 128x256 tile 4-5 % SLOWER, 256x128 tile equal;
@@ -38,7 +61,28 @@
 // PMC picture of the 256x128 tile (tools/pmc_conv_gn.sh): matrix pipe 48-55 % busy, LDS 25 %, L1/TA ~45 %, waves 24 % in s_waitcnt and
 // 38 % ready-but-not-issued: no unit is saturated; two waves per SIMD do not cover each other's dependency stalls.
 #pragma once
-#include "conv_gn.h"
+#include "gemm_dma.h"
+#ifndef NATINF_CG_ABL
+#define NATINF_CG_ABL 0            // development: 1 = no normalisation inside the K loop (timing ablation, wrong results)
+#endif
+// The tile-timeline stamps of k_conv_gn2 (tools/conv_gn_timeline.py) have their own switch since round 4: `make EXTRA="-DNATINF_DEV -DNATINF_CG_TIMELINE"`.
+// With them in every -DNATINF_DEV build the 256-register instantiations spilled 2-4 vector registers (130 scalar spills parked in vector lanes on top of the
+// round-3 kernel) -- among them destinations of asm loads in flight: the development library faulted in its first fused convolution.
+#if defined(NATINF_DEV) && defined(NATINF_CG_TIMELINE)
+// timeline builds: shader-clock stamps at the section boundaries of a K-tile (block 0 / wave 0), summed over the tile's K loop
+__device__ __forceinline__ unsigned long long cg_stamp() {
+    unsigned long long t;
+    __builtin_amdgcn_sched_barrier(0);
+    asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(t) :: "memory");
+    __builtin_amdgcn_sched_barrier(0);
+    return t;
+}
+#define NATINF_CG_STAMP(v) const unsigned long long v = cg_stamp();
+#define NATINF_CG_ADD(acc, a, b) acc += (b) - (a);
+#else
+#define NATINF_CG_STAMP(v)
+#define NATINF_CG_ADD(acc, a, b)
+#endif
 #ifndef NATINF_CG_PK
 #define NATINF_CG_PK 1            // 1 = packed-fp32 arithmetic (v_pk_fma / v_pk_add / v_pk_mul) in the PROLOGUE's normalisation rounds, 0 = scalar (A/B builds)
 #endif
@@ -163,8 +207,8 @@ __global__ __launch_bounds__(256 * NGV, NGV > 1 ? 1 : 2) void k_conv_gn2(const G
     const int nk = 9 * n_half, NT = nk + n_sc;
     const int nh_g = n_half / NG, nsc_g = n_sc / NG;
 
-    // Every LDS access, every LDS-DMA and every weight load of the K loop is inline asm with hand-counted waits (conv_gn.h explains
-    // why: hipcc drains vmcnt in front of any LDS access it can see while an LDS-DMA is in flight).
+    // Every LDS access, every LDS-DMA and every weight load of the K loop is inline asm with hand-counted waits (the head of this file
+    // explains why: hipcc drains vmcnt in front of any LDS access it can see while an LDS-DMA is in flight).
     typedef __attribute__((address_space(3))) unsigned char lds_u8;
     auto glds16 = [](unsigned voff, const void* sbase, unsigned lds_dst) __attribute__((always_inline)) {
         NATINF_M0_ASM_BEGIN
@@ -595,8 +639,10 @@ __global__ __launch_bounds__(256 * NGV, NGV > 1 ? 1 : 2) void k_conv_gn2(const G
                 for (int j = 0; j < TN; ++j) acc[i][j] += red[(gg * TM * TN + i * TN + j) * 256];
         __syncthreads();
     }
-    // the epilogue's arguments are fetched from the kernel-argument segment HERE (conv_gn.h: kept in scalar registers across the K
-    // loop they end up spilled into vector-register lanes)
+    // The epilogue's arguments (bias, row vector, residual, partial-sum table, ...) are fetched from the kernel-argument segment HERE, through a
+    // pointer hipcc cannot see through: kept in scalar registers across the K loop they cost ~40 SGPRs, the allocator spilled them into
+    // vector-register lanes, and the vector registers it took for that tipped the loop into scratch spills -- whose loads and stores would
+    // corrupt the hand-counted vmcnt waits above.
 #if defined(__HIP_DEVICE_COMPILE__)
     typedef const unsigned __attribute__((address_space(4))) *kernarg_u32_t;
     kernarg_u32_t gp = (kernarg_u32_t)__builtin_amdgcn_kernarg_segment_ptr();

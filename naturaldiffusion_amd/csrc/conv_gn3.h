@@ -439,7 +439,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
     NATINF_CG3_PIN8(c.fb[0]) NATINF_CG3_PIN8(c.fb[1]) NATINF_CG3_PIN8(c.fa[0]) NATINF_CG3_PIN8(c.fa[1])
 #undef NATINF_CG3_PIN8
     NATINF_CG3_STAMP(41);
-    // the epilogue's arguments are fetched from the kernel-argument segment HERE (conv_gn.h: kept in scalar registers across the K loop they end up spilled
+    // the epilogue's arguments are fetched from the kernel-argument segment HERE (conv_gn2.h: kept in scalar registers across the K loop they end up spilled
     // into vector-register lanes) -- and IN FRONT of the drain below, pinned by an empty statement that reads them: hipcc otherwise issues the scalar loads
     // behind its ~190 accumulator reads and waits a full round trip for them with nothing else to do (one block per CU)
 #if defined(__HIP_DEVICE_COMPILE__)

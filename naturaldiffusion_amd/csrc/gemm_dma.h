@@ -70,8 +70,8 @@ struct DmaCfg {
 // every run-time branch that touches it.  Not kept.)
 // Epilogue shared by the DMA kernels: in TM/RB passes, RB row-tiles of every wave -> LDS (fp32) -> fused adds
 // (bias, per-sample row vector, residual, scale, SiLU) in fp32 -> 16-byte coalesced stores.
-// Development hooks (tile timelines, epilogue ablations, K-loop ablation kernels) exist only in `make EXTRA=-DNATINF_DEV` builds:
-// the shipped library carries neither the stamps nor the kernels that give wrong results by design.
+// Development hooks (tile-timeline stamps, the epilogue timing modes c_mode 102 / 103) exist only in `make EXTRA=-DNATINF_DEV` builds:
+// the shipped library carries neither.
 #ifdef NATINF_DEV
 #define NATINF_TS(i) do { if (g.dbg_ts && tid == 0 && blockIdx.x == 0) g.dbg_ts[i] = __builtin_amdgcn_s_memtime(); } while (0)
 #else
@@ -799,7 +799,7 @@ constexpr int pipe_lgkm_after(int TM, int st) {
     if (st >= TM && pos_fb1_last > need) need = pos_fb1_last;
     return n - 1 - need;
 }
-template <int TM, int ST, bool NOMFMA = false>       // NOMFMA: ablation (k_gemm_dma<..., 4>): the fragment reads and waits without the MFMAs
+template <int TM, int ST>
 struct PipeStep {
     static __device__ __forceinline__ void run(u32x4 (&fa)[3], u32x4 (&fb)[2][4], f32x4 (&acc)[TM][4],
                                                unsigned a0, unsigned a1, unsigned b1) {
@@ -810,24 +810,21 @@ struct PipeStep {
         }
         if constexpr (ks == 0 && i >= TM - 4) fb[1][i - (TM - 4)] = lds_read16<(i - (TM - 4)) * 2048>(b1);
         wait_lgkmcnt<pipe_lgkm_after(TM, ST)>();
-        if constexpr (!NOMFMA) {
 #pragma unroll
-            for (int j = 0; j < 4; ++j)
-                acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8, fb[ks][j]),
-                                                                    __builtin_bit_cast(bf16x8, fa[ST % 3]), acc[i][j], 0, 0, 0);
-        } else {
-            asm volatile("" :: "v"(fa[ST % 3]), "v"(fb[ks][0]), "v"(fb[ks][1]), "v"(fb[ks][2]), "v"(fb[ks][3]));     // keep the reads alive
-        }
-        if constexpr (ST + 1 < S) PipeStep<TM, ST + 1, NOMFMA>::run(fa, fb, acc, a0, a1, b1);
+        for (int j = 0; j < 4; ++j)
+            acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8, fb[ks][j]),
+                                                                __builtin_bit_cast(bf16x8, fa[ST % 3]), acc[i][j], 0, 0, 0);
+        if constexpr (ST + 1 < S) PipeStep<TM, ST + 1>::run(fa, fb, acc, a0, a1, b1);
     }
 };
 
-// SPREAD = 1: the DMA requests of tile k+1 are not issued in one burst after the barrier (every wave of the block
-// would then be issuing ~100-cycle LDS-DMA instructions at the same moment, with the matrix pipe idle) but one at
-// a time between the MFMA groups of tile k.
+// SPREAD = 2: the hand-counted LDS fragment pipeline (PipeStep), every wave issuing its own LDS-DMA pieces of tile k+1 in one burst after
+// the barrier; SPREAD = 6: the same loop with the burst issued by one wave per SIMD.  (The plain two-stage loop, SPREAD 0, the spread issue, 1,
+// and the two K-loop ablations, 3 / 4, are retired: git history before the commit that removed them.)
 template <int WM, int WN, int TM, int TN, int SPREAD = 0, int EPI = 0>
 __global__ __launch_bounds__(WM * WN * 64, 2) void k_gemm_dma(const GemmArgs g)
 {
+    static_assert(SPREAD == 2 || SPREAD == 6, "the shipped K loops: hand pipeline (2), one issuing wave per SIMD (6)");
     using Cfg = DmaCfg<WM, WN, TM, TN>;
     constexpr int BM_ = Cfg::BM_, BN_ = Cfg::BN_, THREADS = Cfg::THREADS;
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
@@ -897,7 +894,7 @@ __global__ __launch_bounds__(WM * WN * 64, 2) void k_gemm_dma(const GemmArgs g)
     NATINF_TS(1);
 
     const int frow = lane & 15, fq = lane >> 4, fswz = (frow >> 1) & 7;
-    constexpr int NP = PAI + PBI, SLOTS = 2 * TM, STEP = SLOTS / NP > 0 ? SLOTS / NP : 1;
+    constexpr int NP = PAI + PBI;
     for (int kt = 0; kt < nk; ++kt) {
         const int cur = kt & 1;
         const bool more = kt + 1 < nk;
@@ -924,33 +921,14 @@ __global__ __launch_bounds__(WM * WN * 64, 2) void k_gemm_dma(const GemmArgs g)
                 __builtin_amdgcn_global_load_lds(reinterpret_cast<const void*>(pb), (lds_void*)(dBn + (p - PAI) * 1024), 16, 0, 0);
             }
         };
-        if (SPREAD != 1 && SPREAD != 3 && more && issuer) {          // SPREAD 3 / 4: ablations of the hand-pipelined loop (no DMA after tile 0 / no MFMAs)
+        if (more && issuer) {
 #pragma unroll
             for (int p = 0; p < NP; ++p) issue_piece(p);
         }
         const bf16* ta = reinterpret_cast<const bf16*>(smem + cur * Cfg::STAGE_BYTES) + (wm * TM * 16 + frow) * LDS_ROW;
         const bf16* tb = reinterpret_cast<const bf16*>(smem + cur * Cfg::STAGE_BYTES + BM_ * BK * 2) + (wn * TN * 16 + frow) * LDS_ROW;
-        if constexpr (SPREAD < 2) {
-#pragma unroll
-            for (int ks = 0; ks < 2; ++ks) {
-                const int ko = (((ks << 2) | fq) ^ fswz) << 3;
-                bf16x8 fb[TN];
-#pragma unroll
-                for (int j = 0; j < TN; ++j) fb[j] = *reinterpret_cast<const bf16x8*>(tb + j * 16 * LDS_ROW + ko);
-#pragma unroll
-                for (int i = 0; i < TM; ++i) {
-                    const bf16x8 fa = *reinterpret_cast<const bf16x8*>(ta + i * 16 * LDS_ROW + ko);
-#pragma unroll
-                    for (int j = 0; j < TN; ++j)
-                        acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(fb[j], fa, acc[i][j], 0, 0, 0);
-                    if (SPREAD == 1) {
-                        const int slot = ks * TM + i;
-                        if (more && slot % STEP == 0 && slot / STEP < NP) issue_piece(slot / STEP);
-                    }
-                }
-            }
-        } else {
-            static_assert(SPREAD < 2 || TN == 4, "the hand-counted pipeline is written for TN = 4");
+        {
+            static_assert(TN == 4, "the hand-counted pipeline is written for TN = 4");
             typedef __attribute__((address_space(3))) unsigned char lds_u8;
             const unsigned a_lds = (unsigned)(uintptr_t)((lds_u8*)(unsigned char*)const_cast<bf16*>(ta));
             const unsigned b_lds = (unsigned)(uintptr_t)((lds_u8*)(unsigned char*)const_cast<bf16*>(tb));
@@ -959,7 +937,7 @@ __global__ __launch_bounds__(WM * WN * 64, 2) void k_gemm_dma(const GemmArgs g)
             fb[0][0] = lds_read16<0>(b_lds + ko0); fb[0][1] = lds_read16<2048>(b_lds + ko0);
             fb[0][2] = lds_read16<4096>(b_lds + ko0); fb[0][3] = lds_read16<6144>(b_lds + ko0);
             fa[0] = lds_read16<0>(a_lds + ko0); fa[1] = lds_read16<2048>(a_lds + ko0);
-            PipeStep<TM, 0, SPREAD == 4>::run(fa, fb, acc, a_lds + ko0, a_lds + ko1, b_lds + ko1);
+            PipeStep<TM, 0>::run(fa, fb, acc, a_lds + ko0, a_lds + ko1, b_lds + ko1);
         }
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // next tile's LDS-DMA has landed (explicit: not left to the compiler's tracking)
         __syncthreads();

@@ -65,7 +65,7 @@ __device__ __forceinline__ w128_rsrc w128_make_rsrc(const void* base, unsigned b
     return w128_rsrc{(int)__builtin_amdgcn_readfirstlane((unsigned)a), (int)__builtin_amdgcn_readfirstlane((unsigned)(a >> 32) & 0xffffu),
                      (int)__builtin_amdgcn_readfirstlane(bytes), 0x00020000};
 }
-// L2 prefetch (W128SchP, development builds; measured slower): one dword per 128-byte line of K-tile kt + 2 + PF, ahead of the LDS-DMA requests -- an HBM round trip
+// L2 prefetch (a schedule with PF > 0; measured slower, the shipped schedule has PF = 0): one dword per 128-byte line of K-tile kt + 2 + PF, ahead of the LDS-DMA requests -- an HBM round trip
 // under load is longer than the ~1.3 iterations a request has (tile timeline, tools/w128_timeline.py, at (32768, 1536, 6144), where a row panel of A is read by six
 // tiles only: 3,282 clocks per K-tile against 2,222 at 8192^3).  The descriptor's num_records is the operand's real extent: a lane past the last row or K-tile reads nothing.
 template <int OFF> __device__ __forceinline__ void w128_prefetch(unsigned& junk, unsigned vo, const w128_rsrc& rs) {
@@ -97,32 +97,24 @@ __device__ __forceinline__ void w128_bufdma_at(unsigned vo, const w128_rsrc& rs,
 // A schedule SCH names the slots: K step 1's fragment reads (rd1: 0..7 = A, 8..15 = B), the two "half is free" barriers, the sixteen requests (piece p: 0..7 = A,
 // 8..15 = B; destinations 4 KB apart in that order; a schedule may give wave WV of the block its own slots -- unused: see below), the counted wait for tile kt + 1, K step 0's reads of tile kt + 1.
 struct W128SchB {          // shipped: both halves released by ONE barrier behind the sixteen reads of K step 1 (all in the first seventeen slots); the requests four
-    static constexpr bool NO_DMA = false;                        // MFMAs apart in gaps that carry no fragment read; tile kt + 1 awaited at slot 60
+                           // MFMAs apart in gaps that carry no fragment read; tile kt + 1 awaited at slot 60
     static constexpr int WAIT1 = 24, WAIT2 = 24, WAIT3 = 60;
     static constexpr int rd1(int n) { return n < 8 ? 1 + 2 * n : 2 + 2 * (n - 8); }
     static constexpr int dma(int p, int) { return 27 + 4 * p; }
     static constexpr int rd0(int n) { return 90 + 2 * n; }                                      // 0..7 = B, 8..15 = A
-    static constexpr int PF = 0, PF_A = 89, PF_B = 123;                                         // L2 prefetch of K-tile kt + 2 + PF (0 = none; W128SchP): behind the last request / read
+    static constexpr int PF = 0, PF_A = 89, PF_B = 123;                                         // L2 prefetch of K-tile kt + 2 + PF (0 = none): behind the last request / read
 };
-#ifdef NATINF_DEV
-// Measured beside it (tools/ab_w128_sched.py, one box, TFLOP/s at 8192^3 / (32768, 6144, 1536) / (32768, 1536, 1536) / (32768, 1536, 6144); SchB: 1,526-1,620 / 1,325-1,342 /
-// 1,331-1,338 / 1,332-1,381; the two-waves-per-SIMD 256 x 256 tile: 1,243-1,396 / 1,084-1,225 / 1,254-1,262 / 1,109-1,228):
-struct W128SchA {          // the first form: A half and B half released by two barriers, requests two MFMAs apart between the B fragment reads: 1,366-1,581 / 1,272-1,301 / 1,281-1,298 / 1,312-1,358
-    static constexpr bool NO_DMA = false;
-    static constexpr int WAIT1 = 21, WAIT2 = 50, WAIT3 = 88;
-    static constexpr int rd1(int n) { return n < 8 ? 1 + 2 * n : 24 + 2 * (n - 8); }
-    static constexpr int dma(int p, int) { return p < 8 ? 23 + 2 * p : (p < 13 ? 52 + 2 * (p - 8) : 91 + 4 * (p - 13)); }
-    static constexpr int rd0(int n) { return n < 8 ? 90 + 2 * n : 106 + 2 * (n - 8); }
-    static constexpr int PF = 0, PF_A = 0, PF_B = 0;
-};
-// (the reads of tile kt + 1 spread over the second half of the iteration, between the requests -- rd0(n) = 65 + 4 n --: 1,511-1,540 / 1,237 / 1,280-1,290 / 1,308-1,327.  Not kept.)
-struct W128SchP : W128SchB { static constexpr int PF = 3; };              // + L2 prefetch three K-tiles ahead of the requests (w128_prefetch): 8192^3 1,354 against 1,570, (32768, 6144, 1536) 1,125 against
-                                                                           // 1,260 -- a dword load of 64 different lines costs the L1 path eight requests' worth.  Not kept.
-struct W128SchX : W128SchB { static constexpr bool NO_DMA = true; };      // ablation: nothing requested after the prologue (wrong results): 1,806-1,842 / 1,467-1,483 / 1,308-1,408 /
-                                                                           // 1,765-1,784 -- what the sixteen requests of an iteration cost (~19 clocks of matrix pipe each)
+// Measured beside it and retired (git history before the commit that removed them; TFLOP/s at 8192^3 / (32768, 6144, 1536) / (32768, 1536, 1536) / (32768, 1536, 6144);
+// SchB: 1,526-1,620 / 1,325-1,342 / 1,331-1,338 / 1,332-1,381; the two-waves-per-SIMD 256 x 256 tile: 1,243-1,396 / 1,084-1,225 / 1,254-1,262 / 1,109-1,228):
+//  * schedule A, the first form -- A half and B half released by two barriers, requests two MFMAs apart between the B fragment reads: 1,366-1,581 / 1,272-1,301 /
+//    1,281-1,298 / 1,312-1,358;
+//  * the reads of tile kt + 1 spread over the second half of the iteration, between the requests: 1,511-1,540 / 1,237 / 1,280-1,290 / 1,308-1,327;
+//  * schedule P, + L2 prefetch three K-tiles ahead of the requests (PF = 3): 8192^3 1,354 against 1,570, (32768, 6144, 1536) 1,125 against 1,260 -- a dword load
+//    of 64 different lines costs the L1 path eight requests' worth;
+//  * schedule X, the ablation with nothing requested after the prologue (wrong results): 1,806-1,842 / 1,467-1,483 / 1,308-1,408 / 1,765-1,784 -- what the
+//    sixteen requests of an iteration cost (~19 clocks of matrix pipe each).
 // (the four waves' requests one MFMA apart from each other -- four copies of the loop behind a branch on the wave index -- made hipcc spill: 1,630 scratch
 // accesses, fragment registers spilled with their loads in flight: wrong results at 85 TFLOP/s.  Not kept.)
-#endif
 template <class SCH, int WV> constexpr int w128_early() { int c = SCH::PF ? 2 : 0; for (int p = 0; p < 16; ++p) c += SCH::dma(p, WV) < SCH::WAIT3; return c; }      // + the two prefetch loads of the iteration before
 
 template <class SCH, int MODE, int S, int WV>
@@ -159,14 +151,14 @@ struct W128Step {
         if constexpr (S == SCH::WAIT1 || S == SCH::WAIT2 || (S == 127 && MODE < 2)) asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
         if constexpr ((S == SCH::WAIT1 + 1 || S == SCH::WAIT2 + 1) && MODE == 0) asm volatile("s_barrier" ::: "memory");          // the A / B half of stage cur is free
         if constexpr (MODE < 2) {
-            if constexpr (S == SCH::WAIT3 && !(SCH::NO_DMA && MODE == 0)) {          // tile kt + 1 has landed: MODE 0 retires exactly the previous iteration's sixteen requests
+            if constexpr (S == SCH::WAIT3) {          // tile kt + 1 has landed: MODE 0 retires exactly the previous iteration's sixteen requests
                 if constexpr (MODE == 0) asm volatile("s_waitcnt vmcnt(%0)" :: "n"(w128_early<SCH, WV>()) : "memory");
                 else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
             }
             if constexpr (S == SCH::WAIT3 + 1) asm volatile("s_barrier" ::: "memory");
         }
         reads<0>(fa, fb, ad);
-        if constexpr (MODE == 0 && !SCH::NO_DMA) dma<0>(ad, dm);
+        if constexpr (MODE == 0) dma<0>(ad, dm);
         if constexpr (MODE == 0 && SCH::PF > 0) {
             static_assert(SCH::PF == 0 || (SCH::PF_A > SCH::dma(15, WV) && SCH::PF_B > SCH::PF_A && SCH::PF_A > SCH::WAIT3), "behind this iteration's requests: the next counted wait leaves them in flight");
             if constexpr (S == SCH::PF_A) w128_prefetch<SCH::PF * 128>(dm.junk, dm.pfa, dm.ra);

@@ -48,7 +48,7 @@ int g_mmdit_stream16 = MMDIT_STREAM16_DEFAULT;      // natinf_set_mmdit_stream16
 int g_mmdit_text_flat = 1;         // natinf_set_mmdit_text_flat: the text stream's fc1 as ONE GEMM over all sequences' rows (1) or batched per sequence (0: A/B runs)
 int g_mmdit_text_stream = 1;       // natinf_set_mmdit_text_stream: 1 = the text stream's launches of a block (M = 333 rows per sequence: 150 GFLOP per block at under a sixth of the chip's
                                    // rate when they run alone) go to a second HIP stream and join the image stream at the joint attention; 0 = one stream, one launch after the other
-int g_flash_mode = 3;              // natinf_set_flash_mode: 0 = k_flash_attn64, 1 = k_flash_attn64_v2<0> (deferred re-referencing, scores leave the MFMA as exponents), 2 = v2<1> (+ row sums on the matrix pipe), 3 = v2<1, 64> (64-key tiles: 128 registers and 32 KiB of LDS per block, three to four waves per SIMD); default 3
+int g_flash_mode = 3;              // natinf_set_flash_mode: 0 = k_flash_attn64, 3 = k_flash_attn64_v2<1, 64> (deferred re-referencing, scores leave the MFMA as exponents, row sums on the matrix pipe, 64-key tiles: 128 registers and 32 KiB of LDS per block, three to four waves per SIMD); default 3; 1 / 2: retired
 void launch_flash(const bf16* q, const bf16* k, int ld_qk, int64_t qk_bs, const bf16* vT, bf16* o, int ld_o, int64_t o_bs, int B, int H,
                   int Tp, int T, float scale, hipStream_t s, uint8_t* o8 = nullptr, uint8_t* omx = nullptr) {
     FlashArgs a{q, k, ld_qk, qk_bs, vT, (int64_t)H * 64 * Tp, o, ld_o, o_bs, H, Tp, T, scale * 1.4426950408889634f, o8, omx};
@@ -60,10 +60,6 @@ void launch_flash(const bf16* q, const bf16* k, int ld_qk, int64_t qk_bs, const 
     }
     const dim3 grid((unsigned)(B * H * (Tp / FA_QB)));
     if (g_flash_mode == 3) hipLaunchKernelGGL((k_flash_attn64_v2<1, 64>), grid, dim3(256), FA_LDS_BYTES / 2, s, a);
-#ifdef NATINF_DEV
-    else if (g_flash_mode == 2) hipLaunchKernelGGL(k_flash_attn64_v2<1>, grid, dim3(256), FA_LDS_BYTES, s, a);
-    else if (g_flash_mode == 1) hipLaunchKernelGGL(k_flash_attn64_v2<0>, grid, dim3(256), FA_LDS_BYTES, s, a);
-#endif
     else hipLaunchKernelGGL(k_flash_attn64, grid, dim3(256), FA_LDS_BYTES, s, a);
     if (e.first) { (void)hipEventRecord(e.second, s); g_flash_prof.ev.push_back(e); }
 }
@@ -398,9 +394,7 @@ int natinf_attention_hd64_bf16(const void* q, const void* k, int ld_qk, int64_t 
 
 int natinf_set_flash_mode(int mode) {
     if (mode < 0 || mode > 3) return NATINF_EINVAL;
-#ifndef NATINF_DEV
-    if (mode == 1 || mode == 2) return NATINF_ESTATE;       // the intermediate forms (vector-pipe row sums; 128-key tiles) exist in -DNATINF_DEV builds only
-#endif
+    if (mode == 1 || mode == 2) return NATINF_ESTATE;       // the intermediate forms (vector-pipe row sums; 128-key tiles): retired
     g_flash_mode = mode;
     return NATINF_OK;
 }

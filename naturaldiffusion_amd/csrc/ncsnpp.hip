@@ -31,13 +31,8 @@
 #include "gemm_dma.h"
 #include "gemm_w128.h"
 #include "conv_ring.h"
-#include "conv_gn.h"
 #include "conv_gn2.h"
 #include "head_conv.h"
-#ifdef NATINF_DEV                  // superseded kernels kept for A/B runs: development builds only (make EXTRA=-DNATINF_DEV)
-#include "conv_patch.h"
-#include "gemm_8phase.h"
-#endif
 #include "gemm_fp8.h"
 #include "attn_fused.h"
 #include "attn256.h"
@@ -165,44 +160,43 @@ GemmArgs gemm_defaults() {
 constexpr int NUM_CU = 256;
 enum GemmVariant {
     V_AUTO = 0, V_GENERIC = 1,
-    V_DMA_256x256 = 2, V_DMA_256x128 = 3, V_DMA_128x128 = 4,          // 2-stage, BK = 64
-    V_RING_256x256 = 5, V_RING_256x128 = 6, V_RING_128x128 = 7, V_RING_64x128 = 8,   // NS-slot ring, BK = 32
-    V_RING_256x128_W4 = 9, V_DMA_256x128_W4 = 10,                     // 4 waves, wave tile 128x64 (less LDS read traffic per MFMA)
-    V_DMA_256x256_S = 11, V_DMA_128x128_S = 12,                       // two-stage with the DMA issue spread between MFMA groups
-    V_DMA_512x128 = 13,                                                // 8 waves x (128x64), all 160 KiB of LDS
-    V_PATCH_256x256 = 14, V_PATCH_256x128 = 15,                        // 3x3 conv with an LDS-resident input patch
-    V_DMA_256x256_P = 16, V_DMA_128x128_P = 17, V_DMA_256x128W4_P = 18,  // two-stage + hand-counted LDS fragment pipeline
-    V_8PH_256x256 = 19, V_8PH_NOPRIO = 20, V_8PH_READFIRST = 21, V_8PH_BOTH = 22,   // phase-interleaved schedule, counted vmcnt (gemm_8phase.h)
+    V_DMA_256x256 = 2, V_DMA_256x128 = 3, V_DMA_128x128 = 4,          // (retired: 2-stage, BK = 64)
+    V_RING_256x256 = 5, V_RING_256x128 = 6, V_RING_128x128 = 7,       // (retired: NS-slot ring, BK = 32)
+    V_RING_64x128 = 8,                                                 // NS-slot ring, BK = 32
+    V_RING_256x128_W4 = 9,                                             // 4 waves, wave tile 128x64 (less LDS read traffic per MFMA)
+    V_DMA_256x128_W4 = 10,                                             // (retired: the same tile, two-stage)
+    V_DMA_256x256_S = 11, V_DMA_128x128_S = 12,                       // (retired: two-stage with the DMA issue spread between MFMA groups)
+    V_DMA_512x128 = 13,                                                // (retired: 8 waves x (128x64), every wave issuing its own DMA)
+    V_PATCH_256x256 = 14, V_PATCH_256x128 = 15,                        // (retired: 3x3 conv with an LDS-resident input patch)
+    V_DMA_256x256_P = 16, V_DMA_256x128W4_P = 18,                      // (retired: two-stage + hand-counted LDS fragment pipeline)
+    V_DMA_128x128_P = 17,                                              // two-stage + hand-counted LDS fragment pipeline
+    V_8PH_256x256 = 19, V_8PH_NOPRIO = 20, V_8PH_READFIRST = 21, V_8PH_BOTH = 22,   // (retired: phase-interleaved schedule, counted vmcnt)
     V_FP8_256x256 = 23,                                                 // fp8 e4m3 operands (gemm_fp8.h); selected by GemmArgs::deq_m/deq_n callers only
-    V_ABL_NODMA = 24, V_ABL_NOMFMA = 25,
+    V_ABL_NODMA = 24, V_ABL_NOMFMA = 25,                                // (retired: K-loop ablations)
     V_DMA_256x256_H = 26, V_DMA_512x128_H = 27,                         // hand pipeline, DMA issued by one wave per SIMD only
-    V_CONV_GN = 28,                                                     // 3x3 conv with fused GroupNorm-apply + SiLU of its input (conv_gn.h); GemmArgs::gn_scale callers only
+    V_CONV_GN = 28,                                                     // 3x3 conv with fused GroupNorm-apply + SiLU of its input (conv_gn2.h); GemmArgs::gn_scale callers only
     V_W128 = 29,                                                        // 256x256x64, four waves with 128x128 wave tiles (one per SIMD, AGPR accumulators; gemm_w128.h)
-    V_W128_A = 30, V_W128_D = 31, V_W128_X = 32,                               // -DNATINF_DEV: other K-loop schedules of k_gemm_w128 (EPI 1 launches only)
+    V_W128_A = 30, V_W128_D = 31, V_W128_X = 32,                        // (retired: other K-loop schedules of k_gemm_w128)
     V_COUNT
 };
+// Retired ids (superseded pipelines, tile shapes and ablations; their kernels are in git history before the commit that removed them): the numbering
+// stays, natinf_set_gemm_variant / natinf_debug_gemm refuse them with NATINF_ESTATE.
 const char* variant_name(int v) {
     static const char* n[] = {"auto", "generic128", "dma256x256", "dma256x128", "dma128x128", "ring256x256", "ring256x128",
                               "ring128x128", "ring64x128", "ring256x128w4", "dma256x128w4", "dma256x256s", "dma128x128s", "dma512x128", "patch256x256", "patch256x128", "dma256x256p", "dma128x128p", "dma256x128w4p", "gemm8ph", "gemm8ph_np", "gemm8ph_rf", "gemm8ph_nprf", "fp8_256x256", "abl_nodma", "abl_nomfma", "dma256x256h", "dma512x128h", "conv_gn", "w128_256x256", "w128_a", "w128_d", "w128_x"};
     return v >= 0 && v < V_COUNT ? n[v] : "?";
 }
-// The shipped library instantiates only the tile variants the dispatcher selects (choose_variant, splitk) plus the generic kernel; every other
-// variant of the enum -- superseded pipelines kept for A/B runs -- exists in -DNATINF_DEV builds only, and natinf_set_gemm_variant /
-// natinf_debug_gemm refuse it (NATINF_ESTATE) elsewhere.
+// The library instantiates only the tile variants the dispatcher selects (choose_variant, splitk) plus the generic kernel; every other
+// variant of the enum is retired
 inline bool variant_shipped(int v) {
-#ifdef NATINF_DEV
-    return v >= 0 && v < V_COUNT;
-#else
     switch (v) {
         case V_AUTO: case V_GENERIC: case V_RING_64x128: case V_RING_256x128_W4: case V_DMA_128x128_P: case V_FP8_256x256:
         case V_DMA_256x256_H: case V_DMA_512x128_H: case V_CONV_GN: case V_W128: return true;
         default: return false;
     }
-#endif
 }
 unsigned long long* g_dbg_ts = nullptr;
 int g_force_variant = V_AUTO;
-int g_half_issue = 1;              // natinf_set_gemm_half_issue(0): every wave issues its own LDS-DMA pieces (A/B runs)
 int g_round_model = 1;             // natinf_set_gemm_round_model(0): small-M plain GEMMs by the pre-round-4 rules (A/B runs)
 int g_round_model_w128 = 13;       // cost of a round of k_gemm_w128 tiles in tenths of a round of 128 x 128 tiles (two blocks per CU)
 int g_pref_512 = 1;                // N <= 128 layers with >= 2 tiles per CU: the 512x128 hand-pipelined tile (natinf_set_gemm_pref512: A/B runs)      // tuning / tests: force one variant for every DMA-eligible launch
@@ -214,40 +208,25 @@ inline void launch_tiles(K kernel, const GemmArgs& g0, hipStream_t s) {
     const int nM = (g0.M + Cfg::BM_ - 1) / Cfg::BM_, nN = (g0.N + Cfg::BN_ - 1) / Cfg::BN_;
     GemmArgs g = g0;
     g.raster_g = (g_raster_g > 1 && nN >= 8 && nM >= g_raster_g) ? g_raster_g : 0;
-    int lds = Cfg::LDS_BYTES;
-#ifdef NATINF_DEV
-    static const int one_per_cu = getenv("NATINF_ONE_BLOCK_PER_CU") ? 1 : 0;      // occupancy experiment: ask for > 80 KB of LDS
-    if (one_per_cu && lds < 84000) {
-        lds = 84000;
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, lds);
-    }
-#endif
-    hipLaunchKernelGGL(kernel, dim3(nM * nN, 1, g.batch), dim3(Cfg::THREADS), lds, s, g);
+    hipLaunchKernelGGL(kernel, dim3(nM * nN, 1, g.batch), dim3(Cfg::THREADS), Cfg::LDS_BYTES, s, g);
 }
 template <class Cfg, class K>
 inline bool set_lds(K kernel) {
     return hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, Cfg::LDS_BYTES) == hipSuccess;
 }
-using CfgD256x256 = DmaCfg<2, 4, 8, 4>;  using CfgD256x128 = DmaCfg<4, 2, 4, 4>;  using CfgD128x128 = DmaCfg<2, 2, 4, 4>;
-using CfgR256x256 = RingCfg<2, 4, 8, 4, 4>; using CfgR256x128 = RingCfg<4, 2, 4, 4, 6>;
+using CfgD256x256 = DmaCfg<2, 4, 8, 4>;  using CfgD128x128 = DmaCfg<2, 2, 4, 4>;
 using CfgR128x128 = RingCfg<2, 2, 4, 4, 4>; using CfgR64x128 = RingCfg<2, 2, 2, 4, 4>;
-using CfgR256x128W4 = RingCfg<2, 2, 8, 4, 3>; using CfgD256x128W4 = DmaCfg<2, 2, 8, 4>;
+using CfgR256x128W4 = RingCfg<2, 2, 8, 4, 3>;
 using CfgD512x128 = DmaCfg<4, 2, 8, 4>;
 using CfgH32 = ConvGn2Cfg<32>; using CfgH16 = ConvGn2Cfg<16>; using CfgH16W = ConvGn2Cfg<16, true>; using CfgH32W = ConvGn2Cfg<32, true>; using CfgH8T = ConvGn2Cfg<8, true, 4>; using CfgH4T = ConvGn2Cfg<4, true, 4, 2, 2>;
-#ifdef NATINF_DEV
-using CfgH8W = ConvGn2Cfg<8, true>;          // 8x8: two images per 128-pixel tile (superseded by the one-image tile: 0.6 % slower per forward)
-using CfgP256x256 = PatchCfg<2, 4, 8, 4, 344>; using CfgP256x128 = PatchCfg<4, 2, 4, 4, 400>;
-using CfgG32 = ConvGnCfg<32>; using CfgG16 = ConvGnCfg<16>; using CfgG16W = ConvGnCfg<16, true>;
-#endif
 int g_fuse_head = 1;               // natinf_set_fuse_head (read when a plan is BUILT): GroupNorm + SiLU + the 128 -> 3 output convolution as ONE launch (head_conv.h)
-int g_cg8_tm4 = 1;                 // natinf_set_conv_gn8_tile: 1 = 8x8 level on 64-pixel x 256-channel tiles (one image per tile, two blocks per CU), 0 = 128 x 256 (two images per tile; -DNATINF_DEV builds)
+// (the 8x8 level runs on 64-pixel x 256-channel tiles, one image per tile and two blocks per CU; the 128 x 256 tile with two images, natinf_set_conv_gn8_tile(0), is retired)
 constexpr int ATTN_BLK_DEFAULT = 2;
 int g_attn_blk = ATTN_BLK_DEFAULT;  // natinf_set_attn_block (read when a plan is BUILT): the whole 16x16 attention block as ONE launch -- 1: k_qkv256 + k_attn256<true, 8> in one kernel (attn_blk256.h: q stays in
                                    // registers, k / V^T through L2); 2 (default since round 6): k_attn_blk256_v2 -- q k^T and P V against h itself, h resident in LDS (forward -3.3 % at B = 512); 0: two launches
 int g_attn_qkv = 1;                // natinf_set_attn_qkv (read when a plan is BUILT): GroupNorm-apply + the q | k | v projections of the 16x16 attention as ONE launch (attn_qkv.h)
 int g_attn_w8 = 1;                 // natinf_set_attn_waves8: k_attn256<true> as one 8-wave block per sample (1) or two 4-wave blocks (0)
 int g_attn_proj = 1;               // natinf_set_attn_proj (read when a plan is BUILT): the 16x16 attention's output projection + skip + GroupNorm partials inside k_attn256
-int g_attn256 = 1;                 // natinf_set_attn256: 1 = k_attn256 (K / V^T streamed through a two-stage LDS ring, two blocks per CU), 0 = k_attn_fused<8,16,true>
 int g_fuse_gn8 = 1;                // natinf_set_fuse_gn8 (read when a plan is BUILT): the 8x8 level on the fused kernel too (two images per 128-pixel tile)
 int g_cg_warm = 15;                // natinf_set_conv_gn_warm: bit mask by resolution (1: 4x4, 2: 8x8, 4: 16x16, 8: 32x32) of the fused-convolution launches that warm L2 with their weights
 int g_fuse_fin = 3;                // natinf_set_fuse_fin (read when a plan is BUILT): at 8x8 / 4x4 the fused convolution's epilogue writes the GroupNorm table of its
@@ -279,23 +258,12 @@ bool set_lds_epi_all() {
            for_each_epi<EPI_R64>([](auto t) { return set_lds<CfgR64x128>(&k_gemm_ring<2, 2, 2, 4, 4, NATINF_EPI_OF(t)>); }) &&
            for_each_epi<EPI_D256H>([](auto t) { return set_lds<CfgD256x256>(&k_gemm_dma<2, 4, 8, 4, 6, NATINF_EPI_OF(t)>); }) &&
            for_each_epi<EPI_D512H>([](auto t) { return set_lds<CfgD512x128>(&k_gemm_dma<4, 2, 8, 4, 6, NATINF_EPI_OF(t)>); }) &&
-           for_each_epi<EPI_W128>([](auto t) { return set_lds<W128Cfg>(&k_gemm_w128<NATINF_EPI_OF(t)>); }) && set_lds<W128Cfg>(&k_gemm_w128<9>)
-#ifdef NATINF_DEV
-           && set_lds<W128Cfg>(&k_gemm_w128<1, W128SchA>) && set_lds<W128Cfg>(&k_gemm_w128<1, W128SchP>) && set_lds<W128Cfg>(&k_gemm_w128<1, W128SchX>)
-           && for_each_epi<EPI_ALL>([](auto t) { return set_lds<CfgD256x256>(&k_gemm_dma<2, 4, 8, 4, 2, NATINF_EPI_OF(t)>); })
-           && for_each_epi<EPI_ALL>([](auto t) { return set_lds<CfgD512x128>(&k_gemm_dma<4, 2, 8, 4, 2, NATINF_EPI_OF(t)>); })
-#endif
-        ;
+           for_each_epi<EPI_W128>([](auto t) { return set_lds<W128Cfg>(&k_gemm_w128<NATINF_EPI_OF(t)>); }) && set_lds<W128Cfg>(&k_gemm_w128<9>);
 }
 template <int EPI>
 bool set_lds_conv_gn() {
     return set_lds<CfgH32>(&k_conv_gn2<32, false, EPI>) && set_lds<CfgH32W>(&k_conv_gn2<32, true, EPI>) && set_lds<CfgH16>(&k_conv_gn2<16, false, EPI>) && set_lds<CfgH16W>(&k_conv_gn2<16, true, EPI>) &&
-           set_lds<CfgH8T>(&k_conv_gn2<8, true, EPI, 4>) && set_lds<CfgH4T>(&k_conv_gn2<4, true, EPI, 4, 2, 2>)
-#ifdef NATINF_DEV
-           && set_lds<CfgH8W>(&k_conv_gn2<8, true, EPI>)
-           && set_lds<CfgG32>(&k_conv_gn<32, false, EPI>) && set_lds<CfgG16>(&k_conv_gn<16, false, EPI>) && set_lds<CfgG16W>(&k_conv_gn<16, true, EPI>)
-#endif
-        ;
+           set_lds<CfgH8T>(&k_conv_gn2<8, true, EPI, 4>) && set_lds<CfgH4T>(&k_conv_gn2<4, true, EPI, 4, 2, 2>);
 }
 
 bool configure_gemm_kernels() {
@@ -304,26 +272,12 @@ bool configure_gemm_kernels() {
     ok = ok && hipFuncSetAttribute(reinterpret_cast<const void*>(&k_head_conv), hipFuncAttributeMaxDynamicSharedMemorySize, HeadConvCfg::LDS_BYTES) == hipSuccess &&
          set_lds<CfgR128x128>(&k_gemm_ring<2, 2, 4, 4, 4, 9>) &&
          set_lds_epi_all() && ncsn_cg3::configure() && ::configure_conv_ring() && configure_dit_attention() && set_lds_conv_gn<1>() && set_lds_conv_gn<2>() && set_lds_conv_gn<5>() && set_lds_conv_gn<6>() &&
-#ifdef NATINF_DEV
-         set_lds<CfgD256x256>(&k_gemm_dma<2, 4, 8, 4>) && set_lds<CfgD256x128>(&k_gemm_dma<4, 2, 4, 4>) &&
-         set_lds<CfgD128x128>(&k_gemm_dma<2, 2, 4, 4>) && set_lds<CfgR256x256>(&k_gemm_ring<2, 4, 8, 4, 4>) &&
-         set_lds<CfgR256x128>(&k_gemm_ring<4, 2, 4, 4, 6>) && set_lds<CfgR128x128>(&k_gemm_ring<2, 2, 4, 4, 4>) &&
-         set_lds<CfgD256x128W4>(&k_gemm_dma<2, 2, 8, 4>) && set_lds<CfgD256x256>(&k_gemm_dma<2, 4, 8, 4, 1>) &&
-         set_lds<CfgD128x128>(&k_gemm_dma<2, 2, 4, 4, 1>) && set_lds<CfgD512x128>(&k_gemm_dma<4, 2, 8, 4>) &&
-         set_lds<CfgP256x256>(&k_conv_patch<2, 4, 8, 4, 344>) && set_lds<CfgP256x128>(&k_conv_patch<4, 2, 4, 4, 400>) &&
-         set_lds<CfgD256x128W4>(&k_gemm_dma<2, 2, 8, 4, 2>) &&
-         set_lds<CfgD256x256>(&k_gemm_dma<2, 4, 8, 4, 3, 1>) && set_lds<CfgD256x256>(&k_gemm_dma<2, 4, 8, 4, 4, 1>) &&
-         set_lds<Cfg8ph>(&k_gemm_8ph<0>) && set_lds<Cfg8ph>(&k_gemm_8ph<1>) && set_lds<Cfg8ph>(&k_gemm_8ph<2>) && set_lds<Cfg8ph>(&k_gemm_8ph<3>) &&
-#endif
          set_lds<CfgD256x256>(&k_gemm_fp8<false, 0>) && set_lds<CfgD256x256>(&k_gemm_fp8<true, 0>) &&
          set_lds<CfgD256x256>(&k_gemm_fp8<false, 1>) && set_lds<CfgD256x256>(&k_gemm_fp8<true, 1>) &&
          set_lds<CfgD256x256>(&k_gemm_fp8<false, 2>) && set_lds<CfgD256x256>(&k_gemm_fp8<true, 2>) &&
          set_lds<CfgD256x256>(&k_gemm_fp8<false, 3>) && set_lds<CfgD256x256>(&k_gemm_fp8<true, 3>) &&
          set_lds<W128F8Cfg>(&k_gemm_w128_fp8<false, 0>) && set_lds<W128F8Cfg>(&k_gemm_w128_fp8<true, 0>) && set_lds<W128F8Cfg>(&k_gemm_w128_fp8<false, 1>) && set_lds<W128F8Cfg>(&k_gemm_w128_fp8<true, 1>) &&
          set_lds<W128F8Cfg>(&k_gemm_w128_fp8<false, 2>) && set_lds<W128F8Cfg>(&k_gemm_w128_fp8<true, 2>) && set_lds<W128F8Cfg>(&k_gemm_w128_fp8<false, 3>) && set_lds<W128F8Cfg>(&k_gemm_w128_fp8<true, 3>) &&
-#ifdef NATINF_DEV
-         set_lds<AttnCfg<8, 16, true>>(&k_attn_fused<8, 16, true>) &&      // the LDS-resident K / V^T form of the 16x16 attention: superseded by k_attn256
-#endif
          hipFuncSetAttribute(reinterpret_cast<const void*>(&k_qkv256), hipFuncAttributeMaxDynamicSharedMemorySize, QKV_LDS_BYTES) == hipSuccess &&
          hipFuncSetAttribute(reinterpret_cast<const void*>(&k_attn256<false>), hipFuncAttributeMaxDynamicSharedMemorySize, A256_LDS_BYTES) == hipSuccess &&
          hipFuncSetAttribute(reinterpret_cast<const void*>(&k_attn256<true>), hipFuncAttributeMaxDynamicSharedMemorySize, A256_LDS_BYTES) == hipSuccess &&
@@ -332,10 +286,6 @@ bool configure_gemm_kernels() {
          hipFuncSetAttribute(reinterpret_cast<const void*>(&k_attn_blk256_v2), hipFuncAttributeMaxDynamicSharedMemorySize, ABLK2_LDS_BYTES) == hipSuccess &&
          // (k_attn_fused<2,4> / <3,5> / <3,6> with v as V^T: superseded by the row-major-v forms of the DiT engine, configure_dit_attention)
          hipFuncSetAttribute(reinterpret_cast<const void*>(&k_flash_attn64), hipFuncAttributeMaxDynamicSharedMemorySize, FA_LDS_BYTES) == hipSuccess &&
-#ifdef NATINF_DEV
-         hipFuncSetAttribute(reinterpret_cast<const void*>(&k_flash_attn64_v2<0>), hipFuncAttributeMaxDynamicSharedMemorySize, FA_LDS_BYTES) == hipSuccess &&
-         hipFuncSetAttribute(reinterpret_cast<const void*>(&k_flash_attn64_v2<1>), hipFuncAttributeMaxDynamicSharedMemorySize, FA_LDS_BYTES) == hipSuccess &&
-#endif
          hipFuncSetAttribute(reinterpret_cast<const void*>(&k_flash_attn64_v2<1, 64>), hipFuncAttributeMaxDynamicSharedMemorySize, FA_LDS_BYTES / 2) == hipSuccess;
     if (!ok) (void)hipGetLastError();
     return ok;
@@ -344,20 +294,13 @@ bool configure_gemm_kernels() {
 // Automatic choice: the largest block tile that still gives every CU a tile (DMA kernels need K a multiple of
 // 64 per segment and zero-bordered 3x3 operands); the register-staged, fully masked kernel otherwise (4x4
 // attention: K = 16).
-// k_gemm_8ph has no edge clamping and addresses the 1x1 segment row-linearly
-#ifdef NATINF_DEV
-inline bool eligible_8ph(const GemmArgs& g) { return g.M % 256 == 0 && g.N % 256 == 0; }
-#endif
 
 int variant_bm(int v);
-// k_conv_gn instantiations: 32x32 and 16x16 images, 256 x 128 tiles -- 128 x 256 tiles for 16x16 layers whose N is a multiple of 256
-// (natinf_set_conv_gn_wide: A/B runs); packed epilogues 1 / 2 / 5 / 6 only
 int packed_epi(const GemmArgs& g, int bm);
 int g_cg3 = 7;                     // natinf_set_conv_gn_w128: bit 0 = 32x32 layers with N % 256 != 0 on 512 x 128 tiles, bit 1 = 32x32 layers with N % 256 == 0 on 256 x 256
                                    // tiles, bit 2 = 16x16 layers with N % 256 == 0 on 256 x 256 tiles (one image per tile)
 int g_cg_wide = 3;                 // natinf_set_conv_gn_wide: bit 0 = 128 x 256 tiles at 16x16, bit 1 = at 32x32 (N % 256 == 0 layers: the 16 -> 32 up-sampling block)
 int g_fuse_up = 1;                 // natinf_set_fuse_up (read when a plan is BUILT): up blocks at 16x16 / 32x32 fetch their input up-sampled inside k_conv_gn2
-int g_cg_regw = 1;                 // natinf_set_conv_gn_regw: 1 = k_conv_gn2 (weights streamed through registers) where GemmArgs::b_frag is given
 // tile rows of the fused-convolution instantiation a launch takes: 128 x 256 tiles at 16x16 (N % 256 == 0) and at 8x8 (two images per tile), 256 x 128 elsewhere
 // the k_conv_gn3 shape a fused-convolution launch takes (-1: k_conv_gn2).  One block per CU exposes a tile's prologue and epilogue (~28k clocks), which the two
 // co-resident blocks of k_conv_gn2 partly hide: k_conv_gn3 is ahead where the K loop is long (same-process A/B at B = 512, profiles/r05/cg3_v2_ab.log: 1.04-1.08 at
@@ -365,7 +308,7 @@ int g_cg_regw = 1;                 // natinf_set_conv_gn_regw: 1 = k_conv_gn2 (w
 int g_cg3_min_k[3] = {2304, 0, 2304};      // natinf_set_conv_gn_w128_min_k: smallest K (9 cin + shortcut channels) per shape that takes k_conv_gn3
 inline int conv_gn3_shape(const GemmArgs& g) {
     const int res = 1 << g.logW;
-    if (!g_cg3 || !g_cg_regw || !g.b_frag || g.N % 128) return -1;
+    if (!g_cg3 || !g.b_frag || g.N % 128) return -1;
     int sh = -1;
     if (res == 32) sh = g.N % 256 ? ((g_cg3 & 1) ? 0 : -1) : ((g_cg3 & 2) ? 1 : -1);
     else if (res == 16) sh = (g.N % 256 == 0 && (g_cg3 & 4)) ? 2 : -1;
@@ -375,20 +318,14 @@ inline int conv_gn3_shape(const GemmArgs& g) {
 inline int conv_gn_bm(const GemmArgs& g) {
     const int res = 1 << g.logW;
     if (const int sh3 = conv_gn3_shape(g); sh3 >= 0) return ncsn_cg3::tile_rows(sh3);
-    if (res == 8) return g_cg8_tm4 ? 64 : 128;
-    if (res == 4) return 64;
-    if (res == 32) return ((g_cg_wide & 2) && g.N % 256 == 0 && g_cg_regw && g.b_frag) ? 128 : 256;      // (k_conv_gn2 only)
+    if (res == 8 || res == 4) return 64;
+    if (res == 32) return ((g_cg_wide & 2) && g.N % 256 == 0 && g.b_frag) ? 128 : 256;
     return ((g_cg_wide & 1) && res == 16 && g.N % 256 == 0) ? 128 : 256;
 }
 // rows of one GroupNorm-partial table row the launch writes (what the caller divides H*W by): a tile, or one SAMPLE of the two an 8x8 tile holds
 inline int conv_gn_part_rows(const GemmArgs& g) { const int res = 1 << g.logW; return res <= 8 ? res * res : conv_gn_bm(g); }
-inline bool conv_gn_regw(const GemmArgs& g) { return g_cg_regw && g.b_frag && (conv_gn3_shape(g) >= 0 || g.N % ((conv_gn_bm(g) <= 128 && (1 << g.logW) != 4) ? 256 : 128) == 0); }      // (4x4: 64 x 128 tiles)
-#ifdef NATINF_DEV
-constexpr bool HAVE_CONV_GN_V1 = true;              // k_conv_gn (weights through an LDS ring): superseded, development builds only
-#else
-constexpr bool HAVE_CONV_GN_V1 = false;
-#endif
-// k_conv_gn / k_conv_gn2 have packed epilogues only: the fp32-slab A/B knob (natinf_set_gemm_epilogue) does not apply to them.  Per-sample terms need
+inline bool conv_gn_regw(const GemmArgs& g) { return g.b_frag && (conv_gn3_shape(g) >= 0 || g.N % ((conv_gn_bm(g) <= 128 && (1 << g.logW) != 4) ? 256 : 128) == 0); }      // (4x4: 64 x 128 tiles)
+// k_conv_gn2 / k_conv_gn3 have packed epilogues only: the fp32-slab A/B knob (natinf_set_gemm_epilogue) does not apply to them.  Per-sample terms need
 // one sample per tile -- or, at 8x8, per HALF tile (the kernel keeps both samples' row vectors and partials: NSAMP)
 inline int conv_gn_epi(const GemmArgs& g) { GemmArgs t = g; t.epi_fp32_slab = 0; return packed_epi(t, conv_gn_part_rows(g)); }
 inline bool conv_gn_ok(const GemmArgs& g) {
@@ -396,9 +333,9 @@ inline bool conv_gn_ok(const GemmArgs& g) {
     const int res = 1 << g.logW;
     if (g.logHW != 2 * g.logW || (res != 32 && res != 16 && res != 8 && res != 4) || g.N % 8) return false;
     if (res == 4 && (g.a0_C % (64 * CfgH4T::NG) || (g.a1 && g.a1_C % (64 * CfgH4T::NG)))) return false;          // two K groups per block: an even number of half-chunks / shortcut tiles EACH
-    if (res <= 8 ? (g.M % (res * res) || g.N % (res == 4 ? 128 : 256) || g.a0_up || g.a1_up || !conv_gn_regw(g) || (g.resid && g.rowvec)) : g.M % std::max(256, conv_gn_bm(g)) != 0) return false;      // 8x8: whole images, k_conv_gn2 only;
-    // (its residual epilogues keep one set of column terms for both samples of a tile: no per-sample row vector there)
-    if ((g.a0_up || g.a1_up || !HAVE_CONV_GN_V1) && !conv_gn_regw(g)) return false;          // up-sampled fetches: k_conv_gn2 only
+    if (res <= 8 ? (g.M % (res * res) || g.N % (res == 4 ? 128 : 256) || g.a0_up || g.a1_up || (g.resid && g.rowvec)) : g.M % std::max(256, conv_gn_bm(g)) != 0) return false;      // 8x8 / 4x4: whole images;
+    // (the residual epilogues keep one set of column terms for all samples of a tile: no per-sample row vector there)
+    if (!conv_gn_regw(g)) return false;                                                       // the fragment-major weights, whole column tiles
     const int e = conv_gn_epi(g);
     return e == 1 || e == 2 || e == 5 || e == 6;
 }
@@ -415,22 +352,9 @@ int choose_variant(const GemmArgs& g) {
     const bool dma = K0 % BK == 0 && K1 % BK == 0 && (g.taps == 1 || (g.a0_padded && g.a0_C % BK == 0));
     if (!dma) return V_GENERIC;
     if (!variant_shipped(g_force_variant)) { /* refused by natinf_set_gemm_variant; never reached */ }
-#ifdef NATINF_DEV
-    else if (g_force_variant == V_PATCH_256x256 || g_force_variant == V_PATCH_256x128) {
-        const bool patch_ok = g.taps == 9 && g.batch == 1 && g.logW >= 3;
-        if (patch_ok && (g_force_variant == V_PATCH_256x128 || g.logW >= 4)) return g_force_variant;
-    } else if (g_force_variant >= V_8PH_256x256 && g_force_variant <= V_8PH_BOTH) {
-        if (eligible_8ph(g)) return g_force_variant;
-    }
-#endif
     else if (g_force_variant == V_W128) {
         if (w128_ok(g) && (!g.gn_part || (1 << g.logHW) % 256 == 0)) return V_W128;
     }
-#ifdef NATINF_DEV
-    else if (g_force_variant >= V_W128_A && g_force_variant <= V_W128_X) {
-        if (w128_ok(g) && packed_epi(g, 256) == 1) return g_force_variant;
-    }
-#endif
     else if (g_force_variant > V_GENERIC && g_force_variant != V_CONV_GN && g_force_variant != V_FP8_256x256) {
         // a forced tile must keep GroupNorm partial tiles inside one sample (e.g. 512-row tiles on the 16x16 level do not)
         if (!g.gn_part || (g.taps == 9 && (1 << g.logHW) % variant_bm(g_force_variant) == 0)) return g_force_variant;
@@ -440,11 +364,6 @@ int choose_variant(const GemmArgs& g) {
     // 128x128 when 256-row tiles would leave CUs idle; 64x128 for the 4x4 level
     const int64_t mt256 = (g.M + 255) / 256, mt128 = (g.M + 127) / 128;
     const int64_t nt128 = (g.N + 127) / 128;
-#ifdef NATINF_DEV
-    const bool half = g_half_issue != 0;                                       // natinf_set_gemm_half_issue(0): the every-wave-issues pipelines (A/B runs)
-#else
-    constexpr bool half = true;
-#endif
     const bool w128 = g_w128 && w128_ok(g) && (!g.gn_part || (1 << g.logHW) % 256 == 0);       // round 4: plain GEMMs on the one-wave-per-SIMD tile (gemm_w128.h)
     // Round 4: small-M plain GEMMs (the text stream of the MMDiT: M = 8 x 333 rows) by ROUNDS of blocks, not by "enough tiles for every CU": at
     // (2664, 6144, 1536) the rule below took 256 x 256 tiles -- 264 of them: a second round for eight tiles, 77 us -- where 1,008 tiles of 128 x 128 run as two rounds of
@@ -459,12 +378,12 @@ int choose_variant(const GemmArgs& g) {
         // (a round of the four-wave 256 x 256 tile costs ~1.3 rounds of 128 x 128 tiles, not 1.5: DiT-XL/2's fc1 at B = 16, (4096, 4608, 1152), is 288 tiles = two rounds of
         // ~28 us against three rounds of two 128 x 128 blocks per CU in 74.6 us; natinf_set_gemm_round_model(v >= 10) sets the ratio to v / 10 for A/B runs)
         const int64_t c256 = w128 ? g_round_model_w128 : 15;
-        if (mt128 * nt128 >= NUM_CU / 2) return c256 * r256 < 10 * r128 ? (w128 ? V_W128 : half ? V_DMA_256x256_H : V_DMA_256x256_P) : V_DMA_128x128_P;
+        if (mt128 * nt128 >= NUM_CU / 2) return c256 * r256 < 10 * r128 ? (w128 ? V_W128 : V_DMA_256x256_H) : V_DMA_128x128_P;
     }
-    if (n_ok256 && K0 + K1 >= 1024 && mt256 * nt256 * g.batch >= NUM_CU) return w128 ? V_W128 : half ? V_DMA_256x256_H : V_DMA_256x256_P;
+    if (n_ok256 && K0 + K1 >= 1024 && mt256 * nt256 * g.batch >= NUM_CU) return w128 ? V_W128 : V_DMA_256x256_H;
     if (g_pref_512 && g.N <= 128 && K0 + K1 >= 1024 && ((g.M + 511) / 512) * g.batch >= 2 * NUM_CU &&
         (!g.gn_part || (g.taps == 9 && (1 << g.logHW) % 512 == 0)))           // GroupNorm partials: a tile inside one sample
-        return half ? V_DMA_512x128_H : V_DMA_512x128;
+        return V_DMA_512x128_H;
     if (mt256 * nt128 * g.batch >= 2 * NUM_CU) return V_RING_256x128_W4;        // it runs two blocks per CU
     if (mt128 * nt128 * g.batch >= NUM_CU) return V_DMA_128x128_P;
     return V_RING_64x128;
@@ -472,9 +391,8 @@ int choose_variant(const GemmArgs& g) {
 
 int variant_bm(int v) {
     switch (v) {
-        case V_CONV_GN: case V_DMA_256x256: case V_DMA_256x128: case V_RING_256x256: case V_RING_256x128: case V_RING_256x128_W4: case V_DMA_256x128_W4:
-        case V_ABL_NODMA: case V_ABL_NOMFMA: case V_DMA_256x256_H: case V_DMA_256x256_S: case V_PATCH_256x256: case V_PATCH_256x128: case V_DMA_256x256_P: case V_DMA_256x128W4_P: case V_8PH_256x256: case V_8PH_NOPRIO: case V_8PH_READFIRST: case V_8PH_BOTH: case V_FP8_256x256: case V_W128: case V_W128_A: case V_W128_D: case V_W128_X: return 256;
-        case V_DMA_512x128: case V_DMA_512x128_H: return 512;
+        case V_CONV_GN: case V_RING_256x128_W4: case V_DMA_256x256_H: case V_FP8_256x256: case V_W128: return 256;
+        case V_DMA_512x128_H: return 512;
         case V_RING_64x128: return 64;
         default: return 128;
     }
@@ -567,7 +485,6 @@ inline unsigned epi_mask(int v) {
     switch (v) {
         case V_RING_64x128: return EPI_R64;  case V_DMA_128x128_P: return EPI_D128;  case V_RING_256x128_W4: return EPI_RW4;
         case V_DMA_256x256_H: return EPI_D256H;  case V_DMA_512x128_H: return EPI_D512H;
-        case V_DMA_256x256_P: case V_DMA_512x128: return EPI_ALL;
         case V_W128: return EPI_W128;
         default: return 1u;
     }
@@ -713,11 +630,6 @@ int launch_gemm_run(const GemmArgs& g0, hipStream_t s) {
         case V_FP8_256x256: launch_tiles<CfgD256x256>(&k_gemm_fp8<false, 0>, g, s); break;
         case V_DMA_256x256_H: NATINF_LAUNCH_EPI(EPI_D256H, CfgD256x256, k_gemm_dma, 2, 4, 8, 4, 6) break;
         case V_DMA_512x128_H: NATINF_LAUNCH_EPI(EPI_D512H, CfgD512x128, k_gemm_dma, 4, 2, 8, 4, 6) break;
-#ifdef NATINF_DEV
-        case V_W128_A: launch_tiles<W128Cfg>(&k_gemm_w128<1, W128SchA>, g, s); break;
-        case V_W128_D: launch_tiles<W128Cfg>(&k_gemm_w128<1, W128SchP>, g, s); break;        // (variant 31: the shipped schedule + the L2 prefetch)
-        case V_W128_X: launch_tiles<W128Cfg>(&k_gemm_w128<1, W128SchX>, g, s); break;
-#endif
         case V_W128: {
             auto run_ = [&](auto t_) { launch_tiles<W128Cfg>(&k_gemm_w128<NATINF_EPI_OF(t_)>, g, s); };
             switch (effective_epi(v, g)) {
@@ -728,28 +640,6 @@ int launch_gemm_run(const GemmArgs& g0, hipStream_t s) {
             }
             break;
         }
-#ifdef NATINF_DEV
-        case V_DMA_256x256: launch_tiles<CfgD256x256>(&k_gemm_dma<2, 4, 8, 4>, g, s); break;
-        case V_DMA_256x128: launch_tiles<CfgD256x128>(&k_gemm_dma<4, 2, 4, 4>, g, s); break;
-        case V_DMA_128x128: launch_tiles<CfgD128x128>(&k_gemm_dma<2, 2, 4, 4>, g, s); break;
-        case V_RING_256x256: launch_tiles<CfgR256x256>(&k_gemm_ring<2, 4, 8, 4, 4>, g, s); break;
-        case V_RING_256x128: launch_tiles<CfgR256x128>(&k_gemm_ring<4, 2, 4, 4, 6>, g, s); break;
-        case V_RING_128x128: launch_tiles<CfgR128x128>(&k_gemm_ring<2, 2, 4, 4, 4>, g, s); break;
-        case V_DMA_256x128_W4: launch_tiles<CfgD256x128W4>(&k_gemm_dma<2, 2, 8, 4>, g, s); break;
-        case V_DMA_256x256_S: launch_tiles<CfgD256x256>(&k_gemm_dma<2, 4, 8, 4, 1>, g, s); break;
-        case V_DMA_128x128_S: launch_tiles<CfgD128x128>(&k_gemm_dma<2, 2, 4, 4, 1>, g, s); break;
-        case V_DMA_512x128: NATINF_LAUNCH_EPI(EPI_ALL, CfgD512x128, k_gemm_dma, 4, 2, 8, 4, 2) break;
-        case V_PATCH_256x256: launch_tiles<CfgP256x256>(&k_conv_patch<2, 4, 8, 4, 344>, g, s); break;
-        case V_PATCH_256x128: launch_tiles<CfgP256x128>(&k_conv_patch<4, 2, 4, 4, 400>, g, s); break;
-        case V_DMA_256x256_P: NATINF_LAUNCH_EPI(EPI_ALL, CfgD256x256, k_gemm_dma, 2, 4, 8, 4, 2) break;
-        case V_DMA_256x128W4_P: launch_tiles<CfgD256x128W4>(&k_gemm_dma<2, 2, 8, 4, 2>, g, s); break;
-        case V_8PH_256x256: launch_tiles<Cfg8ph>(&k_gemm_8ph<0>, g, s); break;
-        case V_8PH_NOPRIO: launch_tiles<Cfg8ph>(&k_gemm_8ph<1>, g, s); break;
-        case V_8PH_READFIRST: launch_tiles<Cfg8ph>(&k_gemm_8ph<2>, g, s); break;
-        case V_8PH_BOTH: launch_tiles<Cfg8ph>(&k_gemm_8ph<3>, g, s); break;
-        case V_ABL_NODMA: launch_tiles<CfgD256x256>(&k_gemm_dma<2, 4, 8, 4, 3, 1>, g, s); break;
-        case V_ABL_NOMFMA: launch_tiles<CfgD256x256>(&k_gemm_dma<2, 4, 8, 4, 4, 1>, g, s); break;
-#endif
         case V_CONV_GN: {
             GemmArgs gw = g0;
             gw.w_warm = (g_cg_warm >> (g0.logW - 2)) & 1;
@@ -768,45 +658,27 @@ int launch_gemm_run(const GemmArgs& g0, hipStream_t s) {
                 g_fin_written = sh3 == 2 && g.fin_scale && (e == 2 || e == 6) && g.N == 256;      // (k_conv_gn3<16, 2, 2, 2 | 6>: FIN16, conv_gn3.h)
                 return conv_gn_part_rows(g);
             }
-            if (conv_gn_regw(g)) {
-                if ((1 << g.logW) == 8 && g_cg8_tm4) {
-                    switch (e4) {
-                        case 0: launch_tiles<CfgH8T>(&k_conv_gn2<8, true, 1, 4>, g, s); break;
-                        case 1: launch_tiles<CfgH8T>(&k_conv_gn2<8, true, 2, 4>, g, s); break;
-                        case 2: launch_tiles<CfgH8T>(&k_conv_gn2<8, true, 5, 4>, g, s); break;
-                        default: launch_tiles<CfgH8T>(&k_conv_gn2<8, true, 6, 4>, g, s); break;
-                    }
+            if ((1 << g.logW) == 8) {
+                switch (e4) {
+                    case 0: launch_tiles<CfgH8T>(&k_conv_gn2<8, true, 1, 4>, g, s); break;
+                    case 1: launch_tiles<CfgH8T>(&k_conv_gn2<8, true, 2, 4>, g, s); break;
+                    case 2: launch_tiles<CfgH8T>(&k_conv_gn2<8, true, 5, 4>, g, s); break;
+                    default: launch_tiles<CfgH8T>(&k_conv_gn2<8, true, 6, 4>, g, s); break;
                 }
-#ifdef NATINF_DEV
-                else if ((1 << g.logW) == 8) { NATINF_CG2_LAUNCH(CfgH8W, 8, true) }
-#endif
-                else if ((1 << g.logW) == 4) {
-                    switch (e4) {
-                        case 0: launch_tiles<CfgH4T>(&k_conv_gn2<4, true, 1, 4, 2, 2>, g, s); break;
-                        case 1: launch_tiles<CfgH4T>(&k_conv_gn2<4, true, 2, 4, 2, 2>, g, s); break;
-                        case 2: launch_tiles<CfgH4T>(&k_conv_gn2<4, true, 5, 4, 2, 2>, g, s); break;
-                        default: launch_tiles<CfgH4T>(&k_conv_gn2<4, true, 6, 4, 2, 2>, g, s); break;
-                    }
-                }
-                else if ((1 << g.logW) == 32 && conv_gn_bm(g) == 128) { NATINF_CG2_LAUNCH(CfgH32W, 32, true) }
-                else if ((1 << g.logW) == 32) { NATINF_CG2_LAUNCH(CfgH32, 32, false) }
-                else if (conv_gn_bm(g) == 128) { NATINF_CG2_LAUNCH(CfgH16W, 16, true) }
-                else { NATINF_CG2_LAUNCH(CfgH16, 16, false) }
             }
+            else if ((1 << g.logW) == 4) {
+                switch (e4) {
+                    case 0: launch_tiles<CfgH4T>(&k_conv_gn2<4, true, 1, 4, 2, 2>, g, s); break;
+                    case 1: launch_tiles<CfgH4T>(&k_conv_gn2<4, true, 2, 4, 2, 2>, g, s); break;
+                    case 2: launch_tiles<CfgH4T>(&k_conv_gn2<4, true, 5, 4, 2, 2>, g, s); break;
+                    default: launch_tiles<CfgH4T>(&k_conv_gn2<4, true, 6, 4, 2, 2>, g, s); break;
+                }
+            }
+            else if ((1 << g.logW) == 32 && conv_gn_bm(g) == 128) { NATINF_CG2_LAUNCH(CfgH32W, 32, true) }
+            else if ((1 << g.logW) == 32) { NATINF_CG2_LAUNCH(CfgH32, 32, false) }
+            else if (conv_gn_bm(g) == 128) { NATINF_CG2_LAUNCH(CfgH16W, 16, true) }
+            else { NATINF_CG2_LAUNCH(CfgH16, 16, false) }
 #undef NATINF_CG2_LAUNCH
-#ifdef NATINF_DEV
-#define NATINF_CG_LAUNCH(CFG, RES, WIDE)                                                                    \
-            switch (e4) {                                                                                       \
-                case 0: launch_tiles<CFG>(&k_conv_gn<RES, WIDE, 1>, g, s); break;                               \
-                case 1: launch_tiles<CFG>(&k_conv_gn<RES, WIDE, 2>, g, s); break;                               \
-                case 2: launch_tiles<CFG>(&k_conv_gn<RES, WIDE, 5>, g, s); break;                               \
-                default: launch_tiles<CFG>(&k_conv_gn<RES, WIDE, 6>, g, s); break;                              \
-            }
-            else if ((1 << g.logW) == 32) { NATINF_CG_LAUNCH(CfgG32, 32, false) }
-            else if (conv_gn_bm(g) == 128) { NATINF_CG_LAUNCH(CfgG16W, 16, true) }
-            else { NATINF_CG_LAUNCH(CfgG16, 16, false) }
-#undef NATINF_CG_LAUNCH
-#endif
             return conv_gn_part_rows(g);
         }
         default: break;
@@ -925,7 +797,7 @@ struct Builder {
         const int64_t p_c2w = shortcut ? take((int64_t)cout * cin) : -1, p_c2b = shortcut ? take(cout) : -1;
 
         const int K0a = 9 * cin, K1tot = 9 * cout + (shortcut ? cin : 0);
-        // GroupNorm-apply + SiLU inside the consuming convolution (conv_gn.h) where an instantiation exists: output resolution
+        // GroupNorm-apply + SiLU inside the consuming convolution (conv_gn2.h) where an instantiation exists: output resolution
         // 32x32 or 16x16.  Conv_0 of a resampling block reads a resampled tensor and keeps the k_gn_apply pass (which also
         // produces the resampled shortcut input), Conv_1 is fused there too; the 8x8 / 4x4 levels are unfused.  Folded form: the
         // GroupNorm scale / shift carry -log2(e), the 3x3 weights -ln 2 (GemmArgs::gn_folded).
@@ -1047,7 +919,7 @@ struct Builder {
         if (!fuse_qkv) emit_gn_apply(x, sc, sh, h, nullptr, ACT_NONE, RS_NONE);
         const int64_t qk = arena.alloc((int64_t)T * 2 * C * 2), vT = arena.alloc((int64_t)C * T * 2);
         // k_attn_blk256: projections, attention and output projection of a sample in ONE launch (needs the three fusions it is made of)
-        const bool blk = fuse_qkv && g_attn256 && g_attn_proj && g_attn_w8 && g_attn_blk;
+        const bool blk = fuse_qkv && g_attn_proj && g_attn_w8 && g_attn_blk;
         int64_t wqkvf = -1;
         const int64_t sc_q = sc, sh_q = sh;
         if (fuse_qkv) {
@@ -1082,7 +954,7 @@ struct Builder {
         });
         arena.release(h.off);
         // k_attn256<true>: the output projection, skip connection and GroupNorm partials in the attention launch (attn256.h); O never exists
-        const bool proj = T == 256 && C == 256 && g_attn256 && g_attn_proj;
+        const bool proj = T == 256 && C == 256 && g_attn_proj;
         int64_t w3f = -1;
         if (proj) {
             w3f = wres((int64_t)C * C * 2);
@@ -1138,16 +1010,9 @@ struct Builder {
                     if (po_attn.valid) c.part_bm[po_attn.id] = 128;
                     }
                 }
-                else if (g_attn256)
+                else
                     hipLaunchKernelGGL(k_attn256<false>, dim3((unsigned)(2 * c.B)), dim3(256), A256_LDS_BYTES, c.stream, c.at<bf16>(qk), 2 * C, C, c.at<bf16>(vT), c.act(O), C,
                                        1.0f / sqrtf((float)C), (const bf16*)nullptr, (const float*)nullptr, (const bf16*)nullptr, 0, 1.0f, (float2*)nullptr, 0);
-#ifdef NATINF_DEV
-                else {
-                    using Cfg = AttnCfg<8, 16, true>;
-                    hipLaunchKernelGGL((&k_attn_fused<8, 16, true>), dim3((unsigned)c.B), dim3(Cfg::THREADS), Cfg::LDS_BYTES, c.stream, c.at<bf16>(qk), 2 * C, C,
-                                       c.at<bf16>(vT), c.act(O), C, 1, C, 1.0f / sqrtf((float)C));
-                }
-#endif
             });
             arena.release(vT); arena.release(qk);
         } else {
@@ -1612,7 +1477,7 @@ natinf_ncsnpp* make_engine(int flags) {
 const natinf_ncsnpp& reference_engine() {
     static natinf_ncsnpp* e = [] {
         // every knob that is read when a plan is BUILT and adds a repacked weight copy or a table: saved, forced on, restored
-        int* knobs[] = {&g_fuse_gn, &g_fuse_up, &g_fuse_head, &g_fuse_gn8, &g_fuse_gn4, &g_fuse_fin, &g_attn_qkv, &g_attn_proj, &g_attn256};
+        int* knobs[] = {&g_fuse_gn, &g_fuse_up, &g_fuse_head, &g_fuse_gn8, &g_fuse_gn4, &g_fuse_fin, &g_attn_qkv, &g_attn_proj};
         int saved[sizeof(knobs) / sizeof(knobs[0])];
         for (size_t i = 0; i < sizeof(knobs) / sizeof(knobs[0]); ++i) { saved[i] = *knobs[i]; *knobs[i] = 1; }
         g_fuse_fin = 3;                                      // (a bit mask: both levels' producer-written tables)
@@ -1640,7 +1505,7 @@ int64_t natinf_ncsnpp_workspace_bytes(natinf_ncsnpp_t h, int max_batch) {
 
 // every switch a plan builder reads (layout of the packed weights included), one byte each
 static uint64_t plan_signature() {
-    const int k[] = {g_fuse_head, g_cg8_tm4, g_attn_qkv, g_attn_w8, g_attn_proj, g_attn256, g_fuse_gn8, g_fuse_fin, g_fuse_gn4, g_fuse_gn, g_cg_wide, g_fuse_up, g_cg_regw,
+    const int k[] = {g_fuse_head, g_attn_qkv, g_attn_w8, g_attn_proj, g_fuse_gn8, g_fuse_fin, g_fuse_gn4, g_fuse_gn, g_cg_wide, g_fuse_up,
                      g_attn_blk /* (2: the folded attention weights are packed too) */, g_cg3 /* read by the plan builders (which launches exist; which tables a producer may write) */};
     uint64_t h = 1469598103934665603ull;
     for (int v : k) h = (h ^ (uint64_t)(v & 0xff)) * 1099511628211ull;
@@ -1755,7 +1620,7 @@ int natinf_debug_gemm(int variant, int M, int N, int K0, int K1, int taps, int l
     // zero-bordered images, one batch index (a_bs would have to be the padded image size, and a1 shares it)
     if (K0 % taps || N % 8 || (a1 != nullptr) != (K1 > 0)) return NATINF_EINVAL;
     if (taps == 9 && ((K0 / 9) % BK || logW < 1 || logW > 12 || M % (1 << (2 * logW)) || batch != 1)) return NATINF_EINVAL;
-    if (!variant_shipped(variant) || variant == V_CONV_GN || variant == V_FP8_256x256) return NATINF_ESTATE;      // superseded / ablation variants: -DNATINF_DEV builds
+    if (!variant_shipped(variant) || variant == V_CONV_GN || variant == V_FP8_256x256) return NATINF_ESTATE;      // retired variants; operand-type-specific kernels
 #ifndef NATINF_DEV
     if (c_f32 >= 2) return NATINF_ESTATE;      // timing experiments: -DNATINF_DEV builds
 #endif
@@ -1895,12 +1760,7 @@ int natinf_debug_timestamps(void* dev_buf16) {
 int natinf_set_gemm_raster(int rows) { g_raster_g = rows; return NATINF_OK; }
 int natinf_set_fuse_gn(int on) { g_fuse_gn = on != 0; return NATINF_OK; }
 int natinf_set_fuse_gn8(int on) { g_fuse_gn8 = on != 0; return NATINF_OK; }
-int natinf_set_attn256(int on) {
-#ifndef NATINF_DEV
-    if (!on) return NATINF_ESTATE;                 // k_attn_fused<8,16,true> is a development-build kernel
-#endif
-    g_attn256 = on != 0; return NATINF_OK;
-}
+int natinf_set_attn256(int on) { return on ? NATINF_OK : NATINF_ESTATE; }      // (0: k_attn_fused<8,16,true>, retired)
 int natinf_set_conv_gn_warm(int mask) { if (mask < 0 || mask > 15) return NATINF_EINVAL; g_cg_warm = mask; return NATINF_OK; }
 int natinf_set_attn_block(int on) { g_attn_blk = on < 0 ? ATTN_BLK_DEFAULT : (on > 2 ? 2 : on); return NATINF_OK; }
 int natinf_set_attn_qkv(int on) { g_attn_qkv = on != 0; return NATINF_OK; }
@@ -1915,35 +1775,22 @@ int natinf_set_fuse_fin(int on) {              // 1 = every level that can (the 
 int natinf_set_gemm_round_model(int on) { g_round_model = on != 0; g_round_model_w128 = on >= 10 ? on : 13; return NATINF_OK; }
 int natinf_set_gemm_w128(int on) { g_w128 = on < 0 ? 0 : (on > 2 ? 2 : on); return NATINF_OK; }
 int natinf_set_fuse_gn4(int on) { g_fuse_gn4 = on != 0; return NATINF_OK; }
-int natinf_set_conv_gn8_tile(int one_image) {
-#ifndef NATINF_DEV
-    if (!one_image) return NATINF_ESTATE;          // the two-image tile is a development-build kernel
-#endif
-    g_cg8_tm4 = one_image != 0; return NATINF_OK;
-}
+int natinf_set_conv_gn8_tile(int one_image) { return one_image ? NATINF_OK : NATINF_ESTATE; }      // (0: the two-image tile, retired)
 int natinf_set_fuse_head(int on) { g_fuse_head = on != 0; return NATINF_OK; }
 int natinf_set_conv_gn_w128(int mask) { if (mask < 0 || mask > 7) return NATINF_EINVAL; g_cg3 = mask; return NATINF_OK; }
 int natinf_set_conv_gn_w128_min_k(int shape, int k) { if (shape < 0 || shape > 2 || k < 0) return NATINF_EINVAL; g_cg3_min_k[shape] = k; return NATINF_OK; }
 int natinf_set_conv_gn_wide(int mask) { if (mask < 0 || mask > 3) return NATINF_EINVAL; g_cg_wide = mask; return NATINF_OK; }
-int natinf_set_conv_gn_regw(int on) {
-    if (!on && !HAVE_CONV_GN_V1) return NATINF_ESTATE;      // k_conv_gn (the LDS-ring form) exists in -DNATINF_DEV builds only
-    g_cg_regw = on != 0; return NATINF_OK;
-}
+int natinf_set_conv_gn_regw(int on) { return on ? NATINF_OK : NATINF_ESTATE; }      // (0: k_conv_gn, the LDS-ring form, retired)
 int natinf_set_fuse_up(int on) { g_fuse_up = on != 0; return NATINF_OK; }
 int natinf_set_gemm_splitk(int on) { g_splitk = on != 0; return NATINF_OK; }
 int natinf_debug_set_splitk_workspace(float* ws, int max_slices) { g_dbg_splitk_ws = ws; g_dbg_splitk_max = ws ? max_slices : 0; return NATINF_OK; }
-int natinf_set_gemm_half_issue(int on) {
-#ifndef NATINF_DEV
-    if (!on) return NATINF_ESTATE;                          // the every-wave-issues pipelines exist in -DNATINF_DEV builds only
-#endif
-    g_half_issue = on != 0; return NATINF_OK;
-}
+int natinf_set_gemm_half_issue(int on) { return on ? NATINF_OK : NATINF_ESTATE; }      // (0: the every-wave-issues pipelines, retired)
 int natinf_set_gemm_pref512(int on) { g_pref_512 = on != 0; return NATINF_OK; }
 int natinf_set_gemm_epilogue(int fp32_slab) { g_epi_fp32_slab = fp32_slab != 0; return NATINF_OK; }
 
 int natinf_set_gemm_variant(int variant) {
     if (variant < 0 || variant >= V_COUNT) return NATINF_EINVAL;
-    if (!variant_shipped(variant) || variant == V_CONV_GN || variant == V_FP8_256x256) return NATINF_ESTATE;      // development-build variants; operand-type-specific kernels
+    if (!variant_shipped(variant) || variant == V_CONV_GN || variant == V_FP8_256x256) return NATINF_ESTATE;      // retired variants; operand-type-specific kernels
     g_force_variant = variant;
     return NATINF_OK;
 }

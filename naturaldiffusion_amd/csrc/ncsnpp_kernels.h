@@ -101,12 +101,12 @@ struct GemmArgs {
     // tensor's (single) consumer, written by the same epilogue instead of a k_gn_finalize launch: fin_scale / fin_shift [sample][fin_ld] get
     // rstd * gamma * fin_mul and (beta - mean * rstd * gamma) * fin_mul with the consumer's gamma / beta; fin_cg = channels per group
     float* fin_scale; float* fin_shift; const float* fin_gamma; const float* fin_beta; int fin_ld; int fin_cg; float fin_mul; float fin_eps;
-    // fused GroupNorm-apply + SiLU of the INPUT (k_conv_gn, conv_gn.h): a0 is the RAW, unpadded [B][H][W][a0_ld] tensor and every
+    // fused GroupNorm-apply + SiLU of the INPUT (k_conv_gn2 / k_conv_gn3, conv_gn2.h): a0 is the RAW, unpadded [B][H][W][a0_ld] tensor and every
     // element is read as silu(a0 * gn_scale[b*gn_ld + c] + gn_shift[b*gn_ld + c]); a1 (1x1 shortcut segment) stays raw
     // gn_folded: scale / shift arrive multiplied by -log2(e) and the 3x3 weights by -ln 2 (the kernel then computes t = x*scale + shift,
     // t / (1 + exp2(t)) = -log2(e) * silu(v): two vector instructions per element fewer); 0: plain scale / shift / weights
     const float* gn_scale; const float* gn_shift; int gn_ld; int gn_folded;
-    // k_conv_gn2: the weights of a gn_scale launch once more, fragment-major (k_pack_frag); NULL -> k_conv_gn (LDS weight ring)
+    // k_conv_gn2: the weights of a gn_scale launch once more, fragment-major (k_pack_frag); required by every gn_scale launch
     const bf16* b_frag;
     // k_conv_gn2: 1 = the first blocks of every XCD request the whole fragment-major weight matrix once at kernel start (one 4-byte load per 128-byte
     // line, results discarded), in K order: the K loop's one-tap-ahead weight stream then hits L2 instead of paying a memory round trip per tap
@@ -531,7 +531,7 @@ __global__ __launch_bounds__(256) void k_gn_stats(const bf16* __restrict__ x, in
     for (int c = tid; c < C; c += 256) {
         const int gi = c / cg;
         const float sc = s_rstd[gi] * gamma[c];
-        // out_mul: 1, or -log2(e) when the consumer is k_conv_gn in folded form (it then gets exp(-v) = exp2(x*scale + shift) at once)
+        // out_mul: 1, or -log2(e) when the consumer is k_conv_gn2 in folded form (it then gets exp(-v) = exp2(x*scale + shift) at once)
         scale[(int64_t)b * C + c] = sc * out_mul;
         shift[(int64_t)b * C + c] = (beta[c] - s_mean[gi] * sc) * out_mul;
     }
@@ -585,7 +585,7 @@ __global__ __launch_bounds__(256) void k_gn_finalize(const float2* __restrict__ 
         float var = q * inv - mean * mean;
         var = var < 0.f ? 0.f : var;
         const float sc = (1.0f / sqrtf(var + eps)) * ga[k];
-        // out_mul: 1, or -log2(e) when the consumer is k_conv_gn in folded form (it then gets exp(-v) = exp2(x*scale + shift) at once)
+        // out_mul: 1, or -log2(e) when the consumer is k_conv_gn2 in folded form (it then gets exp(-v) = exp2(x*scale + shift) at once)
         scale[(int64_t)b * C + c] = sc * out_mul;
         shift[(int64_t)b * C + c] = (be[k] - mean * sc) * out_mul;
     }
@@ -783,7 +783,7 @@ __global__ void k_pack_conv(const float* __restrict__ src, bf16* __restrict__ ds
     if (i >= (int64_t)N * Cin * taps) return;
     const int tap = (int)(i % taps); const int64_t r = i / taps; const int c = (int)(r % Cin); const int n = (int)(r / Cin);
     const int k = chunked ? ((c >> 6) * taps + tap) * 64 + (c & 63) : tap * tap_stride_c + c;
-    dst[(int64_t)n * dst_ld + koff + k] = (bf16)(src[i] * wmul);      // wmul: 1, or -ln 2 for the 3x3 weights of a folded k_conv_gn launch
+    dst[(int64_t)n * dst_ld + koff + k] = (bf16)(src[i] * wmul);      // wmul: 1, or -ln 2 for the 3x3 weights of a folded k_conv_gn2 launch
 }
 // src [K][N] (NIN.W) -> dst[n*dst_ld + k]
 __global__ void k_pack_transpose(const float* __restrict__ src, bf16* __restrict__ dst, int K, int N, int dst_ld)

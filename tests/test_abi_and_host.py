@@ -261,7 +261,7 @@ def test_generation_pipeline_host_logic(tmp_path):
     for h in (h1, h2, h3):
         lib.natinf_ncsnpp_destroy(h)
     assert lib.natinf_set_flash_mode(7) == -1 and lib.natinf_set_flash_mode(3) == 0 and lib.natinf_set_flash_mode(0) == 0 and lib.natinf_set_flash_mode(3) == 0
-    assert lib.natinf_set_flash_mode(1) in (0, -4) and lib.natinf_set_flash_mode(3) == 0           # intermediate forms: -DNATINF_DEV builds only
+    assert lib.natinf_set_flash_mode(1) in (0, -4) and lib.natinf_set_flash_mode(3) == 0           # intermediate forms: retired
 
 
 def test_bench_line_stays_small(repo_root):

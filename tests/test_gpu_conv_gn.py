@@ -1,4 +1,4 @@
-"""k_conv_gn2 / k_conv_gn (csrc/conv_gn2.h: weights streamed through registers; csrc/conv_gn.h: through an LDS ring) on their own: the 3x3 convolution with GroupNorm-apply + SiLU fused into its operand path, against
+"""k_conv_gn2 (csrc/conv_gn2.h: weights streamed through registers) on its own: the 3x3 convolution with GroupNorm-apply + SiLU fused into its operand path, against
 plain PyTorch fp32 of the same op -- conv2d(silu(x * scale + shift), w, padding=1) + 1x1 shortcut + bias + residual, scaled
 (reference arithmetic: ResnetBlockBigGANpp.forward, deps/score_sde_pytorch/models/layerspp.py:242-274).  Inputs are made
 bf16-representable and the activated operand is rounded to bf16 in the reference too, so what remains is fp32 accumulation order
@@ -74,8 +74,8 @@ def test_conv_gn_matches_torch(res, B, cin, N, c1, resid, parts):
     wf = torch.zeros_like(wd)                              # receives the fragment-major copy of the weights (k_conv_gn2)
     lib.natinf_set_conv_gn_w128(0)                      # this file is about k_conv_gn2 (k_conv_gn3, which takes the long-K launches by default: tests/test_gpu_conv_gn3.py)
     try:
-        assert lib.natinf_set_conv_gn_regw(0) != 0          # k_conv_gn (weights through an LDS ring): -DNATINF_DEV builds only
-        assert lib.natinf_set_conv_gn8_tile(0) != 0         # the two-images-per-tile form of the 8x8 level: -DNATINF_DEV builds only
+        assert lib.natinf_set_conv_gn_regw(0) != 0          # k_conv_gn (weights through an LDS ring): retired
+        assert lib.natinf_set_conv_gn8_tile(0) != 0         # the two-images-per-tile form of the 8x8 level: retired
         for use_wide, regw in (((1, 1), (0, 1)) if wide else ((1, 1),)):
             lib.natinf_set_conv_gn_wide(3 if use_wide else 0)
             rows = res * res if res <= 8 else (128 if (wide and use_wide) else 256)      # (8x8 / 4x4: one partial row per SAMPLE)
@@ -98,7 +98,7 @@ def test_conv_gn_matches_torch(res, B, cin, N, c1, resid, parts):
         lib.natinf_set_conv_gn_w128(7)                  # the library's default, restored on the failure path too (round-5 advisor note)
 
 def test_ragged_channel_counts_are_refused_in_the_shipped_build():
-    """k_conv_gn2 needs whole 128- (or 256-) channel tiles; the LDS-ring kernel that took ragged N is a -DNATINF_DEV kernel now."""
+    """k_conv_gn2 needs whole 128- (or 256-) channel tiles; the LDS-ring kernel that took ragged N is retired."""
     from naturaldiffusion_amd._lib import lib, ptr, stream_ptr
     dev = "cuda"
     x = torch.zeros(1, 16, 16, 64, dtype=torch.bfloat16, device=dev); sc = torch.ones(1, 64, device=dev); sh = torch.zeros(1, 64, device=dev)

@@ -15,7 +15,7 @@ def flash_mode(request):
     from naturaldiffusion_amd._lib import lib, check
     rc = lib.natinf_set_flash_mode(request.param)
     if rc == -4 and request.param in (1, 2):                # NATINF_ESTATE
-        pytest.skip("modes 1 / 2 (intermediate forms) exist in -DNATINF_DEV builds only")
+        pytest.skip("modes 1 / 2 (intermediate forms) are retired")
     check(rc, "natinf_set_flash_mode")
     yield request.param
     check(lib.natinf_set_flash_mode(3), "natinf_set_flash_mode")              # the library's default

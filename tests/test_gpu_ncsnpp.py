@@ -129,7 +129,7 @@ def test_every_gemm_variant_gives_the_same_network(dev, flat, golden_dir):
     outs = {}
     try:
         # 26 / 27 (dma256x256h / dma512x128h) are the automatic choices of the big launches at B = 512, 9 / 17 / 8 of the rest;
-        # the superseded pipelines (2-7, 10-16, 18-22, 24, 25) exist in -DNATINF_DEV builds only and are refused here
+        # the superseded pipelines (2-7, 10-16, 18-22, 24, 25) are retired and refused
         for v in (2, 3, 4, 5, 6, 7, 10, 11, 12, 13, 14, 15, 16, 18, 19, 20, 21, 22, 24, 25):
             assert lib.natinf_set_gemm_variant(v) != 0, v
         for v in (0, 1, 8, 9, 17, 26, 27):
@@ -273,7 +273,7 @@ def test_fused_and_split_k_plans_against_the_unfused_plan(dev, flat, golden_dir)
         assert torch.isfinite(y).all()
         assert _rel(y.cpu(), base.cpu()) < 2e-2, (name, _rel(y.cpu(), base.cpu()))
         assert _rel(y[:2].cpu(), ref) <= TOL, name
-    assert lib.natinf_set_conv_gn8_tile(0) != 0 and lib.natinf_set_conv_gn8_tile(1) == 0      # the two-image tile of the 8x8 level: development builds only
+    assert lib.natinf_set_conv_gn8_tile(0) != 0 and lib.natinf_set_conv_gn8_tile(1) == 0      # the two-image tile of the 8x8 level: retired
     # the fp32-slab A/B knob no longer breaks the fused plan (round-2 advisor, medium): the fused convolutions ignore it
     try:
         assert lib.natinf_set_gemm_epilogue(1) == 0

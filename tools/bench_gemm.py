@@ -1,5 +1,5 @@
 """Micro-benchmark of the GEMM kernel variants on the engine's dominant layer shapes (GPU box).
-usage: bench_gemm.py [variant ids ...]      (default: all DMA / ring variants)"""
+usage: bench_gemm.py [variant ids ...]      (default: the tile variants the dispatcher selects)"""
 import sys, ctypes as C
 from pathlib import Path
 import torch
@@ -7,7 +7,7 @@ ROOT = Path(__file__).resolve().parent.parent
 sys.path.insert(0, str(ROOT))
 from naturaldiffusion_amd._lib import lib, check, stream_ptr
 
-NAMES = {0: "auto", 1: "generic128", 2: "dma256x256", 3: "dma256x128", 4: "dma128x128", 5: "ring256x256", 6: "ring256x128", 7: "ring128x128", 8: "ring64x128", 9: "ring256x128w4", 10: "dma256x128w4", 11: "dma256x256s", 12: "dma128x128s", 13: "dma512x128", 14: "patch256x256", 15: "patch256x128", 16: "dma256x256p", 17: "dma128x128p", 18: "dma256x128w4p", 19: "gemm8ph", 20: "gemm8ph_np", 21: "gemm8ph_rf", 22: "gemm8ph_nprf", 23: "fp8", 24: "abl_nodma", 25: "abl_nomfma", 26: "dma256x256h", 27: "dma512x128h", 28: "conv_gn", 29: "w128_256x256", 30: "w128_schA", 31: "w128_prefetch", 32: "w128_no_dma"}
+NAMES = {0: "auto", 1: "generic128", 8: "ring64x128", 9: "ring256x128w4", 17: "dma128x128p", 26: "dma256x256h", 27: "dma512x128h", 29: "w128_256x256"}      # the ids natinf_debug_gemm accepts
 dev = torch.device("cuda:0")
 torch.manual_seed(0)
 
@@ -73,25 +73,8 @@ SHAPES = [  # (M, N, K0, K1, taps, res)  -- B=512 layer shapes, largest time fir
 ]
 if __name__ != "__main__":
     SHAPES = []
-if len(sys.argv) > 1 and sys.argv[1] == "8ph":
-    # correctness of the 256x256 variants on 256-aligned shapes (many repeats: the schedule is race-prone by nature), then speed
-    vs = [16, 19, 20, 21, 22]
-    for v in vs:
-        for rep in range(1):
-            errs = [run(v, 1024, 512, 256, 128, 1, 0, iters=2, check_ref=True)[2], run(v, 2048, 256, 1536, 0, 1, 0, iters=2, check_ref=True)[2],
-                    run(v, 512, 768, 64, 0, 1, 0, iters=2, check_ref=True)[2], run(v, 256, 256, 128, 64, 1, 0, iters=2, check_ref=True)[2]]
-            cerr = [check_conv(v, *c) for c in ((4, 16, 256, 256, 128), (8, 8, 128, 256, 64), (1, 32, 192, 256, 64), (2, 32, 64, 512, 0))]
-            print(f"check {NAMES[v]:>12}: gemm " + " ".join(f"{e:.1e}" for e in errs) + " | conv " + " ".join(f"{e:.1e}" for e in cerr), flush=True)
-    shapes = [(131072, 256, 2304, 0, 9, 16), (131072, 256, 4608, 0, 9, 16), (524288, 256, 2304, 256, 9, 32), (32768, 256, 2304, 0, 9, 8),
-              (32768, 1536, 1536, 0, 1, 0), (32768, 6144, 1536, 0, 1, 0), (32768, 1536, 6144, 0, 1, 0), (32768, 3072, 1536, 0, 1, 0),
-              (8192, 8192, 8192, 0, 1, 0), (4096, 4096, 4096, 0, 1, 0)]
-    print(f"{'shape':>34} " + " ".join(f"{NAMES[v]:>12}" for v in vs))
-    for (M, N, K0, K1, taps, res) in shapes:
-        cells = [f"{run(v, M, N, K0, K1, taps, res, iters=10)[1]:7.0f}TF/s" for v in vs]
-        print(f"{str((M, N, K0 + K1, taps)):>34} " + " ".join(f"{c:>12}" for c in cells), flush=True)
-    sys.exit(0)
 if len(sys.argv) > 1 and sys.argv[1] == "sd3":
-    vs = [int(v) for v in sys.argv[2:]] or [9, 10, 18, 16, 19, 13]
+    vs = [int(v) for v in sys.argv[2:]] or [9, 26, 27, 29]
     shapes = [(32768, 1536, 1536, 0, 1, 0), (32768, 3072, 1536, 0, 1, 0), (32768, 6144, 1536, 0, 1, 0), (32768, 1536, 6144, 0, 1, 0),
               (65536, 1152, 1152, 0, 1, 0), (65536, 4608, 1152, 0, 1, 0), (65536, 1152, 4608, 0, 1, 0)]
     print(f"{'shape':>34} " + " ".join(f"{NAMES[v]:>13}" for v in vs))
@@ -107,7 +90,7 @@ if len(sys.argv) > 1 and sys.argv[1] == "one":
     ms, tf, _ = run(v, M, N, K0, K1, taps, res, iters=it)
     print(f"{NAMES[v]} {(M, N, K0 + K1, taps)}: {ms*1e3:.1f} us  {tf:.0f} TF/s")
     sys.exit(0)
-variants = ([int(v) for v in sys.argv[1:]] or [26, 27, 4, 6, 8]) if __name__ == "__main__" else []      # (imported by bench_blaslt.py: nothing runs; the defaults are shipped variants)
+variants = ([int(v) for v in sys.argv[1:]] or [26, 27, 8]) if __name__ == "__main__" else []      # (imported by bench_blaslt.py: nothing runs; the defaults are shipped variants)
 # correctness (plain GEMM with both K segments) for every variant first
 for v in variants:
     ms, tf, err = run(v, 1000, 384, 256, 128, 1, 0, iters=2, check_ref=True)
@@ -115,8 +98,6 @@ for v in variants:
 for v in variants:
     errs = []
     for (Bn, res, Cin, N, K1) in ((5, 32, 128, 128, 0), (3, 16, 256, 256, 128), (9, 8, 128, 256, 64), (2, 32, 192, 128, 64)):
-        if v == 14 and res < 16:
-            continue
         errs.append(check_conv(v, Bn, res, Cin, N, K1))
     print(f"conv check {NAMES[v]:>12}: " + " ".join(f"{e:.2e}" for e in errs))
 if variants: print(f"{'shape':>34} " + " ".join(f"{NAMES[v]:>12}" for v in variants))

@@ -35,7 +35,7 @@ def where(name):
 
 out = ["# tools/ -- measurement and A/B scripts (GPU box unless noted)\n",
        "Not product code: nothing under `naturaldiffusion_amd/` imports from here.  Every script names what it measures in its docstring; the DESIGN.md section (or README) that quotes its numbers is",
-       "given where one does (`-` = used by another tool, the Makefile or a test only).  Development libraries (`-DNATINF_DEV`, tile-timeline stamps) are built as the csrc/Makefile header says",
+       "given where one does (`-` = used by another tool, the Makefile or a test only).  Instrumentation libraries (`-DNATINF_DEV`: tile-timeline stamps) are built as the csrc/Makefile header says",
        "and selected with `NATINF_LIB=<path to .so>`.  This file is generated: `python tools/index_tools.py`.\n", "| script | what it does | cited in |", "|---|---|---|"]
 for f, d in rows:
     out.append("| `%s` | %s | %s |" % (f, d.replace("|", "/"), where(f.rstrip("/"))))
