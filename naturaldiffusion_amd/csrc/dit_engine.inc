@@ -1,5 +1,5 @@
-// dit_engine.inc -- DiT denoiser engine (C ABI of include/natinf_dit.h); included at the end of ncsnpp.hip so it
-// shares the GEMM kernel family, the variant chooser and the packing kernels.
+// dit_engine.inc -- DiT denoiser engine (C ABI of include/natinf_dit.h); included at the end of ncsnpp.hip: one translation
+// unit with the GEMM launch layer (gemm_launch.h), the engine base (engine_core.h) and the packing kernels.
 //
 // One forward = patch-embed(+pos) -> conditioning (t-MLP + label row -> SiLU) -> ONE GEMM for every block's adaLN
 // modulation (6*depth+2 vectors per sample) -> depth x { LN+modulate, q|k GEMM, V^T GEMM, per-head QK^T / softmax /
@@ -7,6 +7,9 @@
 // -> LN+modulate -> linear -> unpatchify.  Residual stream fp32, GEMM operands bf16.
 // Reference: deps/DiT/models.py:19-20,27-99,105-146,222-253,279-326.
 #include "natinf_dit.h"
+#include "engine_core.h"
+#include "attn_fused.h"
+#include "dit_flash.h"
 
 namespace ncsn {
 
@@ -51,15 +54,6 @@ __global__ __launch_bounds__(256) void k_patch_embed(const float* __restrict__ z
         }
     }
 }
-// dst[k][n] = src[n][k]
-__global__ void k_transpose_f32(const float* __restrict__ src, float* __restrict__ dst, int N, int K)
-{
-    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= (int64_t)N * K) return;
-    const int n = (int)(i / K), k = (int)(i - (int64_t)n * K);
-    dst[(int64_t)k * N + n] = src[i];
-}
-
 // timestep frequency embedding [B][256] = [cos | sin] (models.py:41-58)
 __global__ void k_dit_time_freq(const float* __restrict__ t, bf16* __restrict__ emb, int B)
 {
@@ -283,32 +277,6 @@ __global__ void k_silu_bf16(const float* __restrict__ c, bf16* __restrict__ cs, 
 
 }  // namespace ncsn
 
-struct EngineCore {                      // what a transformer engine is: a launch plan over a packed-weight image
-    int64_t n_params = 0, packed_bytes = 0, ws_per_image = 0;
-    std::vector<OpFn> ops;
-    std::vector<PackFn> packs;
-    const unsigned char* packed = nullptr;
-    bool configured = false;
-    std::vector<int> part_bm{128};
-    int load(const float* params_f32, int64_t n, void* dst, int64_t dst_bytes, hipStream_t s) {
-        if (!params_f32 || !dst || n != n_params || dst_bytes < packed_bytes) return NATINF_EINVAL;
-        PackCtx p{params_f32, reinterpret_cast<unsigned char*>(dst), s};
-        for (const auto& f : packs) f(p);
-        packed = reinterpret_cast<const unsigned char*>(dst);
-        return hipGetLastError() == hipSuccess ? NATINF_OK : NATINF_ELAUNCH;
-    }
-    int run(const float* x, const float* t, float* out, int B, void* ws, int64_t ws_bytes, hipStream_t s, hipStream_t s2 = nullptr, hipEvent_t* ev = nullptr) {
-        if (!x || !t || !out || !ws || B <= 0) return NATINF_EINVAL;
-        if (!packed) return NATINF_ESTATE;
-        if (ws_bytes < ws_per_image * (int64_t)B) return NATINF_EINVAL;
-        if (!configured) { if (!configure_gemm_kernels()) return NATINF_ENODEV; configured = true; }
-        Ctx c{B, reinterpret_cast<unsigned char*>(ws), packed, s, x, t, out, part_bm.data()};
-        c.stream2 = s2; c.ev = ev;
-        for (const auto& f : ops) f(c);
-        return hipGetLastError() == hipSuccess ? NATINF_OK : NATINF_ELAUNCH;
-    }
-};
-
 struct natinf_dit : EngineCore {
     int depth = 0, D = 0, heads = 0, hd = 0, nmod = 0;
     int input_size = 32, T = 256;        // latent side S and tokens (S / 2)^2: natinf_dit_create_sized
@@ -331,58 +299,10 @@ void launch_attn(const bf16* qkv, bf16* o, int B, int D, int H, int hd, hipStrea
     hipLaunchKernelGGL(kern, dim3((unsigned)(B * H)), dim3(Cfg::THREADS), Cfg::LDS_BYTES, s, qkv, 3 * D, D, qkv + 2 * D, o, D, H, hd,
                        1.0f / sqrtf((float)hd));
 }
-bool configure_dit_attention() {
+bool configure_dit_attention() {      // (k_attn_fused<2,4> / <3,5> / <3,6> with v as V^T: superseded by these row-major-v forms)
     return set_lds<AttnCfg<2, 4>>(&k_attn_fused<2, 4, false, true>) && set_lds<AttnCfg<3, 5>>(&k_attn_fused<3, 5, false, true>) &&
            set_lds<AttnCfg<3, 6>>(&k_attn_fused<3, 6, false, true>);
 }
-
-struct PlanBuilder {
-    EngineCore& E;
-    Arena arena;
-    int64_t wtop = 0, poff = 0;
-    explicit PlanBuilder(EngineCore& e) : E(e) {}
-    int64_t wres(int64_t bytes) { const int64_t o = wtop; wtop += align_up(bytes, 256); return o; }
-    int64_t take(int64_t n) { const int64_t o = poff; poff += n; return o; }
-    void op(OpFn f) { E.ops.push_back(std::move(f)); }
-    int64_t pack_bf16(int64_t src, int rows, int cols) {             // [rows][cols] fp32 -> bf16, same layout
-        const int64_t dst = wres((int64_t)rows * cols * 2);
-        E.packs.push_back([=](const PackCtx& p) {
-            const int64_t n = (int64_t)rows * cols;
-            hipLaunchKernelGGL(k_pack_conv, dim3(grid1d(n, 256, 1 << 30)), dim3(256), 0, p.stream, p.params + src,
-                               reinterpret_cast<bf16*>(p.packed + dst), rows, cols, 1, cols, 0, cols, 0, 1.0f);
-        });
-        return dst;
-    }
-    void pack_bf16_at(int64_t src, int rows, int cols, int64_t dst) {
-        E.packs.push_back([=](const PackCtx& p) {
-            const int64_t n = (int64_t)rows * cols;
-            hipLaunchKernelGGL(k_pack_conv, dim3(grid1d(n, 256, 1 << 30)), dim3(256), 0, p.stream, p.params + src,
-                               reinterpret_cast<bf16*>(p.packed + dst), rows, cols, 1, cols, 0, cols, 0, 1.0f);
-        });
-    }
-    int64_t pack_f32(int64_t src, int64_t n) {
-        const int64_t dst = wres(n * 4);
-        pack_f32_at(src, n, dst);
-        return dst;
-    }
-    int64_t pack_f32_transposed(int64_t src, int rows, int cols) {     // [rows][cols] -> [cols][rows]
-        const int64_t dst = wres((int64_t)rows * cols * 4);
-        E.packs.push_back([=](const PackCtx& p) {
-            const int64_t n = (int64_t)rows * cols;
-            hipLaunchKernelGGL(k_transpose_f32, dim3(grid1d(n, 256, 1 << 30)), dim3(256), 0, p.stream, p.params + src,
-                               reinterpret_cast<float*>(p.packed + dst), rows, cols);
-        });
-        return dst;
-    }
-    void pack_f32_at(int64_t src, int64_t n, int64_t dst) {
-        E.packs.push_back([=](const PackCtx& p) {
-            hipLaunchKernelGGL(k_copy_add_f32, dim3(grid1d(n, 256, 1 << 30)), dim3(256), 0, p.stream, p.params + src,
-                               (const float*)nullptr, reinterpret_cast<float*>(p.packed + dst), (int)n);
-        });
-    }
-
-    void finish() { E.n_params = poff; E.packed_bytes = wtop; E.ws_per_image = arena.peak; }
-};
 
 struct DitBuilder : PlanBuilder {
     natinf_dit& E;

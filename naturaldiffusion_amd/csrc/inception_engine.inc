@@ -19,6 +19,8 @@
 //   * the stem fuses /255, the 299x299 bilinear resize (align_corners = False), 2x - 1 and the patch rows of Conv2d_1a_3x3 in one kernel;
 //   * 3x3 max / average pools (count_include_pad = False, the FID variant): row walkers (k_inc_pool); the final 8x8 average is a small bandwidth kernel.
 #include "natinf_inception.h"
+#include "engine_core.h"
+#include "conv_ring.h"
 
 namespace ncsn {
 

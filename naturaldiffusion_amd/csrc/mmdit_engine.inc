@@ -8,6 +8,8 @@
 // All adaLN linears of the network run as one GEMM per forward.  include/natinf_mmdit.h states what this replaces
 // and the parity status of that third-party arithmetic.
 #include "natinf_mmdit.h"
+#include "engine_core.h"
+#include "flash_attn.h"
 
 struct natinf_mmdit : EngineCore {
     int L = 0, H = 0, D = 0, Jd = 0, Pd = 0, C = 0, g = 0, Tx = 0, Tc = 0, Tp = 0, nmod = 0;
@@ -49,6 +51,10 @@ int g_mmdit_text_flat = 1;         // natinf_set_mmdit_text_flat: the text strea
 int g_mmdit_text_stream = 1;       // natinf_set_mmdit_text_stream: 1 = the text stream's launches of a block (M = 333 rows per sequence: 150 GFLOP per block at under a sixth of the chip's
                                    // rate when they run alone) go to a second HIP stream and join the image stream at the joint attention; 0 = one stream, one launch after the other
 int g_flash_mode = 3;              // natinf_set_flash_mode: 0 = k_flash_attn64, 3 = k_flash_attn64_v2<1, 64> (deferred re-referencing, scores leave the MFMA as exponents, row sums on the matrix pipe, 64-key tiles: 128 registers and 32 KiB of LDS per block, three to four waves per SIMD); default 3; 1 / 2: retired
+bool configure_flash_attention() {
+    return hipFuncSetAttribute(reinterpret_cast<const void*>(&k_flash_attn64), hipFuncAttributeMaxDynamicSharedMemorySize, FA_LDS_BYTES) == hipSuccess &&
+           hipFuncSetAttribute(reinterpret_cast<const void*>(&k_flash_attn64_v2<1, 64>), hipFuncAttributeMaxDynamicSharedMemorySize, FA_LDS_BYTES / 2) == hipSuccess;
+}
 void launch_flash(const bf16* q, const bf16* k, int ld_qk, int64_t qk_bs, const bf16* vT, bf16* o, int ld_o, int64_t o_bs, int B, int H,
                   int Tp, int T, float scale, hipStream_t s, uint8_t* o8 = nullptr, uint8_t* omx = nullptr) {
     FlashArgs a{q, k, ld_qk, qk_bs, vT, (int64_t)H * 64 * Tp, o, ld_o, o_bs, H, Tp, T, scale * 1.4426950408889634f, o8, omx};

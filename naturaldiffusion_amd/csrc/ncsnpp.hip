@@ -1,5 +1,7 @@
-// ncsnpp.hip -- host side of the NCSN++ denoiser engine: static execution plan, weight packing,
-// forward; C ABI of include/natinf_ncsnpp.h.  Kernels: ncsnpp_kernels.h.
+// ncsnpp.hip -- the one translation unit of the engines.  Its own code is the host side of the NCSN++ denoiser engine: the static execution
+// plan (Builder), weight packing, forward; the C ABI of include/natinf_ncsnpp.h with the natinf_debug_* / natinf_set_* entries.  The GEMM
+// launch layer every engine calls is gemm_launch.h, the engine base and the plan builder's shared recipes engine_core.h, the kernels
+// ncsnpp_kernels.h and the headers below; the other four engines are included at the end of this file.
 //
 // Design (MI355X-first, not a translation of the reference's nn.Module tree):
 //   * the network is compiled once into a flat op list (~330 launches) over ONE caller-supplied
@@ -27,21 +29,12 @@
 #include <vector>
 
 #include "natinf_ncsnpp.h"
-#include "ncsnpp_kernels.h"
-#include "gemm_dma.h"
-#include "gemm_w128.h"
-#include "conv_ring.h"
-#include "conv_gn2.h"
+#include "gemm_launch.h"
+#include "engine_core.h"
 #include "head_conv.h"
-#include "gemm_fp8.h"
-#include "attn_fused.h"
 #include "attn256.h"
 #include "attn_qkv.h"
 #include "attn_blk256.h"
-#include "flash_attn.h"
-#include "dit_flash.h"
-
-using namespace ncsn;
 
 namespace {
 
@@ -50,177 +43,15 @@ constexpr int CH_MULT[NLEVEL] = {1, 2, 2, 2};
 constexpr float GN_EPS = 1e-6f;
 constexpr float INV_SQRT2 = 0.70710678118654752440f;
 inline bool attn_at(int res) { return res == 16; }
-inline int ilog2(int v) { int l = 0; while ((1 << l) < v) ++l; return l; }
-inline int64_t align_up(int64_t v, int64_t a) { return (v + a - 1) / a * a; }
 
 enum Kind { K_LIN, K_CONV, K_RES, K_ATTN, K_GN, K_DOWN, K_UP };      // K_DOWN / K_UP: the plain resampling convolutions of the `ddpm` network
 const char* kind_name(int k) { static const char* n[] = {"lin", "conv", "res", "attn", "gn", "down", "up"}; return n[k]; }
 
 struct Mod { int idx, kind, cin, cout, up, down, res; int64_t poff; };
 
-// tensor reference inside the workspace: `off` is BYTES PER IMAGE (actual = off * B)
-// coff: channel offset inside a wider buffer; pad = 1: stored with a one-pixel zero border (3x3 GEMM inputs)
-struct TRef { int64_t off = -1; int C = 0, ld = 0, res = 0, coff = 0, pad = 0; };
-
-struct Ctx {                     // per-forward launch context
-    int B; unsigned char* ws; const unsigned char* wp; hipStream_t stream;
-    const float* x; const float* labels; float* out;
-    int* part_bm;                // [n_parts] block-tile rows (BM) of the GEMM variant that wrote each partial table
-    hipStream_t stream2 = nullptr; hipEvent_t* ev = nullptr;      // MMDiT engine: the text stream's own HIP stream and the fork / join events (null: everything on `stream`)
-    unsigned char* fin_done = nullptr;   // [n_parts] per FORWARD, like part_bm: the launch that wrote partial table i also wrote its consumer's GroupNorm table (see Fin).  Not plan
-                                         // state: a description pass (scratch array) or a second thread's forward on a shared plan cannot flip it under a running forward
-    bf16* act(const TRef& t) const { return reinterpret_cast<bf16*>(ws + t.off * B) + t.coff; }
-    template <class T> T* at(int64_t off) const { return reinterpret_cast<T*>(ws + off * B); }
-    template <class T> const T* w(int64_t off) const { return reinterpret_cast<const T*>(wp + off); }
-};
-using OpFn = std::function<void(const Ctx&)>;
 enum { CLS_GEMM = 0, CLS_OTHER = 1, CLS_CONV_GN = 2, CLS_CONV_GN8 = 3, N_CLS = 4 };      // CLS_CONV_GN: launches of the fused GroupNorm + SiLU + 3x3 conv kernel at 32x32 / 16x16; CLS_CONV_GN8: its 8x8 instantiation
 
-struct PackCtx { const float* params; unsigned char* packed; hipStream_t stream; };
-using PackFn = std::function<void(const PackCtx&)>;
-
-// first-fit arena over "bytes per image"
-struct Arena {
-    bool keep = false; int64_t top = 0, peak = 0;
-    std::map<int64_t, int64_t> free_;      // off -> size
-    std::map<int64_t, int64_t> live_;
-    int64_t alloc(int64_t bytes) {
-        bytes = align_up(bytes, 256);
-        if (!keep)
-            for (auto it = free_.begin(); it != free_.end(); ++it)
-                if (it->second >= bytes) {
-                    const int64_t off = it->first, rest = it->second - bytes;
-                    free_.erase(it);
-                    if (rest) free_[off + bytes] = rest;
-                    live_[off] = bytes;
-                    return off;
-                }
-        const int64_t off = top; top += bytes; if (top > peak) peak = top;
-        live_[off] = bytes;
-        return off;
-    }
-    void release(int64_t off) {
-        if (keep || off < 0) return;
-        auto it = live_.find(off);
-        if (it == live_.end()) return;
-        int64_t o = off, s = it->second;
-        live_.erase(it);
-        auto nx = free_.lower_bound(o);
-        if (nx != free_.end() && o + s == nx->first) { s += nx->second; nx = free_.erase(nx); }
-        if (nx != free_.begin()) { auto pv = std::prev(nx); if (pv->first + pv->second == o) { o = pv->first; s += pv->second; free_.erase(pv); } }
-        if (o + s == top) top = o; else free_[o] = s;
-    }
-};
-
-}  // namespace
-
-struct natinf_ncsnpp {
-    int flags = 0;
-    std::vector<Mod> mods;
-    int64_t n_params = 0;
-    std::vector<OpFn> ops;
-    std::vector<int> op_cls;             // CLS_* per op (profiling)
-    std::vector<PackFn> packs;
-    // profiling: one HIP event pair per op while enabled
-    bool prof = false;
-    struct Rec { hipEvent_t a, b; int cls; };
-    std::vector<Rec> recs;
-    std::vector<hipEvent_t> pool;
-    std::map<int, TRef> taps;            // module idx -> output tensor
-    int64_t ws_per_image = 0, packed_bytes = 0;
-    uint64_t plan_sig = 0;               // the natinf_set_* switches a plan reads when it is BUILT (they decide the pack offsets): natinf_ncsnpp_share compares them
-    const unsigned char* packed = nullptr;
-    bool attr_set = false;
-    int last_B = 0; unsigned char* last_ws = nullptr;
-    std::vector<int> part_bm;            // see Ctx::part_bm
-    std::vector<unsigned char> fin_done; // see Ctx::fin_done
-};
-
-// k_conv_gn3 (conv_gn3.h / conv_gn3.hip: one wave per SIMD, 128 x 128 wave tiles, slot-table K loop) -- a translation unit of its own
-bool configure_conv_ring();          // inception_engine.inc: the k_conv_ring instantiations' LDS sizes
-namespace { bool configure_dit_attention(); }      // dit_engine.inc: the row-major-v forms of k_attn_fused
-namespace ncsn_cg3 { bool configure(); int tile_rows(int shape); int tile_cols(int shape); void launch(const void* gemm_args, int shape, int epi, void* stream); }
-
-namespace {
-
-// ------------------------------------------------------------------------------------------------
-// launch helpers
-// ------------------------------------------------------------------------------------------------
-int g_epi_fp32_slab = 0;           // natinf_set_gemm_epilogue(1): every launch takes the fp32-slab epilogue (A/B runs)
-GemmArgs gemm_defaults() {
-    GemmArgs g;
-    memset(&g, 0, sizeof(g));
-    g.epi_fp32_slab = g_epi_fp32_slab;
-    g.taps = 1; g.batch = 1; g.scale = 1.0f; g.act = ACT_NONE; g.c_mode = OUT_BF16;
-    return g;
-}
-// ------------------------------------------------------------------------------------------------
-// GEMM kernel variants and the choice among them
-// ------------------------------------------------------------------------------------------------
-constexpr int NUM_CU = 256;
-enum GemmVariant {
-    V_AUTO = 0, V_GENERIC = 1,
-    V_DMA_256x256 = 2, V_DMA_256x128 = 3, V_DMA_128x128 = 4,          // (retired: 2-stage, BK = 64)
-    V_RING_256x256 = 5, V_RING_256x128 = 6, V_RING_128x128 = 7,       // (retired: NS-slot ring, BK = 32)
-    V_RING_64x128 = 8,                                                 // NS-slot ring, BK = 32
-    V_RING_256x128_W4 = 9,                                             // 4 waves, wave tile 128x64 (less LDS read traffic per MFMA)
-    V_DMA_256x128_W4 = 10,                                             // (retired: the same tile, two-stage)
-    V_DMA_256x256_S = 11, V_DMA_128x128_S = 12,                       // (retired: two-stage with the DMA issue spread between MFMA groups)
-    V_DMA_512x128 = 13,                                                // (retired: 8 waves x (128x64), every wave issuing its own DMA)
-    V_PATCH_256x256 = 14, V_PATCH_256x128 = 15,                        // (retired: 3x3 conv with an LDS-resident input patch)
-    V_DMA_256x256_P = 16, V_DMA_256x128W4_P = 18,                      // (retired: two-stage + hand-counted LDS fragment pipeline)
-    V_DMA_128x128_P = 17,                                              // two-stage + hand-counted LDS fragment pipeline
-    V_8PH_256x256 = 19, V_8PH_NOPRIO = 20, V_8PH_READFIRST = 21, V_8PH_BOTH = 22,   // (retired: phase-interleaved schedule, counted vmcnt)
-    V_FP8_256x256 = 23,                                                 // fp8 e4m3 operands (gemm_fp8.h); selected by GemmArgs::deq_m/deq_n callers only
-    V_ABL_NODMA = 24, V_ABL_NOMFMA = 25,                                // (retired: K-loop ablations)
-    V_DMA_256x256_H = 26, V_DMA_512x128_H = 27,                         // hand pipeline, DMA issued by one wave per SIMD only
-    V_CONV_GN = 28,                                                     // 3x3 conv with fused GroupNorm-apply + SiLU of its input (conv_gn2.h); GemmArgs::gn_scale callers only
-    V_W128 = 29,                                                        // 256x256x64, four waves with 128x128 wave tiles (one per SIMD, AGPR accumulators; gemm_w128.h)
-    V_W128_A = 30, V_W128_D = 31, V_W128_X = 32,                        // (retired: other K-loop schedules of k_gemm_w128)
-    V_COUNT
-};
-// Retired ids (superseded pipelines, tile shapes and ablations; their kernels are in git history before the commit that removed them): the numbering
-// stays, natinf_set_gemm_variant / natinf_debug_gemm refuse them with NATINF_ESTATE.
-const char* variant_name(int v) {
-    static const char* n[] = {"auto", "generic128", "dma256x256", "dma256x128", "dma128x128", "ring256x256", "ring256x128",
-                              "ring128x128", "ring64x128", "ring256x128w4", "dma256x128w4", "dma256x256s", "dma128x128s", "dma512x128", "patch256x256", "patch256x128", "dma256x256p", "dma128x128p", "dma256x128w4p", "gemm8ph", "gemm8ph_np", "gemm8ph_rf", "gemm8ph_nprf", "fp8_256x256", "abl_nodma", "abl_nomfma", "dma256x256h", "dma512x128h", "conv_gn", "w128_256x256", "w128_a", "w128_d", "w128_x"};
-    return v >= 0 && v < V_COUNT ? n[v] : "?";
-}
-// The library instantiates only the tile variants the dispatcher selects (choose_variant, splitk) plus the generic kernel; every other
-// variant of the enum is retired
-inline bool variant_shipped(int v) {
-    switch (v) {
-        case V_AUTO: case V_GENERIC: case V_RING_64x128: case V_RING_256x128_W4: case V_DMA_128x128_P: case V_FP8_256x256:
-        case V_DMA_256x256_H: case V_DMA_512x128_H: case V_CONV_GN: case V_W128: return true;
-        default: return false;
-    }
-}
-unsigned long long* g_dbg_ts = nullptr;
-int g_force_variant = V_AUTO;
-int g_round_model = 1;             // natinf_set_gemm_round_model(0): small-M plain GEMMs by the pre-round-4 rules (A/B runs)
-int g_round_model_w128 = 13;       // cost of a round of k_gemm_w128 tiles in tenths of a round of 128 x 128 tiles (two blocks per CU)
-int g_pref_512 = 1;                // N <= 128 layers with >= 2 tiles per CU: the 512x128 hand-pipelined tile (natinf_set_gemm_pref512: A/B runs)      // tuning / tests: force one variant for every DMA-eligible launch
-std::string* g_record = nullptr;   // when set, launch_gemm describes the launch instead of issuing it
-
-int g_raster_g = 8;                 // natinf_set_gemm_raster: row-tiles per raster group of wide-N launches (0 / 1 = plain row-major)
-template <class Cfg, class K>
-inline void launch_tiles(K kernel, const GemmArgs& g0, hipStream_t s) {
-    const int nM = (g0.M + Cfg::BM_ - 1) / Cfg::BM_, nN = (g0.N + Cfg::BN_ - 1) / Cfg::BN_;
-    GemmArgs g = g0;
-    g.raster_g = (g_raster_g > 1 && nN >= 8 && nM >= g_raster_g) ? g_raster_g : 0;
-    hipLaunchKernelGGL(kernel, dim3(nM * nN, 1, g.batch), dim3(Cfg::THREADS), Cfg::LDS_BYTES, s, g);
-}
-template <class Cfg, class K>
-inline bool set_lds(K kernel) {
-    return hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, Cfg::LDS_BYTES) == hipSuccess;
-}
-using CfgD256x256 = DmaCfg<2, 4, 8, 4>;  using CfgD128x128 = DmaCfg<2, 2, 4, 4>;
-using CfgR128x128 = RingCfg<2, 2, 4, 4, 4>; using CfgR64x128 = RingCfg<2, 2, 2, 4, 4>;
-using CfgR256x128W4 = RingCfg<2, 2, 8, 4, 3>;
-using CfgD512x128 = DmaCfg<4, 2, 8, 4>;
-using CfgH32 = ConvGn2Cfg<32>; using CfgH16 = ConvGn2Cfg<16>; using CfgH16W = ConvGn2Cfg<16, true>; using CfgH32W = ConvGn2Cfg<32, true>; using CfgH8T = ConvGn2Cfg<8, true, 4>; using CfgH4T = ConvGn2Cfg<4, true, 4, 2, 2>;
 int g_fuse_head = 1;               // natinf_set_fuse_head (read when a plan is BUILT): GroupNorm + SiLU + the 128 -> 3 output convolution as ONE launch (head_conv.h)
-// (the 8x8 level runs on 64-pixel x 256-channel tiles, one image per tile and two blocks per CU; the 128 x 256 tile with two images, natinf_set_conv_gn8_tile(0), is retired)
 constexpr int ATTN_BLK_DEFAULT = 2;
 int g_attn_blk = ATTN_BLK_DEFAULT;  // natinf_set_attn_block (read when a plan is BUILT): the whole 16x16 attention block as ONE launch -- 1: k_qkv256 + k_attn256<true, 8> in one kernel (attn_blk256.h: q stays in
                                    // registers, k / V^T through L2); 2 (default since round 6): k_attn_blk256_v2 -- q k^T and P V against h itself, h resident in LDS (forward -3.3 % at B = 512); 0: two launches
@@ -228,475 +59,48 @@ int g_attn_qkv = 1;                // natinf_set_attn_qkv (read when a plan is B
 int g_attn_w8 = 1;                 // natinf_set_attn_waves8: k_attn256<true> as one 8-wave block per sample (1) or two 4-wave blocks (0)
 int g_attn_proj = 1;               // natinf_set_attn_proj (read when a plan is BUILT): the 16x16 attention's output projection + skip + GroupNorm partials inside k_attn256
 int g_fuse_gn8 = 1;                // natinf_set_fuse_gn8 (read when a plan is BUILT): the 8x8 level on the fused kernel too (two images per 128-pixel tile)
-int g_cg_warm = 15;                // natinf_set_conv_gn_warm: bit mask by resolution (1: 4x4, 2: 8x8, 4: 16x16, 8: 32x32) of the fused-convolution launches that warm L2 with their weights
 int g_fuse_fin = 3;                // natinf_set_fuse_fin (read when a plan is BUILT): at 8x8 / 4x4 the fused convolution's epilogue writes the GroupNorm table of its
                                    // output's consumer itself (whole samples x all channels per tile) instead of a k_gn_finalize launch behind it
 int g_fuse_gn4 = 1;                // natinf_set_fuse_gn4 (read when a plan is BUILT): the 4x4 level on the fused kernel too (four images per 64-pixel tile) instead of
                                    // k_gn_apply + split-K GEMM + k_splitk_reduce + k_gn_stats
 int g_fuse_gn = 1;                 // natinf_set_fuse_gn (read when a plan is BUILT): GroupNorm-apply + SiLU inside the consuming 3x3 conv
-
-// Packed-epilogue specializations (EPI, gemm_dma.h) that exist per tile family, as bit masks: a launch whose epilogue is not
-// instantiated for its tile takes the general fp32-slab epilogue (EPI 0: the same terms, the same single rounding).  Who needs what:
-// 3 (SiLU) only the small time-embedding GEMMs; 4 (tanh-GELU), 7 (fp32 residual stream), 8 (row bias) the transformer engines, none
-// of which ever reaches the N <= 128 tile.
-constexpr unsigned EPI_ALL = 0x1FF;
-constexpr unsigned EPI_R64 = EPI_ALL, EPI_D128 = EPI_ALL, EPI_RW4 = EPI_ALL & ~(1u << 3), EPI_D256H = EPI_ALL & ~(1u << 3),
-                   EPI_D512H = EPI_ALL & ~((1u << 3) | (1u << 4) | (1u << 7) | (1u << 8)),
-                   EPI_W128 = EPI_ALL & ~((1u << 2) | (1u << 3) | (1u << 6));          // plain long-K GEMMs: the transformer engines (GroupNorm partials take the general epilogue there)
-template <unsigned MASK, int E, class F> inline void epi_case(F&& f) { if constexpr ((MASK >> E) & 1u) f(std::integral_constant<int, E>{}); }
-template <unsigned MASK, class F> inline bool for_each_epi(F&& f) {             // f(integral_constant<int, E>) -> bool, over the instantiated ones
-    bool ok = true;
-    auto one = [&](auto tag) { ok = ok && f(tag); };
-    epi_case<MASK, 0>(one); epi_case<MASK, 1>(one); epi_case<MASK, 2>(one); epi_case<MASK, 3>(one); epi_case<MASK, 4>(one);
-    epi_case<MASK, 5>(one); epi_case<MASK, 6>(one); epi_case<MASK, 7>(one); epi_case<MASK, 8>(one);
-    return ok;
-}
-#define NATINF_EPI_OF(tag) decltype(tag)::value
-bool set_lds_epi_all() {
-    return for_each_epi<EPI_D128>([](auto t) { return set_lds<CfgD128x128>(&k_gemm_dma<2, 2, 4, 4, 2, NATINF_EPI_OF(t)>); }) &&
-           for_each_epi<EPI_RW4>([](auto t) { return set_lds<CfgR256x128W4>(&k_gemm_ring<2, 2, 8, 4, 3, NATINF_EPI_OF(t)>); }) &&
-           for_each_epi<EPI_R64>([](auto t) { return set_lds<CfgR64x128>(&k_gemm_ring<2, 2, 2, 4, 4, NATINF_EPI_OF(t)>); }) &&
-           for_each_epi<EPI_D256H>([](auto t) { return set_lds<CfgD256x256>(&k_gemm_dma<2, 4, 8, 4, 6, NATINF_EPI_OF(t)>); }) &&
-           for_each_epi<EPI_D512H>([](auto t) { return set_lds<CfgD512x128>(&k_gemm_dma<4, 2, 8, 4, 6, NATINF_EPI_OF(t)>); }) &&
-           for_each_epi<EPI_W128>([](auto t) { return set_lds<W128Cfg>(&k_gemm_w128<NATINF_EPI_OF(t)>); }) && set_lds<W128Cfg>(&k_gemm_w128<9>);
-}
-template <int EPI>
-bool set_lds_conv_gn() {
-    return set_lds<CfgH32>(&k_conv_gn2<32, false, EPI>) && set_lds<CfgH32W>(&k_conv_gn2<32, true, EPI>) && set_lds<CfgH16>(&k_conv_gn2<16, false, EPI>) && set_lds<CfgH16W>(&k_conv_gn2<16, true, EPI>) &&
-           set_lds<CfgH8T>(&k_conv_gn2<8, true, EPI, 4>) && set_lds<CfgH4T>(&k_conv_gn2<4, true, EPI, 4, 2, 2>);
-}
-
-bool configure_gemm_kernels() {
-    bool ok = hipFuncSetAttribute(reinterpret_cast<const void*>(&k_gemm_bf16), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                  GEMM_LDS_BYTES) == hipSuccess;
-    ok = ok && hipFuncSetAttribute(reinterpret_cast<const void*>(&k_head_conv), hipFuncAttributeMaxDynamicSharedMemorySize, HeadConvCfg::LDS_BYTES) == hipSuccess &&
-         set_lds<CfgR128x128>(&k_gemm_ring<2, 2, 4, 4, 4, 9>) &&
-         set_lds_epi_all() && ncsn_cg3::configure() && ::configure_conv_ring() && configure_dit_attention() && set_lds_conv_gn<1>() && set_lds_conv_gn<2>() && set_lds_conv_gn<5>() && set_lds_conv_gn<6>() &&
-         set_lds<CfgD256x256>(&k_gemm_fp8<false, 0>) && set_lds<CfgD256x256>(&k_gemm_fp8<true, 0>) &&
-         set_lds<CfgD256x256>(&k_gemm_fp8<false, 1>) && set_lds<CfgD256x256>(&k_gemm_fp8<true, 1>) &&
-         set_lds<CfgD256x256>(&k_gemm_fp8<false, 2>) && set_lds<CfgD256x256>(&k_gemm_fp8<true, 2>) &&
-         set_lds<CfgD256x256>(&k_gemm_fp8<false, 3>) && set_lds<CfgD256x256>(&k_gemm_fp8<true, 3>) &&
-         set_lds<W128F8Cfg>(&k_gemm_w128_fp8<false, 0>) && set_lds<W128F8Cfg>(&k_gemm_w128_fp8<true, 0>) && set_lds<W128F8Cfg>(&k_gemm_w128_fp8<false, 1>) && set_lds<W128F8Cfg>(&k_gemm_w128_fp8<true, 1>) &&
-         set_lds<W128F8Cfg>(&k_gemm_w128_fp8<false, 2>) && set_lds<W128F8Cfg>(&k_gemm_w128_fp8<true, 2>) && set_lds<W128F8Cfg>(&k_gemm_w128_fp8<false, 3>) && set_lds<W128F8Cfg>(&k_gemm_w128_fp8<true, 3>) &&
-         hipFuncSetAttribute(reinterpret_cast<const void*>(&k_qkv256), hipFuncAttributeMaxDynamicSharedMemorySize, QKV_LDS_BYTES) == hipSuccess &&
-         hipFuncSetAttribute(reinterpret_cast<const void*>(&k_attn256<false>), hipFuncAttributeMaxDynamicSharedMemorySize, A256_LDS_BYTES) == hipSuccess &&
-         hipFuncSetAttribute(reinterpret_cast<const void*>(&k_attn256<true>), hipFuncAttributeMaxDynamicSharedMemorySize, A256_LDS_BYTES) == hipSuccess &&
-         hipFuncSetAttribute(reinterpret_cast<const void*>(&k_attn256<true, 8>), hipFuncAttributeMaxDynamicSharedMemorySize, A256_LDS_BYTES) == hipSuccess &&
-         hipFuncSetAttribute(reinterpret_cast<const void*>(&k_attn_blk256), hipFuncAttributeMaxDynamicSharedMemorySize, ABLK_LDS_BYTES) == hipSuccess &&
-         hipFuncSetAttribute(reinterpret_cast<const void*>(&k_attn_blk256_v2), hipFuncAttributeMaxDynamicSharedMemorySize, ABLK2_LDS_BYTES) == hipSuccess &&
-         // (k_attn_fused<2,4> / <3,5> / <3,6> with v as V^T: superseded by the row-major-v forms of the DiT engine, configure_dit_attention)
-         hipFuncSetAttribute(reinterpret_cast<const void*>(&k_flash_attn64), hipFuncAttributeMaxDynamicSharedMemorySize, FA_LDS_BYTES) == hipSuccess &&
-         hipFuncSetAttribute(reinterpret_cast<const void*>(&k_flash_attn64_v2<1, 64>), hipFuncAttributeMaxDynamicSharedMemorySize, FA_LDS_BYTES / 2) == hipSuccess;
-    if (!ok) (void)hipGetLastError();
-    return ok;
-}
-
-// Automatic choice: the largest block tile that still gives every CU a tile (DMA kernels need K a multiple of
-// 64 per segment and zero-bordered 3x3 operands); the register-staged, fully masked kernel otherwise (4x4
-// attention: K = 16).
-
-int variant_bm(int v);
-int packed_epi(const GemmArgs& g, int bm);
-int g_cg3 = 7;                     // natinf_set_conv_gn_w128: bit 0 = 32x32 layers with N % 256 != 0 on 512 x 128 tiles, bit 1 = 32x32 layers with N % 256 == 0 on 256 x 256
-                                   // tiles, bit 2 = 16x16 layers with N % 256 == 0 on 256 x 256 tiles (one image per tile)
-int g_cg_wide = 3;                 // natinf_set_conv_gn_wide: bit 0 = 128 x 256 tiles at 16x16, bit 1 = at 32x32 (N % 256 == 0 layers: the 16 -> 32 up-sampling block)
 int g_fuse_up = 1;                 // natinf_set_fuse_up (read when a plan is BUILT): up blocks at 16x16 / 32x32 fetch their input up-sampled inside k_conv_gn2
-// tile rows of the fused-convolution instantiation a launch takes: 128 x 256 tiles at 16x16 (N % 256 == 0) and at 8x8 (two images per tile), 256 x 128 elsewhere
-// the k_conv_gn3 shape a fused-convolution launch takes (-1: k_conv_gn2).  One block per CU exposes a tile's prologue and epilogue (~28k clocks), which the two
-// co-resident blocks of k_conv_gn2 partly hide: k_conv_gn3 is ahead where the K loop is long (same-process A/B at B = 512, profiles/r05/cg3_v2_ab.log: 1.04-1.08 at
-// K >= 2,304 on 512 x 128 tiles, 1.035-1.04 on 256 x 256 tiles at 32x32, 1.01-1.06 at K >= 2,816 at 16x16; inside the network, rocprofv3 trace of both in one process, profiles/r05/cg3_in_network_ab_by_shape.txt: 1.08-1.15 at K >= 2,304 at 32x32, 1.02-1.09 at K >= 2,304 at 16x16) and level or behind at short K (0.97-0.99 at K = 1,152 .. 1,536)
-int g_cg3_min_k[3] = {2304, 0, 2304};      // natinf_set_conv_gn_w128_min_k: smallest K (9 cin + shortcut channels) per shape that takes k_conv_gn3
-inline int conv_gn3_shape(const GemmArgs& g) {
-    const int res = 1 << g.logW;
-    if (!g_cg3 || !g.b_frag || g.N % 128) return -1;
-    int sh = -1;
-    if (res == 32) sh = g.N % 256 ? ((g_cg3 & 1) ? 0 : -1) : ((g_cg3 & 2) ? 1 : -1);
-    else if (res == 16) sh = (g.N % 256 == 0 && (g_cg3 & 4)) ? 2 : -1;
-    if (sh >= 0 && 9 * g.a0_C + (g.a1 ? g.a1_C : 0) < g_cg3_min_k[sh]) sh = -1;
-    return sh;
-}
-inline int conv_gn_bm(const GemmArgs& g) {
-    const int res = 1 << g.logW;
-    if (const int sh3 = conv_gn3_shape(g); sh3 >= 0) return ncsn_cg3::tile_rows(sh3);
-    if (res == 8 || res == 4) return 64;
-    if (res == 32) return ((g_cg_wide & 2) && g.N % 256 == 0 && g.b_frag) ? 128 : 256;
-    return ((g_cg_wide & 1) && res == 16 && g.N % 256 == 0) ? 128 : 256;
-}
-// rows of one GroupNorm-partial table row the launch writes (what the caller divides H*W by): a tile, or one SAMPLE of the two an 8x8 tile holds
-inline int conv_gn_part_rows(const GemmArgs& g) { const int res = 1 << g.logW; return res <= 8 ? res * res : conv_gn_bm(g); }
-inline bool conv_gn_regw(const GemmArgs& g) { return g.b_frag && (conv_gn3_shape(g) >= 0 || g.N % ((conv_gn_bm(g) <= 128 && (1 << g.logW) != 4) ? 256 : 128) == 0); }      // (4x4: 64 x 128 tiles)
-// k_conv_gn2 / k_conv_gn3 have packed epilogues only: the fp32-slab A/B knob (natinf_set_gemm_epilogue) does not apply to them.  Per-sample terms need
-// one sample per tile -- or, at 8x8, per HALF tile (the kernel keeps both samples' row vectors and partials: NSAMP)
-inline int conv_gn_epi(const GemmArgs& g) { GemmArgs t = g; t.epi_fp32_slab = 0; return packed_epi(t, conv_gn_part_rows(g)); }
-inline bool conv_gn_ok(const GemmArgs& g) {
-    if (!g.gn_scale || !g.gn_shift || !g.gn_folded || g.taps != 9 || g.batch != 1 || g.a0_C % BK || (g.a1 && g.a1_C % BK)) return false;
-    const int res = 1 << g.logW;
-    if (g.logHW != 2 * g.logW || (res != 32 && res != 16 && res != 8 && res != 4) || g.N % 8) return false;
-    if (res == 4 && (g.a0_C % (64 * CfgH4T::NG) || (g.a1 && g.a1_C % (64 * CfgH4T::NG)))) return false;          // two K groups per block: an even number of half-chunks / shortcut tiles EACH
-    if (res <= 8 ? (g.M % (res * res) || g.N % (res == 4 ? 128 : 256) || g.a0_up || g.a1_up || (g.resid && g.rowvec)) : g.M % std::max(256, conv_gn_bm(g)) != 0) return false;      // 8x8 / 4x4: whole images;
-    // (the residual epilogues keep one set of column terms for all samples of a tile: no per-sample row vector there)
-    if (!conv_gn_regw(g)) return false;                                                       // the fragment-major weights, whole column tiles
-    const int e = conv_gn_epi(g);
-    return e == 1 || e == 2 || e == 5 || e == 6;
-}
-int g_w128 = 1;                     // natinf_set_gemm_w128(0): plain GEMMs on the two-waves-per-SIMD 256x256 tile as before round 4 (A/B runs)
-// k_gemm_w128 (gemm_w128.h): plain GEMMs only, 32-bit lane offsets into the operands
-bool w128_ok(const GemmArgs& g) {
-    if (g.taps != 1 || g.a1 || g.gn_scale || g.deq_m || g.deq_n || g.splitk > 1) return false;
-    if (g.a0_C % BK || g.a0_C < 2 * BK || g.N % 8 || g.M % 8) return false;
-    return (int64_t)g.M * g.a0_ld * 2 < (int64_t)1 << 32 && (int64_t)g.N * g.b_ld * 2 < (int64_t)1 << 32;
-}
-int choose_variant(const GemmArgs& g) {
-    if (g.gn_scale) return V_CONV_GN;               // the operand is raw: no other kernel can read it (launch_gemm checks conv_gn_ok)
-    const int K0 = g.taps * g.a0_C, K1 = g.a1 ? g.a1_C : 0;
-    const bool dma = K0 % BK == 0 && K1 % BK == 0 && (g.taps == 1 || (g.a0_padded && g.a0_C % BK == 0));
-    if (!dma) return V_GENERIC;
-    if (!variant_shipped(g_force_variant)) { /* refused by natinf_set_gemm_variant; never reached */ }
-    else if (g_force_variant == V_W128) {
-        if (w128_ok(g) && (!g.gn_part || (1 << g.logHW) % 256 == 0)) return V_W128;
-    }
-    else if (g_force_variant > V_GENERIC && g_force_variant != V_CONV_GN && g_force_variant != V_FP8_256x256) {
-        // a forced tile must keep GroupNorm partial tiles inside one sample (e.g. 512-row tiles on the 16x16 level do not)
-        if (!g.gn_part || (g.taps == 9 && (1 << g.logHW) % variant_bm(g_force_variant) == 0)) return g_force_variant;
-    }
-    // measured on the engine's layer shapes (tools/bench_gemm.py, profiles/r01): 256x256 two-stage for wide-N,
-    // long-K layers; the 4-wave 256x128 ring (wave tile 128x64, 2 blocks/CU) for N = 128 and short-K layers;
-    // 128x128 when 256-row tiles would leave CUs idle; 64x128 for the 4x4 level
-    const int64_t mt256 = (g.M + 255) / 256, mt128 = (g.M + 127) / 128;
-    const int64_t nt128 = (g.N + 127) / 128;
-    const bool w128 = g_w128 && w128_ok(g) && (!g.gn_part || (1 << g.logHW) % 256 == 0);       // round 4: plain GEMMs on the one-wave-per-SIMD tile (gemm_w128.h)
-    // Round 4: small-M plain GEMMs (the text stream of the MMDiT: M = 8 x 333 rows) by ROUNDS of blocks, not by "enough tiles for every CU": at
-    // (2664, 6144, 1536) the rule below took 256 x 256 tiles -- 264 of them: a second round for eight tiles, 77 us -- where 1,008 tiles of 128 x 128 run as two rounds of
-    // two blocks per CU in 55 us; at (2664, 4608, 1536) it took 128 x 128 (756 tiles, two rounds, 52 us) where 198 tiles of 256 x 256 are ONE round (43 us).  Measured
-    // cost of a round at K = 1,536: 25-28 us (128 x 128, two blocks per CU) against 37-43 us (256 x 256): ratio 1.5 (tools/scan_small_m_gemm.py).
-    // (round 5: the four-wave tile multiplies its 256 columns as two 128-column halves and skips a half that lies beyond N, so N % 128 == 0 is enough for it --
-    // DiT-XL/2's q | k | v projection, N = 3,456 = 13.5 tiles, had fallen to 128 x 128 tiles: 50.7 us against 30 us)
-    const int64_t nt256 = (g.N + 255) / 256;
-    const bool n_ok256 = g.N % 256 == 0 || (w128 && g.N % 128 == 0);
-    if (g_round_model && g.taps == 1 && !g.gn_part && g.batch == 1 && n_ok256 && K0 + K1 >= 1024 && mt256 * nt256 < 2 * NUM_CU) {
-        const int64_t r256 = (mt256 * nt256 + NUM_CU - 1) / NUM_CU, r128 = (mt128 * nt128 + 2 * NUM_CU - 1) / (2 * NUM_CU);
-        // (a round of the four-wave 256 x 256 tile costs ~1.3 rounds of 128 x 128 tiles, not 1.5: DiT-XL/2's fc1 at B = 16, (4096, 4608, 1152), is 288 tiles = two rounds of
-        // ~28 us against three rounds of two 128 x 128 blocks per CU in 74.6 us; natinf_set_gemm_round_model(v >= 10) sets the ratio to v / 10 for A/B runs)
-        const int64_t c256 = w128 ? g_round_model_w128 : 15;
-        if (mt128 * nt128 >= NUM_CU / 2) return c256 * r256 < 10 * r128 ? (w128 ? V_W128 : V_DMA_256x256_H) : V_DMA_128x128_P;
-    }
-    if (n_ok256 && K0 + K1 >= 1024 && mt256 * nt256 * g.batch >= NUM_CU) return w128 ? V_W128 : V_DMA_256x256_H;
-    if (g_pref_512 && g.N <= 128 && K0 + K1 >= 1024 && ((g.M + 511) / 512) * g.batch >= 2 * NUM_CU &&
-        (!g.gn_part || (g.taps == 9 && (1 << g.logHW) % 512 == 0)))           // GroupNorm partials: a tile inside one sample
-        return V_DMA_512x128_H;
-    if (mt256 * nt128 * g.batch >= 2 * NUM_CU) return V_RING_256x128_W4;        // it runs two blocks per CU
-    if (mt128 * nt128 * g.batch >= NUM_CU) return V_DMA_128x128_P;
-    return V_RING_64x128;
-}
 
-int variant_bm(int v) {
-    switch (v) {
-        case V_CONV_GN: case V_RING_256x128_W4: case V_DMA_256x256_H: case V_FP8_256x256: case V_W128: return 256;
-        case V_DMA_512x128_H: return 512;
-        case V_RING_64x128: return 64;
-        default: return 128;
-    }
-}
+}  // namespace
 
-// fp8 operands (a0 / b point at e4m3 bytes, a0_ld / b_ld / a_bs / b_bs in bytes, a0_C = K % 128 == 0, deq_m / deq_n set)
-int fp8_epi(const GemmArgs& g) {
-    if (g.epi_fp32_slab || g.resid || g.gn_part) return 0;
-    if ((g.rowvec || g.gate) && g.log_rows_per_sample < 30 && ((1 << g.log_rows_per_sample) % 256 != 0)) return 0;
-    if (g.c_mode == OUT_F32 && g.resid_f32 && !g.bias_m && g.act == ACT_NONE && g.resid_f32_ld % 4 == 0 && g.c_ld % 4 == 0) return 3;
-    if (g.resid_f32 || g.gate) return 0;
-    if (g.c_mode == OUT_BF16 && g.act == ACT_NONE) return 1;
-    if (g.c_mode == OUT_FP8_MX && g.act == ACT_GELU_TANH && g.c_mx && g.N % 32 == 0 && !g.bias_m && g.scale == 1.0f) return 2;      // (its epilogue carries neither term)
-    return 0;
-}
-extern int g_w128;
-// k_gemm_w128_fp8 (gemm_w128.h): an even number of 128-byte K-tiles, 32-bit offsets into the operands
-bool w128_fp8_ok(const GemmArgs& g) {
-    // (E8M0 block scales of A arrive by DMA as whole 256-row groups per K-tile: the plane must hold them -- whole row tiles only)
-    return g.taps == 1 && !g.a1 && g.a0_C % 256 == 0 && g.N % 8 == 0 && g.M % 8 == 0 && (!g.a_mx || g.M % 256 == 0) &&
-           (int64_t)g.M * g.a0_ld < (int64_t)1 << 32 && (int64_t)g.N * g.b_ld < (int64_t)1 << 32;
-}
-bool fp8_on_w128(const GemmArgs& g) { return g_w128 && w128_fp8_ok(g) && (fp8_epi(g) != 2 || g_w128 != 2); }      // the four-wave tile takes this launch
-template <bool MXA>
-void launch_gemm_fp8_t(const GemmArgs& g, hipStream_t s) {
-    // (round 5: the e4m3 + E8M0 epilogue with its tanh-GELU -- fc1 -- takes the four-wave tile too: with the GELU issued stage by stage for eight values at a time
-    // (gelu_tanh_fast8) (32768, 6144, 1536) runs 1,756-1,759 TFLOP/s there against 1,641-1,697 on the eight-wave tile, same process (tools/ab_fc1_w128.py).  Round 4 kept it on
-    // the eight-wave tile on a figure -- 1,100-1,130 against 1,300-1,520 -- that the debug entry had measured on the fp32-SLAB epilogue in e4m3 mode (no activation
-    // passed: fp8_epi() = 0), not on this one.  natinf_set_gemm_w128(2) = the round-4 rule, for A/B runs.)
-    if (fp8_on_w128(g)) {
-        switch (fp8_epi(g)) {
-            case 1: launch_tiles<W128F8Cfg>(&k_gemm_w128_fp8<MXA, 1>, g, s); break;
-            case 2: launch_tiles<W128F8Cfg>(&k_gemm_w128_fp8<MXA, 2>, g, s); break;
-            case 3: launch_tiles<W128F8Cfg>(&k_gemm_w128_fp8<MXA, 3>, g, s); break;
-            default: launch_tiles<W128F8Cfg>(&k_gemm_w128_fp8<MXA, 0>, g, s); break;
-        }
-        return;
-    }
-    switch (fp8_epi(g)) {
-        case 1: launch_tiles<CfgD256x256>(&k_gemm_fp8<MXA, 1>, g, s); break;
-        case 2: launch_tiles<CfgD256x256>(&k_gemm_fp8<MXA, 2>, g, s); break;
-        case 3: launch_tiles<CfgD256x256>(&k_gemm_fp8<MXA, 3>, g, s); break;
-        default: launch_tiles<CfgD256x256>(&k_gemm_fp8<MXA, 0>, g, s); break;
-    }
-}
-// natinf_gemm_profile(1): every matmul-shaped launch of every engine -- launch_gemm and launch_gemm_fp8, i.e. the kernel WITH the epilogue it runs in the network, on
-// the stream it runs on, between its real neighbours -- is bracketed by a HIP event pair and tagged with the line natinf_ncsnpp_describe_gemms would print for it.
-// natinf_gemm_profile_read sums them per tag.  (Round-5 review, item 2: the SD3 bench line quoted isolated loops of debug entries with the plain epilogue.)
-// One host thread at a time, like natinf_attention_profile; the events serialise nothing, but two HIP streams still overlap: a launch's span then includes what it
-// shared the chip with -- bench.py reads the image-stream shapes, whose launches are 10-100x the text stream's.
-struct GemmProf {
-    struct Rec { hipEvent_t a, b; std::string tag; };
-    bool on = false; std::vector<Rec> ev; std::vector<std::pair<hipEvent_t, hipEvent_t>> pool;
-    bool begin(Rec& r, hipStream_t s) {
-        r.a = r.b = nullptr;
-        if (!pool.empty()) { r.a = pool.back().first; r.b = pool.back().second; pool.pop_back(); }
-        else if (hipEventCreate(&r.a) != hipSuccess || hipEventCreate(&r.b) != hipSuccess) { r.a = r.b = nullptr; (void)hipGetLastError(); return false; }
-        (void)hipEventRecord(r.a, s);
-        return true;
-    }
-    void end(Rec& r, hipStream_t s) { (void)hipEventRecord(r.b, s); ev.push_back(std::move(r)); }
-} g_gemm_prof;
-void launch_gemm_fp8(const GemmArgs& g, hipStream_t s) {
-    GemmProf::Rec r;
-    const bool prof = g_gemm_prof.on && !g_record && g_gemm_prof.begin(r, s);
-    if (prof) {
-        char line[160];
-        snprintf(line, sizeof(line), "%d %d %d %d %d %d %s%s/e%d", g.M, g.N, g.taps * g.a0_C, 0, g.taps, g.batch, fp8_on_w128(g) ? "w128_fp8" : "fp8_256x256", g.a_mx ? "_mxa" : "", fp8_epi(g));
-        r.tag = line;
-    }
-    if (g.a_mx) launch_gemm_fp8_t<true>(g, s); else launch_gemm_fp8_t<false>(g, s);
-    if (prof) g_gemm_prof.end(r, s);
-}
+struct natinf_ncsnpp : EngineCore {
+    int flags = 0;
+    std::vector<Mod> mods;
+    std::vector<int> op_cls;             // CLS_* per op (profiling)
+    // profiling: one HIP event pair per op while enabled
+    bool prof = false;
+    struct Rec { hipEvent_t a, b; int cls; };
+    std::vector<Rec> recs;
+    std::vector<hipEvent_t> pool;
+    std::map<int, TRef> taps;            // module idx -> output tensor
+    uint64_t plan_sig = 0;               // the natinf_set_* switches a plan reads when it is BUILT (they decide the pack offsets): natinf_ncsnpp_share compares them
+    int last_B = 0; unsigned char* last_ws = nullptr;
+    std::vector<unsigned char> fin_done; // see Ctx::fin_done
+};
 
-// Which epilogue a launch can take (see tile_epilogue in gemm_dma.h): 0 = the general fp32-slab one; 1..6 = packed, when only
-// column terms (bias, a per-sample row vector with every block tile inside one sample) and a bf16 residual are fused, the output is bf16, and
-// GroupNorm partials (no activation, whole tiles) or an activation -- not both -- are asked for.
-int packed_epi(const GemmArgs& g, int bm) {      // resid must be 8-byte aligned per 4-column group: ld % 4, base from the arena
-    if (g.epi_fp32_slab || g.deq_m || g.deq_n || g.act == ACT_RELU) return 0;      // (ReLU: the general epilogue applies it)
-    if (g.bias_m) return (g.c_mode == OUT_BF16 && !g.resid && !g.resid_f32 && !g.gate && !g.rowvec && !g.gn_part && g.act == ACT_NONE) ? 8 : 0;
-    if ((g.rowvec || g.gate) && g.log_rows_per_sample < 30 && ((1 << g.log_rows_per_sample) % bm != 0)) return 0;    // per-sample terms: one sample per tile
-    if (g.c_mode == OUT_F32 && g.resid_f32 && !g.resid && !g.gn_part && g.act == ACT_NONE && g.resid_f32_ld % 4 == 0 && g.c_ld % 4 == 0) return 7;
-    if (g.c_mode != OUT_BF16 || g.resid_f32 || g.gate) return 0;
-    if (g.resid && (g.act != ACT_NONE || g.resid_ld % 4 != 0)) return 0;
-    if (g.gn_part) return (g.act == ACT_NONE && g.M % bm == 0) ? (g.resid ? 6 : 2) : 0;
-    if (g.resid) return 5;
-    return g.act == ACT_NONE ? 1 : (g.act == ACT_SILU ? 3 : 4);
-}
-inline unsigned epi_mask(int v) {
-    switch (v) {
-        case V_RING_64x128: return EPI_R64;  case V_DMA_128x128_P: return EPI_D128;  case V_RING_256x128_W4: return EPI_RW4;
-        case V_DMA_256x256_H: return EPI_D256H;  case V_DMA_512x128_H: return EPI_D512H;
-        case V_W128: return EPI_W128;
-        default: return 1u;
-    }
-}
-// the epilogue specialization a launch on tile variant v runs (0 where its packed one is not instantiated for that tile)
-inline int effective_epi(int v, const GemmArgs& g) { const int e = packed_epi(g, variant_bm(v)); return ((epi_mask(v) >> e) & 1u) ? e : 0; }
-#define NATINF_LAUNCH_EPI(MASK, CFG, KERN, ...)                                                                      \
-    {                                                                                                                \
-        auto run_ = [&](auto t_) { launch_tiles<CFG>(&KERN<__VA_ARGS__, NATINF_EPI_OF(t_)>, g, s); };                \
-        switch (effective_epi(v, g)) {                                                                               \
-            case 1: epi_case<MASK, 1>(run_); break;  case 2: epi_case<MASK, 2>(run_); break;                         \
-            case 3: epi_case<MASK, 3>(run_); break;  case 4: epi_case<MASK, 4>(run_); break;                         \
-            case 5: epi_case<MASK, 5>(run_); break;  case 6: epi_case<MASK, 6>(run_); break;                         \
-            case 7: epi_case<MASK, 7>(run_); break;  case 8: epi_case<MASK, 8>(run_); break;                         \
-            default: run_(std::integral_constant<int, 0>{}); break;                                                  \
-        }                                                                                                            \
-    }
+namespace {
 
-// set when a launch is asked for something no kernel provides (a plan-builder bug, or an A/B knob flipped after the plan was built);
-// natinf_ncsnpp_forward clears it on entry and reports it on exit -- per calling thread, so two engines on two threads do not see
-// each other's, and a description pass (g_record) never sets it
-thread_local int g_launch_error = 0;
-thread_local bool g_fin_written = false;      // set by launch_gemm: the launch that just ran wrote the consumer's GroupNorm table (GemmArgs::fin_*) -- k_conv_gn3 at 16x16
-int g_splitk = 1;                  // natinf_set_gemm_splitk: 0 = never split K
-float* g_dbg_splitk_ws = nullptr; int g_dbg_splitk_max = 0;        // natinf_debug_set_splitk_workspace
-// Split-K for launches that cannot fill the chip otherwise (the 8x8 and 4x4 levels: 32,768 / 8,192 rows x 256 columns, K = 2,304 ..
-// 4,608): 128 x 128 tiles (fill per flop of the large tile) x S slices of K >= 2 blocks per CU, then one reduce pass with the fused
-// terms.  Returns the slice count (1 = do not split).
-int splitk_slices(const GemmArgs& g) {
-    if (!g_splitk || !g.splitk_ws || g.splitk_max < 2 || g.batch != 1 || g.gn_scale || g.c_mode != OUT_BF16 || g.N % 8 || 256 % (g.N / 8)) return 1;
-    if (g.gn_part && (g.M % SPLITK_ROWS || g.act != ACT_NONE || (g.taps == 9 && (1 << g.logHW) % SPLITK_ROWS))) return 1;
-    if (g.bias_m || g.gate || g.resid_f32 || g.deq_m || g.deq_n) return 1;
-    const int K0 = g.taps * g.a0_C, K1 = g.a1 ? g.a1_C : 0;
-    if (K0 % 64 || K1 % 64 || (g.taps == 9 && !g.a0_padded) || K0 + K1 < 2048) return 1;
-    const int64_t tiles = ((g.M + 127) / 128) * ((g.N + 127) / 128);
-    if (tiles >= 2 * NUM_CU) return 1;
-    int S = (int)((2 * NUM_CU + tiles - 1) / tiles);
-    if (S > g.splitk_max) S = g.splitk_max;
-    while (S > 1 && (K0 + K1) / 32 / S < 16) --S;                       // at least 16 K-tiles per slice
-    return S;
-}
-// Split-K on the four-wave tile for under-filled long-K GEMMs with the gated fp32 residual epilogue (gemm_w128.h: k_gemm_w128<9> + k_splitk_reduce_f32).  Returns the
-// slice count (1 = do not split): the tiles of 256 x 256 fill less than half the chip, every slice keeps >= 16 K-tiles.
-int w128_splitk_slices(const GemmArgs& g) {
-    // (batch 1 only: the workspace contract is splitk_max * M * N floats; a batched launch would need batch times that)
-    if (!g_splitk || !g_w128 || !g.splitk_ws || g.splitk_max < 2 || g.batch != 1 || !w128_ok(g) || g.a0_C < 3072) return 1;
-    if (g.c_mode != OUT_F32 || !g.resid_f32 || g.resid || g.rowvec || g.bias_m || g.gn_part || g.act != ACT_NONE || g.epi_fp32_slab || g.N % 4 || g.c_ld % 4 || g.resid_f32_ld % 4) return 1;
-    const int64_t tiles = (int64_t)((g.M + 255) / 256) * ((g.N + 255) / 256) * g.batch;
-    if (tiles * 2 > NUM_CU) return 1;
-    int S = (int)(NUM_CU / tiles);
-    if (S > g.splitk_max) S = g.splitk_max;
-    while (S > 1 && g.a0_C / BK / S < 16) --S;
-    return S;
-}
-int launch_gemm_run(const GemmArgs& g0, hipStream_t s);
-// returns the block-tile row count of the variant used
-int launch_gemm(const GemmArgs& g0, hipStream_t s) {
-    if (!g_gemm_prof.on || g_record) return launch_gemm_run(g0, s);
-    GemmProf::Rec r;
-    std::string tag;
-    g_record = &tag; (void)launch_gemm_run(g0, s); g_record = nullptr;          // description pass: the tag, nothing launched
-    while (!tag.empty() && tag.back() == '\n') tag.pop_back();
-    if (!g_gemm_prof.begin(r, s)) return launch_gemm_run(g0, s);
-    r.tag = std::move(tag);
-    const int bm = launch_gemm_run(g0, s);
-    g_gemm_prof.end(r, s);
-    return bm;
-}
-int launch_gemm_run(const GemmArgs& g0, hipStream_t s) {
-    if (g_force_variant == V_AUTO) {
-        const int S8 = w128_splitk_slices(g0);
-        if (S8 > 1) {
-            if (g_record) {
-                char line[160];
-                snprintf(line, sizeof(line), "%d %d %d %d %d %d splitk%d_w128_256x256/e7\n", g0.M, g0.N, g0.taps * g0.a0_C, 0, g0.taps, g0.batch, S8);
-                *g_record += line;
-                return 256;
-            }
-            GemmArgs p = g0;
-            p.splitk = S8; p.c = g0.splitk_ws; p.c_mode = OUT_F32;
-            const int nM = (p.M + 255) / 256, nN = (p.N + 255) / 256;
-            p.raster_g = 0;
-            hipLaunchKernelGGL((k_gemm_w128<9>), dim3(nM * nN, S8, p.batch), dim3(256), W128Cfg::LDS_BYTES, s, p);
-            const int64_t per = (int64_t)g0.M * (g0.N / 4);
-            hipLaunchKernelGGL(k_splitk_reduce_f32, dim3((unsigned)((per + 255) / 256), (unsigned)g0.batch), dim3(256), 0, s, g0.splitk_ws, S8, (int64_t)g0.batch * g0.M * g0.N, g0.M, g0.N,
-                               g0.bias_n, g0.gate, g0.gate_ld, g0.log_rows_per_sample, g0.z_samples, g0.resid_f32, g0.resid_f32_ld, g0.c_bs, g0.scale,
-                               reinterpret_cast<float*>(g0.c), g0.c_ld, g0.stream_f16);
-            return 256;
-        }
-    }
-    const int S = g_force_variant == V_AUTO ? splitk_slices(g0) : 1;
-    if (S > 1) {
-        if (g_record) {
-            char line[160];
-            snprintf(line, sizeof(line), "%d %d %d %d %d %d splitk%d_ring128x128/e9\n", g0.M, g0.N, g0.taps * g0.a0_C, g0.a1 ? g0.a1_C : 0, g0.taps, g0.batch, S);
-            *g_record += line;
-            return SPLITK_ROWS;
-        }
-        GemmArgs p = g0;
-        p.splitk = S; p.c = g0.splitk_ws; p.c_mode = OUT_F32; p.batch = S;
-        p.bias_n = nullptr; p.rowvec = nullptr; p.resid = nullptr; p.scale = 1.0f; p.act = ACT_NONE; p.gn_part = nullptr;
-        launch_tiles<CfgR128x128>(&k_gemm_ring<2, 2, 4, 4, 4, 9>, p, s);
-        hipLaunchKernelGGL(k_splitk_reduce, dim3((unsigned)((g0.M + SPLITK_ROWS - 1) / SPLITK_ROWS)), dim3(256), 0, s, g0.splitk_ws, S, g0.M, g0.N,
-                           g0.bias_n, g0.rowvec, g0.rowvec_ld, g0.log_rows_per_sample, reinterpret_cast<const bf16*>(g0.resid), g0.resid_ld, g0.scale,
-                           g0.act, reinterpret_cast<bf16*>(g0.c), g0.c_ld, reinterpret_cast<float2*>(g0.gn_part), g0.gn_quads);
-        return SPLITK_ROWS;
-    }
-    const GemmArgs& g = g0;
-    const int v = choose_variant(g);
-    if (g.taps == 9 && v != V_CONV_GN && g.a0_C % BK) {
-        // (the packed weight rows of a 3x3 launch hold ((c / 64) * 9 + tap) * 64 + c % 64 columns: with a0_C % 64 != 0 no kernel has a defined K order)
-        if (g_record) {
-            char line[160];
-            snprintf(line, sizeof(line), "%d %d %d %d %d %d invalid_conv3x3/e0\n", g.M, g.N, g.taps * g.a0_C, g.a1 ? g.a1_C : 0, g.taps, g.batch);
-            *g_record += line;
-        } else g_launch_error = 1;
-        return 256;
-    }
-    if (v == V_CONV_GN && !conv_gn_ok(g)) {
-        if (g_record) {                 // description pass: say so in the table instead of dropping the row
-            char line[160];
-            snprintf(line, sizeof(line), "%d %d %d %d %d %d invalid_conv_gn/e0\n", g.M, g.N, g.taps * g.a0_C, g.a1 ? g.a1_C : 0, g.taps, g.batch);
-            *g_record += line;
-        } else g_launch_error = 1;
-        return 256;
-    }
-    if (g_record) {
-        char line[160];
-        snprintf(line, sizeof(line), "%d %d %d %d %d %d %s/e%d\n", g.M, g.N, g.taps * g.a0_C, g.a1 ? g.a1_C : 0, g.taps, g.batch,
-                 v == V_CONV_GN && conv_gn3_shape(g) >= 0 ? "conv_gn3" : variant_name(v), v == V_CONV_GN ? conv_gn_epi(g) : effective_epi(v, g));
-        *g_record += line;
-        return v == V_CONV_GN ? conv_gn_part_rows(g) : variant_bm(v);
-    }
-    switch (v) {
-        case V_GENERIC: {
-            const int nM = (g.M + BM - 1) / BM, nN = (g.N + BN - 1) / BN;
-            hipLaunchKernelGGL(k_gemm_bf16, dim3(nM * nN, 1, g.batch), dim3(256), GEMM_LDS_BYTES, s, g);
-            break;
-        }
-        case V_RING_64x128: NATINF_LAUNCH_EPI(EPI_R64, CfgR64x128, k_gemm_ring, 2, 2, 2, 4, 4) break;
-        case V_RING_256x128_W4: NATINF_LAUNCH_EPI(EPI_RW4, CfgR256x128W4, k_gemm_ring, 2, 2, 8, 4, 3) break;
-        case V_DMA_128x128_P: NATINF_LAUNCH_EPI(EPI_D128, CfgD128x128, k_gemm_dma, 2, 2, 4, 4, 2) break;
-        case V_FP8_256x256: launch_tiles<CfgD256x256>(&k_gemm_fp8<false, 0>, g, s); break;
-        case V_DMA_256x256_H: NATINF_LAUNCH_EPI(EPI_D256H, CfgD256x256, k_gemm_dma, 2, 4, 8, 4, 6) break;
-        case V_DMA_512x128_H: NATINF_LAUNCH_EPI(EPI_D512H, CfgD512x128, k_gemm_dma, 4, 2, 8, 4, 6) break;
-        case V_W128: {
-            auto run_ = [&](auto t_) { launch_tiles<W128Cfg>(&k_gemm_w128<NATINF_EPI_OF(t_)>, g, s); };
-            switch (effective_epi(v, g)) {
-                case 1: epi_case<EPI_W128, 1>(run_); break;  case 4: epi_case<EPI_W128, 4>(run_); break;
-                case 5: epi_case<EPI_W128, 5>(run_); break;  case 7: epi_case<EPI_W128, 7>(run_); break;
-                case 8: epi_case<EPI_W128, 8>(run_); break;
-                default: run_(std::integral_constant<int, 0>{}); break;
-            }
-            break;
-        }
-        case V_CONV_GN: {
-            GemmArgs gw = g0;
-            gw.w_warm = (g_cg_warm >> (g0.logW - 2)) & 1;
-            const GemmArgs& g = gw;
-            const int e = conv_gn_epi(g);
-            const int e4 = e == 1 ? 0 : (e == 2 ? 1 : (e == 5 ? 2 : 3));
-#define NATINF_CG2_LAUNCH(CFG, RES, WIDE)                                                                   \
-            switch (e4) {                                                                                       \
-                case 0: launch_tiles<CFG>(&k_conv_gn2<RES, WIDE, 1>, g, s); break;                              \
-                case 1: launch_tiles<CFG>(&k_conv_gn2<RES, WIDE, 2>, g, s); break;                              \
-                case 2: launch_tiles<CFG>(&k_conv_gn2<RES, WIDE, 5>, g, s); break;                              \
-                default: launch_tiles<CFG>(&k_conv_gn2<RES, WIDE, 6>, g, s); break;                             \
-            }
-            if (const int sh3 = conv_gn3_shape(g); sh3 >= 0) {
-                ncsn_cg3::launch(&g, sh3, e, (void*)s);
-                g_fin_written = sh3 == 2 && g.fin_scale && (e == 2 || e == 6) && g.N == 256;      // (k_conv_gn3<16, 2, 2, 2 | 6>: FIN16, conv_gn3.h)
-                return conv_gn_part_rows(g);
-            }
-            if ((1 << g.logW) == 8) {
-                switch (e4) {
-                    case 0: launch_tiles<CfgH8T>(&k_conv_gn2<8, true, 1, 4>, g, s); break;
-                    case 1: launch_tiles<CfgH8T>(&k_conv_gn2<8, true, 2, 4>, g, s); break;
-                    case 2: launch_tiles<CfgH8T>(&k_conv_gn2<8, true, 5, 4>, g, s); break;
-                    default: launch_tiles<CfgH8T>(&k_conv_gn2<8, true, 6, 4>, g, s); break;
-                }
-            }
-            else if ((1 << g.logW) == 4) {
-                switch (e4) {
-                    case 0: launch_tiles<CfgH4T>(&k_conv_gn2<4, true, 1, 4, 2, 2>, g, s); break;
-                    case 1: launch_tiles<CfgH4T>(&k_conv_gn2<4, true, 2, 4, 2, 2>, g, s); break;
-                    case 2: launch_tiles<CfgH4T>(&k_conv_gn2<4, true, 5, 4, 2, 2>, g, s); break;
-                    default: launch_tiles<CfgH4T>(&k_conv_gn2<4, true, 6, 4, 2, 2>, g, s); break;
-                }
-            }
-            else if ((1 << g.logW) == 32 && conv_gn_bm(g) == 128) { NATINF_CG2_LAUNCH(CfgH32W, 32, true) }
-            else if ((1 << g.logW) == 32) { NATINF_CG2_LAUNCH(CfgH32, 32, false) }
-            else if (conv_gn_bm(g) == 128) { NATINF_CG2_LAUNCH(CfgH16W, 16, true) }
-            else { NATINF_CG2_LAUNCH(CfgH16, 16, false) }
-#undef NATINF_CG2_LAUNCH
-            return conv_gn_part_rows(g);
-        }
-        default: break;
-    }
-    return variant_bm(v);
-}
-inline int grid1d(int64_t n, int block = 256, int cap = 4096) {
-    int64_t g = (n + block - 1) / block; return (int)(g < 1 ? 1 : (g > cap ? cap : g));
+// LDS sizes of the kernels only this engine launches (configure_gemm_kernels, gemm_launch.h)
+bool configure_ncsnpp_kernels() {
+    return hipFuncSetAttribute(reinterpret_cast<const void*>(&k_head_conv), hipFuncAttributeMaxDynamicSharedMemorySize, HeadConvCfg::LDS_BYTES) == hipSuccess &&
+           hipFuncSetAttribute(reinterpret_cast<const void*>(&k_qkv256), hipFuncAttributeMaxDynamicSharedMemorySize, QKV_LDS_BYTES) == hipSuccess &&
+           hipFuncSetAttribute(reinterpret_cast<const void*>(&k_attn256<false>), hipFuncAttributeMaxDynamicSharedMemorySize, A256_LDS_BYTES) == hipSuccess &&
+           hipFuncSetAttribute(reinterpret_cast<const void*>(&k_attn256<true>), hipFuncAttributeMaxDynamicSharedMemorySize, A256_LDS_BYTES) == hipSuccess &&
+           hipFuncSetAttribute(reinterpret_cast<const void*>(&k_attn256<true, 8>), hipFuncAttributeMaxDynamicSharedMemorySize, A256_LDS_BYTES) == hipSuccess &&
+           hipFuncSetAttribute(reinterpret_cast<const void*>(&k_attn_blk256), hipFuncAttributeMaxDynamicSharedMemorySize, ABLK_LDS_BYTES) == hipSuccess &&
+           hipFuncSetAttribute(reinterpret_cast<const void*>(&k_attn_blk256_v2), hipFuncAttributeMaxDynamicSharedMemorySize, ABLK2_LDS_BYTES) == hipSuccess;
 }
 
 // ------------------------------------------------------------------------------------------------
 // plan builder
 // ------------------------------------------------------------------------------------------------
-struct Builder {
+struct Builder : PlanBuilder {          // (wtop: the packed-weight bump pointer in bytes; poff: the running parameter offset in floats)
     natinf_ncsnpp& E;
-    Arena arena;
-    int64_t wtop = 0;                    // packed-weight bump pointer (bytes)
-    int64_t poff = 0;                    // running parameter offset (floats)
     // time-embedding projection bank
     int dense_total = 0; int64_t dense_w = 0, dense_b = 0, dense_out = 0;
 
@@ -705,13 +109,11 @@ struct Builder {
     const bool ddpm;
     const int NUM_RES;
     const float res_scale;               // 1/sqrt(2) (skip_rescale of the ++ blocks) or 1
-    explicit Builder(natinf_ncsnpp& e) : E(e), ddpm((e.flags & NATINF_NCSNPP_DDPM) != 0), NUM_RES(ddpm ? 2 : 4), res_scale(ddpm ? 1.0f : INV_SQRT2) {
+    explicit Builder(natinf_ncsnpp& e) : PlanBuilder(e), E(e), ddpm((e.flags & NATINF_NCSNPP_DDPM) != 0), NUM_RES(ddpm ? 2 : 4), res_scale(ddpm ? 1.0f : INV_SQRT2) {
         arena.keep = (e.flags & NATINF_NCSNPP_KEEP_ACTIVATIONS) != 0;
     }
 
     void op(int cls, OpFn f) { E.ops.push_back(std::move(f)); E.op_cls.push_back(cls); }
-    int64_t wres(int64_t bytes) { const int64_t o = wtop; wtop += align_up(bytes, 256); return o; }
-    int64_t take(int64_t n) { const int64_t o = poff; poff += n; return o; }
 
     // ---- weight packing recipes -------------------------------------------------------------
     void pack_conv(int64_t src, int64_t dst, int N, int Cin, int taps, int dst_ld, int koff, int tapstride, float wmul = 1.0f) {
@@ -735,24 +137,13 @@ struct Builder {
                                p.params + src, reinterpret_cast<bf16*>(p.packed + dst), K, N, dst_ld);
         });
     }
-    void pack_transpose_at(int64_t src, int64_t dst_bytes, int K, int N, int dst_ld) { pack_transpose(src, dst_bytes, K, N, dst_ld); }
     void pack_zero(int64_t dst, int64_t n) {
         E.packs.push_back([=](const PackCtx& p) {
             hipLaunchKernelGGL(k_fill_bf16_zero, dim3(grid1d(n, 256, 1 << 30)), dim3(256), 0, p.stream,
                                reinterpret_cast<bf16*>(p.packed + dst), n);
         });
     }
-    int64_t pack_f32(int64_t src, int n, int64_t src2 = -1) {          // returns packed offset of an fp32 vector
-        const int64_t dst = wres((int64_t)n * 4);
-        pack_f32_at(src, n, dst, src2);
-        return dst;
-    }
-    void pack_f32_at(int64_t src, int n, int64_t dst, int64_t src2 = -1) {
-        E.packs.push_back([=](const PackCtx& p) {
-            hipLaunchKernelGGL(k_copy_add_f32, dim3(grid1d(n)), dim3(256), 0, p.stream, p.params + src,
-                               src2 >= 0 ? p.params + src2 : nullptr, reinterpret_cast<float*>(p.packed + dst), n);
-        });
-    }
+    // (fp32 vectors: PlanBuilder::pack_f32 / pack_f32_at; the longest one packed here is TEMB = 512 floats = two blocks)
 
     // ---- op emitters ------------------------------------------------------------------------
     struct GN { int64_t gamma, beta; };
@@ -811,7 +202,7 @@ struct Builder {
         pack_conv(p_c0w, w0, cout, cin, 9, K0a, 0, cin, w_mul);
         pack_conv(p_c1w, w1, cout, cout, 9, K1tot, 0, cout, w_mul1);
         if (shortcut && !ddpm) pack_conv(p_c2w, w1, cout, cin, 1, K1tot, 9 * cout, cin);
-        if (shortcut && ddpm) pack_transpose_at(p_c2w, w1 + (int64_t)9 * cout * 2, cin, cout, K1tot);      // NIN_0.W is [in][out] (layers.py:546-555)
+        if (shortcut && ddpm) pack_transpose(p_c2w, w1 + (int64_t)9 * cout * 2, cin, cout, K1tot);      // NIN_0.W is [in][out] (layers.py:546-555)
         // k_conv_gn2 reads the weights fragment-major (after the packs above: the list runs in order)
         const int64_t w0f = (fuse && cout % 16 == 0) ? wres((int64_t)cout * K0a * 2) : -1, w1f = (fuse1 && cout % 16 == 0) ? wres((int64_t)cout * K1tot * 2) : -1;
         if (w0f >= 0) pack_frag(w0, w0f, cout, K0a, cin, 0);
@@ -1412,12 +803,7 @@ struct Builder {
                 emit_gn_stats(last, gn, sc, sh, -1.4426950408889634f);
                 const TRef src = last;
                 op(CLS_GEMM, [=](const Ctx& c) {
-                    if (g_record) {
-                        char line[160];
-                        snprintf(line, sizeof(line), "%d %d %d %d %d %d head_conv/e0\n", c.B * res * res, 3, Kf, 0, 9, 1);
-                        *g_record += line;
-                        return;
-                    }
+                    if (g_record) { *g_record += gemm_row(c.B * res * res, 3, Kf, 0, 9, 1, "head_conv", 0) + "\n"; return; }
                     hipLaunchKernelGGL(k_head_conv, dim3((unsigned)(c.B * (HeadConvCfg::RES / HeadConvCfg::ROWS))), dim3(256), HeadConvCfg::LDS_BYTES, c.stream,
                                        c.act(src), src.ld, c.at<float>(sc), c.at<float>(sh), c.w<bf16>(w16), c.w<float>(b), c.out);
                 });
@@ -1435,11 +821,9 @@ struct Builder {
             }
             E.taps[mg.idx] = last;          // (pre-norm tensor; the GN module's own output is internal)
         }
-        E.n_params = poff;
+        finish();
         E.part_bm.assign(n_parts > 0 ? n_parts : 1, 128);
         E.fin_done.assign(n_parts > 0 ? n_parts : 1, 0);
-        E.ws_per_image = arena.peak;
-        E.packed_bytes = wtop;
         // parameter offsets for describe(): recompute by module in order
     }
 };
@@ -1545,11 +929,7 @@ int natinf_ncsnpp_describe(natinf_ncsnpp_t h, char* buf, int cap) {
 
 int natinf_ncsnpp_load(natinf_ncsnpp_t h, const float* params_f32, int64_t n_params, void* packed, int64_t packed_bytes,
                        natinf_stream_t stream) {
-    if (!h || !params_f32 || !packed || n_params != h->n_params || packed_bytes < h->packed_bytes) return NATINF_EINVAL;
-    PackCtx p{params_f32, reinterpret_cast<unsigned char*>(packed), (hipStream_t)stream};
-    for (const auto& f : h->packs) f(p);
-    h->packed = reinterpret_cast<const unsigned char*>(packed);
-    return hipGetLastError() == hipSuccess ? NATINF_OK : NATINF_ELAUNCH;
+    return h ? h->load(params_f32, n_params, packed, packed_bytes, (hipStream_t)stream) : NATINF_EINVAL;
 }
 
 int natinf_ncsnpp_share(natinf_ncsnpp_t h, natinf_ncsnpp_t loaded) {
@@ -1568,9 +948,9 @@ int natinf_ncsnpp_forward(natinf_ncsnpp_t h, const float* x, const float* labels
     if (!h || !x || !labels || !out || !workspace || B <= 0) return NATINF_EINVAL;
     if (!h->packed) return NATINF_ESTATE;
     if (workspace_bytes < h->ws_per_image * (int64_t)B || (int64_t)B * IMG * IMG >= (1LL << 31)) return NATINF_EINVAL;
-    if (!h->attr_set) {
+    if (!h->configured) {
         if (!configure_gemm_kernels()) return NATINF_ENODEV;
-        h->attr_set = true;
+        h->configured = true;
     }
     Ctx c{B, reinterpret_cast<unsigned char*>(workspace), h->packed, (hipStream_t)stream, x, labels, out, h->part_bm.data()};
     c.fin_done = h->fin_done.data();

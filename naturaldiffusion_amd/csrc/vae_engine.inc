@@ -7,6 +7,7 @@
 // has more than 64 tiles, then k_gn_finalize); below 16x16 the streaming kernel (one block per sample).  The mid-block
 // attention (single head, C = 512) runs as batched GEMMs with the scores materialised (1 GiB per sample at r = 128).
 #include "natinf_vae.h"
+#include "engine_core.h"
 
 namespace ncsn {
 

@@ -72,7 +72,7 @@ def _run(res, B, cin, N, c1, t, up_flags, mask, rows, parts):
     return out.cpu(), (part.cpu() if parts else None)
 
 
-_DEFAULT_MASK, _DEFAULT_MIN_K = 7, (2304, 0, 2304)          # (csrc/ncsnpp.hip: g_cg3, g_cg3_min_k)
+_DEFAULT_MASK, _DEFAULT_MIN_K = 7, (2304, 0, 2304)          # (csrc/gemm_launch.h: g_cg3, g_cg3_min_k)
 
 
 @pytest.mark.parametrize("res,B,cin,N,c1,resid,parts,up", [

@@ -6,7 +6,7 @@ import torch
 
 pytestmark = pytest.mark.gpu
 
-# the shipped tile variants (ncsnpp.hip variant_shipped): 256x256 / 512x128 with one issuing wave per SIMD, 128x128, the two rings
+# the shipped tile variants (gemm_launch.h: GemmFamilies, variant_shipped): 256x256 / 512x128 with one issuing wave per SIMD, 128x128, the two rings
 V_DMA256P, V_DMA128P, V_RING256W4, V_RING64, V_DMA512 = 26, 17, 9, 8, 27
 V_W128 = 29        # 256x256x64, one wave per SIMD with a 128x128 wave tile (gemm_w128.h): two 256x128 half-tile epilogues
 
