@@ -155,6 +155,33 @@ int natinf_step_f32prod(const float* z, const float* cond, const float* uncond, 
                         int k, float c1_f32, float c2_f32,
                         int64_t E, natinf_stream_t stream);
 
+/* The same step with the noise row generated in registers (a generation job: no hist_eps slab, noise keyed by the global
+ * image index).  eps, x0_k, a and z_next operation for operation as natinf_step_f32prod; only the source of eps_j in
+ *
+ *   b      = sum over terms t (ascending idx_b[t]) of (double)(eps_{idx_b[t]} * val_b[t])
+ *
+ * differs: eps_0 is read from `noise` ([E] fp32, the initial noise); eps_j, j >= 1, is NOT read from memory: it is
+ * generated as natinf_randn_philox_col_f32(..., seed, column = j) would return it (same Philox4x32-10 counter, same
+ * Box-Muller, bit for bit).  An image is one sample of sample_elems elements; element e of image i = e / sample_elems
+ * draws counter = (global index lo, global index hi, quad (e % sample_elems) / 4, j), key = (seed lo, seed hi); the
+ * global index is image_index[i] (device int64 array) or, when image_index is NULL, first_index + i*index_stride.
+ * So z_next and hist_x0[k] equal, byte for byte, natinf_step_f32prod on a hist_eps slab whose row 0 is `noise` and whose
+ * row j >= 1 natinf_randn_philox_col_f32(column = j) filled, and an image's trajectory is a function of (seed, global
+ * index) whatever the batch split or GPU count.  A deterministic matrix (column 0 only) goes through unchanged.
+ * n_b == 0 is legal (b = 0).  NATINF_EINVAL, nothing launched: E % 4, sample_elems % 4, E % sample_elems,
+ * sample_elems / 4 >= 2^32 (counter word 3 carries the column), n_b > k + 2 or an idx_b entry outside 0..k+1 (eps_j is
+ * drawn after step j-1), `noise` NULL when the row names column 0.  For that check the n_b indices are read back from the
+ * device on a private stream before the launch: the host waits for that copy alone, not for `stream`; idx_b must be
+ * complete when the call is made (a row table uploaded once), and the call cannot be part of a stream capture. */
+int natinf_step_f32prod_noise(const float* z, const float* cond, const float* uncond, float cfg,
+                              int64_t sample_elems, int64_t eps_sample_stride,
+                              float* hist_x0, const float* noise, float* z_next,
+                              const int32_t* idx_c, const float* val_c, int n_c, float c_diag,
+                              const int32_t* idx_b, const float* val_b, int n_b,
+                              int k, float c1_f32, float c2_f32,
+                              uint64_t seed, const int64_t* image_index, int64_t first_index, int64_t index_stride,
+                              int64_t E, natinf_stream_t stream);
+
 /* src/ValidateNaturalInference.py:198-204 on its own. */
 int natinf_weighted_sum_f32prod(const float* hist, float* out,
                                 const int32_t* idx, const float* val, int n_terms,

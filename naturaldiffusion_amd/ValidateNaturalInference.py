@@ -357,6 +357,119 @@ def natural_inference(alg_name="ddpm", num_step=24):
     return _finish(input_z.clone(), "%s__seed_%d__natural.png" % (weight_name, 0))
 
 
+DEMO_LABELS = (207, 360, 387, 974, 88, 979, 417, 279)     # reference :156: the eight ImageNet classes of the demo row
+
+
+def job_batches(sample_count, batch_size, rank=0, world=1, labels=None):
+    """The batches rank ``rank`` of ``world`` generates: a list of (global image indices, class labels).  Indices are sharded
+    like the other two paths (``shard.rank_batches``: rank r owns r, r+world, ...; only a rank's last batch is ragged).  The
+    label of an image is a function of its GLOBAL index alone, so it is the same image under any split: ``labels`` None
+    cycles the reference's eight demo labels (indices 0-7 are the demo row), a sequence of ``sample_count`` entries is taken
+    per index, a shorter one is cycled.  1000 is the null class of the unconditional half, so a label outside 0..999 is an
+    error.  Pure host code."""
+    from .shard import rank_batches
+    sample_count, batch_size = int(sample_count), int(batch_size)
+    if sample_count < 0 or batch_size <= 0:
+        raise ValueError("sample_count must be >= 0 and batch_size positive")
+    table = [int(v) for v in (DEMO_LABELS if labels is None else labels)]
+    if not table:
+        raise ValueError("labels must not be empty")
+    if len(table) > sample_count and labels is not None:
+        raise ValueError(f"{len(table)} labels for {sample_count} images")
+    bad = [v for v in table if not 0 <= v <= 999]
+    if bad:
+        raise ValueError(f"class labels must be in 0..999 (1000 is the null class of the unconditional half), got {bad[0]}")
+    return [(idx, [table[i % len(table)] for i in idx]) for idx in rank_batches(sample_count, batch_size, rank, world)]
+
+
+def to_pixels_u8(images: torch.Tensor) -> torch.Tensor:
+    """[n, 3, H, W] decoder output -> [n, H, W, 3] uint8 where the tensor lives: ``save_image_grid``'s pixel expression."""
+    x = images.detach().float()
+    return ((((x.clamp(-1, 1) + 1) * 0.5) * 255 + 0.5).clamp(0, 255)).to(torch.uint8).permute(0, 2, 3, 1).contiguous()
+
+
+@torch.no_grad()
+def generate_sharded(sample_count, labels=None, alg_name="ddpm", num_step=24, batch_size=32, rank=0, world=1, seed=0,
+                     cfg_scale=4.0, decode=True, decode_batch=8, model=None, decoder=None, image_sink=None):
+    """A class-conditional generation job on the loop of ``natural_inference`` (reference :311-372): ``sample_count`` images,
+    image i of class ``job_batches``' label of i, sharded by global index over ``world`` ranks with no collective on the data
+    path.  The noise is counter-based: z_0 = eps_0 = ``philox_noise(indices, column=0)`` and the noise a stochastic matrix
+    injects after step j-1 is drawn inside the fused step from Philox(seed, global index, column j)
+    (natinf_step_f32prod_noise), so image i is the same trajectory for any batch size or GPU count wherever the denoiser
+    itself is batch-independent.  Per step: ONE denoiser forward of [z; z] with [labels; 1000...] and one step launch;
+    nothing in the loop waits for the GPU.
+
+    ``model`` None: ``denoiser_factory()`` or the engine of ``model_path`` built for ``2*batch_size`` samples.  ``decoder``
+    None: ``decoder_factory()`` or the VAE engine of ``vae_path`` (here a callable latents/0.18215 -> images in [-1, 1]); with
+    neither, or ``decode=False``, no image is made.  Decoding runs in chunks of ``decode_batch``; ``image_sink(images uint8
+    [n, 8S, 8S, 3] on the device, indices, labels)``, when given, gets each chunk instead of the images being collected.
+
+    -> (latents [n_local, 4, S, S] fp32 on the device, labels [n_local] int64 CPU, global indices [n_local] int64 CPU,
+        images [n_local, 8S, 8S, 3] uint8 CPU or None)"""
+    from .CIFAR10NaturalInference import philox_noise
+    torch.set_grad_enabled(False)
+    batch_size = int(batch_size)
+    batches = job_batches(sample_count, batch_size, rank, world, labels)
+    if model is None:
+        if denoiser_factory is not None:
+            model = denoiser_factory()
+        elif model_path is not None:
+            model = load_dit_engine(model_path, max_batch=2 * batch_size)
+        else:
+            raise RuntimeError("set ValidateNaturalInference.model_path (a DiT-XL/2 state dict, reference :152-154) or "
+                               "ValidateNaturalInference.denoiser_factory, or pass model=; see INTEGRATION.md")
+    S = latent_size(model)
+    if decode and decoder is None:
+        if decoder_factory is not None:
+            decoder = decoder_factory()
+        elif vae_path is not None:
+            decoder = load_vae_decoder(vae_path, max_batch=int(decode_batch), latent_res=S)
+    if not decode:
+        decoder = None
+    weight_path = root_path / ("results/%s/%s_%03d.npz" % (alg_name.replace("_sympy", ""), alg_name, num_step))
+    C, B, node = load_coeff_npz(weight_path)
+    n_step = B.shape[0]
+    tables, _ = skip_ddim_coeff(create_ddim_coeff(), n_step)
+    c1 = np.asarray(tables[2])[::-1].astype(np.float32)
+    c2 = np.asarray(tables[3])[::-1].astype(np.float32)
+    per = 4 * S * S
+    samplers = {}                                                     # batch size -> ValidateNI (the ragged last batch gets its own)
+    out_z, out_img = [], []
+    for indices, labs in batches:
+        n = len(indices)
+        if n not in samplers:
+            samplers[n] = ValidateNI(C, B, node, c1, c2, n * per, device=device, seed=seed, elems_per_image=per)
+        ni = samplers[n]
+        index = torch.tensor(indices, dtype=torch.int64, device=device)
+        classlabels = torch.tensor(labs, dtype=torch.int64, device=device)
+        classnulls = torch.full((n,), 1000, dtype=torch.int64, device=device)
+        steps_t = [torch.full((n,), int(node[kk, 0]), dtype=torch.int32, device=device) for kk in range(n_step)]
+        noise = philox_noise(indices, (4, S, S), seed, device, column=0)
+        flat_noise = noise.reshape(-1)
+        input_z = noise
+        for kk in range(n_step):
+            cond, uncond = _cond_uncond(model, input_z, steps_t[kk], classlabels, classnulls)   # [n, 8, S, S] each; first 4 channels used
+            z = ni.step(kk, input_z.reshape(-1), cond.contiguous(), uncond.contiguous(), float(cfg_scale), per, cond.shape[1] * S * S,
+                        noise=flat_noise, index=index)
+            input_z = z.view(n, 4, S, S)
+        out_z.append(input_z.clone())
+    latents = torch.cat(out_z) if out_z else torch.empty((0, 4, S, S), dtype=torch.float32, device=device)
+    all_idx = [i for idx, _ in batches for i in idx]
+    all_lab = [l for _, lb in batches for l in lb]
+    if decoder is not None:
+        db = max(1, int(decode_batch))
+        for s0 in range(0, len(all_idx), db):
+            u8 = to_pixels_u8(decoder(latents[s0:s0 + db] / 0.18215))
+            if image_sink is not None:
+                image_sink(u8, all_idx[s0:s0 + db], all_lab[s0:s0 + db])
+            else:
+                out_img.append(u8.cpu())
+    images = None
+    if decoder is not None and image_sink is None:
+        images = torch.cat(out_img) if out_img else torch.empty((0, 8 * S, 8 * S, 3), dtype=torch.uint8)
+    return latents, torch.tensor(all_lab, dtype=torch.int64), torch.tensor(all_idx, dtype=torch.int64), images
+
+
 def compare_output_tx():
     ddpm_skip_sample(24)
     ddim_skip_sample(24)

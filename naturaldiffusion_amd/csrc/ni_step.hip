@@ -17,6 +17,7 @@
 // 117-129,157-168,209,215-219; deps/score_sde_pytorch/models/utils.py:157.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include <mutex>
 #include "natinf.h"
 
 #pragma clang fp contract(off)
@@ -370,8 +371,8 @@ __device__ __forceinline__ void philox4x32_10(uint32_t c0, uint32_t c1, uint32_t
 
 // The four normals of one element quad: Philox4x32-10 of counter (gi lo, gi hi, quad lo, word3), then Box-Muller on the
 // two pairs.  word3 is quad >> 32 for the initial noise (column 0) and the column j for the noise injected after step
-// j-1 (quad < 2^32 then): k_randn_philox and k_step_noise_f64 both call this, so the fused step injects exactly the
-// normals natinf_randn_philox_col_f32 returns.
+// j-1 (quad < 2^32 then): k_randn_philox, k_step_noise_f64 and k_step_noise_f32prod all call this, so the fused steps inject
+// exactly the normals natinf_randn_philox_col_f32 returns.
 __device__ __forceinline__ float4 philox_normals(uint64_t gi, uint64_t q, uint32_t word3, uint32_t k0, uint32_t k1)
 {
     uint32_t r[4];
@@ -462,8 +463,105 @@ __global__ __launch_bounds__(kBlock) void k_step_noise_f64(
     }
 }
 
+// ------------------------------------------------------------------------------------------
+// Validate form with the noise row generated in registers.  CFG fuse, x0_k and the signal sum operation for operation
+// as k_step_f32prod; the noise sum b reads eps_0 from the caller's `noise` and draws eps_j, j >= 1, from
+// philox_normals(global image index, element quad, j): what k_step_f32prod reads from a hist_eps slab whose row j
+// natinf_randn_philox_col_f32(column = j) filled, so the two kernels give the same bytes and the (N+1) x E slab is gone.
+// ------------------------------------------------------------------------------------------
+__global__ __launch_bounds__(kBlock) void k_step_noise_f32prod(
+    const float4* __restrict__ z, const float* __restrict__ cond, const float* __restrict__ uncond, float cfg,
+    int64_t svec, int64_t sstride,
+    float* __restrict__ hist_x0, const float4* __restrict__ noise, float4* __restrict__ z_next,
+    const int32_t* __restrict__ idx_c, const float* __restrict__ val_c, int n_c, float c_diag,
+    const int32_t* __restrict__ idx_b, const float* __restrict__ val_b, int n_b,
+    const int64_t* __restrict__ index, int64_t first_index, int64_t index_stride,
+    uint32_t k0, uint32_t k1, int k, float c1, float c2, int64_t nvec, int64_t E)
+{
+    // one element quad per thread, no grid-stride loop (k_step_noise_f64: the loop's carried scalars make the hoisted
+    // Philox round keys spill SGPRs)
+    const int64_t v = (int64_t)blockIdx.x * kBlock + threadIdx.x;
+    if (v < nvec) {
+        const int64_t img = v / svec, q = v - img * svec;            // an image is one sample: svec quads
+        const float4 zv = z[v];
+        float4 ev = *reinterpret_cast<const float4*>(cond + img * sstride + 4 * q);
+        if (uncond) {
+            const float4 uv = *reinterpret_cast<const float4*>(uncond + img * sstride + 4 * q);
+            float d, m;
+            d = ev.x - uv.x; m = cfg * d; ev.x = uv.x + m;
+            d = ev.y - uv.y; m = cfg * d; ev.y = uv.y + m;
+            d = ev.z - uv.z; m = cfg * d; ev.z = uv.z + m;
+            d = ev.w - uv.w; m = cfg * d; ev.w = uv.w + m;
+        }
+        float4 x0;
+        { const float p = c1 * zv.x, r = c2 * ev.x; x0.x = p - r; }
+        { const float p = c1 * zv.y, r = c2 * ev.y; x0.y = p - r; }
+        { const float p = c1 * zv.z, r = c2 * ev.z; x0.z = p - r; }
+        { const float p = c1 * zv.w, r = c2 * ev.w; x0.w = p - r; }
+        reinterpret_cast<float4*>(hist_x0 + (int64_t)k * E)[v] = x0;
+
+        double a[4] = {0.0, 0.0, 0.0, 0.0}, b[4] = {0.0, 0.0, 0.0, 0.0};
+#pragma unroll 4
+        for (int t = 0; t < n_c; ++t) {
+            const float c = val_c[t];
+            const float4 h = reinterpret_cast<const float4*>(hist_x0 + (int64_t)idx_c[t] * E)[v];
+            const float p0 = h.x * c, p1 = h.y * c, p2 = h.z * c, p3 = h.w * c;
+            a[0] = a[0] + (double)p0; a[1] = a[1] + (double)p1; a[2] = a[2] + (double)p2; a[3] = a[3] + (double)p3;
+        }
+        {
+            const float p0 = x0.x * c_diag, p1 = x0.y * c_diag, p2 = x0.z * c_diag, p3 = x0.w * c_diag;
+            a[0] = a[0] + (double)p0; a[1] = a[1] + (double)p1; a[2] = a[2] + (double)p2; a[3] = a[3] + (double)p3;
+        }
+        const uint64_t gi = (uint64_t)(index ? index[img] : first_index + img * index_stride);
+        for (int t = 0; t < n_b; ++t) {                               // wave-uniform column: one Philox call per quad and term
+            const float c = val_b[t];
+            const uint32_t j = (uint32_t)idx_b[t];
+            const float4 e = j == 0 ? noise[v] : philox_normals(gi, (uint64_t)q, j, k0, k1);
+            const float p0 = e.x * c, p1 = e.y * c, p2 = e.z * c, p3 = e.w * c;
+            b[0] = b[0] + (double)p0; b[1] = b[1] + (double)p1; b[2] = b[2] + (double)p2; b[3] = b[3] + (double)p3;
+        }
+        z_next[v] = make_float4((float)a[0] + (float)b[0], (float)a[1] + (float)b[1],
+                                (float)a[2] + (float)b[2], (float)a[3] + (float)b[3]);
+    }
+}
+
 inline int launched() { return hipGetLastError() == hipSuccess ? NATINF_OK : NATINF_ELAUNCH; }
 inline bool terms_ok(const void* idx, const void* val, int n) { return n >= 0 && (n == 0 || (idx && val)); }
+
+// The host-side check of a noise row natinf_step_f32prod_noise makes before it launches: every column is in 0..k+1 and
+// column 0 has a `noise` to read.  The row is device memory, so its n_b <= k+2 indices are read back on a private
+// non-blocking stream of the current device: the host waits for that small copy only, never for the caller's stream.
+// 1 = fine, 0 = a bad row, -1 = a HIP call failed.
+constexpr int kRowChunk = 1024, kMaxDevices = 64;
+inline int noise_row_ok(const int32_t* idx_b, int n_b, int k, bool have_noise)
+{
+    static std::mutex mu;
+    static hipStream_t streams[kMaxDevices] = {};
+    static int32_t* bufs[kMaxDevices] = {};
+    if (n_b == 0) return 1;
+    int dev = 0;
+    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= kMaxDevices) { (void)hipGetLastError(); return -1; }
+    std::lock_guard<std::mutex> lock(mu);
+    if (!streams[dev]) {
+        hipStream_t s = nullptr;
+        void* b = nullptr;
+        if (hipStreamCreateWithFlags(&s, hipStreamNonBlocking) != hipSuccess) { (void)hipGetLastError(); return -1; }
+        if (hipHostMalloc(&b, kRowChunk * sizeof(int32_t), hipHostMallocDefault) != hipSuccess) {
+            (void)hipGetLastError(); (void)hipStreamDestroy(s); return -1;
+        }
+        streams[dev] = s; bufs[dev] = (int32_t*)b;
+    }
+    for (int o = 0; o < n_b; o += kRowChunk) {
+        const int n = n_b - o < kRowChunk ? n_b - o : kRowChunk;
+        if (hipMemcpyAsync(bufs[dev], idx_b + o, n * sizeof(int32_t), hipMemcpyDefault, streams[dev]) != hipSuccess ||
+            hipStreamSynchronize(streams[dev]) != hipSuccess) { (void)hipGetLastError(); return -1; }
+        for (int i = 0; i < n; ++i) {
+            const int32_t j = bufs[dev][i];
+            if (j < 0 || j > k + 1 || (j == 0 && !have_noise)) return 0;
+        }
+    }
+    return 1;
+}
 
 }  // namespace
 
@@ -599,6 +697,31 @@ int natinf_step_f32prod(const float* z, const float* cond, const float* uncond, 
     hipLaunchKernelGGL(k_step_f32prod, dim3(grid_for(nvec)), dim3(kBlock), 0, (hipStream_t)stream,
                        (const float4*)z, cond, uncond, cfg, sample_elems / 4, eps_sample_stride,
                        hist_x0, hist_eps, (float4*)z_next, idx_c, val_c, n_c, c_diag, idx_b, val_b, n_b,
+                       k, c1_f32, c2_f32, nvec, E);
+    return launched();
+}
+
+int natinf_step_f32prod_noise(const float* z, const float* cond, const float* uncond, float cfg,
+                              int64_t sample_elems, int64_t eps_sample_stride,
+                              float* hist_x0, const float* noise, float* z_next,
+                              const int32_t* idx_c, const float* val_c, int n_c, float c_diag,
+                              const int32_t* idx_b, const float* val_b, int n_b,
+                              int k, float c1_f32, float c2_f32,
+                              uint64_t seed, const int64_t* image_index, int64_t first_index, int64_t index_stride,
+                              int64_t E, natinf_stream_t stream)
+{
+    if (!z || !cond || !hist_x0 || !z_next || !terms_ok(idx_c, val_c, n_c) || !terms_ok(idx_b, val_b, n_b) ||
+        k < 0 || n_b > (int64_t)k + 2 || E <= 0 || (E & 3) || sample_elems <= 0 || (sample_elems & 3) || (E % sample_elems) ||
+        eps_sample_stride < sample_elems || (eps_sample_stride & 3) || ((sample_elems / 4) >> 32))
+        return NATINF_EINVAL;
+    const int64_t nvec = E / 4, blocks = (nvec + kBlock - 1) / kBlock;
+    if (blocks > INT32_MAX) return NATINF_EINVAL;                      // one quad per thread (k_step_noise_f32prod)
+    const int row = noise_row_ok(idx_b, n_b, k, noise != nullptr);
+    if (row <= 0) return row < 0 ? NATINF_ELAUNCH : NATINF_EINVAL;
+    hipLaunchKernelGGL(k_step_noise_f32prod, dim3((unsigned)blocks), dim3(kBlock), 0, (hipStream_t)stream,
+                       (const float4*)z, cond, uncond, cfg, sample_elems / 4, eps_sample_stride,
+                       hist_x0, (const float4*)noise, (float4*)z_next, idx_c, val_c, n_c, c_diag, idx_b, val_b, n_b,
+                       image_index, first_index, index_stride, (uint32_t)seed, (uint32_t)(seed >> 32),
                        k, c1_f32, c2_f32, nvec, E);
     return launched();
 }

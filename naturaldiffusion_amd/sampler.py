@@ -30,6 +30,22 @@ def vp_std_f32(t: float, beta_0: float = 0.1, beta_1: float = 20.0) -> float:
     return float(torch.sqrt(1.0 - torch.exp(2.0 * lmc))[0])
 
 
+def image_index_args(index, n_images: int, device):
+    """The global image indices of a batch as the noise-generating steps take them -> (index tensor or None, first index,
+    index stride).  ``index``: an int64 device tensor with one entry per image, an int ``first`` (image i is ``first + i``),
+    a pair ``(first, stride)`` (image i is ``first + i*stride``) or None (= 0)."""
+    if index is None:
+        return None, 0, 1
+    if isinstance(index, torch.Tensor):
+        if (index.dtype != torch.int64 or index.device != device or not index.is_contiguous()
+                or index.numel() != n_images):
+            raise ValueError("index must be a contiguous int64 tensor on the sampler's device, one entry per image")
+        return index, 0, 0
+    if isinstance(index, (tuple, list)):
+        return None, int(index[0]), int(index[1])
+    return None, int(index), 1
+
+
 class CifarNI:
     """x_{k+1} = fp32(sum_j C[k,j]*x0_j) + fp32(B[k,0])*noise with x0_k = ((-out/std)*sigma^2 + x_k)/alpha.
 
@@ -104,17 +120,7 @@ class CifarNI:
         return x_next
 
     def _index(self, index, epi, device):
-        """-> (index tensor or None, first index, index stride)"""
-        if index is None:
-            return None, 0, 1
-        if isinstance(index, torch.Tensor):
-            if (index.dtype != torch.int64 or index.device != device or not index.is_contiguous()
-                    or index.numel() != self.E // epi):
-                raise ValueError("index must be a contiguous int64 tensor on the sampler's device, one entry per image")
-            return index, 0, 0
-        if isinstance(index, (tuple, list)):
-            return None, int(index[0]), int(index[1])
-        return None, int(index), 1
+        return image_index_args(index, self.E // epi, device)
 
     def run(self, model_fn: Callable, noise: torch.Tensor, return_all: bool = False, index=None):
         """``model_fn(x [B,...] fp32, labels [B] fp32) -> out`` (raw network output).  ``index``: see ``step``."""
@@ -136,10 +142,17 @@ class CifarNI:
 
 
 class ValidateNI:
-    """DiT / eps-prediction form with per-step fresh noise and CFG (ValidateNaturalInference.py:311-372)."""
+    """DiT / eps-prediction form with per-step fresh noise and CFG (ValidateNaturalInference.py:311-372).
+
+    Without ``seed`` the caller fills the noise-history slab ``hist_eps`` (row 0 the initial noise, row j the draw after step
+    j-1) and ``step`` is natinf_step_f32prod.  With ``seed`` there is no slab: ``step`` takes the initial noise and the batch's
+    global image indices and draws eps_j, j >= 1, in the kernel from Philox(``seed``, global image index, column j)
+    (include/natinf.h, natinf_step_f32prod_noise) -- the bytes of the slab path on a slab filled by ``philox_noise(column=j)``,
+    for stochastic (``ddpm_*``) and deterministic (``ddim_*``: column 0 only) matrices alike.  ``elems_per_image`` pins the
+    per-image size ``step`` must be called with (None: whatever ``sample_elems`` each call gives)."""
 
     def __init__(self, C: np.ndarray, B: np.ndarray, node: np.ndarray, c1: np.ndarray, c2: np.ndarray, n_elem: int,
-                 device="cuda:0", dense: bool = False):
+                 device="cuda:0", dense: bool = False, *, seed: Optional[int] = None, elems_per_image: Optional[int] = None):
         _lib.require_gpu()
         if n_elem % 4:
             raise ValueError("element count must be a multiple of 4")
@@ -147,16 +160,27 @@ class ValidateNI:
         self.node = np.asarray(node, np.float64)
         self.E = int(n_elem)
         self.device = torch.device(device)
+        self.seed = None if seed is None else int(seed) & (2 ** 64 - 1)
+        if elems_per_image is not None:
+            if seed is None:
+                raise ValueError("elems_per_image belongs to the seeded (in-kernel noise) form: give a seed")
+            if elems_per_image <= 0 or elems_per_image % 4 or self.E % elems_per_image:
+                raise ValueError("elems_per_image must be a positive multiple of 4 dividing the element count")
+        self.epi = None if elems_per_image is None else int(elems_per_image)
         self.rows_c = SparseRows(C, lambda k: k + 1, torch.float32, self.device, dense=dense)
         self.rows_b = SparseRows(B, lambda k: min(k + 2, np.asarray(B).shape[1]), torch.float32, self.device, dense=dense, diag=False)
         self.c1 = [float(np.float32(v)) for v in c1]
         self.c2 = [float(np.float32(v)) for v in c2]
         self.hist_x0 = torch.empty((self.n_step, self.E), dtype=torch.float32, device=self.device)
-        self.hist_eps = torch.empty((self.n_step + 1, self.E), dtype=torch.float32, device=self.device)
+        # the seeded form draws the noise rows in the kernel: no (N+1) x E slab
+        self.hist_eps = None if self.seed is not None else torch.empty((self.n_step + 1, self.E), dtype=torch.float32, device=self.device)
         self._z = [torch.empty(self.E, dtype=torch.float32, device=self.device) for _ in range(2)]
 
     def step(self, k: int, z: torch.Tensor, cond: torch.Tensor, uncond: Optional[torch.Tensor], cfg: float,
-             sample_elems: Optional[int] = None, eps_sample_stride: Optional[int] = None) -> torch.Tensor:
+             sample_elems: Optional[int] = None, eps_sample_stride: Optional[int] = None, *,
+             noise: Optional[torch.Tensor] = None, index=None) -> torch.Tensor:
+        """``noise`` / ``index`` (seeded form only): the initial noise eps_0 ([E] fp32, contiguous) and the batch's global image
+        indices in one of ``image_index_args``' forms; an image is one sample of ``sample_elems`` elements."""
         se = self.E if sample_elems is None else int(sample_elems)
         st = se if eps_sample_stride is None else int(eps_sample_stride)
         z_next = self._z[k & 1]
@@ -164,9 +188,25 @@ class ValidateNI:
             z_next = self._z[(k + 1) & 1]
         ic, vc, nc = self.rows_c.ptrs(k)
         ib, vb, nb = self.rows_b.ptrs(k)
-        check(lib.natinf_step_f32prod(ptr(z), ptr(cond), ptr(uncond), float(cfg), se, st, ptr(self.hist_x0),
-                                      ptr(self.hist_eps), ptr(z_next), ic, vc, nc, self.rows_c.rows[k].diag,
-                                      ib, vb, nb, k, self.c1[k], self.c2[k], self.E, stream_ptr()), "natinf_step_f32prod")
+        if self.seed is None:
+            if noise is not None or index is not None:
+                raise ValueError("noise / index belong to the seeded form; without a seed the noises are read from hist_eps")
+            check(lib.natinf_step_f32prod(ptr(z), ptr(cond), ptr(uncond), float(cfg), se, st, ptr(self.hist_x0),
+                                          ptr(self.hist_eps), ptr(z_next), ic, vc, nc, self.rows_c.rows[k].diag,
+                                          ib, vb, nb, k, self.c1[k], self.c2[k], self.E, stream_ptr()), "natinf_step_f32prod")
+            return z_next
+        if noise is None:
+            raise ValueError("seeded form: step needs the initial noise (noise=); there is no hist_eps slab to read it from")
+        if noise.dtype != torch.float32 or noise.numel() != self.E or not noise.is_contiguous() or noise.device != z.device:
+            raise ValueError("noise must be a contiguous fp32 tensor of n_elem elements on the sampler's device")
+        if se <= 0 or se % 4 or self.E % se or (self.epi is not None and se != self.epi):
+            raise ValueError("sample_elems must be the per-image element count: a multiple of 4 dividing the element count"
+                             + ("" if self.epi is None else f" (elems_per_image = {self.epi})"))
+        index, first, stride = image_index_args(index, self.E // se, z.device)
+        check(lib.natinf_step_f32prod_noise(ptr(z), ptr(cond), ptr(uncond), float(cfg), se, st, ptr(self.hist_x0), ptr(noise),
+                                            ptr(z_next), ic, vc, nc, self.rows_c.rows[k].diag, ib, vb, nb, k, self.c1[k],
+                                            self.c2[k], self.seed, ptr(index), first, stride, self.E, stream_ptr()),
+              "natinf_step_f32prod_noise")
         return z_next
 
 
