@@ -12,6 +12,10 @@
 // one IEEE rounding per reference operation.  The file is compiled -ffp-contract=off and the
 // pragma below repeats it, so no mul+add pair is ever fused.
 //
+// Every expression of that contract is written ONCE, as a __device__ __forceinline__ piece that keeps
+// the named fp32 / fp64 temporaries which fix its roundings; a kernel is a short composition of pieces,
+// so a kernel with in-kernel noise cannot drift from its slab twin (DESIGN.md section 3 lists them).
+//
 // Reference lines replaced: src/CIFAR10NaturalInference.py:219-238,299-304;
 // src/ValidateNaturalInference.py:193,198-204,355,362-366; src/SD3NaturalInference.py:61-69,
 // 117-129,157-168,209,215-219; deps/score_sde_pytorch/models/utils.py:157.
@@ -32,6 +36,10 @@ inline int grid_for(int64_t nvec) {
     return (int)(g < 1 ? 1 : (g > kMaxGrid ? kMaxGrid : g));
 }
 
+// grid-stride loop: for (v = first_vec(); v < nvec; v += vec_stride())
+__device__ __forceinline__ int64_t first_vec() { return (int64_t)blockIdx.x * kBlock + threadIdx.x; }
+__device__ __forceinline__ int64_t vec_stride() { return (int64_t)gridDim.x * kBlock; }
+
 struct alignas(16) d2 { double x, y; };
 typedef _Float16 h16;
 struct alignas(16) h8 { h16 v[8]; };
@@ -46,6 +54,13 @@ __device__ __forceinline__ h16 hmulf(float s, h16 a) {
 }
 __device__ __forceinline__ h16 hadd(h16 a, h16 b) { return (h16)((float)a + (float)b); }
 __device__ __forceinline__ h16 hsub(h16 a, h16 b) { return (h16)((float)a - (float)b); }
+
+__device__ __forceinline__ h8 h8_zero() {
+    h8 z;
+#pragma unroll
+    for (int i = 0; i < 8; ++i) z.v[i] = (h16)0.0f;
+    return z;
+}
 
 // acc <- fp16 chain over the sparse row; hand-unrolled by 4 so four row loads are in flight
 // (the asm pin in hmulf keeps the compiler from unrolling the loop itself).
@@ -75,6 +90,108 @@ __device__ __forceinline__ void chain_terms(h8& acc, const h16* __restrict__ his
     }
 }
 
+// fp16 row mean: fp32 division of the fp16 sum, rounded to fp16
+__device__ __forceinline__ h8 mean_of(h8 acc, float w_total) {
+    h8 mean;
+#pragma unroll
+    for (int i = 0; i < 8; ++i) mean.v[i] = (h16)((float)acc.v[i] / w_total);
+    return mean;
+}
+
+// next flow input sig*noise + oms*mean, every operation rounded to fp16
+__device__ __forceinline__ h8 flow_input(h8 nz, h8 m, float sig, float oms) {
+    h8 r;
+#pragma unroll
+    for (int i = 0; i < 8; ++i) r.v[i] = hadd(hmulf(sig, nz.v[i]), hmulf(oms, m.v[i]));
+    return r;
+}
+
+// ---- pieces of the CIFAR10 form (fp64 history) ----
+// x0 = ((-out/std) * sigma^2 + x) / alpha: the score in fp32, then three fp64 roundings; stored as quad v of the slab row
+__device__ __forceinline__ void x0_from_score_f64(double (&x0)[4], float4 xv, float4 ov, float stdv, double sigma2,
+                                                  double alpha, double* hist_k, int64_t v)
+{
+    const float xs[4] = {xv.x, xv.y, xv.z, xv.w};
+    const float os[4] = {ov.x, ov.y, ov.z, ov.w};
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+        const float s = (-os[i]) / stdv;                          // score, fp32
+        x0[i] = ((double)s * sigma2 + (double)xs[i]) / alpha;     // fp64, three roundings
+    }
+    d2* hk = reinterpret_cast<d2*>(hist_k) + 2 * v;
+    hk[0] = d2{x0[0], x0[1]};
+    hk[1] = d2{x0[2], x0[3]};
+}
+
+// acc <- acc + h*c, four lanes: one fp64 product, one fp64 sum
+__device__ __forceinline__ void acc_f64(double (&acc)[4], double h0, double h1, double h2, double h3, double c) {
+    acc[0] = acc[0] + h0 * c; acc[1] = acc[1] + h1 * c;
+    acc[2] = acc[2] + h2 * c; acc[3] = acc[3] + h3 * c;
+}
+
+__device__ __forceinline__ void wsum_f64(double (&acc)[4], const double* hist, const int32_t* idx, const double* val,
+                                         int n_terms, int64_t v, int64_t E)
+{
+#pragma unroll 4
+    for (int t = 0; t < n_terms; ++t) {
+        const double c = val[t];
+        const d2* hj = reinterpret_cast<const d2*>(hist + (int64_t)idx[t] * E) + 2 * v;
+        const d2 a = hj[0], b = hj[1];
+        acc_f64(acc, a.x, a.y, b.x, b.y, c);
+    }
+}
+
+// ---- pieces of the Validate form (fp32 products, fp64 accumulate) ----
+// quad q of sample img of the logical [B][sample_elems] tensor inside a [B][sstride] buffer
+__device__ __forceinline__ float4 ld_eps(const float* p, int64_t img, int64_t q, int64_t sstride) {
+    return *reinterpret_cast<const float4*>(p + img * sstride + 4 * q);
+}
+
+// the model's eps: cond, or the CFG fuse uncond + cfg*(cond - uncond) in three fp32 roundings
+__device__ __forceinline__ float4 cfg_eps(const float* cond, const float* uncond, float cfg, int64_t img, int64_t q,
+                                          int64_t sstride)
+{
+    float4 ev = ld_eps(cond, img, q, sstride);
+    if (uncond) {
+        const float4 uv = ld_eps(uncond, img, q, sstride);
+        const float e[4] = {ev.x, ev.y, ev.z, ev.w}, u[4] = {uv.x, uv.y, uv.z, uv.w};
+        float r[4];
+#pragma unroll
+        for (int i = 0; i < 4; ++i) { const float d = e[i] - u[i], m = cfg * d; r[i] = u[i] + m; }
+        ev = make_float4(r[0], r[1], r[2], r[3]);
+    }
+    return ev;
+}
+
+// x0 = c1*z - c2*eps: two fp32 products and a subtraction
+__device__ __forceinline__ float4 x0_f32prod(float c1, float4 zv, float c2, float4 ev) {
+    const float z[4] = {zv.x, zv.y, zv.z, zv.w}, e[4] = {ev.x, ev.y, ev.z, ev.w};
+    float x0[4];
+#pragma unroll
+    for (int i = 0; i < 4; ++i) { const float p = c1 * z[i], q = c2 * e[i]; x0[i] = p - q; }
+    return make_float4(x0[0], x0[1], x0[2], x0[3]);
+}
+
+// acc <- acc + (double)fp32(h*c), four lanes: history rows, the diagonal term and the noise row all go through here
+__device__ __forceinline__ void acc_prod(double (&acc)[4], float4 h, float c) {
+    const float p0 = h.x * c, p1 = h.y * c, p2 = h.z * c, p3 = h.w * c;
+    acc[0] = acc[0] + (double)p0; acc[1] = acc[1] + (double)p1; acc[2] = acc[2] + (double)p2; acc[3] = acc[3] + (double)p3;
+}
+
+__device__ __forceinline__ void wsum_f32prod(double (&acc)[4], const float* hist, const int32_t* idx, const float* val,
+                                             int n_terms, int64_t v, int64_t E)
+{
+#pragma unroll 4
+    for (int t = 0; t < n_terms; ++t)
+        acc_prod(acc, reinterpret_cast<const float4*>(hist + (int64_t)idx[t] * E)[v], val[t]);
+}
+
+// (float)a + (float)b: each fp64 sum is cast once, then one fp32 addition
+__device__ __forceinline__ float4 combine(const double (&a)[4], const double (&b)[4]) {
+    return make_float4((float)a[0] + (float)b[0], (float)a[1] + (float)b[1],
+                       (float)a[2] + (float)b[2], (float)a[3] + (float)b[3]);
+}
+
 // ------------------------------------------------------------------------------------------
 // CIFAR10 form, fp64 history
 // ------------------------------------------------------------------------------------------
@@ -84,38 +201,14 @@ __global__ __launch_bounds__(kBlock) void k_step_f64hist(
     const int32_t* __restrict__ idx, const double* __restrict__ val, int n_terms, double c_diag,
     int k, double alpha, double sigma2, float stdv, float b0, int64_t nvec, int64_t E)
 {
-    const int64_t stride = (int64_t)gridDim.x * kBlock;
-    for (int64_t v = (int64_t)blockIdx.x * kBlock + threadIdx.x; v < nvec; v += stride) {
-        const float4 xv = x_k[v], ov = mout[v], nv = noise[v];
-        const float xs[4] = {xv.x, xv.y, xv.z, xv.w};
-        const float os[4] = {ov.x, ov.y, ov.z, ov.w};
-        const float ns[4] = {nv.x, nv.y, nv.z, nv.w};
-        double x0[4];
-#pragma unroll
-        for (int i = 0; i < 4; ++i) {
-            const float s = (-os[i]) / stdv;                          // score, fp32
-            x0[i] = ((double)s * sigma2 + (double)xs[i]) / alpha;     // fp64, three roundings
-        }
-        d2* hk = reinterpret_cast<d2*>(hist + (int64_t)k * E) + 2 * v;
-        hk[0] = d2{x0[0], x0[1]};
-        hk[1] = d2{x0[2], x0[3]};
-
-        double acc[4] = {0.0, 0.0, 0.0, 0.0};
-#pragma unroll 4
-        for (int t = 0; t < n_terms; ++t) {
-            const double c = val[t];
-            const d2* hj = reinterpret_cast<const d2*>(hist + (int64_t)idx[t] * E) + 2 * v;
-            const d2 a = hj[0], b = hj[1];
-            acc[0] = acc[0] + a.x * c; acc[1] = acc[1] + a.y * c;
-            acc[2] = acc[2] + b.x * c; acc[3] = acc[3] + b.y * c;
-        }
-        float r[4];
-#pragma unroll
-        for (int i = 0; i < 4; ++i) {
-            acc[i] = acc[i] + x0[i] * c_diag;
-            r[i] = (float)acc[i] + b0 * ns[i];
-        }
-        x_next[v] = make_float4(r[0], r[1], r[2], r[3]);
+    for (int64_t v = first_vec(); v < nvec; v += vec_stride()) {
+        const float4 nv = noise[v];
+        double x0[4], acc[4] = {0.0, 0.0, 0.0, 0.0};
+        x0_from_score_f64(x0, x_k[v], mout[v], stdv, sigma2, alpha, hist + (int64_t)k * E, v);
+        wsum_f64(acc, hist, idx, val, n_terms, v, E);
+        acc_f64(acc, x0[0], x0[1], x0[2], x0[3], c_diag);
+        x_next[v] = make_float4((float)acc[0] + b0 * nv.x, (float)acc[1] + b0 * nv.y,
+                                (float)acc[2] + b0 * nv.z, (float)acc[3] + b0 * nv.w);
     }
 }
 
@@ -123,17 +216,9 @@ __global__ __launch_bounds__(kBlock) void k_wsum_f64(
     const double* __restrict__ hist, float4* __restrict__ out,
     const int32_t* __restrict__ idx, const double* __restrict__ val, int n_terms, int64_t nvec, int64_t E)
 {
-    const int64_t stride = (int64_t)gridDim.x * kBlock;
-    for (int64_t v = (int64_t)blockIdx.x * kBlock + threadIdx.x; v < nvec; v += stride) {
+    for (int64_t v = first_vec(); v < nvec; v += vec_stride()) {
         double acc[4] = {0.0, 0.0, 0.0, 0.0};
-#pragma unroll 4
-        for (int t = 0; t < n_terms; ++t) {
-            const double c = val[t];
-            const d2* hj = reinterpret_cast<const d2*>(hist + (int64_t)idx[t] * E) + 2 * v;
-            const d2 a = hj[0], b = hj[1];
-            acc[0] = acc[0] + a.x * c; acc[1] = acc[1] + a.y * c;
-            acc[2] = acc[2] + b.x * c; acc[3] = acc[3] + b.y * c;
-        }
+        wsum_f64(acc, hist, idx, val, n_terms, v, E);
         out[v] = make_float4((float)acc[0], (float)acc[1], (float)acc[2], (float)acc[3]);
     }
 }
@@ -145,8 +230,7 @@ __global__ __launch_bounds__(kBlock) void k_step_f32hist(
     const int32_t* __restrict__ idx, const float* __restrict__ val, int n_terms, float c_diag,
     int k, float inv_alpha, float sigma2_over_std, float b0, int64_t nvec, int64_t E)
 {
-    const int64_t stride = (int64_t)gridDim.x * kBlock;
-    for (int64_t v = (int64_t)blockIdx.x * kBlock + threadIdx.x; v < nvec; v += stride) {
+    for (int64_t v = first_vec(); v < nvec; v += vec_stride()) {
         const float4 xv = x_k[v], ov = mout[v], nv = noise[v];
         float4 x0;
         x0.x = __builtin_fmaf(-ov.x, sigma2_over_std, xv.x) * inv_alpha;
@@ -189,12 +273,6 @@ __global__ __launch_bounds__(kBlock) void k_to_pixel(
 // ------------------------------------------------------------------------------------------
 // Validate form: fp32 products, fp64 accumulate
 // ------------------------------------------------------------------------------------------
-__device__ __forceinline__ float4 ld_eps(const float* p, int64_t v, int64_t svec, int64_t sstride) {
-    // vector v of the logical [B][sample_elems] tensor inside a [B][sstride] buffer
-    const int64_t n = v / svec, r = v - n * svec;
-    return *reinterpret_cast<const float4*>(p + n * sstride + 4 * r);
-}
-
 __global__ __launch_bounds__(kBlock) void k_step_f32prod(
     const float4* __restrict__ z, const float* __restrict__ cond, const float* __restrict__ uncond, float cfg,
     int64_t svec, int64_t sstride,
@@ -203,46 +281,16 @@ __global__ __launch_bounds__(kBlock) void k_step_f32prod(
     const int32_t* __restrict__ idx_b, const float* __restrict__ val_b, int n_b,
     int k, float c1, float c2, int64_t nvec, int64_t E)
 {
-    const int64_t stride = (int64_t)gridDim.x * kBlock;
-    for (int64_t v = (int64_t)blockIdx.x * kBlock + threadIdx.x; v < nvec; v += stride) {
-        const float4 zv = z[v];
-        float4 ev = ld_eps(cond, v, svec, sstride);
-        if (uncond) {
-            const float4 uv = ld_eps(uncond, v, svec, sstride);
-            float d, m;
-            d = ev.x - uv.x; m = cfg * d; ev.x = uv.x + m;
-            d = ev.y - uv.y; m = cfg * d; ev.y = uv.y + m;
-            d = ev.z - uv.z; m = cfg * d; ev.z = uv.z + m;
-            d = ev.w - uv.w; m = cfg * d; ev.w = uv.w + m;
-        }
-        float4 x0;
-        { const float p = c1 * zv.x, q = c2 * ev.x; x0.x = p - q; }
-        { const float p = c1 * zv.y, q = c2 * ev.y; x0.y = p - q; }
-        { const float p = c1 * zv.z, q = c2 * ev.z; x0.z = p - q; }
-        { const float p = c1 * zv.w, q = c2 * ev.w; x0.w = p - q; }
+    for (int64_t v = first_vec(); v < nvec; v += vec_stride()) {
+        const int64_t img = v / svec, q = v - img * svec;
+        const float4 x0 = x0_f32prod(c1, z[v], c2, cfg_eps(cond, uncond, cfg, img, q, sstride));
         reinterpret_cast<float4*>(hist_x0 + (int64_t)k * E)[v] = x0;
 
         double a[4] = {0.0, 0.0, 0.0, 0.0}, b[4] = {0.0, 0.0, 0.0, 0.0};
-#pragma unroll 4
-        for (int t = 0; t < n_c; ++t) {
-            const float c = val_c[t];
-            const float4 h = reinterpret_cast<const float4*>(hist_x0 + (int64_t)idx_c[t] * E)[v];
-            const float p0 = h.x * c, p1 = h.y * c, p2 = h.z * c, p3 = h.w * c;
-            a[0] = a[0] + (double)p0; a[1] = a[1] + (double)p1; a[2] = a[2] + (double)p2; a[3] = a[3] + (double)p3;
-        }
-        {
-            const float p0 = x0.x * c_diag, p1 = x0.y * c_diag, p2 = x0.z * c_diag, p3 = x0.w * c_diag;
-            a[0] = a[0] + (double)p0; a[1] = a[1] + (double)p1; a[2] = a[2] + (double)p2; a[3] = a[3] + (double)p3;
-        }
-#pragma unroll 4
-        for (int t = 0; t < n_b; ++t) {
-            const float c = val_b[t];
-            const float4 h = reinterpret_cast<const float4*>(hist_eps + (int64_t)idx_b[t] * E)[v];
-            const float p0 = h.x * c, p1 = h.y * c, p2 = h.z * c, p3 = h.w * c;
-            b[0] = b[0] + (double)p0; b[1] = b[1] + (double)p1; b[2] = b[2] + (double)p2; b[3] = b[3] + (double)p3;
-        }
-        z_next[v] = make_float4((float)a[0] + (float)b[0], (float)a[1] + (float)b[1],
-                                (float)a[2] + (float)b[2], (float)a[3] + (float)b[3]);
+        wsum_f32prod(a, hist_x0, idx_c, val_c, n_c, v, E);
+        acc_prod(a, x0, c_diag);
+        wsum_f32prod(b, hist_eps, idx_b, val_b, n_b, v, E);
+        z_next[v] = combine(a, b);
     }
 }
 
@@ -250,16 +298,9 @@ __global__ __launch_bounds__(kBlock) void k_wsum_f32prod(
     const float* __restrict__ hist, float4* __restrict__ out,
     const int32_t* __restrict__ idx, const float* __restrict__ val, int n_terms, int64_t nvec, int64_t E)
 {
-    const int64_t stride = (int64_t)gridDim.x * kBlock;
-    for (int64_t v = (int64_t)blockIdx.x * kBlock + threadIdx.x; v < nvec; v += stride) {
+    for (int64_t v = first_vec(); v < nvec; v += vec_stride()) {
         double a[4] = {0.0, 0.0, 0.0, 0.0};
-#pragma unroll 4
-        for (int t = 0; t < n_terms; ++t) {
-            const float c = val[t];
-            const float4 h = reinterpret_cast<const float4*>(hist + (int64_t)idx[t] * E)[v];
-            const float p0 = h.x * c, p1 = h.y * c, p2 = h.z * c, p3 = h.w * c;
-            a[0] = a[0] + (double)p0; a[1] = a[1] + (double)p1; a[2] = a[2] + (double)p2; a[3] = a[3] + (double)p3;
-        }
+        wsum_f32prod(a, hist, idx, val, n_terms, v, E);
         out[v] = make_float4((float)a[0], (float)a[1], (float)a[2], (float)a[3]);
     }
 }
@@ -274,8 +315,7 @@ __global__ __launch_bounds__(kBlock) void k_step_f16chain(
     const int32_t* __restrict__ idx, const float* __restrict__ val, int n_terms, float c_diag, float w_total,
     int k, float sig, float sig_next, float oms_next, float cfg, int64_t nvec, int64_t E)
 {
-    const int64_t stride = (int64_t)gridDim.x * kBlock;
-    for (int64_t v = (int64_t)blockIdx.x * kBlock + threadIdx.x; v < nvec; v += stride) {
+    for (int64_t v = first_vec(); v < nvec; v += vec_stride()) {
         const h8 xv = x[v], tv = v_text[v], uv = v_null[v];
         h8 f;
 #pragma unroll
@@ -293,43 +333,21 @@ __global__ __launch_bounds__(kBlock) void k_step_f16chain(
         }
         reinterpret_cast<h8*>(hist + (int64_t)k * E)[v] = f;
 
-        h8 acc;
-#pragma unroll
-        for (int i = 0; i < 8; ++i) acc.v[i] = (h16)0.0f;
+        h8 acc = h8_zero();
         chain_terms(acc, hist, idx, val, n_terms, v, E);
-        h8 mean;
 #pragma unroll
-        for (int i = 0; i < 8; ++i) {
-            acc.v[i] = hadd(acc.v[i], hmulf(c_diag, f.v[i]));
-            mean.v[i] = (h16)((float)acc.v[i] / w_total);
-        }
+        for (int i = 0; i < 8; ++i) acc.v[i] = hadd(acc.v[i], hmulf(c_diag, f.v[i]));
+        const h8 mean = mean_of(acc, w_total);
         if (mean_out) mean_out[v] = mean;
-        if (x_next) {
-            const h8 nz = noise[v];
-            h8 r;
-#pragma unroll
-            for (int i = 0; i < 8; ++i) r.v[i] = hadd(hmulf(sig_next, nz.v[i]), hmulf(oms_next, mean.v[i]));
-            x_next[v] = r;
-        }
+        if (x_next) x_next[v] = flow_input(noise[v], mean, sig_next, oms_next);
     }
 }
 
 __global__ __launch_bounds__(kBlock) void k_flow_input_f16(
     const h8* __restrict__ noise, const h8* __restrict__ mean, h8* __restrict__ out, float sig, float oms, int64_t nvec)
 {
-    const int64_t stride = (int64_t)gridDim.x * kBlock;
-    for (int64_t v = (int64_t)blockIdx.x * kBlock + threadIdx.x; v < nvec; v += stride) {
-        const h8 nz = noise[v];
-        h8 m, r;
-        if (mean) m = mean[v];
-        else {
-#pragma unroll
-            for (int i = 0; i < 8; ++i) m.v[i] = (h16)0.0f;
-        }
-#pragma unroll
-        for (int i = 0; i < 8; ++i) r.v[i] = hadd(hmulf(sig, nz.v[i]), hmulf(oms, m.v[i]));
-        out[v] = r;
-    }
+    for (int64_t v = first_vec(); v < nvec; v += vec_stride())
+        out[v] = flow_input(noise[v], mean ? mean[v] : h8_zero(), sig, oms);
 }
 
 __global__ __launch_bounds__(kBlock) void k_wmean_f16(
@@ -337,16 +355,10 @@ __global__ __launch_bounds__(kBlock) void k_wmean_f16(
     const int32_t* __restrict__ idx, const float* __restrict__ val, int n_terms, float w_total,
     int64_t nvec, int64_t E)
 {
-    const int64_t stride = (int64_t)gridDim.x * kBlock;
-    for (int64_t v = (int64_t)blockIdx.x * kBlock + threadIdx.x; v < nvec; v += stride) {
-        h8 acc;
-#pragma unroll
-        for (int i = 0; i < 8; ++i) acc.v[i] = (h16)0.0f;
+    for (int64_t v = first_vec(); v < nvec; v += vec_stride()) {
+        h8 acc = h8_zero();
         chain_terms(acc, hist, idx, val, n_terms, v, E);
-        h8 mean;
-#pragma unroll
-        for (int i = 0; i < 8; ++i) mean.v[i] = (h16)((float)acc.v[i] / w_total);
-        out[v] = mean;
+        out[v] = mean_of(acc, w_total);
     }
 }
 
@@ -371,8 +383,8 @@ __device__ __forceinline__ void philox4x32_10(uint32_t c0, uint32_t c1, uint32_t
 
 // The four normals of one element quad: Philox4x32-10 of counter (gi lo, gi hi, quad lo, word3), then Box-Muller on the
 // two pairs.  word3 is quad >> 32 for the initial noise (column 0) and the column j for the noise injected after step
-// j-1 (quad < 2^32 then): k_randn_philox, k_step_noise_f64 and k_step_noise_f32prod all call this, so the fused steps inject
-// exactly the normals natinf_randn_philox_col_f32 returns.
+// j-1 (quad < 2^32 then): k_randn_philox and noise_row_sum both call this, so the fused steps inject exactly the normals
+// natinf_randn_philox_col_f32 returns.
 __device__ __forceinline__ float4 philox_normals(uint64_t gi, uint64_t q, uint32_t word3, uint32_t k0, uint32_t k1)
 {
     uint32_t r[4];
@@ -390,25 +402,41 @@ __device__ __forceinline__ float4 philox_normals(uint64_t gi, uint64_t q, uint32
     return make_float4(z[0], z[1], z[2], z[3]);
 }
 
+// global index of image img of the batch: from the caller's array, or first + img*stride
+__device__ __forceinline__ uint64_t global_index(const int64_t* index, int64_t first, int64_t stride, int64_t img) {
+    return (uint64_t)(index ? index[img] : first + img * stride);
+}
+
+// acc <- the noise row sum_t val_b[t] * eps_{idx_b[t]} in the Validate form's arithmetic
+// (src/ValidateNaturalInference.py:198-204: fp32 product, fp64 accumulate in ascending column order).  eps_0 is the caller's
+// noise; eps_j, j >= 1, is generated in registers (philox_normals with word3 = j): what a slab whose row j
+// natinf_randn_philox_col_f32(column = j) filled would hold.
+__device__ __forceinline__ void noise_row_sum(double (&acc)[4], const float4* noise, const int32_t* idx_b, const float* val_b,
+                                              int n_b, int64_t v, uint64_t gi, int64_t q, uint32_t k0, uint32_t k1)
+{
+    for (int t = 0; t < n_b; ++t) {                               // wave-uniform column: one Philox call per quad and term
+        const float c = val_b[t];
+        const uint32_t j = (uint32_t)idx_b[t];
+        const float4 e = j == 0 ? noise[v] : philox_normals(gi, (uint64_t)q, j, k0, k1);
+        acc_prod(acc, e, c);
+    }
+}
+
 __global__ __launch_bounds__(kBlock) void k_randn_philox(
     float4* __restrict__ out, const int64_t* __restrict__ index, int64_t first_index, int64_t index_stride,
     int64_t quads_per_image, int64_t total_quads, uint32_t column, uint32_t k0, uint32_t k1)
 {
-    const int64_t stride = (int64_t)gridDim.x * kBlock;
-    for (int64_t v = (int64_t)blockIdx.x * kBlock + threadIdx.x; v < total_quads; v += stride) {
+    for (int64_t v = first_vec(); v < total_quads; v += vec_stride()) {
         const int64_t img = v / quads_per_image, q = v - img * quads_per_image;
-        const uint64_t gi = (uint64_t)(index ? index[img] : first_index + img * index_stride);
+        const uint64_t gi = global_index(index, first_index, index_stride, img);
         out[v] = philox_normals(gi, (uint64_t)q, column ? column : (uint32_t)((uint64_t)q >> 32), k0, k1);
     }
 }
 
 // ------------------------------------------------------------------------------------------
-// CIFAR10 form with per-step noise (stochastic matrices: B[k, j >= 1] != 0).  x0_k and the signal sum exactly as
-// k_step_f64hist; the noise row sum_t val_b[t] * eps_{idx_b[t]} in the Validate form's arithmetic
-// (src/ValidateNaturalInference.py:198-204: fp32 product, fp64 accumulate in ascending column order, one cast), then
-// x_next = (float)acc_x0 + (float)acc_eps.  eps_0 is the caller's noise; eps_j, j >= 1, is generated in registers
-// (philox_normals with word3 = j): no noise slab, and every image's noise is a function of (seed, global index, column).
-// A row whose only entry is column 0 gives (float)acc + b0*noise, the bits of k_step_f64hist.
+// CIFAR10 form with per-step noise (stochastic matrices: B[k, j >= 1] != 0): k_step_f64hist's x0_k and signal sum, then
+// noise_row_sum and x_next = (float)acc_x0 + (float)acc_eps.  No noise slab, and every image's noise is a function of
+// (seed, global index, column).  A row whose only entry is column 0 gives (float)acc + b0*noise, the bits of k_step_f64hist.
 // ------------------------------------------------------------------------------------------
 __global__ __launch_bounds__(kBlock) void k_step_noise_f64(
     const float4* __restrict__ x_k, const float4* __restrict__ mout, const float4* __restrict__ noise,
@@ -420,54 +448,22 @@ __global__ __launch_bounds__(kBlock) void k_step_noise_f64(
 {
     // one element quad per thread, no grid-stride loop: with the loop's carried scalars the 20 Philox round keys the
     // compiler hoists into SGPRs spill (10-35 SGPRs); without it the kernel needs 57 SGPRs and spills nothing
-    const int64_t v = (int64_t)blockIdx.x * kBlock + threadIdx.x;
+    const int64_t v = first_vec();
     if (v < nvec) {
-        const float4 xv = x_k[v], ov = mout[v];
-        const float xs[4] = {xv.x, xv.y, xv.z, xv.w};
-        const float os[4] = {ov.x, ov.y, ov.z, ov.w};
-        double x0[4];
-#pragma unroll
-        for (int i = 0; i < 4; ++i) {
-            const float s = (-os[i]) / stdv;                          // score, fp32
-            x0[i] = ((double)s * sigma2 + (double)xs[i]) / alpha;     // fp64, three roundings
-        }
-        d2* hk = reinterpret_cast<d2*>(hist + (int64_t)k * E) + 2 * v;
-        hk[0] = d2{x0[0], x0[1]};
-        hk[1] = d2{x0[2], x0[3]};
-
-        double acc[4] = {0.0, 0.0, 0.0, 0.0};
-#pragma unroll 4
-        for (int t = 0; t < n_terms; ++t) {
-            const double c = val[t];
-            const d2* hj = reinterpret_cast<const d2*>(hist + (int64_t)idx[t] * E) + 2 * v;
-            const d2 a = hj[0], b = hj[1];
-            acc[0] = acc[0] + a.x * c; acc[1] = acc[1] + a.y * c;
-            acc[2] = acc[2] + b.x * c; acc[3] = acc[3] + b.y * c;
-        }
-#pragma unroll
-        for (int i = 0; i < 4; ++i) acc[i] = acc[i] + x0[i] * c_diag;
+        double x0[4], acc[4] = {0.0, 0.0, 0.0, 0.0}, nacc[4] = {0.0, 0.0, 0.0, 0.0};
+        x0_from_score_f64(x0, x_k[v], mout[v], stdv, sigma2, alpha, hist + (int64_t)k * E, v);
+        wsum_f64(acc, hist, idx, val, n_terms, v, E);
+        acc_f64(acc, x0[0], x0[1], x0[2], x0[3], c_diag);
 
         const int64_t img = v / quads_per_image, q = v - img * quads_per_image;
-        const uint64_t gi = (uint64_t)(index ? index[img] : first_index + img * index_stride);
-        double nacc[4] = {0.0, 0.0, 0.0, 0.0};
-        for (int t = 0; t < n_b; ++t) {                               // wave-uniform column: one Philox call per quad and term
-            const float c = val_b[t];
-            const uint32_t j = (uint32_t)idx_b[t];
-            const float4 e = j == 0 ? noise[v] : philox_normals(gi, (uint64_t)q, j, k0, k1);
-            const float p0 = e.x * c, p1 = e.y * c, p2 = e.z * c, p3 = e.w * c;
-            nacc[0] = nacc[0] + (double)p0; nacc[1] = nacc[1] + (double)p1;
-            nacc[2] = nacc[2] + (double)p2; nacc[3] = nacc[3] + (double)p3;
-        }
-        x_next[v] = make_float4((float)acc[0] + (float)nacc[0], (float)acc[1] + (float)nacc[1],
-                                (float)acc[2] + (float)nacc[2], (float)acc[3] + (float)nacc[3]);
+        noise_row_sum(nacc, noise, idx_b, val_b, n_b, v, global_index(index, first_index, index_stride, img), q, k0, k1);
+        x_next[v] = combine(acc, nacc);
     }
 }
 
 // ------------------------------------------------------------------------------------------
-// Validate form with the noise row generated in registers.  CFG fuse, x0_k and the signal sum operation for operation
-// as k_step_f32prod; the noise sum b reads eps_0 from the caller's `noise` and draws eps_j, j >= 1, from
-// philox_normals(global image index, element quad, j): what k_step_f32prod reads from a hist_eps slab whose row j
-// natinf_randn_philox_col_f32(column = j) filled, so the two kernels give the same bytes and the (N+1) x E slab is gone.
+// Validate form with the noise row generated in registers: k_step_f32prod with noise_row_sum in place of the row sum over a
+// hist_eps slab, so the two kernels give the same bytes and the (N+1) x E slab is gone.
 // ------------------------------------------------------------------------------------------
 __global__ __launch_bounds__(kBlock) void k_step_noise_f32prod(
     const float4* __restrict__ z, const float* __restrict__ cond, const float* __restrict__ uncond, float cfg,
@@ -480,53 +476,35 @@ __global__ __launch_bounds__(kBlock) void k_step_noise_f32prod(
 {
     // one element quad per thread, no grid-stride loop (k_step_noise_f64: the loop's carried scalars make the hoisted
     // Philox round keys spill SGPRs)
-    const int64_t v = (int64_t)blockIdx.x * kBlock + threadIdx.x;
+    const int64_t v = first_vec();
     if (v < nvec) {
         const int64_t img = v / svec, q = v - img * svec;            // an image is one sample: svec quads
-        const float4 zv = z[v];
-        float4 ev = *reinterpret_cast<const float4*>(cond + img * sstride + 4 * q);
-        if (uncond) {
-            const float4 uv = *reinterpret_cast<const float4*>(uncond + img * sstride + 4 * q);
-            float d, m;
-            d = ev.x - uv.x; m = cfg * d; ev.x = uv.x + m;
-            d = ev.y - uv.y; m = cfg * d; ev.y = uv.y + m;
-            d = ev.z - uv.z; m = cfg * d; ev.z = uv.z + m;
-            d = ev.w - uv.w; m = cfg * d; ev.w = uv.w + m;
-        }
-        float4 x0;
-        { const float p = c1 * zv.x, r = c2 * ev.x; x0.x = p - r; }
-        { const float p = c1 * zv.y, r = c2 * ev.y; x0.y = p - r; }
-        { const float p = c1 * zv.z, r = c2 * ev.z; x0.z = p - r; }
-        { const float p = c1 * zv.w, r = c2 * ev.w; x0.w = p - r; }
+        const float4 x0 = x0_f32prod(c1, z[v], c2, cfg_eps(cond, uncond, cfg, img, q, sstride));
         reinterpret_cast<float4*>(hist_x0 + (int64_t)k * E)[v] = x0;
 
         double a[4] = {0.0, 0.0, 0.0, 0.0}, b[4] = {0.0, 0.0, 0.0, 0.0};
-#pragma unroll 4
-        for (int t = 0; t < n_c; ++t) {
-            const float c = val_c[t];
-            const float4 h = reinterpret_cast<const float4*>(hist_x0 + (int64_t)idx_c[t] * E)[v];
-            const float p0 = h.x * c, p1 = h.y * c, p2 = h.z * c, p3 = h.w * c;
-            a[0] = a[0] + (double)p0; a[1] = a[1] + (double)p1; a[2] = a[2] + (double)p2; a[3] = a[3] + (double)p3;
-        }
-        {
-            const float p0 = x0.x * c_diag, p1 = x0.y * c_diag, p2 = x0.z * c_diag, p3 = x0.w * c_diag;
-            a[0] = a[0] + (double)p0; a[1] = a[1] + (double)p1; a[2] = a[2] + (double)p2; a[3] = a[3] + (double)p3;
-        }
-        const uint64_t gi = (uint64_t)(index ? index[img] : first_index + img * index_stride);
-        for (int t = 0; t < n_b; ++t) {                               // wave-uniform column: one Philox call per quad and term
-            const float c = val_b[t];
-            const uint32_t j = (uint32_t)idx_b[t];
-            const float4 e = j == 0 ? noise[v] : philox_normals(gi, (uint64_t)q, j, k0, k1);
-            const float p0 = e.x * c, p1 = e.y * c, p2 = e.z * c, p3 = e.w * c;
-            b[0] = b[0] + (double)p0; b[1] = b[1] + (double)p1; b[2] = b[2] + (double)p2; b[3] = b[3] + (double)p3;
-        }
-        z_next[v] = make_float4((float)a[0] + (float)b[0], (float)a[1] + (float)b[1],
-                                (float)a[2] + (float)b[2], (float)a[3] + (float)b[3]);
+        wsum_f32prod(a, hist_x0, idx_c, val_c, n_c, v, E);
+        acc_prod(a, x0, c_diag);
+        noise_row_sum(b, noise, idx_b, val_b, n_b, v, global_index(index, first_index, index_stride, img), q, k0, k1);
+        z_next[v] = combine(a, b);
     }
 }
 
+// ---- host side: argument checks and launch geometry shared by the ABI entries ----
 inline int launched() { return hipGetLastError() == hipSuccess ? NATINF_OK : NATINF_ELAUNCH; }
 inline bool terms_ok(const void* idx, const void* val, int n) { return n >= 0 && (n == 0 || (idx && val)); }
+
+// E / lanes vectors when E is a positive multiple of lanes (4 or 8); 0 = refuse
+inline int64_t vec_count(int64_t E, int lanes) { return E > 0 && !(E & (lanes - 1)) ? E / lanes : 0; }
+
+// a per-image (per-sample) element count: a positive multiple of 4 dividing E
+inline bool image_ok(int64_t elems, int64_t E) { return elems > 0 && !(elems & 3) && !(E % elems); }
+
+// blocks of a one-quad-per-thread launch (k_step_noise_f64, k_step_noise_f32prod); 0 = more than a grid holds
+inline unsigned quad_blocks(int64_t nvec) {
+    const int64_t blocks = (nvec + kBlock - 1) / kBlock;
+    return blocks > INT32_MAX ? 0u : (unsigned)blocks;
+}
 
 // The host-side check of a noise row natinf_step_f32prod_noise makes before it launches: every column is in 0..k+1 and
 // column 0 has a `noise` to read.  The row is device memory, so its n_b <= k+2 indices are read back on a private
@@ -597,9 +575,9 @@ int natinf_step_f64hist(const float* x_k, const float* model_out, const float* n
                         int k, double alpha, double sigma, float std_f32, float b0_f32,
                         int64_t E, natinf_stream_t stream)
 {
-    if (!x_k || !model_out || !noise || !hist || !x_next || !terms_ok(idx, val, n_terms) || k < 0 || E <= 0 || (E & 3))
+    const int64_t nvec = vec_count(E, 4);
+    if (!x_k || !model_out || !noise || !hist || !x_next || !terms_ok(idx, val, n_terms) || k < 0 || !nvec)
         return NATINF_EINVAL;
-    const int64_t nvec = E / 4;
     hipLaunchKernelGGL(k_step_f64hist, dim3(grid_for(nvec)), dim3(kBlock), 0, (hipStream_t)stream,
                        (const float4*)x_k, (const float4*)model_out, (const float4*)noise, hist, (float4*)x_next,
                        idx, val, n_terms, c_diag, k, alpha, sigma * sigma, std_f32, b0_f32, nvec, E);
@@ -612,9 +590,9 @@ int natinf_step_f32hist(const float* x_k, const float* model_out, const float* n
                         int k, float alpha, float sigma, float std_f32, float b0_f32,
                         int64_t E, natinf_stream_t stream)
 {
-    if (!x_k || !model_out || !noise || !hist || !x_next || !terms_ok(idx, val, n_terms) || k < 0 || E <= 0 || (E & 3))
+    const int64_t nvec = vec_count(E, 4);
+    if (!x_k || !model_out || !noise || !hist || !x_next || !terms_ok(idx, val, n_terms) || k < 0 || !nvec)
         return NATINF_EINVAL;
-    const int64_t nvec = E / 4;
     hipLaunchKernelGGL(k_step_f32hist, dim3(grid_for(nvec)), dim3(kBlock), 0, (hipStream_t)stream,
                        (const float4*)x_k, (const float4*)model_out, (const float4*)noise, hist, (float4*)x_next,
                        idx, val, n_terms, c_diag, k, 1.0f / alpha, sigma * sigma / std_f32, b0_f32, nvec, E);
@@ -625,9 +603,10 @@ int natinf_randn_philox_col_f32(float* out, int64_t n_images, int64_t elems_per_
                                 int64_t first_index, int64_t index_stride, uint64_t seed, uint32_t column,
                                 natinf_stream_t stream)
 {
-    if (!out || n_images <= 0 || elems_per_image <= 0 || (elems_per_image & 3)) return NATINF_EINVAL;
-    const int64_t qpi = elems_per_image / 4, total = qpi * n_images;
+    const int64_t qpi = vec_count(elems_per_image, 4);
+    if (!out || n_images <= 0 || !qpi) return NATINF_EINVAL;
     if (column && (qpi >> 32)) return NATINF_EINVAL;               // counter word 3 carries the column: the quad must fit word 2
+    const int64_t total = qpi * n_images;
     hipLaunchKernelGGL(k_randn_philox, dim3(grid_for(total)), dim3(kBlock), 0, (hipStream_t)stream, (float4*)out,
                        image_index, first_index, index_stride, qpi, total, column, (uint32_t)seed, (uint32_t)(seed >> 32));
     return launched();
@@ -647,13 +626,13 @@ int natinf_step_f64hist_noise(const float* x_k, const float* model_out, const fl
                               uint64_t seed, const int64_t* image_index, int64_t first_index, int64_t index_stride,
                               int64_t elems_per_image, int64_t E, natinf_stream_t stream)
 {
+    const int64_t nvec = vec_count(E, 4);
+    const unsigned blocks = quad_blocks(nvec);
     if (!x_k || !model_out || !noise || !hist || !x_next || !terms_ok(idx, val, n_terms) || !terms_ok(idx_b, val_b, n_b) ||
-        k < 0 || E <= 0 || (E & 3) || elems_per_image <= 0 || (elems_per_image & 3) || (E % elems_per_image) ||
-        ((elems_per_image / 4) >> 32))
+        k < 0 || !nvec || !image_ok(elems_per_image, E) || ((elems_per_image / 4) >> 32) || !blocks)
         return NATINF_EINVAL;
-    const int64_t nvec = E / 4, blocks = (nvec + kBlock - 1) / kBlock;
-    if (blocks > INT32_MAX) return NATINF_EINVAL;                      // one quad per thread (k_step_noise_f64)
-    hipLaunchKernelGGL(k_step_noise_f64, dim3((unsigned)blocks), dim3(kBlock), 0, (hipStream_t)stream,
+    // no read-back of the noise row here (natinf_step_f32prod_noise makes one): the caller keeps its columns in 0..k+1
+    hipLaunchKernelGGL(k_step_noise_f64, dim3(blocks), dim3(kBlock), 0, (hipStream_t)stream,
                        (const float4*)x_k, (const float4*)model_out, (const float4*)noise, hist, (float4*)x_next,
                        idx, val, n_terms, c_diag, idx_b, val_b, n_b, image_index, first_index, index_stride,
                        elems_per_image / 4, (uint32_t)seed, (uint32_t)(seed >> 32), k, alpha, sigma * sigma, std_f32,
@@ -664,8 +643,8 @@ int natinf_step_f64hist_noise(const float* x_k, const float* model_out, const fl
 int natinf_weighted_sum_f64(const double* hist, float* out, const int32_t* idx, const double* val, int n_terms,
                             int64_t E, natinf_stream_t stream)
 {
-    if (!hist || !out || !terms_ok(idx, val, n_terms) || E <= 0 || (E & 3)) return NATINF_EINVAL;
-    const int64_t nvec = E / 4;
+    const int64_t nvec = vec_count(E, 4);
+    if (!hist || !out || !terms_ok(idx, val, n_terms) || !nvec) return NATINF_EINVAL;
     hipLaunchKernelGGL(k_wsum_f64, dim3(grid_for(nvec)), dim3(kBlock), 0, (hipStream_t)stream,
                        hist, (float4*)out, idx, val, n_terms, nvec, E);
     return launched();
@@ -689,11 +668,10 @@ int natinf_step_f32prod(const float* z, const float* cond, const float* uncond, 
                         const int32_t* idx_b, const float* val_b, int n_b,
                         int k, float c1_f32, float c2_f32, int64_t E, natinf_stream_t stream)
 {
+    const int64_t nvec = vec_count(E, 4);
     if (!z || !cond || !hist_x0 || !hist_eps || !z_next || !terms_ok(idx_c, val_c, n_c) || !terms_ok(idx_b, val_b, n_b) ||
-        k < 0 || E <= 0 || (E & 3) || sample_elems <= 0 || (sample_elems & 3) || (E % sample_elems) ||
-        eps_sample_stride < sample_elems || (eps_sample_stride & 3))
+        k < 0 || !nvec || !image_ok(sample_elems, E) || eps_sample_stride < sample_elems || (eps_sample_stride & 3))
         return NATINF_EINVAL;
-    const int64_t nvec = E / 4;
     hipLaunchKernelGGL(k_step_f32prod, dim3(grid_for(nvec)), dim3(kBlock), 0, (hipStream_t)stream,
                        (const float4*)z, cond, uncond, cfg, sample_elems / 4, eps_sample_stride,
                        hist_x0, hist_eps, (float4*)z_next, idx_c, val_c, n_c, c_diag, idx_b, val_b, n_b,
@@ -710,15 +688,15 @@ int natinf_step_f32prod_noise(const float* z, const float* cond, const float* un
                               uint64_t seed, const int64_t* image_index, int64_t first_index, int64_t index_stride,
                               int64_t E, natinf_stream_t stream)
 {
+    const int64_t nvec = vec_count(E, 4);
+    const unsigned blocks = quad_blocks(nvec);
     if (!z || !cond || !hist_x0 || !z_next || !terms_ok(idx_c, val_c, n_c) || !terms_ok(idx_b, val_b, n_b) ||
-        k < 0 || n_b > (int64_t)k + 2 || E <= 0 || (E & 3) || sample_elems <= 0 || (sample_elems & 3) || (E % sample_elems) ||
-        eps_sample_stride < sample_elems || (eps_sample_stride & 3) || ((sample_elems / 4) >> 32))
+        k < 0 || n_b > (int64_t)k + 2 || !nvec || !image_ok(sample_elems, E) || eps_sample_stride < sample_elems ||
+        (eps_sample_stride & 3) || ((sample_elems / 4) >> 32) || !blocks)
         return NATINF_EINVAL;
-    const int64_t nvec = E / 4, blocks = (nvec + kBlock - 1) / kBlock;
-    if (blocks > INT32_MAX) return NATINF_EINVAL;                      // one quad per thread (k_step_noise_f32prod)
     const int row = noise_row_ok(idx_b, n_b, k, noise != nullptr);
     if (row <= 0) return row < 0 ? NATINF_ELAUNCH : NATINF_EINVAL;
-    hipLaunchKernelGGL(k_step_noise_f32prod, dim3((unsigned)blocks), dim3(kBlock), 0, (hipStream_t)stream,
+    hipLaunchKernelGGL(k_step_noise_f32prod, dim3(blocks), dim3(kBlock), 0, (hipStream_t)stream,
                        (const float4*)z, cond, uncond, cfg, sample_elems / 4, eps_sample_stride,
                        hist_x0, (const float4*)noise, (float4*)z_next, idx_c, val_c, n_c, c_diag, idx_b, val_b, n_b,
                        image_index, first_index, index_stride, (uint32_t)seed, (uint32_t)(seed >> 32),
@@ -729,8 +707,8 @@ int natinf_step_f32prod_noise(const float* z, const float* cond, const float* un
 int natinf_weighted_sum_f32prod(const float* hist, float* out, const int32_t* idx, const float* val, int n_terms,
                                 int64_t E, natinf_stream_t stream)
 {
-    if (!hist || !out || !terms_ok(idx, val, n_terms) || E <= 0 || (E & 3)) return NATINF_EINVAL;
-    const int64_t nvec = E / 4;
+    const int64_t nvec = vec_count(E, 4);
+    if (!hist || !out || !terms_ok(idx, val, n_terms) || !nvec) return NATINF_EINVAL;
     hipLaunchKernelGGL(k_wsum_f32prod, dim3(grid_for(nvec)), dim3(kBlock), 0, (hipStream_t)stream,
                        hist, (float4*)out, idx, val, n_terms, nvec, E);
     return launched();
@@ -742,28 +720,23 @@ int natinf_step_f16chain(const void* x, const void* v_text, const void* v_null, 
                          int k, float sig, float sig_next, float one_minus_sig_next, float cfg,
                          int flags, int64_t E, natinf_stream_t stream)
 {
-    if (!x || !v_text || !v_null || !hist || !terms_ok(idx, val, n_terms) || k < 0 || E <= 0 || (E & 7) ||
+    const int64_t nvec = vec_count(E, 8);
+    if (!x || !v_text || !v_null || !hist || !terms_ok(idx, val, n_terms) || k < 0 || !nvec ||
         (x_next && !noise) || (flags & ~NATINF_SD3_CFG_ON_VELOCITY))
         return NATINF_EINVAL;
-    const int64_t nvec = E / 8;
-    if (flags & NATINF_SD3_CFG_ON_VELOCITY)
-        hipLaunchKernelGGL(k_step_f16chain<true>, dim3(grid_for(nvec)), dim3(kBlock), 0, (hipStream_t)stream,
-                           (const h8*)x, (const h8*)v_text, (const h8*)v_null, (const h8*)noise, (h16*)hist,
-                           (h8*)mean_out, (h8*)x_next, idx, val, n_terms, c_diag, w_total, k, sig, sig_next,
-                           one_minus_sig_next, cfg, nvec, E);
-    else
-        hipLaunchKernelGGL(k_step_f16chain<false>, dim3(grid_for(nvec)), dim3(kBlock), 0, (hipStream_t)stream,
-                           (const h8*)x, (const h8*)v_text, (const h8*)v_null, (const h8*)noise, (h16*)hist,
-                           (h8*)mean_out, (h8*)x_next, idx, val, n_terms, c_diag, w_total, k, sig, sig_next,
-                           one_minus_sig_next, cfg, nvec, E);
+    const auto kern = (flags & NATINF_SD3_CFG_ON_VELOCITY) ? k_step_f16chain<true> : k_step_f16chain<false>;
+    hipLaunchKernelGGL(kern, dim3(grid_for(nvec)), dim3(kBlock), 0, (hipStream_t)stream,
+                       (const h8*)x, (const h8*)v_text, (const h8*)v_null, (const h8*)noise, (h16*)hist,
+                       (h8*)mean_out, (h8*)x_next, idx, val, n_terms, c_diag, w_total, k, sig, sig_next,
+                       one_minus_sig_next, cfg, nvec, E);
     return launched();
 }
 
 int natinf_flow_input_f16(const void* noise, const void* mean, void* out, float sig, float one_minus_sig,
                           int64_t E, natinf_stream_t stream)
 {
-    if (!noise || !out || E <= 0 || (E & 7)) return NATINF_EINVAL;
-    const int64_t nvec = E / 8;
+    const int64_t nvec = vec_count(E, 8);
+    if (!noise || !out || !nvec) return NATINF_EINVAL;
     hipLaunchKernelGGL(k_flow_input_f16, dim3(grid_for(nvec)), dim3(kBlock), 0, (hipStream_t)stream,
                        (const h8*)noise, (const h8*)mean, (h8*)out, sig, one_minus_sig, nvec);
     return launched();
@@ -772,8 +745,8 @@ int natinf_flow_input_f16(const void* noise, const void* mean, void* out, float 
 int natinf_weighted_mean_f16(const void* hist, void* out, const int32_t* idx, const float* val, int n_terms,
                              float w_total, int64_t E, natinf_stream_t stream)
 {
-    if (!hist || !out || !terms_ok(idx, val, n_terms) || E <= 0 || (E & 7)) return NATINF_EINVAL;
-    const int64_t nvec = E / 8;
+    const int64_t nvec = vec_count(E, 8);
+    if (!hist || !out || !terms_ok(idx, val, n_terms) || !nvec) return NATINF_EINVAL;
     hipLaunchKernelGGL(k_wmean_f16, dim3(grid_for(nvec)), dim3(kBlock), 0, (hipStream_t)stream,
                        (const h16*)hist, (h8*)out, idx, val, n_terms, w_total, nvec, E);
     return launched();

@@ -46,6 +46,17 @@ def image_index_args(index, n_images: int, device):
     return None, int(index), 1
 
 
+def _pingpong(bufs, k: int, src: torch.Tensor) -> torch.Tensor:
+    """The output buffer of step k: ``bufs[k & 1]``, or the other one when that is the step's input ``src``."""
+    out = bufs[k & 1]
+    return bufs[(k + 1) & 1] if out.data_ptr() == src.data_ptr() else out
+
+
+def _check_elems_per_image(epi: Optional[int], E: int) -> None:
+    if epi is not None and (epi <= 0 or epi % 4 or E % epi):
+        raise ValueError("elems_per_image must be a positive multiple of 4 dividing the element count")
+
+
 class CifarNI:
     """x_{k+1} = fp32(sum_j C[k,j]*x0_j) + fp32(B[k,0])*noise with x0_k = ((-out/std)*sigma^2 + x_k)/alpha.
 
@@ -73,8 +84,7 @@ class CifarNI:
                 raise ValueError("stochastic NI matrix (B[k, j >= 1] != 0): the injected noise needs a seed")
             if self.fast:
                 raise ValueError("stochastic NI matrix: fast_f32 mode only covers column 0 of B")
-            if elems_per_image is not None and (elems_per_image <= 0 or elems_per_image % 4 or self.E % elems_per_image):
-                raise ValueError("elems_per_image must be a positive multiple of 4 dividing the element count")
+            _check_elems_per_image(elems_per_image, self.E)
             self.rows_b = SparseRows(self.B, lambda k: min(k + 2, self.B.shape[1]), torch.float32, self.device,
                                      diag=False, dense=dense)
         self.seed = None if seed is None else int(seed) & (2 ** 64 - 1)
@@ -95,9 +105,7 @@ class CifarNI:
         None = 0.  ``elems_per_image`` overrides the constructor's value for this call."""
         epi = self.epi if elems_per_image is None else int(elems_per_image)
         if x_next is None:
-            x_next = self._x[k & 1]
-            if x_next.data_ptr() == x_k.data_ptr():
-                x_next = self._x[(k + 1) & 1]
+            x_next = _pingpong(self._x, k, x_k)
         for t in (x_k, model_out, noise):
             if t.dtype != torch.float32 or t.numel() != self.E or not t.is_contiguous():
                 raise ValueError("x_k / model_out / noise must be contiguous fp32 tensors of n_elem elements")
@@ -108,7 +116,7 @@ class CifarNI:
             if epi is None:
                 raise ValueError("stochastic NI matrix: elems_per_image is needed to key the injected noise")
             ib, vb, nb = self.rows_b.ptrs(k)
-            index, first, stride = self._index(index, epi, x_k.device)
+            index, first, stride = image_index_args(index, self.E // epi, x_k.device)
             check(lib.natinf_step_f64hist_noise(ptr(x_k), ptr(model_out), ptr(noise), ptr(self.hist), ptr(x_next), idx, val, n,
                                                 r.diag, ib, vb, nb, k, a, s, self.std[k], self.seed, ptr(index), first, stride,
                                                 epi, self.E, stream_ptr()), "natinf_step_f64hist_noise")
@@ -118,9 +126,6 @@ class CifarNI:
         check(fn(ptr(x_k), ptr(model_out), ptr(noise), ptr(self.hist), ptr(x_next), idx, val, n, r.diag, k,
                  a, s, self.std[k], b0, self.E, stream_ptr()), "natinf_step_f64hist")
         return x_next
-
-    def _index(self, index, epi, device):
-        return image_index_args(index, self.E // epi, device)
 
     def run(self, model_fn: Callable, noise: torch.Tensor, return_all: bool = False, index=None):
         """``model_fn(x [B,...] fp32, labels [B] fp32) -> out`` (raw network output).  ``index``: see ``step``."""
@@ -164,8 +169,7 @@ class ValidateNI:
         if elems_per_image is not None:
             if seed is None:
                 raise ValueError("elems_per_image belongs to the seeded (in-kernel noise) form: give a seed")
-            if elems_per_image <= 0 or elems_per_image % 4 or self.E % elems_per_image:
-                raise ValueError("elems_per_image must be a positive multiple of 4 dividing the element count")
+            _check_elems_per_image(elems_per_image, self.E)
         self.epi = None if elems_per_image is None else int(elems_per_image)
         self.rows_c = SparseRows(C, lambda k: k + 1, torch.float32, self.device, dense=dense)
         self.rows_b = SparseRows(B, lambda k: min(k + 2, np.asarray(B).shape[1]), torch.float32, self.device, dense=dense, diag=False)
@@ -183,9 +187,7 @@ class ValidateNI:
         indices in one of ``image_index_args``' forms; an image is one sample of ``sample_elems`` elements."""
         se = self.E if sample_elems is None else int(sample_elems)
         st = se if eps_sample_stride is None else int(eps_sample_stride)
-        z_next = self._z[k & 1]
-        if z_next.data_ptr() == z.data_ptr():
-            z_next = self._z[(k + 1) & 1]
+        z_next = _pingpong(self._z, k, z)
         ic, vc, nc = self.rows_c.ptrs(k)
         ib, vb, nb = self.rows_b.ptrs(k)
         if self.seed is None:
@@ -268,9 +270,7 @@ class SD3NI:
 
     def step(self, k: int, x: torch.Tensor, v_text: torch.Tensor, v_null: torch.Tensor, noises: torch.Tensor,
              want_next: bool = True):
-        x_next = self._x[k & 1]
-        if x_next.data_ptr() == x.data_ptr():
-            x_next = self._x[(k + 1) & 1]
+        x_next = _pingpong(self._x, k, x)
         idx, val, n = self.rows.ptrs(k)
         r = self.rows.rows[k]
         flags = _lib.SD3_CFG_ON_VELOCITY if self.euler else 0
