@@ -29,7 +29,25 @@ typedef struct natinf_dit* natinf_dit_t;
  * GEMM path instead (the one used for larger heads), for testing one against the other. */
 #define NATINF_DIT_UNFUSED_ATTENTION 1
 
-/* hidden % 64 == 0, hidden <= 1536, hidden % heads == 0, (hidden / heads) % 8 == 0; input size 32 */
+/* fp8 projections: per block, the q | k | v, fc1 and fc2 GEMMs run on fp8 e4m3 operands (v_mfma_f32_16x16x128_f8f6f4) with fp32
+ * accumulation.
+ *   - Their weights are quantised when natinf_dit_load packs them: one fp32 scale per OUTPUT CHANNEL (max |w| / 448), e4m3 bytes.
+ *   - The two LayerNorm-modulate passes of a block write e4m3 rows with one fp32 scale per TOKEN (max |h| / 448); the q | k | v and
+ *     fc1 GEMMs apply both scales to the fp32 sum in their epilogue.  q | k | v leave that GEMM as bf16 and the attention
+ *     (softmax(q k^T) v) runs on bf16 operands exactly as without the flag.
+ *   - fc1's epilogue applies the bias and the tanh-GELU in fp32 and writes e4m3 with one E8M0 (power-of-two) scale per 32
+ *     columns; fc2 feeds those block scales to the scaled MFMA and applies its weight scales, bias, gate and the residual in
+ *     its epilogue.
+ *   - Everything else stays bf16: patch embedding, the t / y embedders, the adaLN-modulation GEMM of all blocks, the attention
+ *     output projection (its operand is the attention's bf16 output: a quantising pass over it costs what the fp8 GEMM saves,
+ *     DESIGN.md section 4b) and the final layer.  The residual stream is as without the flag (natinf_set_dit_stream16).
+ * Needs hidden % 128 == 0 (whole 128-byte K-tiles), else NATINF_EINVAL: there is no fallback to bf16.  Combines with
+ * NATINF_DIT_UNFUSED_ATTENTION and both input sizes.  natinf_dit_load takes the SAME fp32 parameter vector;
+ * natinf_dit_packed_bytes / natinf_dit_workspace_bytes answer for the handle's mode (the packed image is smaller by
+ * depth * (11 hidden^2 - 32 hidden) bytes at DiT-XL/2's sizes: 11 hidden^2 matrix bytes saved, 8 hidden scales of 4 bytes added, per block). */
+#define NATINF_DIT_FP8 2
+
+/* hidden % 64 == 0, hidden <= 1536, hidden % heads == 0, (hidden / heads) % 8 == 0; input size 32.  Any flag bit other than the two above: NATINF_EINVAL */
 int natinf_dit_create(natinf_dit_t* out, int depth, int hidden, int heads, int flags);
 /* the same at input size 32 or 64 (the latent side S: 256 or 1,024 tokens; anything else is NATINF_EINVAL) */
 int natinf_dit_create_sized(natinf_dit_t* out, int depth, int hidden, int heads, int input_size, int flags);

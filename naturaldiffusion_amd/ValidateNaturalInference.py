@@ -159,23 +159,24 @@ def weighted_sum(weights, seq_elem):
 _engine_cache = {}
 
 
-def load_dit_engine(path, max_batch=16):
+def load_dit_engine(path, max_batch=16, fp8=False):
     """Reference :150-154 (``DiT_models['DiT-XL/2'](input_size=32, num_classes=1000)`` + ``load_state_dict``) on the
     gfx950 engine: the checkpoint's tensors go straight into ``natinf_dit_load``; one engine per checkpoint path and
     input size.  The input size is the checkpoint's own (``pos_embed``): 32 for ``DiT-XL-2-256x256.pt``, 64 for
-    ``DiT-XL-2-512x512.pt``."""
+    ``DiT-XL-2-512x512.pt``.  ``fp8``: the engine's fp8 projections (include/natinf_dit.h, NATINF_DIT_FP8); the two modes
+    are two engines."""
     from .dit import DiTEngine, flatten_state_dict, input_size_of, XL2
     sd = None
     size = _engine_sizes.get(str(path))
     if size is None:
         sd = torch.load(path, map_location="cpu", weights_only=True)
         size = _engine_sizes[str(path)] = input_size_of(sd)
-    key = (str(path), max_batch, size)
+    key = (str(path), max_batch, size, bool(fp8))
     if key not in _engine_cache:
         if sd is None:
             sd = torch.load(path, map_location="cpu", weights_only=True)
         _engine_cache[key] = DiTEngine(flatten_state_dict(sd, XL2["depth"], XL2["hidden"], size), max_batch, device=device,
-                                       input_size=size, **XL2)
+                                       input_size=size, fp8=bool(fp8), **XL2)
     return _engine_cache[key]
 
 
@@ -390,7 +391,7 @@ def to_pixels_u8(images: torch.Tensor) -> torch.Tensor:
 
 @torch.no_grad()
 def generate_sharded(sample_count, labels=None, alg_name="ddpm", num_step=24, batch_size=32, rank=0, world=1, seed=0,
-                     cfg_scale=4.0, decode=True, decode_batch=8, model=None, decoder=None, image_sink=None):
+                     cfg_scale=4.0, decode=True, decode_batch=8, model=None, decoder=None, image_sink=None, fp8=False):
     """A class-conditional generation job on the loop of ``natural_inference`` (reference :311-372): ``sample_count`` images,
     image i of class ``job_batches``' label of i, sharded by global index over ``world`` ranks with no collective on the data
     path.  The noise is counter-based: z_0 = eps_0 = ``philox_noise(indices, column=0)`` and the noise a stochastic matrix
@@ -399,7 +400,8 @@ def generate_sharded(sample_count, labels=None, alg_name="ddpm", num_step=24, ba
     itself is batch-independent.  Per step: ONE denoiser forward of [z; z] with [labels; 1000...] and one step launch;
     nothing in the loop waits for the GPU.
 
-    ``model`` None: ``denoiser_factory()`` or the engine of ``model_path`` built for ``2*batch_size`` samples.  ``decoder``
+    ``model`` None: ``denoiser_factory()`` or the engine of ``model_path`` built for ``2*batch_size`` samples -- with
+    ``fp8`` its fp8-projection form (``load_dit_engine(..., fp8=True)``; a ``model`` or factory given carries its own mode).  ``decoder``
     None: ``decoder_factory()`` or the VAE engine of ``vae_path`` (here a callable latents/0.18215 -> images in [-1, 1]); with
     neither, or ``decode=False``, no image is made.  Decoding runs in chunks of ``decode_batch``; ``image_sink(images uint8
     [n, 8S, 8S, 3] on the device, indices, labels)``, when given, gets each chunk instead of the images being collected.
@@ -414,10 +416,12 @@ def generate_sharded(sample_count, labels=None, alg_name="ddpm", num_step=24, ba
         if denoiser_factory is not None:
             model = denoiser_factory()
         elif model_path is not None:
-            model = load_dit_engine(model_path, max_batch=2 * batch_size)
+            model = load_dit_engine(model_path, max_batch=2 * batch_size, fp8=fp8)
         else:
             raise RuntimeError("set ValidateNaturalInference.model_path (a DiT-XL/2 state dict, reference :152-154) or "
                                "ValidateNaturalInference.denoiser_factory, or pass model=; see INTEGRATION.md")
+    if fp8 and not getattr(model, "fp8", False):
+        raise ValueError("fp8=True, but the denoiser given is not an fp8 engine (DiTEngine(..., fp8=True))")
     S = latent_size(model)
     if decode and decoder is None:
         if decoder_factory is not None:

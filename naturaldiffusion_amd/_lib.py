@@ -154,6 +154,8 @@ for _name, (_res, _args) in SIGNATURES.items():
     _fn.restype, _fn.argtypes = _res, _args
 
 SD3_CFG_ON_VELOCITY = 1
+DIT_UNFUSED_ATTENTION = 1                               # include/natinf_dit.h: flags of natinf_dit_create / natinf_dit_create_sized
+DIT_FP8 = 2
 
 
 def check(rc: int, what: str) -> None:

@@ -5,6 +5,7 @@
 // modulation (6*depth+2 vectors per sample) -> depth x { LN+modulate, q|k GEMM, V^T GEMM, per-head QK^T / softmax /
 // PV, proj GEMM with gate*(.)+x epilogue, LN+modulate, fc1 GEMM + GELU(tanh), fc2 GEMM with gate*(.)+x epilogue }
 // -> LN+modulate -> linear -> unpatchify.  Residual stream fp32, GEMM operands bf16.
+// NATINF_DIT_FP8: the q | k | v, fc1 and fc2 GEMMs of every block on e4m3 operands (include/natinf_dit.h states the arithmetic); everything else as above.
 // Reference: deps/DiT/models.py:19-20,27-99,105-146,222-253,279-326.
 #include "natinf_dit.h"
 #include "engine_core.h"
@@ -282,6 +283,7 @@ struct natinf_dit : EngineCore {
     int input_size = 32, T = 256;        // latent side S and tokens (S / 2)^2: natinf_dit_create_sized
     const int32_t* y = nullptr;          // per-forward
     bool unfused_attention = false;      // NATINF_DIT_UNFUSED_ATTENTION: per-head GEMM / softmax / GEMM (also used when head_dim > 96)
+    bool fp8 = false;                    // NATINF_DIT_FP8: q | k | v, fc1 and fc2 on e4m3 operands (weights: a scale per output channel; LN-modulate rows: a scale per token; GELU(fc1): E8M0 block scales)
     bool stream16 = false;               // natinf_set_dit_stream16 (read when the plan is BUILT): the residual stream x [T][D] in IEEE half, not fp32 (as the MMDiT engine's image stream)
 };
 
@@ -329,7 +331,13 @@ struct DitBuilder : PlanBuilder {
         const int64_t x = arena.alloc((int64_t)T * D * (s16 ? 2 : 4)), h = arena.alloc((int64_t)T * D * 2), qk = arena.alloc((int64_t)T * QL * 2);
         const int64_t vT = fused_attn ? 0 : arena.alloc((int64_t)D * T * 2);
         const int64_t S = fused_attn ? 0 : arena.alloc((int64_t)H * T * T * 4), P = fused_attn ? 0 : arena.alloc((int64_t)H * T * T * 2);
-        const int64_t o = arena.alloc((int64_t)T * D * 2), f = arena.alloc((int64_t)T * 4 * D * 2), mod = arena.alloc((int64_t)nmod * 4);
+        const bool fp8 = E.fp8;
+        const int64_t o = arena.alloc((int64_t)T * D * 2), f = fp8 ? 0 : arena.alloc((int64_t)T * 4 * D * 2), mod = arena.alloc((int64_t)nmod * 4);
+        // fp8 mode: LN-modulate rows as e4m3 + a scale per token; GELU(fc1) as e4m3 + one E8M0 scale per 32 columns, K-tile-major planes of B * T rows (ncsnpp_kernels.h).
+        // Every GEMM here has M = B * T rows, a whole number of 256-row tiles, and an attention launch is one (sample, head) of exactly T rows: no kernel reads an fp8 / MX
+        // operand beyond the rows the same forward wrote, so nothing has to be zeroed (the MMDiT's padded joint sequence does: mmdit_engine.inc).
+        const int64_t h8 = fp8 ? arena.alloc((int64_t)T * D) : 0, sx = fp8 ? arena.alloc((int64_t)T * 4) : 0;
+        const int64_t f8 = fp8 ? arena.alloc((int64_t)T * 4 * D) : 0, fmx = fp8 ? arena.alloc((int64_t)T * 4 * D / 32) : 0;
         constexpr int SK_MAX = 4;                                   // split-K slices of fc2 at small batches (launch_gemm decides: w128_splitk_slices)
         const int64_t skw = arena.alloc((int64_t)SK_MAX * T * D * 4);
         const int64_t tf = arena.alloc(256 * 2), t1 = arena.alloc((int64_t)D * 2), c0 = arena.alloc((int64_t)D * 4), cs = arena.alloc((int64_t)D * 2);
@@ -366,25 +374,48 @@ struct DitBuilder : PlanBuilder {
             };
         };
 
+        auto ln_mod8 = [=](int shift_off, int scale_off) {         // -> e4m3 rows + per-token scales
+            return [=](const Ctx& c) {
+                launch_ln_modulate_fp8(c.at<float>(x), c.at<float>(mod) + shift_off, c.at<float>(mod) + scale_off, nmod, c.at<uint8_t>(h8), c.at<float>(sx), D, (int64_t)c.B * T, T,
+                                       c.stream, s16);
+            };
+        };
+        auto pack8 = [&](int64_t src, int rows, int cols) {          // e4m3 bytes [rows][cols] + one scale per row: {weights, scales}
+            const std::pair<int64_t, int64_t> r{wres((int64_t)rows * cols), wres((int64_t)rows * 4)};
+            pack_fp8_at(src, rows, cols, r.first, r.second);
+            return r;
+        };
+
         for (int i = 0; i < depth; ++i) {
             const int64_t p_qkvw = take((int64_t)3 * D * D), p_qkvb = take(3 * D), p_pw2 = take((int64_t)D * D), p_pb2 = take(D);
             const int64_t p_f1w = take((int64_t)4 * D * D), p_f1b = take(4 * D), p_f2w = take((int64_t)4 * D * D), p_f2b = take(D);
             const int64_t p_mw = take((int64_t)6 * D * D), p_mb = take(6 * D);
-            const int64_t w_qk = pack_bf16(p_qkvw, QL, D), b_qk = pack_f32(p_qkvb, QL);       // (the checkpoint's qkv rows are q, k, v in this order)
-            const int64_t w_v = fused_attn ? 0 : pack_bf16(p_qkvw + (int64_t)2 * D * D, D, D), b_v = fused_attn ? 0 : pack_f32(p_qkvb + 2 * D, D);
+            // (the checkpoint's qkv rows are q, k, v in this order)      fp8: {e4m3 bytes, per-output-channel scales} in place of the bf16 matrix
+            const std::pair<int64_t, int64_t> q8 = fp8 ? pack8(p_qkvw, QL, D) : std::pair<int64_t, int64_t>{0, 0};
+            const std::pair<int64_t, int64_t> v8 = fp8 && !fused_attn ? pack8(p_qkvw + (int64_t)2 * D * D, D, D) : std::pair<int64_t, int64_t>{0, 0};
+            const int64_t w_qk = fp8 ? q8.first : pack_bf16(p_qkvw, QL, D), s_qk = q8.second, b_qk = pack_f32(p_qkvb, QL);
+            const int64_t w_v = fused_attn ? 0 : (fp8 ? v8.first : pack_bf16(p_qkvw + (int64_t)2 * D * D, D, D)), s_v = v8.second, b_v = fused_attn ? 0 : pack_f32(p_qkvb + 2 * D, D);
             const int64_t w_pr = pack_bf16(p_pw2, D, D), b_pr = pack_f32(p_pb2, D);
-            const int64_t w_f1 = pack_bf16(p_f1w, 4 * D, D), b_f1 = pack_f32(p_f1b, 4 * D);
-            const int64_t w_f2 = pack_bf16(p_f2w, D, 4 * D), b_f2 = pack_f32(p_f2b, D);
+            const std::pair<int64_t, int64_t> f18 = fp8 ? pack8(p_f1w, 4 * D, D) : std::pair<int64_t, int64_t>{0, 0};
+            const int64_t w_f1 = fp8 ? f18.first : pack_bf16(p_f1w, 4 * D, D), s_f1 = f18.second, b_f1 = pack_f32(p_f1b, 4 * D);
+            const std::pair<int64_t, int64_t> f28 = fp8 ? pack8(p_f2w, D, 4 * D) : std::pair<int64_t, int64_t>{0, 0};
+            const int64_t w_f2 = fp8 ? f28.first : pack_bf16(p_f2w, D, 4 * D), s_f2 = f28.second, b_f2 = pack_f32(p_f2b, D);
             const int m0 = i * 6 * D;                                // shift_msa, scale_msa, gate_msa, shift_mlp, scale_mlp, gate_mlp
             pack_bf16_at(p_mw, 6 * D, D, w_mod + (int64_t)m0 * D * 2);
             pack_f32_at(p_mb, 6 * D, b_mod + (int64_t)m0 * 4);
 
-            op(ln_mod(m0, m0 + D));
+            op(fp8 ? OpFn(ln_mod8(m0, m0 + D)) : OpFn(ln_mod(m0, m0 + D)));
             op([=](const Ctx& c) {
                 GemmArgs g = gemm_defaults();                       // q | k (| v)
-                g.a0 = c.at<bf16>(h); g.a0_ld = D; g.a0_C = D; g.M = c.B * T; g.N = QL; g.b = c.w<bf16>(w_qk); g.b_ld = D;
-                g.bias_n = c.w<float>(b_qk); g.c = c.at<bf16>(qk); g.c_ld = QL;
-                launch_gemm(g, c.stream);
+                g.M = c.B * T; g.N = QL; g.bias_n = c.w<float>(b_qk); g.c = c.at<bf16>(qk); g.c_ld = QL;      // (bf16 out in both modes: the attention stays bf16)
+                if (fp8) {
+                    g.a0 = reinterpret_cast<const bf16*>(c.at<uint8_t>(h8)); g.a0_ld = D; g.a0_C = D; g.b = reinterpret_cast<const bf16*>(c.w<uint8_t>(w_qk)); g.b_ld = D;
+                    g.deq_m = c.at<float>(sx); g.deq_n = c.w<float>(s_qk);
+                    launch_gemm_fp8(g, c.stream);
+                } else {
+                    g.a0 = c.at<bf16>(h); g.a0_ld = D; g.a0_C = D; g.b = c.w<bf16>(w_qk); g.b_ld = D;
+                    launch_gemm(g, c.stream);
+                }
                 if (fused_attn && T != 256) {                       // keys streamed through LDS (dit_flash.h)
                     const bf16* qkv = c.at<bf16>(qk);
                     launch_dit_flash(qkv, qkv + D, qkv + 2 * D, 3 * D, c.at<bf16>(o), D, c.B, H, T, hd, c.stream);
@@ -394,10 +425,16 @@ struct DitBuilder : PlanBuilder {
                     else launch_attn<3, 6>(c.at<bf16>(qk), c.at<bf16>(o), c.B, D, H, hd, c.stream);
                 } else {
                 g = gemm_defaults();                                // V^T[b] = Wv h[b]^T + bv  ([D][T] per sample)
-                g.a0 = c.w<bf16>(w_v); g.a0_ld = D; g.a0_C = D; g.a_bs = 0; g.M = D; g.N = T;
-                g.b = c.at<bf16>(h); g.b_ld = D; g.b_bs = (int64_t)T * D; g.bias_m = c.w<float>(b_v);
+                g.a0_ld = D; g.a0_C = D; g.a_bs = 0; g.M = D; g.N = T; g.b_ld = D; g.b_bs = (int64_t)T * D; g.bias_m = c.w<float>(b_v);
                 g.c = c.at<bf16>(vT); g.c_ld = T; g.c_bs = (int64_t)D * T; g.batch = c.B;
-                launch_gemm(g, c.stream);
+                if (fp8) {                                          // the weights as the row operand: their scales per row, the tokens' per column
+                    g.a0 = reinterpret_cast<const bf16*>(c.w<uint8_t>(w_v)); g.b = reinterpret_cast<const bf16*>(c.at<uint8_t>(h8));
+                    g.deq_m = c.w<float>(s_v); g.deq_m_bs = 0; g.deq_n = c.at<float>(sx); g.deq_n_bs = T;
+                    launch_gemm_fp8(g, c.stream);
+                } else {
+                    g.a0 = c.w<bf16>(w_v); g.b = c.at<bf16>(h);
+                    launch_gemm(g, c.stream);
+                }
                 for (int hh = 0; hh < H; ++hh) {                    // S[b][hh] = q k^T / sqrt(hd)
                     g = gemm_defaults();
                     g.a0 = c.at<bf16>(qk) + hh * hd; g.a0_ld = 2 * D; g.a0_C = hd; g.a_bs = (int64_t)T * 2 * D; g.M = T; g.N = T;
@@ -423,8 +460,24 @@ struct DitBuilder : PlanBuilder {
                 g.resid_f32 = c.at<float>(x); g.resid_f32_ld = D; g.c = c.at<float>(x); g.c_ld = D; g.c_mode = OUT_F32; g.stream_f16 = s16;
                 launch_gemm(g, c.stream);
             });
-            op(ln_mod(m0 + 3 * D, m0 + 4 * D));
-            op([=](const Ctx& c) {
+            op(fp8 ? OpFn(ln_mod8(m0 + 3 * D, m0 + 4 * D)) : OpFn(ln_mod(m0 + 3 * D, m0 + 4 * D)));
+            if (fp8) op([=](const Ctx& c) {
+                const int M = c.B * T;
+                GemmArgs g = gemm_defaults();                       // GELU_tanh(fc1) -> e4m3 + a scale per 32 columns: fc2's operand
+                g.a0 = reinterpret_cast<const bf16*>(c.at<uint8_t>(h8)); g.a0_ld = D; g.a0_C = D; g.M = M; g.N = 4 * D;
+                g.b = reinterpret_cast<const bf16*>(c.w<uint8_t>(w_f1)); g.b_ld = D; g.deq_m = c.at<float>(sx); g.deq_n = c.w<float>(s_f1);
+                g.bias_n = c.w<float>(b_f1); g.act = ACT_GELU_TANH; g.c = c.at<uint8_t>(f8); g.c_ld = 4 * D; g.c_mode = OUT_FP8_MX;
+                g.c_mx = c.at<uint8_t>(fmx); g.c_mx_ld = M;
+                launch_gemm_fp8(g, c.stream);
+                g = gemm_defaults();                                // x += gate_mlp * (f8 W2^T + b)
+                g.a0 = reinterpret_cast<const bf16*>(c.at<uint8_t>(f8)); g.a0_ld = 4 * D; g.a0_C = 4 * D; g.M = M; g.N = D;
+                g.a_mx = c.at<uint8_t>(fmx); g.a_mx_ld = M;
+                g.b = reinterpret_cast<const bf16*>(c.w<uint8_t>(w_f2)); g.b_ld = 4 * D; g.deq_n = c.w<float>(s_f2);
+                g.bias_n = c.w<float>(b_f2); g.gate = c.at<float>(mod) + m0 + 5 * D; g.gate_ld = nmod; g.log_rows_per_sample = log_T;
+                g.resid_f32 = c.at<float>(x); g.resid_f32_ld = D; g.c = c.at<float>(x); g.c_ld = D; g.c_mode = OUT_F32; g.stream_f16 = s16;
+                launch_gemm_fp8(g, c.stream);
+            });
+            else op([=](const Ctx& c) {
                 GemmArgs g = gemm_defaults();                       // GELU_tanh(fc1)
                 g.a0 = c.at<bf16>(h); g.a0_ld = D; g.a0_C = D; g.M = c.B * T; g.N = 4 * D; g.b = c.w<bf16>(w_f1); g.b_ld = D;
                 g.bias_n = c.w<float>(b_f1); g.act = ACT_GELU_TANH; g.c = c.at<bf16>(f); g.c_ld = 4 * D;
@@ -464,13 +517,14 @@ int natinf_dit_create(natinf_dit_t* out, int depth, int hidden, int heads, int f
     return natinf_dit_create_sized(out, depth, hidden, heads, 32, flags);
 }
 int natinf_dit_create_sized(natinf_dit_t* out, int depth, int hidden, int heads, int input_size, int flags) {
-    if (!out || (flags & ~NATINF_DIT_UNFUSED_ATTENTION) || depth <= 0 || hidden <= 0 || heads <= 0 || hidden % 64 || hidden % heads || (hidden / heads) % 8 || hidden > 1536)
+    if (!out || (flags & ~(NATINF_DIT_UNFUSED_ATTENTION | NATINF_DIT_FP8)) || ((flags & NATINF_DIT_FP8) && hidden % 128) || depth <= 0 || hidden <= 0 || heads <= 0 || hidden % 64 || hidden % heads || (hidden / heads) % 8 || hidden > 1536)
         return NATINF_EINVAL;
     if (input_size != 32 && input_size != 64) return NATINF_EINVAL;
     natinf_dit* e = new natinf_dit();
     e->depth = depth; e->D = hidden; e->heads = heads; e->hd = hidden / heads;
     e->input_size = input_size; e->T = (input_size / 2) * (input_size / 2);
     e->unfused_attention = (flags & NATINF_DIT_UNFUSED_ATTENTION) != 0;
+    e->fp8 = (flags & NATINF_DIT_FP8) != 0;
     e->stream16 = g_dit_stream16 != 0;
     DitBuilder b(*e);
     b.build();

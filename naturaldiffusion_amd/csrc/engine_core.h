@@ -154,6 +154,13 @@ struct PlanBuilder {
         });
     }
 
+    void pack_fp8_at(int64_t src, int rows, int cols, int64_t wdst, int64_t sdst) {      // [rows][cols] fp32 -> e4m3 bytes, same layout, + one fp32 scale per row (output channel)
+        E.packs.push_back([=](const PackCtx& p) {
+            hipLaunchKernelGGL(k_pack_fp8_rows, dim3((unsigned)((rows + 3) / 4)), dim3(256), 0, p.stream, p.params + src,
+                               reinterpret_cast<uint8_t*>(p.packed + wdst), reinterpret_cast<float*>(p.packed + sdst), rows, cols);
+        });
+    }
+
     void finish() { E.n_params = poff; E.packed_bytes = wtop; E.ws_per_image = arena.peak; }
 };
 

@@ -173,27 +173,30 @@ __global__ __launch_bounds__(256) void k_ln_modulate_fp8(const float* __restrict
     }
 }
 
-// The same for D = NC * 256 with 16-byte loads and 4-byte stores (k_ln_modulate_v4's access pattern, dit_engine.inc)
-template <int NC, bool XH = false>                                      // XH: x is IEEE half (the MMDiT engine's 16-bit image stream): 8-byte loads of four columns
+// The same for D = NC * 256 + REM with 16-byte loads and 4-byte stores (k_ln_modulate_v4's access pattern, dit_engine.inc)
+// REM % 4 == 0: the last, partial chunk is owned by lanes 0 .. REM / 4 - 1 (DiT-XL/2: 1152 = 4 * 256 + 128)
+template <int NC, bool XH = false, int REM = 0>                         // XH: x is IEEE half (the transformer engines' 16-bit residual stream): 8-byte loads of four columns
 __global__ __launch_bounds__(256) void k_ln_modulate_fp8_v4(const float* __restrict__ x, const float* __restrict__ shift,
                                                             const float* __restrict__ scale, int mod_ld, uint8_t* __restrict__ h,
                                                             float* __restrict__ row_scale, int64_t rows, int rows_per_sample)
 {
-    constexpr int D = NC * 256;
+    constexpr int D = NC * 256 + REM, NV = NC + (REM ? 1 : 0);
+    static_assert(REM % 4 == 0 && REM < 256, "a partial chunk of whole float4s");
     const int lane = threadIdx.x & 63;
     const int64_t row = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
     if (row >= rows) return;
+    const bool tail = lane < REM / 4;                                   // this lane owns columns of the partial chunk
     const float4* xr = reinterpret_cast<const float4*>(x + row * D) + lane;
     const uint2* xh = reinterpret_cast<const uint2*>(reinterpret_cast<const _Float16*>(x) + row * D) + lane;
-    float4 v[NC];
+    float4 v[NV];
     float s = 0.f;
 #pragma unroll
-    for (int i = 0; i < NC; ++i) {
+    for (int i = 0; i < NV; ++i) {
         if constexpr (XH) {
             typedef _Float16 f16x4_ln8 __attribute__((ext_vector_type(4)));
-            const f16x4_ln8 hv = __builtin_bit_cast(f16x4_ln8, xh[64 * i]);
+            const f16x4_ln8 hv = (i < NC || tail) ? __builtin_bit_cast(f16x4_ln8, xh[64 * i]) : f16x4_ln8{0, 0, 0, 0};
             v[i] = make_float4((float)hv[0], (float)hv[1], (float)hv[2], (float)hv[3]);
-        } else v[i] = xr[64 * i];
+        } else v[i] = (i < NC || tail) ? xr[64 * i] : make_float4(0.f, 0.f, 0.f, 0.f);
         s += (v[i].x + v[i].y) + (v[i].z + v[i].w);
     }
 #pragma unroll
@@ -201,9 +204,11 @@ __global__ __launch_bounds__(256) void k_ln_modulate_fp8_v4(const float* __restr
     const float mean = s / (float)D;
     float qq = 0.f;
 #pragma unroll
-    for (int i = 0; i < NC; ++i) {
-        const float a = v[i].x - mean, b_ = v[i].y - mean, c = v[i].z - mean, d = v[i].w - mean;
-        qq += (a * a + b_ * b_) + (c * c + d * d);
+    for (int i = 0; i < NV; ++i) {
+        if (i < NC || tail) {
+            const float a = v[i].x - mean, b_ = v[i].y - mean, c = v[i].z - mean, d = v[i].w - mean;
+            qq += (a * a + b_ * b_) + (c * c + d * d);
+        }
     }
 #pragma unroll
     for (int o = 32; o > 0; o >>= 1) qq += __shfl_xor(qq, o);
@@ -213,11 +218,13 @@ __global__ __launch_bounds__(256) void k_ln_modulate_fp8_v4(const float* __restr
     const float4* sc = reinterpret_cast<const float4*>(scale + b * mod_ld) + lane;
     float amax = 0.f;
 #pragma unroll
-    for (int i = 0; i < NC; ++i) {
-        const float4 g = sc[64 * i], t = sh[64 * i];
-        v[i].x = (v[i].x - mean) * rstd * (1.0f + g.x) + t.x; v[i].y = (v[i].y - mean) * rstd * (1.0f + g.y) + t.y;
-        v[i].z = (v[i].z - mean) * rstd * (1.0f + g.z) + t.z; v[i].w = (v[i].w - mean) * rstd * (1.0f + g.w) + t.w;
-        amax = fmaxf(amax, fmaxf(fmaxf(fabsf(v[i].x), fabsf(v[i].y)), fmaxf(fabsf(v[i].z), fabsf(v[i].w))));
+    for (int i = 0; i < NV; ++i) {
+        if (i < NC || tail) {
+            const float4 g = sc[64 * i], t = sh[64 * i];
+            v[i].x = (v[i].x - mean) * rstd * (1.0f + g.x) + t.x; v[i].y = (v[i].y - mean) * rstd * (1.0f + g.y) + t.y;
+            v[i].z = (v[i].z - mean) * rstd * (1.0f + g.z) + t.z; v[i].w = (v[i].w - mean) * rstd * (1.0f + g.w) + t.w;
+            amax = fmaxf(amax, fmaxf(fmaxf(fabsf(v[i].x), fabsf(v[i].y)), fmaxf(fabsf(v[i].z), fabsf(v[i].w))));
+        }
     }
 #pragma unroll
     for (int o = 32; o > 0; o >>= 1) amax = fmaxf(amax, __shfl_xor(amax, o));
@@ -225,7 +232,8 @@ __global__ __launch_bounds__(256) void k_ln_modulate_fp8_v4(const float* __restr
     if (lane == 0) row_scale[row] = qs;
     unsigned* out = reinterpret_cast<unsigned*>(h + row * D) + lane;
 #pragma unroll
-    for (int i = 0; i < NC; ++i) out[64 * i] = pack_fp8x4(v[i].x * inv, v[i].y * inv, v[i].z * inv, v[i].w * inv);
+    for (int i = 0; i < NV; ++i)
+        if (i < NC || tail) out[64 * i] = pack_fp8x4(v[i].x * inv, v[i].y * inv, v[i].z * inv, v[i].w * inv);
 }
 // The half stream in 16-byte accesses (D = NC8 * 512; SD3: 1536), as k_ln_modulate_h8 (dit_engine.inc): eight consecutive columns per lane and 512-column chunk, one
 // 16-byte load of x and one 8-byte store of e4m3 bytes per chunk (32 us alone; ~49 us mean inside a forward, beside the text stream's launches, like the four-column form).
@@ -290,11 +298,13 @@ inline void launch_ln_modulate_fp8(const float* x, const float* shift, const flo
     if (x_f16) {
         if (D == 1536 && al) hipLaunchKernelGGL(k_ln_modulate_fp8_h8<3>, grid, dim3(256), 0, s, x, shift, scale, mod_ld, h, row_scale, rows, rows_per_sample);
         else if (D == 256 && al) hipLaunchKernelGGL((k_ln_modulate_fp8_v4<1, true>), grid, dim3(256), 0, s, x, shift, scale, mod_ld, h, row_scale, rows, rows_per_sample);
+        else if (D == 1152 && al) hipLaunchKernelGGL((k_ln_modulate_fp8_v4<4, true, 128>), grid, dim3(256), 0, s, x, shift, scale, mod_ld, h, row_scale, rows, rows_per_sample);      // DiT-XL/2
         else hipLaunchKernelGGL(k_ln_modulate_fp8, grid, dim3(256), 0, s, x, shift, scale, mod_ld, h, row_scale, D, rows, rows_per_sample, 1);
         return;
     }
     if (D == 1536 && al) hipLaunchKernelGGL(k_ln_modulate_fp8_v4<6>, grid, dim3(256), 0, s, x, shift, scale, mod_ld, h, row_scale, rows, rows_per_sample);
     else if (D == 256 && al) hipLaunchKernelGGL(k_ln_modulate_fp8_v4<1>, grid, dim3(256), 0, s, x, shift, scale, mod_ld, h, row_scale, rows, rows_per_sample);
+    else if (D == 1152 && al) hipLaunchKernelGGL((k_ln_modulate_fp8_v4<4, false, 128>), grid, dim3(256), 0, s, x, shift, scale, mod_ld, h, row_scale, rows, rows_per_sample);      // DiT-XL/2
     else hipLaunchKernelGGL(k_ln_modulate_fp8, grid, dim3(256), 0, s, x, shift, scale, mod_ld, h, row_scale, D, rows, rows_per_sample, 0);
 }
 

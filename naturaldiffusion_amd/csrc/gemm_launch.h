@@ -299,6 +299,11 @@ int fp8_epi(const GemmArgs& g) {
     return 0;
 }
 // k_gemm_w128_fp8 (gemm_w128.h): an even number of 128-byte K-tiles, 32-bit offsets into the operands
+// (DiT-XL/2's K = 1,152 is NINE K-tiles: an odd-count form of the four-wave kernel -- the parity kept a template parameter, one more steady-state iteration and the two
+// closing iterations on swapped stages; no spill, same bytes -- was measured against the eight-wave tile in one process and not kept, TFLOP/s four-wave / eight-wave:
+// (4096, 3456, 1152) -> bf16 1,391 / 1,384, (4096, 1152, 1152) 539 / 582, (4096, 4608, 1152) GELU -> e4m3 + E8M0 875 / 885; at M = 8,192 1,479 / 1,478, 990 / 1,010, 1,115 / 1,140;
+// at M = 32,768 1,683 / 1,683, 1,388 / 1,386, 1,464 / 1,475: level or behind on every shape -- nine K-tiles are too short a loop for the one-wave-per-SIMD schedule to earn
+// back its longer prologue and epilogue.  Those GEMMs run on k_gemm_fp8; profiles/dit_fp8/ab_k1152.txt)
 bool w128_fp8_ok(const GemmArgs& g) {
     // (E8M0 block scales of A arrive by DMA as whole 256-row groups per K-tile: the plane must hold them -- whole row tiles only)
     return g.taps == 1 && !g.a1 && g.a0_C % 256 == 0 && g.N % 8 == 0 && g.M % 8 == 0 && (!g.a_mx || g.M % 256 == 0) &&

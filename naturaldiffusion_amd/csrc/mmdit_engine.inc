@@ -76,12 +76,6 @@ struct MMDitBuilder : PlanBuilder {
 
     struct Lin { int64_t w, b; };
     struct Lin8 { int64_t w, s, b; };                              // fp8 bytes [out][in], per-output-channel scale, fp32 bias
-    void pack_fp8_at(int64_t src, int rows, int cols, int64_t wdst, int64_t sdst) {
-        E.packs.push_back([=](const PackCtx& p) {
-            hipLaunchKernelGGL(k_pack_fp8_rows, dim3((unsigned)((rows + 3) / 4)), dim3(256), 0, p.stream, p.params + src,
-                               reinterpret_cast<uint8_t*>(p.packed + wdst), reinterpret_cast<float*>(p.packed + sdst), rows, cols);
-        });
-    }
     Lin8 linear8(int out, int in) {
         const int64_t pw = take((int64_t)out * in), pb = take(out);
         const Lin8 r{wres((int64_t)out * in), wres((int64_t)out * 4), pack_f32(pb, out)};

@@ -14,7 +14,8 @@ import torch
 from . import _lib
 from ._lib import lib, check, ptr, stream_ptr
 
-UNFUSED_ATTENTION = 1
+UNFUSED_ATTENTION = _lib.DIT_UNFUSED_ATTENTION
+FP8 = _lib.DIT_FP8                                   # q | k | v, fc1 and fc2 of every block on e4m3 operands (include/natinf_dit.h); hidden % 128 == 0
 XL2 = dict(depth=28, hidden=1152, heads=16)          # deps/DiT/models.py:333-334
 INPUT_SIZES = (32, 64)                               # latent side of the 256x256 / 512x512 checkpoints (patch 2: 256 / 1,024 tokens)
 
@@ -71,11 +72,14 @@ def flatten_state_dict(sd: Dict[str, torch.Tensor], depth: int, hidden: int, inp
 
 class DiTEngine:
     def __init__(self, flat_params: torch.Tensor, max_batch: int, depth: int = 28, hidden: int = 1152, heads: int = 16,
-                 device="cuda:0", unfused_attention: bool = False, stream16=None, input_size: int = 32):
+                 device="cuda:0", unfused_attention: bool = False, stream16=None, input_size: int = 32, fp8: bool = False):
         self.input_size = _check_input_size(input_size)
+        self.fp8 = bool(fp8)
         _lib.require_gpu()
         if depth <= 0 or hidden <= 0 or heads <= 0 or hidden % 64 or hidden > 1536 or hidden % heads or (hidden // heads) % 8:
             raise ValueError("hidden must be a multiple of 64 (<= 1536) and of heads, head_dim a multiple of 8")
+        if fp8 and hidden % 128:
+            raise ValueError("fp8 mode needs hidden to be a multiple of 128 (whole 128-byte K-tiles); there is no bf16 fallback")
         self.device = torch.device(device)
         self.max_batch = int(max_batch)
         self._h = C.c_void_p()
@@ -87,8 +91,8 @@ class DiTEngine:
         if stream16 is not None:
             check(lib.natinf_set_dit_stream16(int(bool(stream16))), "natinf_set_dit_stream16")
         try:
-            check(lib.natinf_dit_create_sized(C.byref(self._h), depth, hidden, heads, self.input_size, UNFUSED_ATTENTION if unfused_attention else 0),
-                  "natinf_dit_create_sized")
+            check(lib.natinf_dit_create_sized(C.byref(self._h), depth, hidden, heads, self.input_size,
+                                              (UNFUSED_ATTENTION if unfused_attention else 0) | (FP8 if fp8 else 0)), "natinf_dit_create_sized")
         finally:
             if stream16 is not None:
                 lib.natinf_set_dit_stream16(-1)

@@ -3,7 +3,11 @@
 One JSON object on stdout.  Every row: one untimed warm-up job, then ``--reps`` timed jobs of one batch each, device-synchronised on both
 sides; images/s from the median, the spread (min / max seconds) beside it.  GPU box; run from the repository root:
 
-    python tools/dit_job.py [--input-size 64] [--batches 8,16,32,64] [--reps 5]
+    python tools/dit_job.py [--input-size 64] [--batches 8,16,32,64] [--reps 5] [--fp8]
+
+``--fp8``: every generate_sharded row is measured twice in the same process -- the bf16 engine, then the engine with fp8 projections (NATINF_DIT_FP8), alternating row by
+row -- and carries ``"fp8": false / true``; each (batch size, mode) also gets a ``forwards`` entry: ms per denoiser forward of 2 x batch samples (HIP events over 20
+forwards) and the per-shape GEMM table of one forward (natinf_gemm_profile_read: tag, launches, ms, TFLOP/s).
 """
 import argparse
 import json
@@ -17,6 +21,7 @@ import torch
 sys.path.insert(0, str(Path(__file__).resolve().parent.parent))
 
 from naturaldiffusion_amd import ValidateNaturalInference as V                      # noqa: E402
+from naturaldiffusion_amd._lib import lib, check                                    # noqa: E402
 from naturaldiffusion_amd.dit import DiTEngine, flatten_state_dict, XL2           # noqa: E402
 from naturaldiffusion_amd.synth import synthetic_dit_state_dict, synthetic_vae_flat  # noqa: E402
 from naturaldiffusion_amd.vae import VAEDecoder                                    # noqa: E402
@@ -34,6 +39,43 @@ def timed(fn, reps):
     return statistics.median(ts), min(ts), max(ts)
 
 
+def forward_profile(eng, n, S):
+    """ms per forward of n samples (20 forwards between two events, after 3 untimed) and the GEMM launches of one forward by shape."""
+    import ctypes as C
+    g = torch.Generator().manual_seed(0)
+    z = torch.randn(n, 4, S, S, generator=g).cuda()
+    t = torch.linspace(999.0, 3.0, n).cuda()
+    y = (torch.arange(n) % 1001).cuda()
+    out = torch.empty(n, 8, S, S, device="cuda")
+    for _ in range(3):
+        eng(z, t, y, out)
+    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    e0.record()
+    for _ in range(20):
+        eng(z, t, y, out)
+    e1.record()
+    torch.cuda.synchronize()
+    ms = e0.elapsed_time(e1) / 20
+    check(lib.natinf_gemm_profile(1), "natinf_gemm_profile")
+    try:
+        eng(z, t, y, out)
+        torch.cuda.synchronize()
+        buf = C.create_string_buffer(1 << 16)
+        rc = lib.natinf_gemm_profile_read(buf, len(buf))
+        if rc < 0:
+            check(rc, "natinf_gemm_profile_read")
+    finally:
+        lib.natinf_gemm_profile(0)
+    shapes = []
+    for line in buf.value.decode().splitlines():
+        f = line.split()
+        M, N, K0, K1, taps, batch = (int(v) for v in f[:6])
+        launches, tot = int(f[7]), float(f[8])
+        flop = 2.0 * M * N * (K0 + K1) * batch * launches
+        shapes.append({"tag": " ".join(f[:7]), "launches": launches, "ms": round(tot, 4), "tflops": round(flop / (tot * 1e-3) / 1e12, 1) if tot > 0 else None})
+    return {"forward_samples": n, "forward_ms": round(ms, 3), "gemms": shapes}
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--input-size", type=int, default=32, choices=(32, 64))
@@ -41,16 +83,21 @@ def main():
     ap.add_argument("--steps", type=int, default=24)
     ap.add_argument("--reps", type=int, default=5)
     ap.add_argument("--no-decode", action="store_true")
+    ap.add_argument("--fp8", action="store_true", help="measure the fp8-projection engine beside the bf16 one, alternating, in this process")
     a = ap.parse_args()
     S = a.input_size
     flat = flatten_state_dict(synthetic_dit_state_dict(input_size=S), XL2["depth"], XL2["hidden"], S)
     vae = None if a.no_decode else VAEDecoder(synthetic_vae_flat(4), max_batch=8, latent_ch=4, latent_res=S)
     rows = []
 
-    def row(path, alg, bs, decode, ws, sec):
+    forwards = []
+
+    def row(path, alg, bs, decode, ws, sec, fp8=False):
         med, lo, hi = sec
         rows.append({"path": path, "alg": alg, "batch_size": bs, "forward_samples": 2 * bs, "decode": decode, "images_per_s": round(bs / med, 2),
                      "median_s": round(med, 4), "min_s": round(lo, 4), "max_s": round(hi, 4), "engine_workspace_bytes": int(ws)})
+        if a.fp8:
+            rows[-1]["fp8"] = fp8
 
     # the baseline: natural_inference as it stands (eight demo labels, torch.randn_like copied into the noise slab, natinf_step_f32prod)
     eng = DiTEngine(flat, max_batch=16, input_size=S, **XL2)
@@ -62,16 +109,25 @@ def main():
     V.denoiser_factory = V.decoder_factory = None
     del eng
     for bs in [int(v) for v in a.batches.split(",")]:
-        eng = DiTEngine(flat, max_batch=2 * bs, input_size=S, **XL2)
+        engines = [(False, DiTEngine(flat, max_batch=2 * bs, input_size=S, **XL2))]
+        if a.fp8:
+            engines.append((True, DiTEngine(flat, max_batch=2 * bs, input_size=S, fp8=True, **XL2)))
         for alg in ("ddim", "ddpm"):
             for decode in ((False,) if vae is None else (False, True)):
-                job = lambda: V.generate_sharded(bs, None, alg_name=alg, num_step=a.steps, batch_size=bs, seed=0, decode=decode, decode_batch=8,
-                                                 model=eng, decoder=vae)
-                row("generate_sharded", alg, bs, decode, eng.workspace_bytes, timed(job, a.reps))
-        del eng
+                for fp8, eng in engines:                                      # the two modes alternate, row by row
+                    job = lambda: V.generate_sharded(bs, None, alg_name=alg, num_step=a.steps, batch_size=bs, seed=0, decode=decode, decode_batch=8,
+                                                     model=eng, decoder=vae)
+                    row("generate_sharded", alg, bs, decode, eng.workspace_bytes, timed(job, a.reps), fp8)
+        if a.fp8:
+            for fp8, eng in engines:
+                forwards.append(dict(fp8=fp8, batch_size=bs, **forward_profile(eng, 2 * bs, S)))
+        del engines, eng
         torch.cuda.empty_cache()
-    print(json.dumps({"tool": "dit_job", "model": "DiT-XL/2 synthetic", "input_size": S, "steps": a.steps, "cfg_scale": 4.0, "reps": a.reps,
-                      "device": torch.cuda.get_device_name(0), "rows": rows}))
+    res = {"tool": "dit_job", "model": "DiT-XL/2 synthetic", "input_size": S, "steps": a.steps, "cfg_scale": 4.0, "reps": a.reps,
+           "device": torch.cuda.get_device_name(0), "rows": rows}
+    if a.fp8:
+        res["forwards"] = forwards
+    print(json.dumps(res))
 
 
 if __name__ == "__main__":
