@@ -47,7 +47,20 @@ typedef struct natinf_dit* natinf_dit_t;
  * depth * (11 hidden^2 - 32 hidden) bytes at DiT-XL/2's sizes: 11 hidden^2 matrix bytes saved, 8 hidden scales of 4 bytes added, per block). */
 #define NATINF_DIT_FP8 2
 
-/* hidden % 64 == 0, hidden <= 1536, hidden % heads == 0, (hidden / heads) % 8 == 0; input size 32.  Any flag bit other than the two above: NATINF_EINVAL */
+/* Stream guard: the residual stream cannot leave the range of its number format unnoticed.  A SITE is one launch of the plan that writes the stream: the patch embedding
+ * (site 0), then per block i the attention-projection update (site 1 + 2 i) and the MLP update (site 2 + 2 i): 1 + 2 depth sites.  Each site owns a slot
+ * {uint32 max_bits, uint32 clamped} of a status block that lives in the caller's workspace (its first 8 * sites bytes; natinf_dit_workspace_bytes of a guarded handle
+ * counts it), and every guarded kernel, with the fp32 result v of an update in hand and before it rounds it:
+ *   - tracks max |v|: max_bits = the largest bit pattern of |v| seen (non-negative floats order as unsigned integers; a NaN sorts above +inf and reads back as NaN);
+ *   - on a half stream (natinf_set_dit_stream16 = 1) writes |v| > 65504 as +-65504 instead of +-inf and counts it in `clamped` (a NaN stays NaN and is counted);
+ *     in range it writes the very bytes the unguarded engine writes.  An fp32 stream is tracked only: `clamped` stays 0 there.
+ * The block ACCUMULATES over forwards (max, add; uint32, wrapping) until natinf_dit_stream_status_reset -- nothing else zeroes it, not even the first forward on a fresh
+ * workspace -- so one read covers a whole trajectory.  Combines with both other flags, both input sizes and either stream format.  An engine created without the flag runs
+ * the kernels it ran before this flag existed.  The flag is bit 4 (16): bits 2 and 3 (4, 8) stay unassigned and NATINF_EINVAL, as callers written against the
+ * two-flag library expect of them. */
+#define NATINF_DIT_STREAM_GUARD 16
+
+/* hidden % 64 == 0, hidden <= 1536, hidden % heads == 0, (hidden / heads) % 8 == 0; input size 32.  Any flag bit other than the three above: NATINF_EINVAL */
 int natinf_dit_create(natinf_dit_t* out, int depth, int hidden, int heads, int flags);
 /* the same at input size 32 or 64 (the latent side S: 256 or 1,024 tokens; anything else is NATINF_EINVAL) */
 int natinf_dit_create_sized(natinf_dit_t* out, int depth, int hidden, int heads, int input_size, int flags);
@@ -60,6 +73,11 @@ int natinf_dit_destroy(natinf_dit_t h);
 int64_t natinf_dit_param_count(natinf_dit_t h);           /* incl. the frozen pos_embed (tokens x hidden) */
 int64_t natinf_dit_packed_bytes(natinf_dit_t h);
 int64_t natinf_dit_workspace_bytes(natinf_dit_t h, int max_batch);
+/* Guarded handles (NATINF_DIT_STREAM_GUARD); NATINF_EINVAL on any other.  `workspace` is the pointer natinf_dit_forward gets: the block's place in it does not depend on the
+ * batch of a forward.  Both calls only enqueue on `stream` (a memset; a device-to-device copy of 2 * sites uint32: {max_bits, clamped} per site, in site order). */
+int natinf_dit_stream_sites(natinf_dit_t h);
+int natinf_dit_stream_status_reset(natinf_dit_t h, void* workspace, natinf_stream_t stream);
+int natinf_dit_stream_status(natinf_dit_t h, const void* workspace, uint32_t* out_dev, natinf_stream_t stream);
 
 /* params_f32: all parameters, fp32, concatenated in this order (reference state-dict names):
  *   pos_embed, x_embedder.proj.{weight,bias}, t_embedder.mlp.0.{weight,bias}, t_embedder.mlp.2.{weight,bias},

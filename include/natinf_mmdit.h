@@ -32,6 +32,9 @@ typedef struct natinf_mmdit* natinf_mmdit_t;
  * instruction itself.  Attention (Q K^T, P V) and the text-stream projections other than the attention output stay bf16.
  * Needs an even head count (hidden % 128 == 0). */
 #define NATINF_MMDIT_FP8 1
+/* The stream guard of include/natinf_dit.h (NATINF_DIT_STREAM_GUARD: same status block, same kernels) on the IMAGE stream: site 0 = the patch embedding, 1 + 2 i / 2 + 2 i =
+ * the attention-projection / MLP update of block i; 1 + 2 layers sites.  The text stream is fp32 and unguarded.  Any flag bit other than these two: NATINF_EINVAL. */
+#define NATINF_MMDIT_STREAM_GUARD 2
 
 /* grid = image tokens per side (latent side / 2), grid*grid % 8 == 0; ctx_tokens = text tokens per sequence;
  * hidden = 64*heads <= 1536; joint_dim % 8 == 0, pooled_dim % 8 == 0; in_ch even, <= 16. */
@@ -41,6 +44,10 @@ int natinf_mmdit_destroy(natinf_mmdit_t h);
 int64_t natinf_mmdit_param_count(natinf_mmdit_t h);
 int64_t natinf_mmdit_packed_bytes(natinf_mmdit_t h);
 int64_t natinf_mmdit_workspace_bytes(natinf_mmdit_t h, int max_batch);
+/* guarded handles only (else NATINF_EINVAL); as natinf_dit_stream_sites / _status_reset / _status */
+int natinf_mmdit_stream_sites(natinf_mmdit_t h);
+int natinf_mmdit_stream_status_reset(natinf_mmdit_t h, void* workspace, natinf_stream_t stream);
+int natinf_mmdit_stream_status(natinf_mmdit_t h, const void* workspace, uint32_t* out_dev, natinf_stream_t stream);
 
 /* params_f32: fp32, concatenated in this order (diffusers state-dict names; D = 64*heads):
  *   pos_embed.pos_embed CROPPED to the grid ([grid*grid][D], the centre window of the checkpoint's table),

@@ -159,24 +159,28 @@ def weighted_sum(weights, seq_elem):
 _engine_cache = {}
 
 
-def load_dit_engine(path, max_batch=16, fp8=False):
+def load_dit_engine(path, max_batch=16, fp8=False, stream16=None):
     """Reference :150-154 (``DiT_models['DiT-XL/2'](input_size=32, num_classes=1000)`` + ``load_state_dict``) on the
     gfx950 engine: the checkpoint's tensors go straight into ``natinf_dit_load``; one engine per checkpoint path and
     input size.  The input size is the checkpoint's own (``pos_embed``): 32 for ``DiT-XL-2-256x256.pt``, 64 for
     ``DiT-XL-2-512x512.pt``.  ``fp8``: the engine's fp8 projections (include/natinf_dit.h, NATINF_DIT_FP8); the two modes
-    are two engines."""
+    are two engines.  ``stream16``: None = the library's default residual-stream format, True / False = IEEE half / fp32, ``"auto"`` = the
+    half stream with the stream guard (``DiTEngine(..., stream16=True, guard=True)``: what ``generate_sharded(stream16="auto")`` runs first); one
+    engine per mode, like ``fp8``."""
     from .dit import DiTEngine, flatten_state_dict, input_size_of, XL2
+    if stream16 not in (None, True, False, "auto"):
+        raise ValueError(f'stream16 must be None, True, False or "auto", got {stream16!r}')
     sd = None
     size = _engine_sizes.get(str(path))
     if size is None:
         sd = torch.load(path, map_location="cpu", weights_only=True)
         size = _engine_sizes[str(path)] = input_size_of(sd)
-    key = (str(path), max_batch, size, bool(fp8))
+    key = (str(path), max_batch, size, bool(fp8)) + (() if stream16 is None else (stream16,))
     if key not in _engine_cache:
         if sd is None:
             sd = torch.load(path, map_location="cpu", weights_only=True)
         _engine_cache[key] = DiTEngine(flatten_state_dict(sd, XL2["depth"], XL2["hidden"], size), max_batch, device=device,
-                                       input_size=size, fp8=bool(fp8), **XL2)
+                                       input_size=size, fp8=bool(fp8), stream16=True if stream16 == "auto" else stream16, guard=stream16 == "auto", **XL2)
     return _engine_cache[key]
 
 
@@ -391,7 +395,8 @@ def to_pixels_u8(images: torch.Tensor) -> torch.Tensor:
 
 @torch.no_grad()
 def generate_sharded(sample_count, labels=None, alg_name="ddpm", num_step=24, batch_size=32, rank=0, world=1, seed=0,
-                     cfg_scale=4.0, decode=True, decode_batch=8, model=None, decoder=None, image_sink=None, fp8=False):
+                     cfg_scale=4.0, decode=True, decode_batch=8, model=None, decoder=None, image_sink=None, fp8=False, stream16=None,
+                     fallback=None, report=None):
     """A class-conditional generation job on the loop of ``natural_inference`` (reference :311-372): ``sample_count`` images,
     image i of class ``job_batches``' label of i, sharded by global index over ``world`` ranks with no collective on the data
     path.  The noise is counter-based: z_0 = eps_0 = ``philox_noise(indices, column=0)`` and the noise a stochastic matrix
@@ -406,22 +411,43 @@ def generate_sharded(sample_count, labels=None, alg_name="ddpm", num_step=24, ba
     neither, or ``decode=False``, no image is made.  Decoding runs in chunks of ``decode_batch``; ``image_sink(images uint8
     [n, 8S, 8S, 3] on the device, indices, labels)``, when given, gets each chunk instead of the images being collected.
 
+    ``stream16`` None / True / False: the residual-stream format of the engine built from ``model_path`` (``load_dit_engine``; a ``model`` or factory given
+    carries its own).  ``"auto"``: every batch runs on a GUARDED half-stream engine (``model`` given: it must be one, ``DiTEngine(..., guard=True)``) whose status is
+    reset in front of the batch and read once behind its last step; a batch in which any update left the half range (a ``clamped`` counter is not zero) is run again
+    on the fp32-stream engine -- ``fallback()``, or ``load_dit_engine(model_path, ..., stream16=False)``, built at the first such batch -- and, the noise being a
+    function of (seed, global index, column), the rerun IS the fp32-stream job's batch.  ``report`` (a dict, filled): ``batches``, ``rerun_batches`` (positions in
+    this rank's batch list), ``first_clamp`` ({batch, site, site_name, max_abs, clamped} or None).  A ``report`` given is filled in every mode; without ``"auto"`` nothing is monitored, so it
+    says ``rerun_batches == []`` and ``first_clamp is None`` whatever the stream did.
+
     -> (latents [n_local, 4, S, S] fp32 on the device, labels [n_local] int64 CPU, global indices [n_local] int64 CPU,
         images [n_local, 8S, 8S, 3] uint8 CPU or None)"""
     from .CIFAR10NaturalInference import philox_noise
     torch.set_grad_enabled(False)
     batch_size = int(batch_size)
     batches = job_batches(sample_count, batch_size, rank, world, labels)
+    if stream16 not in (None, True, False, "auto"):
+        raise ValueError(f'stream16 must be None, True, False or "auto", got {stream16!r}')
+    auto = stream16 == "auto"
+    if auto and fallback is None and model_path is not None and model is None and denoiser_factory is None:
+        fallback = lambda: load_dit_engine(model_path, max_batch=2 * batch_size, fp8=fp8, stream16=False)
     if model is None:
         if denoiser_factory is not None:
             model = denoiser_factory()
         elif model_path is not None:
-            model = load_dit_engine(model_path, max_batch=2 * batch_size, fp8=fp8)
+            model = load_dit_engine(model_path, max_batch=2 * batch_size, fp8=fp8, stream16=stream16)
         else:
             raise RuntimeError("set ValidateNaturalInference.model_path (a DiT-XL/2 state dict, reference :152-154) or "
                                "ValidateNaturalInference.denoiser_factory, or pass model=; see INTEGRATION.md")
     if fp8 and not getattr(model, "fp8", False):
         raise ValueError("fp8=True, but the denoiser given is not an fp8 engine (DiTEngine(..., fp8=True))")
+    if auto and not (getattr(model, "guard", False) and hasattr(model, "stream_status")):
+        raise ValueError('stream16="auto" needs a guarded denoiser (DiTEngine(..., guard=True)): an unguarded one cannot say that it overflowed')
+    if auto and fallback is None:
+        raise ValueError('stream16="auto" with a denoiser of the caller\'s needs fallback=: a callable that returns the fp32-stream denoiser')
+    if report is None:
+        report = {}
+    report.update(batches=len(batches), rerun_batches=[], first_clamp=None)
+    wide = None                                                       # the fp32-stream denoiser: built at the first batch that needs it
     S = latent_size(model)
     if decode and decoder is None:
         if decoder_factory is not None:
@@ -439,24 +465,42 @@ def generate_sharded(sample_count, labels=None, alg_name="ddpm", num_step=24, ba
     per = 4 * S * S
     samplers = {}                                                     # batch size -> ValidateNI (the ragged last batch gets its own)
     out_z, out_img = [], []
-    for indices, labs in batches:
+
+    def trajectory(denoiser, ni, noise, index, steps_t, classlabels, classnulls):
+        n = noise.shape[0]
+        input_z, flat_noise = noise, noise.reshape(-1)
+        for kk in range(n_step):
+            cond, uncond = _cond_uncond(denoiser, input_z, steps_t[kk], classlabels, classnulls)   # [n, 8, S, S] each; first 4 channels used
+            z = ni.step(kk, input_z.reshape(-1), cond.contiguous(), uncond.contiguous(), float(cfg_scale), per, cond.shape[1] * S * S,
+                        noise=flat_noise, index=index)
+            input_z = z.view(n, 4, S, S)
+        return input_z.clone()
+
+    for bi, (indices, labs) in enumerate(batches):
         n = len(indices)
         if n not in samplers:
             samplers[n] = ValidateNI(C, B, node, c1, c2, n * per, device=device, seed=seed, elems_per_image=per)
-        ni = samplers[n]
         index = torch.tensor(indices, dtype=torch.int64, device=device)
         classlabels = torch.tensor(labs, dtype=torch.int64, device=device)
         classnulls = torch.full((n,), 1000, dtype=torch.int64, device=device)
         steps_t = [torch.full((n,), int(node[kk, 0]), dtype=torch.int32, device=device) for kk in range(n_step)]
         noise = philox_noise(indices, (4, S, S), seed, device, column=0)
-        flat_noise = noise.reshape(-1)
-        input_z = noise
-        for kk in range(n_step):
-            cond, uncond = _cond_uncond(model, input_z, steps_t[kk], classlabels, classnulls)   # [n, 8, S, S] each; first 4 channels used
-            z = ni.step(kk, input_z.reshape(-1), cond.contiguous(), uncond.contiguous(), float(cfg_scale), per, cond.shape[1] * S * S,
-                        noise=flat_noise, index=index)
-            input_z = z.view(n, 4, S, S)
-        out_z.append(input_z.clone())
+        run = (samplers[n], noise, index, steps_t, classlabels, classnulls)
+        if auto:
+            model.reset_stream_status()
+        latents_b = trajectory(model, *run)
+        if auto:
+            st = model.stream_status()                                # the job's one wait per batch
+            hit = np.flatnonzero(np.asarray(st["clamped"]))
+            if len(hit):
+                if report["first_clamp"] is None:
+                    k = int(hit[0])
+                    report["first_clamp"] = dict(batch=bi, site=k, site_name=model.site_names[k], max_abs=float(st["max_abs"][k]), clamped=int(st["clamped"][k]))
+                report["rerun_batches"].append(bi)
+                if wide is None:
+                    wide = fallback()
+                latents_b = trajectory(wide, *run)                        # same noise, same labels, same indices: the fp32-stream job's batch
+        out_z.append(latents_b)
     latents = torch.cat(out_z) if out_z else torch.empty((0, 4, S, S), dtype=torch.float32, device=device)
     all_idx = [i for idx, _ in batches for i in idx]
     all_lab = [l for _, lb in batches for l in lb]

@@ -109,6 +109,9 @@ SIGNATURES = {
     "natinf_dit_workspace_bytes": (C.c_int64, [_p, _i32]),
     "natinf_dit_load": (C.c_int, [_p, _p, _i64, _p, _i64, _p]),
     "natinf_dit_forward": (C.c_int, [_p, _p, _p, _p, _p, _i32, _p, _i64, _p]),
+    "natinf_dit_stream_sites": (C.c_int, [_p]),
+    "natinf_dit_stream_status_reset": (C.c_int, [_p, _p, _p]),
+    "natinf_dit_stream_status": (C.c_int, [_p, _p, _p, _p]),
     # include/natinf_mmdit.h
     "natinf_mmdit_create": (C.c_int, [C.POINTER(_p), _i32, _i32, _i32, _i32, _i32, _i32, _i32, _i32]),
     "natinf_mmdit_destroy": (C.c_int, [_p]),
@@ -117,6 +120,9 @@ SIGNATURES = {
     "natinf_mmdit_workspace_bytes": (C.c_int64, [_p, _i32]),
     "natinf_mmdit_load": (C.c_int, [_p, _p, _i64, _p, _i64, _p]),
     "natinf_mmdit_forward": (C.c_int, [_p, _p, _p, _p, _p, _p, _i32, _p, _i64, _p]),
+    "natinf_mmdit_stream_sites": (C.c_int, [_p]),
+    "natinf_mmdit_stream_status_reset": (C.c_int, [_p, _p, _p]),
+    "natinf_mmdit_stream_status": (C.c_int, [_p, _p, _p, _p]),
     "natinf_attention_hd64_bf16": (C.c_int, [_p, _p, _i32, _i64, _p, _p, _i32, _i64, _i32, _i32, _i32, _i32, C.c_float, _p]),
     "natinf_inception_create": (C.c_int, [_p, _i32, _i32]),
     "natinf_inception_destroy": (C.c_int, [_p]),
@@ -156,6 +162,9 @@ for _name, (_res, _args) in SIGNATURES.items():
 SD3_CFG_ON_VELOCITY = 1
 DIT_UNFUSED_ATTENTION = 1                               # include/natinf_dit.h: flags of natinf_dit_create / natinf_dit_create_sized
 DIT_FP8 = 2
+DIT_STREAM_GUARD = 16
+MMDIT_FP8 = 1                                           # include/natinf_mmdit.h: flags of natinf_mmdit_create
+MMDIT_STREAM_GUARD = 2
 
 
 def check(rc: int, what: str) -> None:
@@ -171,6 +180,42 @@ def stream_ptr(stream=None) -> int:
 
 def ptr(t) -> int:
     return 0 if t is None else int(t.data_ptr())
+
+
+class StreamGuardStatus:
+    """The stream-guard side of a transformer engine wrapper (include/natinf_dit.h, NATINF_DIT_STREAM_GUARD): ``_guard_api`` names the C entries' prefix
+    (``natinf_dit`` / ``natinf_mmdit``); the wrapper sets ``guard``, ``_h`` and ``_ws``."""
+    _guard_api = ""
+    guard = False
+
+    def _guard_entry(self, name):
+        if not self.guard:
+            raise RuntimeError("this engine was created without guard=True: it keeps no stream status")
+        return getattr(lib, f"{self._guard_api}_{name}")
+
+    @property
+    def site_names(self):
+        """One name per site, in the status block's order: ``patch_embed``, ``blocks.0.attn``, ``blocks.0.mlp``, ..."""
+        n = self._guard_entry("stream_sites")(self._h)
+        check(min(n, 0), f"{self._guard_api}_stream_sites")
+        return ["patch_embed"] + [f"blocks.{i // 2}.{'mlp' if i % 2 else 'attn'}" for i in range(n - 1)]
+
+    def reset_stream_status(self) -> None:
+        """Zero the status block (enqueued on the current stream; nothing else ever zeroes it: it accumulates over forwards)."""
+        import torch
+        with torch.cuda.device(self._ws.device):
+            check(self._guard_entry("stream_status_reset")(self._h, ptr(self._ws), stream_ptr()), f"{self._guard_api}_stream_status_reset")
+
+    def stream_status(self):
+        """{"max_abs": float32 [sites], "clamped": uint32 [sites]} (numpy) accumulated since the last reset: the largest |v| an update of the site produced, before
+        rounding (NaN if one was NaN), and how many values left the half range and were written as +-65504 (or were NaN).  The one call here that waits for the GPU."""
+        import torch
+        n = len(self.site_names)
+        buf = torch.empty(2 * n, dtype=torch.int32, device=self._ws.device)
+        with torch.cuda.device(self._ws.device):
+            check(self._guard_entry("stream_status")(self._h, ptr(self._ws), ptr(buf), stream_ptr()), f"{self._guard_api}_stream_status")
+        raw = buf.cpu().numpy().view("uint32").reshape(n, 2)
+        return {"max_abs": raw[:, 0].copy().view("float32"), "clamped": raw[:, 1].copy()}
 
 
 def require_gpu() -> None:

@@ -55,6 +55,14 @@ __global__ __launch_bounds__(256) void k_patch_embed(const float* __restrict__ z
         }
     }
 }
+// the patch embedding of a plan: plain or guarded (guard: the site's slot), onto an fp32 or a half stream
+inline void launch_patch_embed(const float* z, const float* Wt, const float* bias, const float* pos, float* x, int C, int g, int D, int64_t rows, bool x_f16, uint32_t* guard, hipStream_t s)
+{
+    const dim3 grid((unsigned)((D + 255) / 256), (unsigned)((rows + PE_TOK - 1) / PE_TOK));
+    if (guard) ncsn_sg::launch_patch_embed(z, Wt, bias, pos, x, C, g, D, rows, x_f16, guard, (void*)s);      // k_patch_embed_guard (stream_guard.hip)
+    else if (x_f16) hipLaunchKernelGGL(k_patch_embed<true>, grid, dim3(256), 0, s, z, Wt, bias, pos, x, C, g, D, rows);
+    else hipLaunchKernelGGL(k_patch_embed<false>, grid, dim3(256), 0, s, z, Wt, bias, pos, x, C, g, D, rows);
+}
 // timestep frequency embedding [B][256] = [cos | sin] (models.py:41-58)
 __global__ void k_dit_time_freq(const float* __restrict__ t, bf16* __restrict__ emb, int B)
 {
@@ -285,6 +293,7 @@ struct natinf_dit : EngineCore {
     bool unfused_attention = false;      // NATINF_DIT_UNFUSED_ATTENTION: per-head GEMM / softmax / GEMM (also used when head_dim > 96)
     bool fp8 = false;                    // NATINF_DIT_FP8: q | k | v, fc1 and fc2 on e4m3 operands (weights: a scale per output channel; LN-modulate rows: a scale per token; GELU(fc1): E8M0 block scales)
     bool stream16 = false;               // natinf_set_dit_stream16 (read when the plan is BUILT): the residual stream x [T][D] in IEEE half, not fp32 (as the MMDiT engine's image stream)
+    // NATINF_DIT_STREAM_GUARD: EngineCore::guard_sites = 1 + 2 depth -- the patch embedding (site 0), then per block the attention-projection update (1 + 2 i) and the MLP update (2 + 2 i)
 };
 
 namespace {
@@ -346,10 +355,7 @@ struct DitBuilder : PlanBuilder {
         natinf_dit* eng = &E;
         op([=](const Ctx& c) {                                      // embeddings and conditioning
             const int64_t prow = (int64_t)c.B * T;
-            if (s16) hipLaunchKernelGGL(k_patch_embed<true>, dim3((unsigned)((D + 255) / 256), (unsigned)((prow + PE_TOK - 1) / PE_TOK)), dim3(256), 0, c.stream, c.x,
-                                        c.w<float>(w_pw), c.w<float>(w_pb), c.w<float>(w_pos), c.at<float>(x), 4, gs, D, prow);
-            else hipLaunchKernelGGL(k_patch_embed<false>, dim3((unsigned)((D + 255) / 256), (unsigned)((prow + PE_TOK - 1) / PE_TOK)), dim3(256), 0, c.stream, c.x,
-                                    c.w<float>(w_pw), c.w<float>(w_pb), c.w<float>(w_pos), c.at<float>(x), 4, gs, D, prow);
+            launch_patch_embed(c.x, c.w<float>(w_pw), c.w<float>(w_pb), c.w<float>(w_pos), c.at<float>(x), 4, gs, D, prow, s16, c.site(0), c.stream);
             hipLaunchKernelGGL(k_dit_time_freq, dim3(grid1d((int64_t)c.B * 256)), dim3(256), 0, c.stream, c.labels, c.at<bf16>(tf), c.B);
             GemmArgs g = gemm_defaults();                           // SiLU(Linear_0(t_freq))
             g.a0 = c.at<bf16>(tf); g.a0_ld = 256; g.a0_C = 256; g.M = c.B; g.N = D; g.b = c.w<bf16>(w_t0); g.b_ld = 256;
@@ -458,6 +464,7 @@ struct DitBuilder : PlanBuilder {
                 g.a0 = c.at<bf16>(o); g.a0_ld = D; g.a0_C = D; g.M = c.B * T; g.N = D; g.b = c.w<bf16>(w_pr); g.b_ld = D;
                 g.bias_n = c.w<float>(b_pr); g.gate = c.at<float>(mod) + m0 + 2 * D; g.gate_ld = nmod; g.log_rows_per_sample = log_T;
                 g.resid_f32 = c.at<float>(x); g.resid_f32_ld = D; g.c = c.at<float>(x); g.c_ld = D; g.c_mode = OUT_F32; g.stream_f16 = s16;
+                g.stream_guard = c.site(1 + 2 * i);
                 launch_gemm(g, c.stream);
             });
             op(fp8 ? OpFn(ln_mod8(m0 + 3 * D, m0 + 4 * D)) : OpFn(ln_mod(m0 + 3 * D, m0 + 4 * D)));
@@ -475,6 +482,7 @@ struct DitBuilder : PlanBuilder {
                 g.b = reinterpret_cast<const bf16*>(c.w<uint8_t>(w_f2)); g.b_ld = 4 * D; g.deq_n = c.w<float>(s_f2);
                 g.bias_n = c.w<float>(b_f2); g.gate = c.at<float>(mod) + m0 + 5 * D; g.gate_ld = nmod; g.log_rows_per_sample = log_T;
                 g.resid_f32 = c.at<float>(x); g.resid_f32_ld = D; g.c = c.at<float>(x); g.c_ld = D; g.c_mode = OUT_F32; g.stream_f16 = s16;
+                g.stream_guard = c.site(2 + 2 * i);
                 launch_gemm_fp8(g, c.stream);
             });
             else op([=](const Ctx& c) {
@@ -487,6 +495,7 @@ struct DitBuilder : PlanBuilder {
                 g.bias_n = c.w<float>(b_f2); g.gate = c.at<float>(mod) + m0 + 5 * D; g.gate_ld = nmod; g.log_rows_per_sample = log_T;
                 g.resid_f32 = c.at<float>(x); g.resid_f32_ld = D; g.c = c.at<float>(x); g.c_ld = D; g.c_mode = OUT_F32; g.stream_f16 = s16;
                 g.splitk_ws = c.at<float>(skw); g.splitk_max = SK_MAX;
+                g.stream_guard = c.site(2 + 2 * i);
                 launch_gemm(g, c.stream);
             });
         }
@@ -517,7 +526,7 @@ int natinf_dit_create(natinf_dit_t* out, int depth, int hidden, int heads, int f
     return natinf_dit_create_sized(out, depth, hidden, heads, 32, flags);
 }
 int natinf_dit_create_sized(natinf_dit_t* out, int depth, int hidden, int heads, int input_size, int flags) {
-    if (!out || (flags & ~(NATINF_DIT_UNFUSED_ATTENTION | NATINF_DIT_FP8)) || ((flags & NATINF_DIT_FP8) && hidden % 128) || depth <= 0 || hidden <= 0 || heads <= 0 || hidden % 64 || hidden % heads || (hidden / heads) % 8 || hidden > 1536)
+    if (!out || (flags & ~(NATINF_DIT_UNFUSED_ATTENTION | NATINF_DIT_FP8 | NATINF_DIT_STREAM_GUARD)) || ((flags & NATINF_DIT_FP8) && hidden % 128) || depth <= 0 || hidden <= 0 || heads <= 0 || hidden % 64 || hidden % heads || (hidden / heads) % 8 || hidden > 1536)
         return NATINF_EINVAL;
     if (input_size != 32 && input_size != 64) return NATINF_EINVAL;
     natinf_dit* e = new natinf_dit();
@@ -526,6 +535,7 @@ int natinf_dit_create_sized(natinf_dit_t* out, int depth, int hidden, int heads,
     e->unfused_attention = (flags & NATINF_DIT_UNFUSED_ATTENTION) != 0;
     e->fp8 = (flags & NATINF_DIT_FP8) != 0;
     e->stream16 = g_dit_stream16 != 0;
+    e->guard_sites = (flags & NATINF_DIT_STREAM_GUARD) ? 1 + 2 * depth : 0;
     DitBuilder b(*e);
     b.build();
     *out = e;
@@ -536,7 +546,10 @@ int natinf_dit_input_size(natinf_dit_t h) { return h ? h->input_size : NATINF_EI
 int natinf_dit_destroy(natinf_dit_t h) { if (!h) return NATINF_EINVAL; delete h; return NATINF_OK; }
 int64_t natinf_dit_param_count(natinf_dit_t h) { return h ? h->n_params : NATINF_EINVAL; }
 int64_t natinf_dit_packed_bytes(natinf_dit_t h) { return h ? h->packed_bytes : NATINF_EINVAL; }
-int64_t natinf_dit_workspace_bytes(natinf_dit_t h, int max_batch) { return h && max_batch > 0 ? h->ws_per_image * (int64_t)max_batch : NATINF_EINVAL; }
+int64_t natinf_dit_workspace_bytes(natinf_dit_t h, int max_batch) { return h && max_batch > 0 ? h->workspace_bytes(max_batch) : NATINF_EINVAL; }
+int natinf_dit_stream_sites(natinf_dit_t h) { return h && h->guard_sites ? h->guard_sites : NATINF_EINVAL; }
+int natinf_dit_stream_status_reset(natinf_dit_t h, void* workspace, natinf_stream_t stream) { return h ? h->status_reset(workspace, (hipStream_t)stream) : NATINF_EINVAL; }
+int natinf_dit_stream_status(natinf_dit_t h, const void* workspace, uint32_t* out_dev, natinf_stream_t stream) { return h ? h->status_read(workspace, out_dev, (hipStream_t)stream) : NATINF_EINVAL; }
 
 int natinf_dit_load(natinf_dit_t h, const float* params_f32, int64_t n_params, void* packed, int64_t packed_bytes, natinf_stream_t stream) {
     return h ? h->load(params_f32, n_params, packed, packed_bytes, (hipStream_t)stream) : NATINF_EINVAL;

@@ -37,6 +37,8 @@ struct Ctx {                     // per-forward launch context
     hipStream_t stream2 = nullptr; hipEvent_t* ev = nullptr;      // MMDiT engine: the text stream's own HIP stream and the fork / join events (null: everything on `stream`)
     unsigned char* fin_done = nullptr;   // [n_parts] per FORWARD, like part_bm: the launch that wrote partial table i also wrote its consumer's GroupNorm table (see Fin).  Not plan
                                          // state: a description pass (scratch array) or a second thread's forward on a shared plan cannot flip it under a running forward
+    uint32_t* guard = nullptr;           // guarded transformer engines: the status block {max_bits, clamped} x sites at the head of the caller's workspace (EngineCore::guard_sites); null = unguarded
+    uint32_t* site(int i) const { return guard ? guard + 2 * i : nullptr; }      // GemmArgs::stream_guard of stream-writing launch i of the plan
     bf16* act(const TRef& t) const { return reinterpret_cast<bf16*>(ws + t.off * B) + t.coff; }
     template <class T> T* at(int64_t off) const { return reinterpret_cast<T*>(ws + off * B); }
     template <class T> const T* w(int64_t off) const { return reinterpret_cast<const T*>(wp + off); }
@@ -88,6 +90,20 @@ struct EngineCore {                      // what an engine is: a launch plan ove
     const unsigned char* packed = nullptr;
     bool configured = false;
     std::vector<int> part_bm{128};
+    // Stream guard (NATINF_DIT_STREAM_GUARD / NATINF_MMDIT_STREAM_GUARD): guard_sites stream-writing launches, each with a slot {uint32 max_bits, uint32 clamped} in a status
+    // block of guard_bytes() at the HEAD of the caller's workspace -- in front of the arena, whose offsets scale with the batch of a forward, so that the block is where
+    // it is for any batch size and the status entries need the workspace pointer only.  Forwards accumulate into it (atomic max / add); nothing zeroes it but status_reset.
+    int guard_sites = 0;
+    int64_t guard_bytes() const { return guard_sites ? align_up((int64_t)guard_sites * 8, 256) : 0; }
+    int64_t workspace_bytes(int max_batch) const { return ws_per_image * (int64_t)max_batch + guard_bytes(); }
+    int status_reset(void* ws, hipStream_t s) const {
+        if (!guard_sites || !ws) return NATINF_EINVAL;
+        return hipMemsetAsync(ws, 0, (size_t)guard_sites * 8, s) == hipSuccess ? NATINF_OK : NATINF_ELAUNCH;
+    }
+    int status_read(const void* ws, uint32_t* out_dev, hipStream_t s) const {
+        if (!guard_sites || !ws || !out_dev) return NATINF_EINVAL;
+        return hipMemcpyAsync(out_dev, ws, (size_t)guard_sites * 8, hipMemcpyDeviceToDevice, s) == hipSuccess ? NATINF_OK : NATINF_ELAUNCH;
+    }
     int load(const float* params_f32, int64_t n, void* dst, int64_t dst_bytes, hipStream_t s) {
         if (!params_f32 || !dst || n != n_params || dst_bytes < packed_bytes) return NATINF_EINVAL;
         PackCtx p{params_f32, reinterpret_cast<unsigned char*>(dst), s};
@@ -98,11 +114,13 @@ struct EngineCore {                      // what an engine is: a launch plan ove
     int run(const float* x, const float* t, float* out, int B, void* ws, int64_t ws_bytes, hipStream_t s, hipStream_t s2 = nullptr, hipEvent_t* ev = nullptr) {
         if (!x || !t || !out || !ws || B <= 0) return NATINF_EINVAL;
         if (!packed) return NATINF_ESTATE;
-        if (ws_bytes < ws_per_image * (int64_t)B) return NATINF_EINVAL;
+        if (ws_bytes < workspace_bytes(B)) return NATINF_EINVAL;
         if (!configured) { if (!configure_gemm_kernels()) return NATINF_ENODEV; configured = true; }
-        Ctx c{B, reinterpret_cast<unsigned char*>(ws), packed, s, x, t, out, part_bm.data()};
+        Ctx c{B, reinterpret_cast<unsigned char*>(ws) + guard_bytes(), packed, s, x, t, out, part_bm.data()};
         c.stream2 = s2; c.ev = ev;
+        if (guard_sites) { c.guard = reinterpret_cast<uint32_t*>(ws); g_launch_error = 0; }
         for (const auto& f : ops) f(c);
+        if (guard_sites && g_launch_error) { g_launch_error = 0; return NATINF_ESTATE; }      // a guarded site whose launch has no guarded kernel: refused, not written unguarded
         return hipGetLastError() == hipSuccess ? NATINF_OK : NATINF_ELAUNCH;
     }
 };

@@ -617,7 +617,9 @@ __device__ __forceinline__ void dma_tile_epilogue(const GemmArgs& g, unsigned ch
 // instruction), no LDS, no barrier.  The residual rows are fetched half a tile at a time (64 VGPRs in flight).
 // HI_ (0 = by the register budget of a 256-register kernel): residual row-tiles fetched per round trip.  The w128 kernels (accumulators in AGPRs, the fragment
 // registers dead by the epilogue) fetch all eight at once: one memory round trip per half tile instead of four -- with one block per CU nothing hides them.
-template <int WM, int WN, int TM, int TN, bool DEQ = false, int HI_ = 0>
+// GUARD (EPI 10 / fp8 EPI 4; GemmArgs::stream_guard): every stored value passes stream_guard_value first -- clamped to the half range on a half stream, its |v| tracked on
+// both -- and the wave commits its maximum and its count to the site's slot once per call (ncsnpp_kernels.h).  Without GUARD the code is what it was.
+template <int WM, int WN, int TM, int TN, bool DEQ = false, int HI_ = 0, bool GUARD = false>
 __device__ __forceinline__ void direct_f32_epilogue(const GemmArgs& g, f32x4 (&acc)[TM][TN], int m0, int n0, int z, int lane, int wm, int wn)
 {
     const int r = lane & 15, q = lane >> 4;
@@ -654,6 +656,7 @@ __device__ __forceinline__ void direct_f32_epilogue(const GemmArgs& g, f32x4 (&a
     const int64_t eoff = (int64_t)z * g.c_bs + n0 + wn * TN * 16 + q * 4;                        // element offset of the lane's first column (fp32 and half streams alike)
     constexpr int HI = HI_ > 0 ? HI_ : (DEQ ? (TM > 2 ? 2 : TM) : (TM > 4 ? TM / 2 : TM));      // residual row-tiles in flight (register budget)
     typedef _Float16 f16x4_ds __attribute__((ext_vector_type(4)));
+    StreamGuardAcc ga;
     // F16 (GemmArgs::stream_f16, kernel-uniform): the stream's rows are IEEE half -- 8 bytes per lane and access instead of 16, half the bytes of the epilogue that
     // bounds these launches (gemm_w128.h); the update itself stays fp32 with ONE rounding to half
     auto sweep = [&](auto f16_tag) __attribute__((always_inline)) {
@@ -691,6 +694,10 @@ __device__ __forceinline__ void direct_f32_epilogue(const GemmArgs& g, f32x4 (&a
                         v[e] = ((a0 + ct[j][e]) * gt[j][e] + x_) * scale;
                     }
                     if (m < g.M && n_ok[j]) {
+                        if constexpr (GUARD) {
+#pragma unroll
+                            for (int e = 0; e < 4; ++e) v[e] = stream_guard_value<F16>(ga, v[e]);
+                        }
                         if constexpr (F16) {
                             const f16x4_ds o = {(_Float16)v[0], (_Float16)v[1], (_Float16)v[2], (_Float16)v[3]};
                             *reinterpret_cast<uint2*>(cbh + (int64_t)m * g.c_ld + j * 16) = __builtin_bit_cast(uint2, o);
@@ -734,8 +741,12 @@ __device__ __forceinline__ void direct_f32_epilogue(const GemmArgs& g, f32x4 (&a
                     for (int e = 0; e < 4; ++e) {
                         const float a0 = DEQ ? acc[h * HI + i][2 * p][e] * (rsc[h * HI + i] * dn[2 * p][e]) : acc[h * HI + i][2 * p][e];
                         const float a1 = DEQ ? acc[h * HI + i][2 * p + 1][e] * (rsc[h * HI + i] * dn[2 * p + 1][e]) : acc[h * HI + i][2 * p + 1][e];
-                        o0[e] = (_Float16)(((a0 + ct[2 * p][e]) * gt[2 * p][e] + (float)x0[e]) * scale);
-                        o1[e] = (_Float16)(((a1 + ct[2 * p + 1][e]) * gt[2 * p + 1][e] + (float)x1[e]) * scale);
+                        float v0 = ((a0 + ct[2 * p][e]) * gt[2 * p][e] + (float)x0[e]) * scale, v1 = ((a1 + ct[2 * p + 1][e]) * gt[2 * p + 1][e] + (float)x1[e]) * scale;
+                        if constexpr (GUARD) {
+                            if (m < g.M) { v0 = stream_guard_value<true>(ga, v0); v1 = stream_guard_value<true>(ga, v1); }
+                        }
+                        o0[e] = (_Float16)v0;
+                        o1[e] = (_Float16)v1;
                     }
                     const uint2 u0 = __builtin_bit_cast(uint2, o0), u1 = __builtin_bit_cast(uint2, o1);
                     auto t0 = __builtin_amdgcn_permlane16_swap(u0.x, u1.x, false, false);          // the same trade back: (x, y, z, w) = the lane's eight consecutive columns
@@ -751,11 +762,12 @@ __device__ __forceinline__ void direct_f32_epilogue(const GemmArgs& g, f32x4 (&a
         if (wide) { if constexpr (TN % 2 == 0) sweep16(); }
         else sweep(std::integral_constant<bool, true>{});
     } else sweep(std::integral_constant<bool, false>{});
+    if constexpr (GUARD) stream_guard_commit(ga, g.stream_guard);
 }
 
 // EPI (kernel template parameter, chosen on the host by packed_epi()): 0 = fp32-slab epilogue with every fused term as a run-time
 // flag; 1..6 = packed epilogue: plain / + GroupNorm partials / + SiLU / + tanh-GELU / + bf16 residual / + residual and partials;
-// 7 = the direct fp32 residual-stream epilogue; 8 = packed with row terms (a row bias: the V^T = W h^T + b GEMMs).  One epilogue per kernel: with both in one
+// 7 = the direct fp32 residual-stream epilogue (10 = its guarded form, GemmArgs::stream_guard); 8 = packed with row terms (a row bias: the V^T = W h^T + b GEMMs).  One epilogue per kernel: with both in one
 // kernel behind a run-time branch hipcc spilled inside the packed register phase (measured: isolated GEMMs +15..23 %, the
 // network 8 % SLOWER).
 template <int WM, int WN, int TM, int TN, class Cfg, int EPI, int NSAMP = 1, bool FIN = false, bool PAIR = false>
@@ -764,6 +776,7 @@ __device__ __forceinline__ void tile_epilogue(const GemmArgs& g, unsigned char* 
 {
     if constexpr (EPI == 0) dma_tile_epilogue<WM, WN, TM, TN, Cfg>(g, smem, acc, m0, n0, z, tid, lane, wm, wn);
     else if constexpr (EPI == 7) direct_f32_epilogue<WM, WN, TM, TN>(g, acc, m0, n0, z, lane, wm, wn);
+    else if constexpr (EPI == 10) direct_f32_epilogue<WM, WN, TM, TN, false, 0, true>(g, acc, m0, n0, z, lane, wm, wn);
     else {
         static_assert(Cfg::PACK_OK, "packed epilogue needs the whole bf16 tile in LDS");
         NATINF_TS(2);

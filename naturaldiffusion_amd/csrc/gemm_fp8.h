@@ -122,6 +122,9 @@ __global__ __launch_bounds__(512, 2) void k_gemm_fp8(const GemmArgs g)
     if constexpr (EPI == 1) packed_tile_epilogue<2, 4, 8, 4, typename Cfg::Epi, ACT_NONE, false, false, true, false>(g, smem, acc, m0, n0, z, tid, lane, wm, wn);
     else if constexpr (EPI == 2) packed_tile_epilogue<2, 4, 8, 4, typename Cfg::Epi, ACT_GELU_TANH, false, false, true, true>(g, smem, acc, m0, n0, z, tid, lane, wm, wn);
     else if constexpr (EPI == 3) direct_f32_epilogue<2, 4, 8, 4, true>(g, acc, m0, n0, z, lane, wm, wn);
+    // 3 guarded (GemmArgs::stream_guard).  One residual row-tile in flight instead of two: with two, the guard's two accumulators and its constants cost this 256-register
+    // kernel five spilled registers; the arithmetic per value is the same
+    else if constexpr (EPI == 4) direct_f32_epilogue<2, 4, 8, 4, true, 1, true>(g, acc, m0, n0, z, lane, wm, wn);
     else dma_tile_epilogue<2, 4, 8, 4, typename Cfg::Epi>(g, smem, acc, m0, n0, z, tid, lane, wm, wn);
 }
 

@@ -27,6 +27,11 @@ namespace { bool configure_ncsnpp_kernels();         // ncsnpp.hip: the output h
             bool configure_dit_attention();          // dit_engine.inc: the row-major-v forms of k_attn_fused
             bool configure_flash_attention(); }      // mmdit_engine.inc: the joint-sequence flash kernels
 // k_conv_gn3 (conv_gn3.h / conv_gn3.hip: one wave per SIMD, 128 x 128 wave tiles, slot-table K loop) -- a translation unit of its own
+// the guarded forms of the stream-writing kernels (stream_guard.hip, a translation unit of its own like conv_gn3.hip): the direct residual epilogue with GemmArgs::stream_guard on
+// the five bf16 tile families that have it (EPI 10 beside 7) and on the four fp8 instances (EPI 4 beside 3), the split-K reduce and the patch embedding.  raster: g_raster_g
+namespace ncsn_sg { bool configure(); bool has_tile(int variant); void launch_tile(const void* gemm_args, int variant, int raster, void* stream);
+                    void launch_fp8(const void* gemm_args, int mxa, int w128, int raster, void* stream); void launch_splitk_reduce(const void* gemm_args, int slices, void* stream);
+                    void launch_patch_embed(const float* z, const float* Wt, const float* bias, const float* pos, float* x, int C, int g, int D, int64_t rows, int x_f16, uint32_t* guard, void* stream); }
 namespace ncsn_cg3 { bool configure(); int tile_rows(int shape); int tile_cols(int shape); void launch(const void* gemm_args, int shape, int epi, void* stream); }
 
 namespace {
@@ -187,7 +192,7 @@ bool configure_gemm_kernels() {
                                   GEMM_LDS_BYTES) == hipSuccess;
     ok = ok && set_lds<CfgR128x128>(&k_gemm_ring<2, 2, 4, 4, 4, 9>) && set_lds<W128Cfg>(&k_gemm_w128<9>) &&
          configure_families(GemmFamilies{}) && configure_families(ConvGnShapes{}) && configure_families(Fp8Families{}) &&
-         ncsn_cg3::configure() && ::configure_conv_ring() && configure_ncsnpp_kernels() && configure_dit_attention() && configure_flash_attention();
+         ncsn_cg3::configure() && ncsn_sg::configure() && ::configure_conv_ring() && configure_ncsnpp_kernels() && configure_dit_attention() && configure_flash_attention();
     if (!ok) (void)hipGetLastError();
     return ok;
 }
@@ -343,11 +348,14 @@ struct GemmProf {
     }
     void end(Rec& r, hipStream_t s) { (void)hipEventRecord(r.b, s); ev.push_back(std::move(r)); }
 } g_gemm_prof;
+thread_local int g_launch_error = 0;
 void launch_gemm_fp8(const GemmArgs& g, hipStream_t s) {
+    if (g.stream_guard && fp8_epi(g) != 3) { g_launch_error = 1; return; }      // only the direct residual epilogue has a guarded form: never an unguarded write of a guarded site
     GemmProf::Rec r;
     const bool prof = g_gemm_prof.on && !g_record && g_gemm_prof.begin(r, s);
-    if (prof) r.tag = gemm_row(g.M, g.N, g.taps * g.a0_C, 0, g.taps, g.batch, std::string(fp8_on_w128(g) ? "w128_fp8" : "fp8_256x256") + (g.a_mx ? "_mxa" : ""), fp8_epi(g));
-    if (g.a_mx) launch_gemm_fp8_t<true>(g, s); else launch_gemm_fp8_t<false>(g, s);
+    if (prof) r.tag = gemm_row(g.M, g.N, g.taps * g.a0_C, 0, g.taps, g.batch, std::string(fp8_on_w128(g) ? "w128_fp8" : "fp8_256x256") + (g.a_mx ? "_mxa" : ""), g.stream_guard ? 4 : fp8_epi(g));
+    if (g.stream_guard) ncsn_sg::launch_fp8(&g, g.a_mx != nullptr, fp8_on_w128(g), g_raster_g, (void*)s);      // the same tile, EPI 4
+    else if (g.a_mx) launch_gemm_fp8_t<true>(g, s); else launch_gemm_fp8_t<false>(g, s);
     if (prof) g_gemm_prof.end(r, s);
 }
 
@@ -370,8 +378,7 @@ inline int effective_epi(int v, const GemmArgs& g) { const int e = packed_epi(g,
 
 // set when a launch is asked for something no kernel provides (a plan-builder bug, or an A/B knob flipped after the plan was built);
 // natinf_ncsnpp_forward clears it on entry and reports it on exit -- per calling thread, so two engines on two threads do not see
-// each other's, and a description pass (g_record) never sets it
-thread_local int g_launch_error = 0;
+// each other's, and a description pass (g_record) never sets it (g_launch_error: declared in front of launch_gemm_fp8; guarded engines check it too, EngineCore::run)
 thread_local bool g_fin_written = false;      // set by launch_gemm: the launch that just ran wrote the consumer's GroupNorm table (GemmArgs::fin_*) -- k_conv_gn3 at 16x16
 int g_splitk = 1;                  // natinf_set_gemm_splitk: 0 = never split K
 float* g_dbg_splitk_ws = nullptr; int g_dbg_splitk_max = 0;        // natinf_debug_set_splitk_workspace
@@ -429,6 +436,8 @@ int launch_gemm_run(const GemmArgs& g0, hipStream_t s) {
             p.raster_g = 0;
             hipLaunchKernelGGL((k_gemm_w128<9>), dim3(nM * nN, S8, p.batch), dim3(256), W128Cfg::LDS_BYTES, s, p);
             const int64_t per = (int64_t)g0.M * (g0.N / 4);
+            if (g0.stream_guard) ncsn_sg::launch_splitk_reduce(&g0, S8, (void*)s);
+            else
             hipLaunchKernelGGL(k_splitk_reduce_f32, dim3((unsigned)((per + 255) / 256), (unsigned)g0.batch), dim3(256), 0, s, g0.splitk_ws, S8, (int64_t)g0.batch * g0.M * g0.N, g0.M, g0.N,
                                g0.bias_n, g0.gate, g0.gate_ld, g0.log_rows_per_sample, g0.z_samples, g0.resid_f32, g0.resid_f32_ld, g0.c_bs, g0.scale,
                                reinterpret_cast<float*>(g0.c), g0.c_ld, g0.stream_f16);
@@ -458,11 +467,14 @@ int launch_gemm_run(const GemmArgs& g0, hipStream_t s) {
         if (g_record) record_gemm(g, "invalid_conv_gn", 0); else g_launch_error = 1;      // description pass: say so in the table instead of dropping the row
         return 256;
     }
+    const bool guarded = g.stream_guard != nullptr;      // the same tile with EPI 10 in place of 7 (stream_guard.hip); anything else is refused: no unguarded write of a guarded site
+    if (guarded && !g_record && (!ncsn_sg::has_tile(v) || effective_epi(v, g) != 7)) { g_launch_error = 1; return 256; }
     if (g_record) {
-        record_gemm(g, v == V_CONV_GN && conv_gn3_shape(g) >= 0 ? "conv_gn3" : variant_name(v), v == V_CONV_GN ? conv_gn_epi(g) : effective_epi(v, g));
+        record_gemm(g, v == V_CONV_GN && conv_gn3_shape(g) >= 0 ? "conv_gn3" : variant_name(v), v == V_CONV_GN ? conv_gn_epi(g) : (guarded && effective_epi(v, g) == 7 ? 10 : effective_epi(v, g)));
         return v == V_CONV_GN ? conv_gn_part_rows(g) : variant_bm(v);
     }
-    if (v == V_GENERIC) {
+    if (guarded) ncsn_sg::launch_tile(&g, v, g_raster_g, (void*)s);
+    else if (v == V_GENERIC) {
         const int nM = (g.M + BM - 1) / BM, nN = (g.N + BN - 1) / BN;
         hipLaunchKernelGGL(k_gemm_bf16, dim3(nM * nN, 1, g.batch), dim3(256), GEMM_LDS_BYTES, s, g);
     } else if (v == V_CONV_GN) {

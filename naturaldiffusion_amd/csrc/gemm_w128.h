@@ -292,10 +292,10 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
         }
         return;
     }
-    if constexpr (EPI == 7) {                                            // direct fp32 residual stream: no LDS, the whole half tile's residual in one round trip
-        direct_f32_epilogue<2, 2, 8, 4, false, 8>(g, accL, m0, n0, z, lane, wm, wn);
+    if constexpr (EPI == 7 || EPI == 10) {                               // direct fp32 residual stream: no LDS, the whole half tile's residual in one round trip (10: guarded, GemmArgs::stream_guard)
+        direct_f32_epilogue<2, 2, 8, 4, false, 8, EPI == 10>(g, accL, m0, n0, z, lane, wm, wn);
         NATINF_TS(6);
-        if (n0 + 128 < g.N) direct_f32_epilogue<2, 2, 8, 4, false, 8>(g, accH, m0, n0 + 128, z, lane, wm, wn);
+        if (n0 + 128 < g.N) direct_f32_epilogue<2, 2, 8, 4, false, 8, EPI == 10>(g, accH, m0, n0 + 128, z, lane, wm, wn);
 #ifdef NATINF_DEV
         if (g.dbg_ts) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");      // (timeline runs: stamp 7 is "the tile's stores have been acknowledged")
 #endif
@@ -463,7 +463,7 @@ __device__ __forceinline__ void w128f8_first(u32x4 (&fal)[8], u32x4 (&fah)[8], u
 #undef NATINF_W128F8_B
 }
 
-// EPI as k_gemm_fp8: 0 = general fp32-slab epilogue, 1 = packed bf16, 2 = packed e4m3 + E8M0 with tanh-GELU, 3 = direct fp32 residual stream.
+// EPI as k_gemm_fp8: 0 = general fp32-slab epilogue, 1 = packed bf16, 2 = packed e4m3 + E8M0 with tanh-GELU, 3 = direct fp32 residual stream, 4 = 3 guarded.
 template <bool MXA, int EPI>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) void k_gemm_w128_fp8(const GemmArgs g)
 {
@@ -549,13 +549,13 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
     auto epi = [&](f32x4 (&acc)[8][4], int nb, unsigned char* slab) __attribute__((always_inline)) {
         if constexpr (EPI == 1) packed_tile_epilogue<2, 2, 8, 4, typename Cfg::Epi, ACT_NONE, false, false, true, false>(g, slab, acc, m0, nb, z, tid, lane, wm, wn);
         else if constexpr (EPI == 2) packed_tile_epilogue<2, 2, 8, 4, typename Cfg::Epi, ACT_GELU_TANH, false, false, true, true>(g, slab, acc, m0, nb, z, tid, lane, wm, wn);
-        else if constexpr (EPI == 3) direct_f32_epilogue<2, 2, 8, 4, true, 8>(g, acc, m0, nb, z, lane, wm, wn);      // (the whole half tile's residual in one round trip)
+        else if constexpr (EPI == 3 || EPI == 4) direct_f32_epilogue<2, 2, 8, 4, true, 8, EPI == 4>(g, acc, m0, nb, z, lane, wm, wn);      // (the whole half tile's residual in one round trip; 4: guarded)
         else dma_tile_epilogue<2, 2, 8, 4, typename Cfg::Epi>(g, slab, acc, m0, nb, z, tid, lane, wm, wn);
     };
     epi(accL, n0, smem);
     if (n0 + 128 < g.N) {
         if constexpr (EPI == 0) __syncthreads();
-        epi(accH, n0 + 128, smem + (EPI == 0 || EPI == 3 ? 0 : Cfg::SLAB2_OFF));      // packed epilogues: a slab of its own, no barrier between the halves
+        epi(accH, n0 + 128, smem + (EPI == 0 || EPI == 3 || EPI == 4 ? 0 : Cfg::SLAB2_OFF));      // packed epilogues: a slab of its own, no barrier between the halves
     }
 }
 

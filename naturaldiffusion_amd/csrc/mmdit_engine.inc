@@ -137,10 +137,7 @@ struct MMDitBuilder : PlanBuilder {
                 (void)hipMemset2DAsync(c.at<bf16>(qk) + (int64_t)(Tx + Tc) * 2 * D, (size_t)Tp * 2 * D * 2, 0, (size_t)(Tp - Tx - Tc) * 2 * D * 2, (size_t)c.B, c.stream);
             }
             const int64_t prow = (int64_t)c.B * Tx;
-            if (s16) hipLaunchKernelGGL(k_patch_embed<true>, dim3((unsigned)((D + 255) / 256), (unsigned)((prow + PE_TOK - 1) / PE_TOK)), dim3(256), 0, c.stream, c.x,
-                                        c.w<float>(w_pw), c.w<float>(w_pb), c.w<float>(w_pos), c.at<float>(x), C, gr, D, prow);
-            else hipLaunchKernelGGL(k_patch_embed<false>, dim3((unsigned)((D + 255) / 256), (unsigned)((prow + PE_TOK - 1) / PE_TOK)), dim3(256), 0, c.stream, c.x,
-                                    c.w<float>(w_pw), c.w<float>(w_pb), c.w<float>(w_pos), c.at<float>(x), C, gr, D, prow);
+            launch_patch_embed(c.x, c.w<float>(w_pw), c.w<float>(w_pb), c.w<float>(w_pos), c.at<float>(x), C, gr, D, prow, s16, c.site(0), c.stream);
             hipLaunchKernelGGL(k_dit_time_freq, dim3(grid1d((int64_t)c.B * 256, 256, 1 << 30)), dim3(256), 0, c.stream, c.labels, c.at<bf16>(tf), c.B);
             const int64_t np = (int64_t)c.B * Pd, nt = (int64_t)c.B * Tc * Jd;
             hipLaunchKernelGGL(k_f32_to_bf16, dim3(grid1d(np, 256, 1 << 30)), dim3(256), 0, c.stream, eng->pooled, c.at<bf16>(pl), np);
@@ -180,7 +177,8 @@ struct MMDitBuilder : PlanBuilder {
             g.c = out; g.c_ld = ld; g.c_bs = c_bs; g.c_mode = mode; g.batch = c.B;
             return g;
         };
-        auto gated = [=](GemmArgs g, const Ctx& c, int gate_off, int64_t stream_off) {      // stream += gate * (. + bias)
+        auto gated = [=](GemmArgs g, const Ctx& c, int gate_off, int64_t stream_off, int site = -1) {      // stream += gate * (. + bias); site: the launch's slot of the stream guard (image stream only)
+            g.stream_guard = site >= 0 ? c.site(site) : nullptr;
             g.gate = c.at<float>(mod) + gate_off; g.gate_ld = nmod; g.log_rows_per_sample = 30; g.z_samples = 1;
             g.resid_f32 = c.at<float>(stream_off); g.resid_f32_ld = D;
             g.stream_f16 = s16 && stream_off == x;                     // (g.c is the same stream: both sides of the update are half rows then)
@@ -278,17 +276,17 @@ struct MMDitBuilder : PlanBuilder {
                 }
             });
             op(ev_record(2 + 2 * i, false));
-            auto proj8 = [=](const Ctx& c, const Lin8& w, int row0, int T, float* stream_ptr_, int64_t stream_off, int gate_off) {     // stream += gate * (O8 W^T + b)
+            auto proj8 = [=](const Ctx& c, const Lin8& w, int row0, int T, float* stream_ptr_, int64_t stream_off, int gate_off, int site = -1) {     // stream += gate * (O8 W^T + b)
                 GemmArgs g = gemm_defaults();
                 g.a0 = reinterpret_cast<const bf16*>(c.at<uint8_t>(o8) + (int64_t)row0 * D); g.a0_ld = D; g.a0_C = D; g.a_bs = (int64_t)Tp * D; g.M = T; g.N = D;
                 g.a_mx = c.at<uint8_t>(omx) + (int64_t)row0 * 4; g.a_mx_ld = Tp; g.a_mx_bs = (int64_t)Tp * (D / 32);      // K-tile-major planes of Tp rows
                 g.b = reinterpret_cast<const bf16*>(c.w<uint8_t>(w.w)); g.b_ld = D; g.deq_n = c.w<float>(w.s); g.bias_n = c.w<float>(w.b);
                 g.c = stream_ptr_; g.c_ld = D; g.c_bs = (int64_t)T * D; g.c_mode = OUT_F32; g.batch = c.B;
-                launch_gemm_fp8(gated(g, c, gate_off, stream_off), c.stream);
+                launch_gemm_fp8(gated(g, c, gate_off, stream_off, site), c.stream);
             };
             op([=](const Ctx& c) {                          // image stream's output projection
-                if (fp8) proj8(c, ox8, 0, Tx, c.at<float>(x), x, mx + 2 * D);
-                else launch_gemm(gated(seq_gemm(c, c.at<bf16>(o), D, (int64_t)Tp * D, Tx, ox, D, c.at<float>(x), D, (int64_t)Tx * D, OUT_F32), c, mx + 2 * D, x), c.stream);
+                if (fp8) proj8(c, ox8, 0, Tx, c.at<float>(x), x, mx + 2 * D, 1 + 2 * i);
+                else launch_gemm(gated(seq_gemm(c, c.at<bf16>(o), D, (int64_t)Tp * D, Tx, ox, D, c.at<float>(x), D, (int64_t)Tx * D, OUT_F32), c, mx + 2 * D, x, 1 + 2 * i), c.stream);
             });
             if (!last) {
                 op(ev_wait(2 + 2 * i, true));
@@ -312,14 +310,14 @@ struct MMDitBuilder : PlanBuilder {
                     g.a_mx = c.at<uint8_t>(fmx); g.a_mx_ld = Tx; g.a_mx_bs = (int64_t)Tx * (4 * D / 32);
                     g.b = reinterpret_cast<const bf16*>(c.w<uint8_t>(f28.w)); g.b_ld = 4 * D; g.deq_n = c.w<float>(f28.s); g.bias_n = c.w<float>(f28.b);
                     g.c = c.at<float>(x); g.c_ld = D; g.c_bs = (int64_t)Tx * D; g.c_mode = OUT_F32; g.batch = c.B;
-                    launch_gemm_fp8(gated(g, c, mx + 5 * D, x), c.stream);
+                    launch_gemm_fp8(gated(g, c, mx + 5 * D, x, 2 + 2 * i), c.stream);
                     return;
                 } else {
                 GemmArgs g = seq_gemm(c, c.at<bf16>(hx), D, (int64_t)Tx * D, Tx, f1, 4 * D, c.at<bf16>(fx), 4 * D, (int64_t)Tx * 4 * D, OUT_BF16);
                 g.act = ACT_GELU_TANH;
                 launch_gemm(g, c.stream);
                 }
-                launch_gemm(gated(seq_gemm(c, c.at<bf16>(fx), 4 * D, (int64_t)Tx * 4 * D, Tx, f2, D, c.at<float>(x), D, (int64_t)Tx * D, OUT_F32), c, mx + 5 * D, x), c.stream);
+                launch_gemm(gated(seq_gemm(c, c.at<bf16>(fx), 4 * D, (int64_t)Tx * 4 * D, Tx, f2, D, c.at<float>(x), D, (int64_t)Tx * D, OUT_F32), c, mx + 5 * D, x, 2 + 2 * i), c.stream);
             });
             if (!last) {
                 op(on_text(ln_mod(e, Tc, me + 3 * D, me + 4 * D, he)));
@@ -354,7 +352,7 @@ struct MMDitBuilder : PlanBuilder {
 extern "C" {
 
 int natinf_mmdit_create(natinf_mmdit_t* out, int layers, int heads, int joint_dim, int pooled_dim, int in_ch, int grid, int ctx_tokens, int flags) {
-    if (!out || (flags & ~NATINF_MMDIT_FP8) || ((flags & NATINF_MMDIT_FP8) && heads % 2) || layers <= 0 || heads <= 0 || heads * 64 > 1536 || joint_dim <= 0 || joint_dim % 8 || pooled_dim <= 0 || pooled_dim % 8 ||
+    if (!out || (flags & ~(NATINF_MMDIT_FP8 | NATINF_MMDIT_STREAM_GUARD)) || ((flags & NATINF_MMDIT_FP8) && heads % 2) || layers <= 0 || heads <= 0 || heads * 64 > 1536 || joint_dim <= 0 || joint_dim % 8 || pooled_dim <= 0 || pooled_dim % 8 ||
         in_ch <= 0 || in_ch > 16 || (in_ch * 4) % 8 || grid <= 0 || (grid * grid) % 8 || ctx_tokens <= 0)
         return NATINF_EINVAL;
     natinf_mmdit* e = new natinf_mmdit();
@@ -362,6 +360,7 @@ int natinf_mmdit_create(natinf_mmdit_t* out, int layers, int heads, int joint_di
     e->Tx = grid * grid; e->Tc = ctx_tokens; e->Tp = (int)align_up(e->Tx + e->Tc, 128);
     e->fp8 = (flags & NATINF_MMDIT_FP8) != 0;
     e->stream16 = g_mmdit_stream16 != 0;
+    e->guard_sites = (flags & NATINF_MMDIT_STREAM_GUARD) ? 1 + 2 * layers : 0;      // the image stream: patch embedding, then per block the attention-projection and the MLP update (the text stream is fp32: unguarded)
     MMDitBuilder b(*e);
     b.build();
     *out = e;
@@ -370,7 +369,10 @@ int natinf_mmdit_create(natinf_mmdit_t* out, int layers, int heads, int joint_di
 int natinf_mmdit_destroy(natinf_mmdit_t h) { if (!h) return NATINF_EINVAL; delete h; return NATINF_OK; }
 int64_t natinf_mmdit_param_count(natinf_mmdit_t h) { return h ? h->n_params : NATINF_EINVAL; }
 int64_t natinf_mmdit_packed_bytes(natinf_mmdit_t h) { return h ? h->packed_bytes : NATINF_EINVAL; }
-int64_t natinf_mmdit_workspace_bytes(natinf_mmdit_t h, int max_batch) { return h && max_batch > 0 ? h->ws_per_image * (int64_t)max_batch : NATINF_EINVAL; }
+int64_t natinf_mmdit_workspace_bytes(natinf_mmdit_t h, int max_batch) { return h && max_batch > 0 ? h->workspace_bytes(max_batch) : NATINF_EINVAL; }
+int natinf_mmdit_stream_sites(natinf_mmdit_t h) { return h && h->guard_sites ? h->guard_sites : NATINF_EINVAL; }
+int natinf_mmdit_stream_status_reset(natinf_mmdit_t h, void* workspace, natinf_stream_t stream) { return h ? h->status_reset(workspace, (hipStream_t)stream) : NATINF_EINVAL; }
+int natinf_mmdit_stream_status(natinf_mmdit_t h, const void* workspace, uint32_t* out_dev, natinf_stream_t stream) { return h ? h->status_read(workspace, out_dev, (hipStream_t)stream) : NATINF_EINVAL; }
 
 int natinf_mmdit_load(natinf_mmdit_t h, const float* params_f32, int64_t n_params, void* packed, int64_t packed_bytes, natinf_stream_t stream) {
     return h ? h->load(params_f32, n_params, packed, packed_bytes, (hipStream_t)stream) : NATINF_EINVAL;

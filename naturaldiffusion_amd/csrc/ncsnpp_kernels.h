@@ -119,7 +119,43 @@ struct GemmArgs {
     // direct residual-stream epilogue (EPI 7 / fp8 EPI 3) on a 16-bit stream: resid_f32 and c point at IEEE-half rows (same element strides); the arithmetic stays
     // fp32, one rounding to half per update (the MMDiT engine's image stream, natinf_set_mmdit_stream16: the reference's SD3 pipeline is fp16)
     int stream_f16;
+    // guarded form of that epilogue (EPI 10 / fp8 EPI 4, the guarded split-K reduce): the site's status slot {uint32 max_bits, uint32 clamped}; launch_gemm
+    // takes the guarded instance when this is set.  Last member: the kernel-argument offsets of every other field are what they were
+    uint32_t* stream_guard;
 };
+
+// The guard of a residual-stream write (include/natinf_dit.h, NATINF_DIT_STREAM_GUARD).  A lane feeds every value it is about to STORE through stream_guard_value --
+// the fp32 update result, before the rounding -- and a wave ends with one stream_guard_commit:
+//   * track: the running maximum of |v| as an unsigned bit pattern (non-negative floats order as their bits; a NaN pattern sorts above inf and reads back as NaN);
+//   * count + clamp (half stream only): |v| > 65504 or NaN is counted, a non-NaN one is written as +-65504 (v_med3_f32; NaN stays NaN).  In range the value is
+//     returned bit for bit, so a guarded launch writes the unguarded launch's bytes.  An fp32 stream is tracked, never clamped or counted.
+// commit: the two figures reduced over the wave, then ONE lane issues at most one vector atomic max (none when the slot already holds as much) and -- when the count is not zero -- one vector atomic add.
+struct StreamGuardAcc { unsigned mx = 0u, cnt = 0u; };
+constexpr unsigned HALF_MAX_BITS = 0x477FE000u;      // 65504.0f
+template <bool F16>
+__device__ __forceinline__ float stream_guard_value(StreamGuardAcc& a, float v)
+{
+    const unsigned bits = __builtin_bit_cast(unsigned, v) & 0x7FFFFFFFu;
+    a.mx = max(a.mx, bits);
+    if constexpr (F16) {
+        a.cnt += bits > HALF_MAX_BITS ? 1u : 0u;
+        const float c = __builtin_amdgcn_fmed3f(v, -65504.0f, 65504.0f);
+        return v != v ? v : c;
+    }
+    return v;
+}
+__device__ __forceinline__ void stream_guard_commit(const StreamGuardAcc& a, uint32_t* slot)
+{
+    unsigned mx = a.mx, cnt = a.cnt;
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) { mx = max(mx, (unsigned)__shfl_xor((int)mx, o)); cnt += (unsigned)__shfl_xor((int)cnt, o); }
+    if ((threadIdx.x & 63) == 0) {
+        // the maximum only grows: a wave that cannot raise what the slot already holds skips its atomic (a stale, smaller reading costs an atomic, never a wrong result).
+        // The split-K reduce commits from 18,000 waves per launch to ONE address; after the first few, almost none of them has anything to add
+        if (mx > *reinterpret_cast<const volatile uint32_t*>(slot)) atomicMax(slot, mx);
+        if (cnt) atomicAdd(slot + 1, cnt);
+    }
+}
 
 __device__ __forceinline__ float silu_f(float v) { return v / (1.0f + __expf(-v)); }
 // v_rcp_f32 instead of the IEEE division sequence (1 ulp; the result is rounded to bf16 right after)

@@ -15,6 +15,7 @@ from . import _lib
 from ._lib import lib, check, ptr, stream_ptr
 
 UNFUSED_ATTENTION = _lib.DIT_UNFUSED_ATTENTION
+STREAM_GUARD = _lib.DIT_STREAM_GUARD                 # the residual stream cannot overflow silently: clamp + per-site status block (include/natinf_dit.h)
 FP8 = _lib.DIT_FP8                                   # q | k | v, fc1 and fc2 of every block on e4m3 operands (include/natinf_dit.h); hidden % 128 == 0
 XL2 = dict(depth=28, hidden=1152, heads=16)          # deps/DiT/models.py:333-334
 INPUT_SIZES = (32, 64)                               # latent side of the 256x256 / 512x512 checkpoints (patch 2: 256 / 1,024 tokens)
@@ -70,11 +71,16 @@ def flatten_state_dict(sd: Dict[str, torch.Tensor], depth: int, hidden: int, inp
     return torch.cat(parts)
 
 
-class DiTEngine:
+class DiTEngine(_lib.StreamGuardStatus):
+    """``guard=True`` (NATINF_DIT_STREAM_GUARD): every write of the residual stream is clamped to the half range and monitored; ``stream_status()``,
+    ``reset_stream_status()`` and ``site_names`` read what the forwards since the last reset left (``_lib.StreamGuardStatus``)."""
+    _guard_api = "natinf_dit"
+
     def __init__(self, flat_params: torch.Tensor, max_batch: int, depth: int = 28, hidden: int = 1152, heads: int = 16,
-                 device="cuda:0", unfused_attention: bool = False, stream16=None, input_size: int = 32, fp8: bool = False):
+                 device="cuda:0", unfused_attention: bool = False, stream16=None, input_size: int = 32, fp8: bool = False, guard: bool = False):
         self.input_size = _check_input_size(input_size)
         self.fp8 = bool(fp8)
+        self.guard = bool(guard)
         _lib.require_gpu()
         if depth <= 0 or hidden <= 0 or heads <= 0 or hidden % 64 or hidden > 1536 or hidden % heads or (hidden // heads) % 8:
             raise ValueError("hidden must be a multiple of 64 (<= 1536) and of heads, head_dim a multiple of 8")
@@ -92,7 +98,8 @@ class DiTEngine:
             check(lib.natinf_set_dit_stream16(int(bool(stream16))), "natinf_set_dit_stream16")
         try:
             check(lib.natinf_dit_create_sized(C.byref(self._h), depth, hidden, heads, self.input_size,
-                                              (UNFUSED_ATTENTION if unfused_attention else 0) | (FP8 if fp8 else 0)), "natinf_dit_create_sized")
+                                              (UNFUSED_ATTENTION if unfused_attention else 0) | (FP8 if fp8 else 0) | (STREAM_GUARD if guard else 0)),
+                  "natinf_dit_create_sized")
         finally:
             if stream16 is not None:
                 lib.natinf_set_dit_stream16(-1)
@@ -107,6 +114,8 @@ class DiTEngine:
             torch.cuda.current_stream().synchronize()
             self.workspace_bytes = lib.natinf_dit_workspace_bytes(self._h, self.max_batch)
             self._ws = torch.empty(self.workspace_bytes, dtype=torch.uint8, device=self.device)
+            if self.guard:
+                self.reset_stream_status()
 
     def __call__(self, z: torch.Tensor, t: torch.Tensor, y: torch.Tensor, out: torch.Tensor = None) -> torch.Tensor:
         S = self.input_size

@@ -17,7 +17,8 @@ import torch
 from . import _lib
 from ._lib import lib, check, ptr, stream_ptr
 
-FP8 = 1
+FP8 = _lib.MMDIT_FP8
+STREAM_GUARD = _lib.MMDIT_STREAM_GUARD               # the image stream cannot overflow silently (include/natinf_mmdit.h; the text stream is fp32)
 SD3_MEDIUM = dict(layers=24, heads=24, joint_dim=4096, pooled_dim=2048, in_ch=16)
 
 
@@ -68,11 +69,16 @@ def flatten_state_dict(sd: Dict[str, torch.Tensor], grid: int, layers: int, head
     return torch.cat(parts)
 
 
-class MMDiTEngine:
+class MMDiTEngine(_lib.StreamGuardStatus):
+    """``guard=True`` (NATINF_MMDIT_STREAM_GUARD): the image stream's writes are clamped to the half range and monitored; ``stream_status()``,
+    ``reset_stream_status()`` and ``site_names`` as on ``DiTEngine``."""
+    _guard_api = "natinf_mmdit"
+
     def __init__(self, flat_params: torch.Tensor, max_batch: int, grid: int = 64, ctx_tokens: int = 333, layers: int = 24,
                  heads: int = 24, joint_dim: int = 4096, pooled_dim: int = 2048, in_ch: int = 16, device="cuda:0", fp8: bool = False,
-                 stream16: Optional[bool] = None):
+                 stream16: Optional[bool] = None, guard: bool = False):
         _lib.require_gpu()
+        self.guard = bool(guard)
         if min(layers, heads, joint_dim, pooled_dim, in_ch, grid, ctx_tokens) <= 0 or heads > 24 or joint_dim % 8 or pooled_dim % 8 \
                 or in_ch % 2 or (grid * grid) % 8:
             raise ValueError("unsupported MMDiT configuration (see include/natinf_mmdit.h)")
@@ -88,7 +94,8 @@ class MMDiTEngine:
         if stream16 is not None:
             check(lib.natinf_set_mmdit_stream16(int(bool(stream16))), "natinf_set_mmdit_stream16")
         try:
-            check(lib.natinf_mmdit_create(C.byref(self._h), layers, heads, joint_dim, pooled_dim, in_ch, grid, ctx_tokens, FP8 if fp8 else 0), "natinf_mmdit_create")
+            check(lib.natinf_mmdit_create(C.byref(self._h), layers, heads, joint_dim, pooled_dim, in_ch, grid, ctx_tokens, (FP8 if fp8 else 0) | (STREAM_GUARD if guard else 0)),
+                  "natinf_mmdit_create")
         finally:
             if stream16 is not None:
                 lib.natinf_set_mmdit_stream16(-1)
@@ -102,6 +109,8 @@ class MMDiTEngine:
             torch.cuda.current_stream().synchronize()
             self.workspace_bytes = lib.natinf_mmdit_workspace_bytes(self._h, self.max_batch)
             self._ws = torch.empty(self.workspace_bytes, dtype=torch.uint8, device=self.device)
+            if self.guard:
+                self.reset_stream_status()
 
     def forward(self, latents: torch.Tensor, timestep: torch.Tensor, text: torch.Tensor, pooled: torch.Tensor) -> torch.Tensor:
         S = 2 * self.grid

@@ -3,11 +3,15 @@
 One JSON object on stdout.  Every row: one untimed warm-up job, then ``--reps`` timed jobs of one batch each, device-synchronised on both
 sides; images/s from the median, the spread (min / max seconds) beside it.  GPU box; run from the repository root:
 
-    python tools/dit_job.py [--input-size 64] [--batches 8,16,32,64] [--reps 5] [--fp8]
+    python tools/dit_job.py [--input-size 64] [--batches 8,16,32,64] [--reps 5] [--fp8] [--guard | --stream16 auto] [--no-baseline]
 
 ``--fp8``: every generate_sharded row is measured twice in the same process -- the bf16 engine, then the engine with fp8 projections (NATINF_DIT_FP8), alternating row by
 row -- and carries ``"fp8": false / true``; each (batch size, mode) also gets a ``forwards`` entry: ms per denoiser forward of 2 x batch samples (HIP events over 20
 forwards) and the per-shape GEMM table of one forward (natinf_gemm_profile_read: tag, launches, ms, TFLOP/s).
+
+``--guard`` (= ``--stream16 auto``): the cost of the stream guard (NATINF_DIT_STREAM_GUARD).  Every generate_sharded row is measured, alternating in this process, on three
+engines per projection mode -- the half stream unguarded (``"stream": "half"``: the default path), the guarded half stream run as ``generate_sharded(stream16="auto")``
+(``"half_guarded"``; the synthetic weights stay in range, so no batch reruns -- ``"reruns"`` says so) and the fp32 stream (``"fp32"``: what a rerun costs).
 """
 import argparse
 import json
@@ -84,7 +88,13 @@ def main():
     ap.add_argument("--reps", type=int, default=5)
     ap.add_argument("--no-decode", action="store_true")
     ap.add_argument("--fp8", action="store_true", help="measure the fp8-projection engine beside the bf16 one, alternating, in this process")
+    ap.add_argument("--guard", action="store_true", help="measure the guarded half stream (stream16='auto') and the fp32 stream beside the unguarded half stream, alternating")
+    ap.add_argument("--stream16", choices=("auto",), default=None, help="'auto': the same as --guard")
+    ap.add_argument("--algs", default="ddim,ddpm")
+    ap.add_argument("--no-baseline", action="store_true", help="skip the natural_inference (slab) baseline rows")
     a = ap.parse_args()
+    a.guard = a.guard or a.stream16 == "auto"
+    algs = tuple(a.algs.split(","))
     S = a.input_size
     flat = flatten_state_dict(synthetic_dit_state_dict(input_size=S), XL2["depth"], XL2["hidden"], S)
     vae = None if a.no_decode else VAEDecoder(synthetic_vae_flat(4), max_batch=8, latent_ch=4, latent_res=S)
@@ -92,40 +102,45 @@ def main():
 
     forwards = []
 
-    def row(path, alg, bs, decode, ws, sec, fp8=False):
+    def row(path, alg, bs, decode, ws, sec, fp8=False, stream=None, reruns=None):
         med, lo, hi = sec
         rows.append({"path": path, "alg": alg, "batch_size": bs, "forward_samples": 2 * bs, "decode": decode, "images_per_s": round(bs / med, 2),
                      "median_s": round(med, 4), "min_s": round(lo, 4), "max_s": round(hi, 4), "engine_workspace_bytes": int(ws)})
         if a.fp8:
             rows[-1]["fp8"] = fp8
+        if stream is not None:
+            rows[-1].update(stream=stream, reruns=reruns)
 
     # the baseline: natural_inference as it stands (eight demo labels, torch.randn_like copied into the noise slab, natinf_step_f32prod)
     eng = DiTEngine(flat, max_batch=16, input_size=S, **XL2)
     V.denoiser_factory = lambda: eng
-    for alg in ("ddim", "ddpm"):
+    for alg in (() if a.no_baseline else algs):
         for decode in ((False,) if vae is None else (False, True)):
             V.decoder_factory = (lambda: (lambda lat, path: V.to_pixels_u8(vae(lat)).cpu())) if decode else None
             row("natural_inference (slab, torch.randn_like)", alg, 8, decode, eng.workspace_bytes, timed(lambda: V.natural_inference(alg, a.steps), a.reps))
     V.denoiser_factory = V.decoder_factory = None
     del eng
     for bs in [int(v) for v in a.batches.split(",")]:
-        engines = [(False, DiTEngine(flat, max_batch=2 * bs, input_size=S, **XL2))]
-        if a.fp8:
-            engines.append((True, DiTEngine(flat, max_batch=2 * bs, input_size=S, fp8=True, **XL2)))
-        for alg in ("ddim", "ddpm"):
+        # (fp8, stream, engine): without --guard one engine per projection mode, the library's default stream
+        streams = (("half", dict(stream16=True)), ("half_guarded", dict(stream16=True, guard=True)), ("fp32", dict(stream16=False))) if a.guard else ((None, {}),)
+        engines = [(fp8, name, DiTEngine(flat, max_batch=2 * bs, input_size=S, fp8=fp8, **kw, **XL2)) for fp8 in ((False, True) if a.fp8 else (False,)) for name, kw in streams]
+        wide = {fp8: eng for fp8, name, eng in engines if name == "fp32"}
+        for alg in algs:
             for decode in ((False,) if vae is None else (False, True)):
-                for fp8, eng in engines:                                      # the two modes alternate, row by row
+                for fp8, stream, eng in engines:                              # the modes alternate, row by row
+                    rep = {}
+                    auto = dict(stream16="auto", fallback=lambda: wide[fp8], report=rep) if stream == "half_guarded" else {}
                     job = lambda: V.generate_sharded(bs, None, alg_name=alg, num_step=a.steps, batch_size=bs, seed=0, decode=decode, decode_batch=8,
-                                                     model=eng, decoder=vae)
-                    row("generate_sharded", alg, bs, decode, eng.workspace_bytes, timed(job, a.reps), fp8)
-        if a.fp8:
-            for fp8, eng in engines:
-                forwards.append(dict(fp8=fp8, batch_size=bs, **forward_profile(eng, 2 * bs, S)))
+                                                     model=eng, decoder=vae, **auto)
+                    row("generate_sharded", alg, bs, decode, eng.workspace_bytes, timed(job, a.reps), fp8, stream, len(rep["rerun_batches"]) if auto else None)
+        if a.fp8 or a.guard:
+            for fp8, stream, eng in engines:
+                forwards.append(dict(fp8=fp8, batch_size=bs, **({"stream": stream} if stream else {}), **forward_profile(eng, 2 * bs, S)))
         del engines, eng
         torch.cuda.empty_cache()
     res = {"tool": "dit_job", "model": "DiT-XL/2 synthetic", "input_size": S, "steps": a.steps, "cfg_scale": 4.0, "reps": a.reps,
            "device": torch.cuda.get_device_name(0), "rows": rows}
-    if a.fp8:
+    if a.fp8 or a.guard:
         res["forwards"] = forwards
     print(json.dumps(res))
 
