@@ -131,6 +131,33 @@ int natinf_debug_conv_gn_up(int flags);
 int natinf_debug_conv_gn(int res, int B, int N, int cin, int c1, const void* x, const float* scale, const float* shift, const void* w_packed, void* w_frag,
                          const void* a1, const float* bias_n, const void* resid, float out_scale, void* out, float* gn_part, int iters,
                          natinf_stream_t stream);
+/* One 16x16 attention block of NCSN++ (AttnBlockpp, layerspp.py:75-91; 256 tokens, one head of 256 channels) on caller-supplied operands, through the pack kernels and the
+ * launch code the engine itself uses (csrc/attn_qkv.h, attn256.h, attn_blk256.h):
+ *   h = x * scale + shift;  q, k, v = h W_i + b_i (i = 0, 1, 2);  P = softmax(q k^T / 16);  out = (x + (P v) W_3 + b_3) * out_scale.
+ * plan: 0 = k_qkv256 + k_attn256<true> (one 8-wave block per sample, or two 4-wave blocks under natinf_set_attn_waves8(0), read at this call as the engine reads it at a forward),
+ *       1 = k_attn_blk256, 2 = k_attn_blk256_v2 (natinf_set_attn_block's numbering).
+ * x: bf16 [B*256][x_ld]; scale, shift: fp32 [B][256], the plain GroupNorm tables; w: fp32 [4][256][256], NIN_0..3.W as [in][out]; bias: fp32 [4][256];
+ * out: bf16 [B*256][o_ld] (columns 256.. of x are not read, of out not written); x_ld, o_ld >= 256 and multiples of 8; every pointer 16-byte aligned.
+ * packed: a caller-owned buffer of NATINF_ATTN_BLOCK_PACKED_BYTES that receives the packed weights of the plan (byte offsets below): plans 0 / 1 write the q | k | v tiles
+ * (k_pack_qkv_w) and the W_3 tiles (k_pack_attn_w3); plan 2 writes the fp32 fold of k_attn_fold_w -- Wqk = W_0 W_1^T [in][out], cq = b_0 W_1^T [256], Wvo = W_2 W_3
+ * [in][out], bo = b_2 W_3 + b_3 [256], left there for the caller to read -- and its two bf16 packs.
+ * scratch: plans 0 / 1: B * NATINF_ATTN_BLOCK_SCRATCH_BYTES_PER_SAMPLE bytes ([q | k] bf16 [B*256][512], then V^T bf16 [B][256][256]); NULL allowed for plan 2.
+ * gn_part: NULL, or fp32 [B][64][2]: (sum, sum of squares) of the block's fp32 output values per sample and 4-channel quad -- except plan 0 under
+ * natinf_set_attn_waves8(0), which writes one row per 128-token half: [B][2][64][2].
+ * NATINF_EINVAL, nothing launched: a NULL x / scale / shift / w / bias / packed / out, plan outside 0..2, B < 1, x_ld or o_ld below 256 or not a multiple of 8, a NULL scratch
+ * for plans 0 / 1.  Nothing is allocated and nothing waits for the device: the packs and the block are enqueued on `stream` in order. */
+#define NATINF_ATTN_BLOCK_OFF_WQKV 0             /* bf16 [48 n-tiles][8][64][8]: k_pack_qkv_w */
+#define NATINF_ATTN_BLOCK_OFF_W3 393216          /* bf16 [16 n-tiles][8][64][8]: k_pack_attn_w3 */
+#define NATINF_ATTN_BLOCK_OFF_FOLD_WQK 524288    /* fp32 [256 in][256 out] */
+#define NATINF_ATTN_BLOCK_OFF_FOLD_WVO 786432    /* fp32 [256 in][256 out] */
+#define NATINF_ATTN_BLOCK_OFF_FOLD_CQ 1048576    /* fp32 [256] */
+#define NATINF_ATTN_BLOCK_OFF_FOLD_BO 1049600    /* fp32 [256] */
+#define NATINF_ATTN_BLOCK_OFF_WQK_PACKED 1050624 /* bf16: k_pack_qkv_w's q tiles of Wqk */
+#define NATINF_ATTN_BLOCK_OFF_WVO_PACKED 1181696 /* bf16: k_pack_attn_w3 of Wvo */
+#define NATINF_ATTN_BLOCK_PACKED_BYTES 1312768
+#define NATINF_ATTN_BLOCK_SCRATCH_BYTES_PER_SAMPLE 393216
+int natinf_debug_attn_block(int plan, int B, const void* x, int x_ld, const float* scale, const float* shift, const float* w, const float* bias,
+                            void* packed, void* scratch, void* out, int o_ld, float out_scale, float* gn_part, natinf_stream_t stream);
 int natinf_set_gemm_variant(int variant);
 /* A/B switch for tuning: 1 = every k_gemm_* launch takes the fp32-slab epilogue, 0 (default) = the packed bf16 epilogue where it applies.
    The fused GroupNorm + 3x3 convolution kernels (k_conv_gn2) have packed epilogues only and ignore the switch. */

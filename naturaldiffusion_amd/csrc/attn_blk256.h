@@ -363,8 +363,10 @@ __global__ __launch_bounds__(512, 1) void k_attn_blk256(const bf16* __restrict__
 // k_attn_blk256_v2 (round 6): the same block with q k^T and P V taken against h ITSELF -- no k, no V^T, nothing written or re-read between the phases.
 //   q k^T = (h Wq + bq)(h' Wk + bk)^T = (h Wqk + cq) h'^T + [terms that depend on the query only: softmax over the keys cancels them],  Wqk = Wq Wk^T, cq = bq Wk^T
 //   (P v) W3 + b3 = P (h' Wv + bv) W3 + b3 = (P h') Wvo + bo   (the rows of P sum to one),                                            Wvo = Wv W3,  bo = bv W3 + b3
-// (AttnBlockpp, layerspp.py:75-91; exact in real arithmetic: 2e-7 in fp32, and with the engine's bf16 rounding points the block's error against fp32 is the same --
-// 4.30e-3 against 4.37e-3 of its output's range -- CPU study in DESIGN.md section 4 "Round 6").  Two projections instead of four (134 MFLOP per sample instead of 201),
+// (AttnBlockpp, layerspp.py:75-91; exact in real arithmetic: 2e-7 in fp32.  With the bf16 rounding points the block's error against fp64, run alone on the MI355X, is per case
+// (this kernel / k_attn_blk256, of the output's range): synthetic weights 2.4e-3 / 3.1e-3, logit rows of standard deviation 12: 2.6e-2 / 3.5e-2, of 20: 3.6e-2 / 4.1e-2, biases at
+// 10 x the weight scale 3.0e-3 / 3.0e-3, eight rows of each matrix x 15: 3.2e-2 / 4.2e-2, outlier tokens and a 50 x channel 7.5e-3 / 9.0e-3, all logits equal 2.4e-3 / 2.7e-3 --
+// tests/test_gpu_attn_block_alone.py, profiles/attn_block_alone/errors.txt, DESIGN.md section 4 "Round 6").  Two projections instead of four (134 MFLOP per sample instead of 201),
 // and the sample's normalised tokens h [256][256] bf16 = 128 KB are the ONLY operand of both attention products: they live in LDS, written once by the waves that
 // hold them in registers.  HBM sees x in and the output out: 134 MB per launch at B = 512 against 495.
 //   * A' = h Wqk + cq stays in registers exactly as k_attn_blk256's q does (k_pack_qkv_w's q tiles of the folded matrix: eight 16-KB tiles, three ahead through four
@@ -376,7 +378,8 @@ __global__ __launch_bounds__(512, 1) void k_attn_blk256(const bf16* __restrict__
 //     every tile, both read kinds and the guide's lane groups);
 //   * the output projection (k_pack_attn_w3 of the folded Wvo: four 32-KB tiles): tile 0 is requested before P V into the 32 KB behind the image, tiles 1-3 into
 //     the image's bytes once P V is done; residual, rescale, store and the GroupNorm partial sums as before (same order: dpp_row_sum_tau).
-// Not the bytes of k_attn_blk256 (another arithmetic); the per-module taps and the isolated fp32 comparison bound it (tests/test_gpu_attn_block.py).
+// Not the bytes of k_attn_blk256 (another arithmetic); the per-module taps, the isolated fp32 comparison (tests/test_gpu_attn_block.py) and the block alone against fp64 and
+// its own rounding model (tests/test_gpu_attn_block_alone.py) bound it.
 constexpr int ABLK2_IMG = 131072, ABLK2_LDS_BYTES = ABLK2_IMG + A256_STAGE;
 static_assert(4 * QKV_STAGE <= ABLK2_IMG && ABLK2_LDS_BYTES <= 163840, "the q phase's four stages inside the image's bytes; image + one W3 tile in 160 KB");
 

@@ -97,9 +97,61 @@ bool configure_ncsnpp_kernels() {
 }
 
 // ------------------------------------------------------------------------------------------------
+// the 16x16 attention block (256 tokens, 256 channels): its weight packs and its launches -- ONE copy, called by the plan builder (Builder::emit_attn)
+// and by natinf_debug_attn_block
+// ------------------------------------------------------------------------------------------------
+struct AttnBlk256 {
+    int plan = 0;                    // 2: k_attn_blk256_v2; 1: k_attn_blk256; 0: k_qkv256 (launch_attn_qkv256, or the GEMMs that write the same tensors) + k_attn256<true>
+    int B = 0;
+    const bf16* x = nullptr; int x_ld = 0;                             // raw block input (normalised for the projections; the residual of the output)
+    const float* sc = nullptr; const float* sh = nullptr;              // GroupNorm (scale | shift) tables [B][256]
+    const bf16* wqkvf = nullptr; const float* bqk = nullptr; const float* bv = nullptr; bf16* qk = nullptr; bf16* vT = nullptr;      // plans 0 / 1 (pack_attn_qkv_w; [q | k] and V^T scratch)
+    const bf16* w3f = nullptr; const float* b3 = nullptr;              // plans 0 / 1 (pack_attn_w3)
+    const bf16* wqf2 = nullptr; const float* cq2 = nullptr; const bf16* wvof2 = nullptr; const float* bo2 = nullptr;                  // plan 2 (pack_attn_fold)
+    bf16* out = nullptr; int o_ld = 0; float out_scale = 1.0f;
+    float2* gn_part = nullptr; int gn_quads = 0;
+};
+void pack_attn_qkv_w(const float* w0, const float* w1, const float* w2, bf16* wqkvf, hipStream_t s) {
+    hipLaunchKernelGGL(k_pack_qkv_w, dim3(3 * 256), dim3(256), 0, s, w0, w1, w2, wqkvf);
+}
+void pack_attn_w3(const float* w3, bf16* w3f, hipStream_t s) { hipLaunchKernelGGL(k_pack_attn_w3, dim3(256), dim3(256), 0, s, w3, w3f); }
+// the folded matrices of k_attn_blk256_v2: Wqk = Wq Wk^T, cq = bq Wk^T, Wvo = Wv W3, bo = bv W3 + b3 in fp32 (fq / fv: [256][256] temporaries), packed like the q tiles / W3 of the four-projection plans
+void pack_attn_fold(const float* w0, const float* w1, const float* w2, const float* w3, const float* b0, const float* b2, const float* b3,
+                    float* fq, float* cq, float* fv, float* bo, bf16* wqf2, bf16* wvof2, hipStream_t s) {
+    hipLaunchKernelGGL(k_attn_fold_w, dim3(257), dim3(256), 0, s, w0, w1, w2, w3, b0, b2, b3, fq, cq, fv, bo);
+    hipLaunchKernelGGL(k_pack_qkv_w, dim3(256), dim3(256), 0, s, (const float*)fq, (const float*)fq, (const float*)fq, wqf2, 1);
+    hipLaunchKernelGGL(k_pack_attn_w3, dim3(256), dim3(256), 0, s, (const float*)fv, wvof2);
+}
+void launch_attn_qkv256(const AttnBlk256& a, hipStream_t s) {          // plan 0's first launch: x -> [q | k], V^T
+    hipLaunchKernelGGL(k_qkv256, dim3((unsigned)a.B), dim3(512), QKV_LDS_BYTES, s, a.x, a.x_ld, a.sc, a.sh, a.wqkvf, a.bqk, a.bv, a.qk, a.vT);
+}
+// returns the rows one GroupNorm partial row of the launch covers (Ctx::part_bm): a sample, or its half (k_attn256<true> as two 4-wave blocks)
+int launch_attn_blk256(const AttnBlk256& a, hipStream_t s) {
+    constexpr int C = 256;
+    if (a.plan == 2) {
+        hipLaunchKernelGGL(k_attn_blk256_v2, dim3((unsigned)a.B), dim3(512), ABLK2_LDS_BYTES, s, a.x, a.x_ld, a.sc, a.sh,
+                           a.wqf2, a.cq2, 1.0f / sqrtf((float)C), a.wvof2, a.bo2, a.out, a.o_ld, a.out_scale, a.gn_part, a.gn_quads);
+        return 256;
+    }
+    if (a.plan == 1) {
+        hipLaunchKernelGGL(k_attn_blk256, dim3((unsigned)a.B), dim3(512), ABLK_LDS_BYTES, s, a.x, a.x_ld, a.sc, a.sh,
+                           a.wqkvf, a.bqk, a.bv, a.qk, a.vT, 1.0f / sqrtf((float)C), a.w3f, a.b3, a.out, a.o_ld, a.out_scale, a.gn_part, a.gn_quads);
+        return 256;
+    }
+    if (g_attn_w8) {
+        hipLaunchKernelGGL((k_attn256<true, 8>), dim3((unsigned)a.B), dim3(512), A256_LDS_BYTES, s, (const bf16*)a.qk, 2 * C, C, (const bf16*)a.vT, a.out, a.o_ld,
+                           1.0f / sqrtf((float)C), a.w3f, a.b3, a.x, a.x_ld, a.out_scale, a.gn_part, a.gn_quads);
+        return 256;
+    }
+    hipLaunchKernelGGL(k_attn256<true>, dim3((unsigned)(2 * a.B)), dim3(256), A256_LDS_BYTES, s, (const bf16*)a.qk, 2 * C, C, (const bf16*)a.vT, a.out, a.o_ld,
+                       1.0f / sqrtf((float)C), a.w3f, a.b3, a.x, a.x_ld, a.out_scale, a.gn_part, a.gn_quads);
+    return 128;
+}
+
+// ------------------------------------------------------------------------------------------------
 // plan builder
 // ------------------------------------------------------------------------------------------------
-struct Builder : PlanBuilder {          // (wtop: the packed-weight bump pointer in bytes; poff: the running parameter offset in floats)
+struct Builder : PlanBuilder {        // (wtop: the packed-weight bump pointer in bytes; poff: the running parameter offset in floats)
     natinf_ncsnpp& E;
     // time-embedding projection bank
     int dense_total = 0; int64_t dense_w = 0, dense_b = 0, dense_out = 0;
@@ -316,15 +368,15 @@ struct Builder : PlanBuilder {          // (wtop: the packed-weight bump pointer
         if (fuse_qkv) {
             wqkvf = wres((int64_t)3 * C * C * 2);
             const int64_t s0 = pw[0], s1 = pw[1], s2 = pw[2];
-            E.packs.push_back([=](const PackCtx& p) {
-                hipLaunchKernelGGL(k_pack_qkv_w, dim3(3 * 256), dim3(256), 0, p.stream, p.params + s0, p.params + s1, p.params + s2, reinterpret_cast<bf16*>(p.packed + wqkvf));
-            });
+            E.packs.push_back([=](const PackCtx& p) { pack_attn_qkv_w(p.params + s0, p.params + s1, p.params + s2, reinterpret_cast<bf16*>(p.packed + wqkvf), p.stream); });
             const int64_t sc_ = sc, sh_ = sh;
             if (!blk)
             op(CLS_GEMM, [=](const Ctx& c) {
                 if (g_record) return;
-                hipLaunchKernelGGL(k_qkv256, dim3((unsigned)c.B), dim3(512), QKV_LDS_BYTES, c.stream, (const bf16*)c.act(x), x.ld, c.at<float>(sc_), c.at<float>(sh_),
-                                   c.w<bf16>(wqkvf), c.w<float>(bqk), c.w<float>(bv), c.at<bf16>(qk), c.at<bf16>(vT));
+                AttnBlk256 a;
+                a.B = c.B; a.x = c.act(x); a.x_ld = x.ld; a.sc = c.at<float>(sc_); a.sh = c.at<float>(sh_);
+                a.wqkvf = c.w<bf16>(wqkvf); a.bqk = c.w<float>(bqk); a.bv = c.w<float>(bv); a.qk = c.at<bf16>(qk); a.vT = c.at<bf16>(vT);
+                launch_attn_qkv256(a, c.stream);
             });
         }
         if (!fuse_qkv)
@@ -350,9 +402,7 @@ struct Builder : PlanBuilder {          // (wtop: the packed-weight bump pointer
         if (proj) {
             w3f = wres((int64_t)C * C * 2);
             const int64_t src = pw[3];
-            E.packs.push_back([=](const PackCtx& p) {
-                hipLaunchKernelGGL(k_pack_attn_w3, dim3(256), dim3(256), 0, p.stream, p.params + src, reinterpret_cast<bf16*>(p.packed + w3f));
-            });
+            E.packs.push_back([=](const PackCtx& p) { pack_attn_w3(p.params + src, reinterpret_cast<bf16*>(p.packed + w3f), p.stream); });
         }
         // k_attn_blk256_v2 (natinf_set_attn_block(2)): q k^T and P V against h itself -- the folded matrices Wqk = Wq Wk^T, Wvo = Wv W3 and their bias vectors, computed in
         // fp32 at load time (k_attn_fold_w) and packed like the q tiles / W3 of the four-projection plans
@@ -364,11 +414,9 @@ struct Builder : PlanBuilder {          // (wtop: the packed-weight bump pointer
             wqf2 = wres((int64_t)C * C * 2); wvof2 = wres((int64_t)C * C * 2);
             const int64_t w0_ = pw[0], w1_ = pw[1], w2_ = pw[2], w3_ = pw[3], b0_ = pb[0], b2_ = pb[2], b3_ = pb[3], cq_ = cq2, bo_ = bo2, wq_ = wqf2, wv_ = wvof2;
             E.packs.push_back([=](const PackCtx& p) {
-                float* fqp = reinterpret_cast<float*>(p.packed + fq); float* fvp = reinterpret_cast<float*>(p.packed + fv);
-                hipLaunchKernelGGL(k_attn_fold_w, dim3(257), dim3(256), 0, p.stream, p.params + w0_, p.params + w1_, p.params + w2_, p.params + w3_, p.params + b0_, p.params + b2_,
-                                   p.params + b3_, fqp, reinterpret_cast<float*>(p.packed + cq_), fvp, reinterpret_cast<float*>(p.packed + bo_));
-                hipLaunchKernelGGL(k_pack_qkv_w, dim3(256), dim3(256), 0, p.stream, (const float*)fqp, (const float*)fqp, (const float*)fqp, reinterpret_cast<bf16*>(p.packed + wq_), 1);
-                hipLaunchKernelGGL(k_pack_attn_w3, dim3(256), dim3(256), 0, p.stream, (const float*)fvp, reinterpret_cast<bf16*>(p.packed + wv_));
+                pack_attn_fold(p.params + w0_, p.params + w1_, p.params + w2_, p.params + w3_, p.params + b0_, p.params + b2_, p.params + b3_,
+                               reinterpret_cast<float*>(p.packed + fq), reinterpret_cast<float*>(p.packed + cq_), reinterpret_cast<float*>(p.packed + fv),
+                               reinterpret_cast<float*>(p.packed + bo_), reinterpret_cast<bf16*>(p.packed + wq_), reinterpret_cast<bf16*>(p.packed + wv_), p.stream);
             });
         }
         const Part po_attn = proj ? register_output(out) : Part();
@@ -378,28 +426,16 @@ struct Builder : PlanBuilder {          // (wtop: the packed-weight bump pointer
             // 16x16 attention: scores, softmax and P V of a sample in one block (attn_fused.h, two-phase: V^T follows K through LDS)
             op(CLS_GEMM, [=](const Ctx& c) {
                 if (g_record) return;                    // natinf_ncsnpp_describe_gemms: GEMM launches only, nothing touches memory
-                if (blk2) {
-                    hipLaunchKernelGGL(k_attn_blk256_v2, dim3((unsigned)c.B), dim3(512), ABLK2_LDS_BYTES, c.stream, (const bf16*)c.act(x), x.ld, c.at<float>(sc_q), c.at<float>(sh_q),
-                                       c.w<bf16>(wqf2), c.w<float>(cq2), 1.0f / sqrtf((float)C), c.w<bf16>(wvof2), c.w<float>(bo2),
-                                       c.act(out), out.ld, rs_attn, po_attn.valid ? c.at<float2>(po_attn.off) : (float2*)nullptr, po_attn.quads);
-                    if (po_attn.valid) c.part_bm[po_attn.id] = 256;
-                } else if (blk) {
-                    hipLaunchKernelGGL(k_attn_blk256, dim3((unsigned)c.B), dim3(512), ABLK_LDS_BYTES, c.stream, (const bf16*)c.act(x), x.ld, c.at<float>(sc_q), c.at<float>(sh_q),
-                                       c.w<bf16>(wqkvf), c.w<float>(bqk), c.w<float>(bv), c.at<bf16>(qk), c.at<bf16>(vT), 1.0f / sqrtf((float)C), c.w<bf16>(w3f), c.w<float>(b3),
-                                       c.act(out), out.ld, rs_attn, po_attn.valid ? c.at<float2>(po_attn.off) : (float2*)nullptr, po_attn.quads);
-                    if (po_attn.valid) c.part_bm[po_attn.id] = 256;
-                } else if (proj) {
-                    if (g_attn_w8) {
-                        hipLaunchKernelGGL((k_attn256<true, 8>), dim3((unsigned)c.B), dim3(512), A256_LDS_BYTES, c.stream, c.at<bf16>(qk), 2 * C, C, c.at<bf16>(vT), c.act(out), out.ld,
-                                           1.0f / sqrtf((float)C), c.w<bf16>(w3f), c.w<float>(b3), (const bf16*)c.act(x), x.ld, rs_attn,
-                                           po_attn.valid ? c.at<float2>(po_attn.off) : (float2*)nullptr, po_attn.quads);
-                        if (po_attn.valid) c.part_bm[po_attn.id] = 256;
-                    } else {
-                    hipLaunchKernelGGL(k_attn256<true>, dim3((unsigned)(2 * c.B)), dim3(256), A256_LDS_BYTES, c.stream, c.at<bf16>(qk), 2 * C, C, c.at<bf16>(vT), c.act(out), out.ld,
-                                       1.0f / sqrtf((float)C), c.w<bf16>(w3f), c.w<float>(b3), (const bf16*)c.act(x), x.ld, rs_attn,
-                                       po_attn.valid ? c.at<float2>(po_attn.off) : (float2*)nullptr, po_attn.quads);
-                    if (po_attn.valid) c.part_bm[po_attn.id] = 128;
-                    }
+                if (proj) {                              // the one-launch plans and k_attn256<true>: launch_attn_blk256, shared with natinf_debug_attn_block
+                    AttnBlk256 a;
+                    a.plan = blk2 ? 2 : (blk ? 1 : 0); a.B = c.B; a.x = c.act(x); a.x_ld = x.ld; a.sc = c.at<float>(sc_q); a.sh = c.at<float>(sh_q);
+                    if (wqkvf >= 0) a.wqkvf = c.w<bf16>(wqkvf);
+                    a.bqk = c.w<float>(bqk); a.bv = c.w<float>(bv); a.qk = c.at<bf16>(qk); a.vT = c.at<bf16>(vT); a.w3f = c.w<bf16>(w3f); a.b3 = c.w<float>(b3);
+                    if (blk2) { a.wqf2 = c.w<bf16>(wqf2); a.cq2 = c.w<float>(cq2); a.wvof2 = c.w<bf16>(wvof2); a.bo2 = c.w<float>(bo2); }
+                    a.out = c.act(out); a.o_ld = out.ld; a.out_scale = rs_attn;
+                    if (po_attn.valid) { a.gn_part = c.at<float2>(po_attn.off); a.gn_quads = po_attn.quads; }
+                    const int rows = launch_attn_blk256(a, c.stream);
+                    if (po_attn.valid) c.part_bm[po_attn.id] = rows;
                 }
                 else
                     hipLaunchKernelGGL(k_attn256<false>, dim3((unsigned)(2 * c.B)), dim3(256), A256_LDS_BYTES, c.stream, c.at<bf16>(qk), 2 * C, C, c.at<bf16>(vT), c.act(O), C,
@@ -1103,6 +1139,38 @@ int natinf_debug_conv_gn(int res, int B, int N, int cin, int c1, const void* x, 
         hipLaunchKernelGGL(k_pack_frag, dim3(grid1d(n, 256, 1 << 30)), dim3(256), 0, (hipStream_t)stream, (const bf16*)w_packed, (bf16*)w_frag, N, g.b_ld, cin, c1);
     }
     for (int i = 0; i < iters; ++i) launch_gemm(g, (hipStream_t)stream);
+    return hipGetLastError() == hipSuccess ? NATINF_OK : NATINF_ELAUNCH;
+}
+
+// One 16x16 attention block on caller-supplied operands (tests/test_gpu_attn_block_alone.py): the engine's own packs and launches (pack_attn_* / launch_attn_*
+// above), nothing else.  bias [4][256]: rows 0, 1 ARE the engine's bqk table (q then k), rows 2, 3 its bv and b3.
+int natinf_debug_attn_block(int plan, int B, const void* x, int x_ld, const float* scale, const float* shift, const float* w, const float* bias,
+                            void* packed, void* scratch, void* out, int o_ld, float out_scale, float* gn_part, natinf_stream_t stream) {
+    if (plan < 0 || plan > 2 || B < 1 || !x || !scale || !shift || !w || !bias || !packed || !out || x_ld < 256 || x_ld % 8 || o_ld < 256 || o_ld % 8 ||
+        (plan != 2 && !scratch)) return NATINF_EINVAL;
+    static bool configured = false;
+    if (!configured) { if (!configure_gemm_kernels()) return NATINF_ENODEV; configured = true; }
+    constexpr int64_t WW = 256 * 256;
+    unsigned char* pk = reinterpret_cast<unsigned char*>(packed);
+    hipStream_t s = (hipStream_t)stream;
+    AttnBlk256 a;
+    a.plan = plan; a.B = B; a.x = (const bf16*)x; a.x_ld = x_ld; a.sc = scale; a.sh = shift;
+    a.out = (bf16*)out; a.o_ld = o_ld; a.out_scale = out_scale; a.gn_part = reinterpret_cast<float2*>(gn_part); a.gn_quads = 64;
+    if (plan == 2) {
+        float* fq = reinterpret_cast<float*>(pk + NATINF_ATTN_BLOCK_OFF_FOLD_WQK); float* fv = reinterpret_cast<float*>(pk + NATINF_ATTN_BLOCK_OFF_FOLD_WVO);
+        float* cq = reinterpret_cast<float*>(pk + NATINF_ATTN_BLOCK_OFF_FOLD_CQ); float* bo = reinterpret_cast<float*>(pk + NATINF_ATTN_BLOCK_OFF_FOLD_BO);
+        bf16* wqf2 = reinterpret_cast<bf16*>(pk + NATINF_ATTN_BLOCK_OFF_WQK_PACKED); bf16* wvof2 = reinterpret_cast<bf16*>(pk + NATINF_ATTN_BLOCK_OFF_WVO_PACKED);
+        pack_attn_fold(w, w + WW, w + 2 * WW, w + 3 * WW, bias, bias + 512, bias + 768, fq, cq, fv, bo, wqf2, wvof2, s);
+        a.wqf2 = wqf2; a.cq2 = cq; a.wvof2 = wvof2; a.bo2 = bo;
+    } else {
+        bf16* wqkvf = reinterpret_cast<bf16*>(pk + NATINF_ATTN_BLOCK_OFF_WQKV); bf16* w3f = reinterpret_cast<bf16*>(pk + NATINF_ATTN_BLOCK_OFF_W3);
+        pack_attn_qkv_w(w, w + WW, w + 2 * WW, wqkvf, s);
+        pack_attn_w3(w + 3 * WW, w3f, s);
+        a.wqkvf = wqkvf; a.bqk = bias; a.bv = bias + 512; a.w3f = w3f; a.b3 = bias + 768;
+        a.qk = reinterpret_cast<bf16*>(scratch); a.vT = a.qk + (int64_t)B * 256 * 512;
+        if (plan == 0) launch_attn_qkv256(a, s);
+    }
+    launch_attn_blk256(a, s);
     return hipGetLastError() == hipSuccess ? NATINF_OK : NATINF_ELAUNCH;
 }
 

@@ -199,6 +199,25 @@ def test_attention_abi_rejects_padding_beyond_the_masked_tile():
     assert lib.natinf_attention_hd64_bf16(dummy, dummy, 64, 256 * 64, dummy, dummy, 64, 256 * 64, 1, 1, 256, 300, 0.125, None) == -1
 
 
+def test_attention_block_hook_rejects_bad_arguments():
+    """natinf_debug_attn_block (include/natinf_ncsnpp.h): every argument error is NATINF_EINVAL before anything is configured or launched (there is no GPU here)."""
+    from naturaldiffusion_amd._lib import lib
+    d = 4096                                                # a non-NULL dummy: never dereferenced by the argument check
+    call = lambda **kw: lib.natinf_debug_attn_block(*[{**dict(plan=2, B=1, x=d, x_ld=256, scale=d, shift=d, w=d, bias=d, packed=d, scratch=d, out=d, o_ld=256,
+                                                                out_scale=1.0, gn_part=None, stream=None), **kw}[k]
+                                                      for k in ("plan", "B", "x", "x_ld", "scale", "shift", "w", "bias", "packed", "scratch", "out", "o_ld", "out_scale", "gn_part", "stream")])
+    for plan in (-1, 3):
+        assert call(plan=plan) == -1
+    for B in (0, -2):
+        assert call(B=B) == -1
+    for ld in (0, 248, 255, 260, 388):                      # below 256, or not a multiple of 8
+        assert call(x_ld=ld) == -1 and call(o_ld=ld) == -1
+    for name in ("x", "scale", "shift", "w", "bias", "packed", "out"):
+        for plan in (0, 1, 2):
+            assert call(plan=plan, **{name: None}) == -1, name
+    assert call(plan=0, scratch=None) == -1 and call(plan=1, scratch=None) == -1      # (plan 2 needs no scratch)
+
+
 def test_validation_grid_is_one_row_of_eight(tmp_path):
     """reference ValidateNaturalInference.py:236: save_image(samples, path, nrow=8, ...): 8 images -> 1 x 8."""
     import torch
