@@ -146,6 +146,10 @@ int natinf_to_pixel_u8(const float* x, uint8_t* out, int B, int C, int H, int W,
  * sample n sits at n*eps_sample_stride + (e % sample_elems).  hist_eps [n_slots+1][E] already
  * holds every noise the row refers to (slot 0 = initial noise, slot j = the draw after step j-1).
  * E % 4 == 0, sample_elems % 4 == 0.
+ *
+ * Three entries share this arithmetic: natinf_step_f32prod (noises read from the hist_eps slab), natinf_step_f32prod_noise
+ * (noises drawn in the kernel; one cfg and uncond row i for image i) and natinf_step_f32prod_noise_guided (the same with
+ * a scale and an unconditional row PER IMAGE: guidance intervals and mixed-scale batches).
  * ------------------------------------------------------------------------------------------ */
 int natinf_step_f32prod(const float* z, const float* cond, const float* uncond, float cfg,
                         int64_t sample_elems, int64_t eps_sample_stride,
@@ -181,6 +185,39 @@ int natinf_step_f32prod_noise(const float* z, const float* cond, const float* un
                               int k, float c1_f32, float c2_f32,
                               uint64_t seed, const int64_t* image_index, int64_t first_index, int64_t index_stride,
                               int64_t E, natinf_stream_t stream);
+
+/* natinf_step_f32prod_noise with per-image guidance (a guidance interval, a scale sweep, guided and unguided images in
+ * one batch): every image carries its own CFG scale, and the unconditional rows are compacted to the images that are
+ * guided.  With n_images = E / sample_elems, the model's eps of image i is
+ *
+ *   uncond_slot[i] < 0 : eps = cond[i]
+ *   otherwise          : u = uncond[uncond_slot[i]] ; d = cond[i] - u ; m = cfg_image[i]*d ; eps = u + m
+ *
+ * (fp32, the three roundings of the launch-wide form in the same order); x0_k, a, b and z_next are those of
+ * natinf_step_f32prod_noise.  cfg_image: device [n_images] fp32.  uncond_slot: device [n_images] int32, each -1 or a row
+ * 0..n_uncond-1 of `uncond`; rows may repeat or be left out.  `uncond` holds n_uncond samples at the per-sample stride of
+ * `cond` (eps_sample_stride), so it may be the tail of a denoiser output [n_images + n_uncond, 2*C, H, W]; it may be
+ * NULL when n_uncond == 0.  cfg_image[i] of an image without a slot is not read.
+ *
+ * Identity rule: with cfg_image[i] == cfg and uncond_slot[i] == i for every i, z_next and hist_x0[k] are byte for byte
+ * those of natinf_step_f32prod_noise(..., uncond, cfg, ...); with every slot -1 they are those of that entry with
+ * uncond == NULL.  A step is a per-image function, so a mixed launch gives each image the bytes of that entry run on the
+ * images that share its scale.
+ *
+ * NATINF_EINVAL, nothing launched: every refusal of natinf_step_f32prod_noise; cfg_image or uncond_slot NULL;
+ * n_uncond < 0; n_uncond > 0 with `uncond` NULL; a slot outside -1..n_uncond-1.  The slots are checked the way idx_b
+ * is: read back on the same private stream before the launch, so uncond_slot must be complete when the call is made (a
+ * table uploaded once per batch) and the call cannot be part of a stream capture.  The VALUES of cfg_image are not
+ * inspected (any fp32, NaN included, goes into the arithmetic above), and it is read by the kernel only, in stream order. */
+int natinf_step_f32prod_noise_guided(const float* z, const float* cond, const float* uncond,
+                                     const float* cfg_image, const int32_t* uncond_slot, int n_uncond,
+                                     int64_t sample_elems, int64_t eps_sample_stride,
+                                     float* hist_x0, const float* noise, float* z_next,
+                                     const int32_t* idx_c, const float* val_c, int n_c, float c_diag,
+                                     const int32_t* idx_b, const float* val_b, int n_b,
+                                     int k, float c1_f32, float c2_f32,
+                                     uint64_t seed, const int64_t* image_index, int64_t first_index, int64_t index_stride,
+                                     int64_t E, natinf_stream_t stream);
 
 /* src/ValidateNaturalInference.py:198-204 on its own. */
 int natinf_weighted_sum_f32prod(const float* hist, float* out,

@@ -387,6 +387,42 @@ def job_batches(sample_count, batch_size, rank=0, world=1, labels=None):
     return [(idx, [table[i % len(table)] for i in idx]) for idx in rank_batches(sample_count, batch_size, rank, world)]
 
 
+def job_scales(cfg_scale, sample_count):
+    """The CFG scale of every image of a job, by GLOBAL index: a number is every image's scale, a sequence must have exactly
+    ``sample_count`` entries (image i carries ``cfg_scale[i]`` whatever the rank, world or batch split, like its label).  Each
+    is rounded to fp32, the value the step kernel multiplies by.  Pure host code."""
+    sample_count = int(sample_count)
+    if isinstance(cfg_scale, (int, float, np.floating, np.integer)):
+        return [float(np.float32(cfg_scale))] * sample_count
+    table = [float(np.float32(v)) for v in cfg_scale]
+    if len(table) != sample_count:
+        raise ValueError(f"{len(table)} CFG scales for {sample_count} images: a scale sequence has one entry per image of the job")
+    return table
+
+
+def guidance_plan(node, n_step, scales, interval=None):
+    """The guidance of one batch -> (guided, slots, scales).  ``scales``: the batch's per-image CFG scales (``job_scales``
+    taken at the batch's global indices); ``interval`` None or ``(t_lo, t_hi)``, integers on the scale of the timestep the
+    job feeds the denoiser at step kk, ``int(node[kk, 0])``, both ends inclusive.
+
+    ``slots[i]``: the row of image i among the batch's unconditional samples, or -1 for an image whose scale is exactly 1.0
+    (unguided: eps = cond, no unconditional sample); the images that are guided take rows 0, 1, ... in batch order.
+    ``guided[kk]``: whether step kk runs the unconditional samples at all -- its timestep lies in the interval and at
+    least one image has a slot.  A step that is not guided is unguided for every image.  ``scales`` comes back as the
+    fp32 values.  Pure host code: at most two forward shapes per batch, n + max(slots) + 1 samples and n."""
+    scales = [float(np.float32(v)) for v in scales]
+    slots, g = [], 0
+    for v in scales:
+        slots.append(-1 if v == 1.0 else g)
+        g += v != 1.0
+    if interval is None:
+        inside = [True] * int(n_step)
+    else:
+        t_lo, t_hi = (int(v) for v in interval)
+        inside = [t_lo <= int(node[kk, 0]) <= t_hi for kk in range(int(n_step))]
+    return [bool(g) and ok for ok in inside], slots, scales
+
+
 def to_pixels_u8(images: torch.Tensor) -> torch.Tensor:
     """[n, 3, H, W] decoder output -> [n, H, W, 3] uint8 where the tensor lives: ``save_image_grid``'s pixel expression."""
     x = images.detach().float()
@@ -396,7 +432,7 @@ def to_pixels_u8(images: torch.Tensor) -> torch.Tensor:
 @torch.no_grad()
 def generate_sharded(sample_count, labels=None, alg_name="ddpm", num_step=24, batch_size=32, rank=0, world=1, seed=0,
                      cfg_scale=4.0, decode=True, decode_batch=8, model=None, decoder=None, image_sink=None, fp8=False, stream16=None,
-                     fallback=None, report=None):
+                     fallback=None, report=None, guidance_interval=None):
     """A class-conditional generation job on the loop of ``natural_inference`` (reference :311-372): ``sample_count`` images,
     image i of class ``job_batches``' label of i, sharded by global index over ``world`` ranks with no collective on the data
     path.  The noise is counter-based: z_0 = eps_0 = ``philox_noise(indices, column=0)`` and the noise a stochastic matrix
@@ -419,12 +455,33 @@ def generate_sharded(sample_count, labels=None, alg_name="ddpm", num_step=24, ba
     this rank's batch list), ``first_clamp`` ({batch, site, site_name, max_abs, clamped} or None).  A ``report`` given is filled in every mode; without ``"auto"`` nothing is monitored, so it
     says ``rerun_batches == []`` and ``first_clamp is None`` whatever the stream did.
 
+    Guidance.  ``cfg_scale`` a float and ``guidance_interval`` None (the defaults' form) is the reference's one hard-wired form and makes exactly the calls
+    it always made: every step a forward of [z; z] and natinf_step_f32prod_noise with the one scale -- byte-identical latents.  Two arguments go beyond it
+    (``guidance_plan``, natinf_step_f32prod_noise_guided):
+
+    * ``cfg_scale`` a sequence of ``sample_count`` floats, by GLOBAL image index: image i carries its own scale whatever the rank, world or batch split.  A scale
+      exactly 1.0 means unguided: no unconditional sample for that image at any step, eps = cond.
+    * ``guidance_interval=(t_lo, t_hi)``: guide only at the steps whose timestep ``int(node[kk, 0])`` (what the denoiser is fed) lies in t_lo..t_hi, both ends
+      inclusive; every other step is unguided for every image (Kynkaanniemi et al., 2024).  With it a scalar ``cfg_scale == 1.0`` means unguided as well.
+
+    With G the guided images of a batch at a step: G empty -> ONE forward of the n conditional samples and the step with ``uncond=None``; otherwise one forward
+    of [z; z[G]] with [labels; 1000 x |G|] and the guided step, slots 0..|G|-1 at the positions in G and -1 elsewhere.  Slot and scale tensors are built once
+    per batch; nothing in the loop waits for the GPU beyond the slot read-back the C entry makes.  Contract: with either new argument image i is still a
+    function of (seed, global index, its label, its scale, the interval) up to the denoiser's own batch dependence -- the same function, not the same bytes as
+    the default form: the engine picks GEMM tile variants by row count, so a forward of n + |G| rows and one of 2n may differ by bf16 rounding flips (DESIGN.md 4d
+    records the same caveat for the VAE).  ``stream16="auto"``, ``fp8``, ``image_sink``, ``report`` and ``fallback`` compose unchanged; the rerun of a clamped
+    batch uses the same plan.
+
     -> (latents [n_local, 4, S, S] fp32 on the device, labels [n_local] int64 CPU, global indices [n_local] int64 CPU,
         images [n_local, 8S, 8S, 3] uint8 CPU or None)"""
     from .CIFAR10NaturalInference import philox_noise
     torch.set_grad_enabled(False)
     batch_size = int(batch_size)
     batches = job_batches(sample_count, batch_size, rank, world, labels)
+    planned = guidance_interval is not None or not isinstance(cfg_scale, (int, float, np.floating, np.integer))   # False: the reference's form, today's calls
+    scale_of = job_scales(cfg_scale, sample_count) if planned else None
+    if guidance_interval is not None and (len(guidance_interval) != 2 or int(guidance_interval[0]) > int(guidance_interval[1])):
+        raise ValueError(f"guidance_interval must be (t_lo, t_hi) with t_lo <= t_hi, got {guidance_interval!r}")
     if stream16 not in (None, True, False, "auto"):
         raise ValueError(f'stream16 must be None, True, False or "auto", got {stream16!r}')
     auto = stream16 == "auto"
@@ -476,6 +533,33 @@ def generate_sharded(sample_count, labels=None, alg_name="ddpm", num_step=24, ba
             input_z = z.view(n, 4, S, S)
         return input_z.clone()
 
+    def planned_trajectory(denoiser, ni, noise, index, steps_t, classlabels, plan):
+        """``trajectory`` under a ``guidance_plan``: a guided step forwards [z; z[G]] (one call when the denoiser takes n + |G| samples) and makes the per-image
+        step, every other step forwards the n conditional samples alone"""
+        guided, pick, labels_g, steps_g, slots_t, scales_t = plan
+        n, g = noise.shape[0], len(pick)
+        joint = getattr(denoiser, "max_batch", 0) >= n + g
+        nulls = labels_g[n:]
+        input_z, flat_noise = noise, noise.reshape(-1)
+        for kk in range(n_step):
+            if not guided[kk]:
+                cond = denoiser.forward(input_z, steps_t[kk], classlabels).contiguous()
+                z = ni.step(kk, input_z.reshape(-1), cond, None, 1.0, per, cond.shape[1] * S * S, noise=flat_noise, index=index)
+            else:
+                zg = input_z if g == n else input_z[pick]
+                if joint:
+                    both = denoiser.forward(torch.cat([input_z, zg]), steps_g[kk], labels_g).contiguous()
+                    cond, uncond = both[:n], both[n:]
+                else:
+                    cond = denoiser.forward(input_z, steps_t[kk], classlabels).contiguous()
+                    uncond = denoiser.forward(zg, steps_g[kk][n:], nulls).contiguous()
+                z = ni.step(kk, input_z.reshape(-1), cond, uncond, scales_t, per, cond.shape[1] * S * S, noise=flat_noise, index=index,
+                            uncond_slot=slots_t, n_uncond=g)
+            input_z = z.view(n, 4, S, S)
+        return input_z.clone()
+
+    if planned:
+        trajectory = planned_trajectory
     for bi, (indices, labs) in enumerate(batches):
         n = len(indices)
         if n not in samplers:
@@ -486,6 +570,14 @@ def generate_sharded(sample_count, labels=None, alg_name="ddpm", num_step=24, ba
         steps_t = [torch.full((n,), int(node[kk, 0]), dtype=torch.int32, device=device) for kk in range(n_step)]
         noise = philox_noise(indices, (4, S, S), seed, device, column=0)
         run = (samplers[n], noise, index, steps_t, classlabels, classnulls)
+        if planned:                                                   # slot and scale tensors once per batch; the rerun of a clamped batch uses the same plan
+            guided, slots, scales = guidance_plan(node, n_step, [scale_of[i] for i in indices], guidance_interval)
+            pick = [i for i, s in enumerate(slots) if s >= 0]
+            g = len(pick)
+            plan = (guided, torch.tensor(pick, dtype=torch.int64, device=device), torch.cat([classlabels, classnulls[:g]]),
+                    [torch.full((n + g,), int(node[kk, 0]), dtype=torch.int32, device=device) for kk in range(n_step)],
+                    torch.tensor(slots, dtype=torch.int32, device=device), torch.tensor(scales, dtype=torch.float32, device=device))
+            run = (samplers[n], noise, index, steps_t, classlabels, plan)
         if auto:
             model.reset_stream_status()
         latents_b = trajectory(model, *run)

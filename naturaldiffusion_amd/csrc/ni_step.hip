@@ -147,20 +147,32 @@ __device__ __forceinline__ float4 ld_eps(const float* p, int64_t img, int64_t q,
     return *reinterpret_cast<const float4*>(p + img * sstride + 4 * q);
 }
 
-// the model's eps: cond, or the CFG fuse uncond + cfg*(cond - uncond) in three fp32 roundings
+// the CFG fuse uncond + cfg*(cond - uncond), four lanes: three fp32 roundings
+__device__ __forceinline__ float4 cfg_fuse(float4 ev, float4 uv, float cfg) {
+    const float e[4] = {ev.x, ev.y, ev.z, ev.w}, u[4] = {uv.x, uv.y, uv.z, uv.w};
+    float r[4];
+#pragma unroll
+    for (int i = 0; i < 4; ++i) { const float d = e[i] - u[i], m = cfg * d; r[i] = u[i] + m; }
+    return make_float4(r[0], r[1], r[2], r[3]);
+}
+
+// the model's eps: cond, or cfg_fuse with the unconditional row at the same index
 __device__ __forceinline__ float4 cfg_eps(const float* cond, const float* uncond, float cfg, int64_t img, int64_t q,
                                           int64_t sstride)
 {
-    float4 ev = ld_eps(cond, img, q, sstride);
-    if (uncond) {
-        const float4 uv = ld_eps(uncond, img, q, sstride);
-        const float e[4] = {ev.x, ev.y, ev.z, ev.w}, u[4] = {uv.x, uv.y, uv.z, uv.w};
-        float r[4];
-#pragma unroll
-        for (int i = 0; i < 4; ++i) { const float d = e[i] - u[i], m = cfg * d; r[i] = u[i] + m; }
-        ev = make_float4(r[0], r[1], r[2], r[3]);
-    }
-    return ev;
+    const float4 ev = ld_eps(cond, img, q, sstride);
+    return uncond ? cfg_fuse(ev, ld_eps(uncond, img, q, sstride), cfg) : ev;
+}
+
+// the model's eps with per-image guidance: image img's unconditional row is uncond[uncond_slot[img]] and its scale
+// cfg_image[img]; a negative slot = an unguided image, eps = cond (neither uncond nor cfg_image[img] is read then).
+// Both per-image values are uniform over the svec consecutive threads of an image: plain vector loads, served by one cache line.
+__device__ __forceinline__ float4 cfg_eps_image(const float* cond, const float* uncond, const float* cfg_image,
+                                                const int32_t* uncond_slot, int64_t img, int64_t q, int64_t sstride)
+{
+    const float4 ev = ld_eps(cond, img, q, sstride);
+    const int32_t slot = uncond_slot[img];
+    return slot >= 0 ? cfg_fuse(ev, ld_eps(uncond, slot, q, sstride), cfg_image[img]) : ev;
 }
 
 // x0 = c1*z - c2*eps: two fp32 products and a subtraction
@@ -490,6 +502,36 @@ __global__ __launch_bounds__(kBlock) void k_step_noise_f32prod(
     }
 }
 
+// ------------------------------------------------------------------------------------------
+// k_step_noise_f32prod with per-image guidance (cfg_eps_image in place of cfg_eps): the unconditional rows are compacted to
+// the images that are guided, each image carries its own scale.  Everything behind eps is the same composition, so with
+// uncond_slot[i] == i and cfg_image[i] == cfg the two kernels give the same bytes.
+// ------------------------------------------------------------------------------------------
+__global__ __launch_bounds__(kBlock) void k_step_guided_f32prod(
+    const float4* __restrict__ z, const float* __restrict__ cond, const float* __restrict__ uncond,
+    const float* __restrict__ cfg_image, const int32_t* __restrict__ uncond_slot, int64_t svec, int64_t sstride,
+    float* __restrict__ hist_x0, const float4* __restrict__ noise, float4* __restrict__ z_next,
+    const int32_t* __restrict__ idx_c, const float* __restrict__ val_c, int n_c, float c_diag,
+    const int32_t* __restrict__ idx_b, const float* __restrict__ val_b, int n_b,
+    const int64_t* __restrict__ index, int64_t first_index, int64_t index_stride,
+    uint32_t k0, uint32_t k1, int k, float c1, float c2, int64_t nvec, int64_t E)
+{
+    // one element quad per thread, no grid-stride loop (k_step_noise_f64: the loop's carried scalars make the hoisted
+    // Philox round keys spill SGPRs)
+    const int64_t v = first_vec();
+    if (v < nvec) {
+        const int64_t img = v / svec, q = v - img * svec;            // an image is one sample: svec quads
+        const float4 x0 = x0_f32prod(c1, z[v], c2, cfg_eps_image(cond, uncond, cfg_image, uncond_slot, img, q, sstride));
+        reinterpret_cast<float4*>(hist_x0 + (int64_t)k * E)[v] = x0;
+
+        double a[4] = {0.0, 0.0, 0.0, 0.0}, b[4] = {0.0, 0.0, 0.0, 0.0};
+        wsum_f32prod(a, hist_x0, idx_c, val_c, n_c, v, E);
+        acc_prod(a, x0, c_diag);
+        noise_row_sum(b, noise, idx_b, val_b, n_b, v, global_index(index, first_index, index_stride, img), q, k0, k1);
+        z_next[v] = combine(a, b);
+    }
+}
+
 // ---- host side: argument checks and launch geometry shared by the ABI entries ----
 inline int launched() { return hipGetLastError() == hipSuccess ? NATINF_OK : NATINF_ELAUNCH; }
 inline bool terms_ok(const void* idx, const void* val, int n) { return n >= 0 && (n == 0 || (idx && val)); }
@@ -506,17 +548,17 @@ inline unsigned quad_blocks(int64_t nvec) {
     return blocks > INT32_MAX ? 0u : (unsigned)blocks;
 }
 
-// The host-side check of a noise row natinf_step_f32prod_noise makes before it launches: every column is in 0..k+1 and
-// column 0 has a `noise` to read.  The row is device memory, so its n_b <= k+2 indices are read back on a private
-// non-blocking stream of the current device: the host waits for that small copy only, never for the caller's stream.
-// 1 = fine, 0 = a bad row, -1 = a HIP call failed.
+// Host-side check of a small device int32 array before a launch (the noise row of natinf_step_f32prod_noise, the slots of
+// natinf_step_f32prod_noise_guided): every one of the n values lies in lo..hi.  They are read back, kRowChunk at a time into
+// one pinned buffer, on a private non-blocking stream of the current device: the host waits for those small copies only,
+// never for the caller's stream.  1 = fine, 0 = a value outside the range, -1 = a HIP call failed.
 constexpr int kRowChunk = 1024, kMaxDevices = 64;
-inline int noise_row_ok(const int32_t* idx_b, int n_b, int k, bool have_noise)
+inline int device_i32_in_range(const int32_t* p, int64_t n, int64_t lo, int64_t hi)
 {
     static std::mutex mu;
     static hipStream_t streams[kMaxDevices] = {};
     static int32_t* bufs[kMaxDevices] = {};
-    if (n_b == 0) return 1;
+    if (n == 0) return 1;
     int dev = 0;
     if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= kMaxDevices) { (void)hipGetLastError(); return -1; }
     std::lock_guard<std::mutex> lock(mu);
@@ -529,16 +571,23 @@ inline int noise_row_ok(const int32_t* idx_b, int n_b, int k, bool have_noise)
         }
         streams[dev] = s; bufs[dev] = (int32_t*)b;
     }
-    for (int o = 0; o < n_b; o += kRowChunk) {
-        const int n = n_b - o < kRowChunk ? n_b - o : kRowChunk;
-        if (hipMemcpyAsync(bufs[dev], idx_b + o, n * sizeof(int32_t), hipMemcpyDefault, streams[dev]) != hipSuccess ||
+    for (int64_t o = 0; o < n; o += kRowChunk) {
+        const int c = n - o < kRowChunk ? (int)(n - o) : kRowChunk;
+        if (hipMemcpyAsync(bufs[dev], p + o, c * sizeof(int32_t), hipMemcpyDefault, streams[dev]) != hipSuccess ||
             hipStreamSynchronize(streams[dev]) != hipSuccess) { (void)hipGetLastError(); return -1; }
-        for (int i = 0; i < n; ++i) {
-            const int32_t j = bufs[dev][i];
-            if (j < 0 || j > k + 1 || (j == 0 && !have_noise)) return 0;
-        }
+        for (int i = 0; i < c; ++i)
+            if (bufs[dev][i] < lo || bufs[dev][i] > hi) return 0;
     }
     return 1;
+}
+
+// a noise row: every column is in 0..k+1 (eps_j is drawn after step j-1) and column 0 has a `noise` to read
+inline int noise_row_ok(const int32_t* idx_b, int n_b, int k, bool have_noise) {
+    return device_i32_in_range(idx_b, n_b, have_noise ? 0 : 1, (int64_t)k + 1);
+}
+// a slot array: -1 (no unconditional row) or a row of `uncond`
+inline int slots_ok(const int32_t* uncond_slot, int64_t n_images, int n_uncond) {
+    return device_i32_in_range(uncond_slot, n_images, -1, (int64_t)n_uncond - 1);
 }
 
 }  // namespace
@@ -698,6 +747,35 @@ int natinf_step_f32prod_noise(const float* z, const float* cond, const float* un
     if (row <= 0) return row < 0 ? NATINF_ELAUNCH : NATINF_EINVAL;
     hipLaunchKernelGGL(k_step_noise_f32prod, dim3(blocks), dim3(kBlock), 0, (hipStream_t)stream,
                        (const float4*)z, cond, uncond, cfg, sample_elems / 4, eps_sample_stride,
+                       hist_x0, (const float4*)noise, (float4*)z_next, idx_c, val_c, n_c, c_diag, idx_b, val_b, n_b,
+                       image_index, first_index, index_stride, (uint32_t)seed, (uint32_t)(seed >> 32),
+                       k, c1_f32, c2_f32, nvec, E);
+    return launched();
+}
+
+int natinf_step_f32prod_noise_guided(const float* z, const float* cond, const float* uncond,
+                                     const float* cfg_image, const int32_t* uncond_slot, int n_uncond,
+                                     int64_t sample_elems, int64_t eps_sample_stride,
+                                     float* hist_x0, const float* noise, float* z_next,
+                                     const int32_t* idx_c, const float* val_c, int n_c, float c_diag,
+                                     const int32_t* idx_b, const float* val_b, int n_b,
+                                     int k, float c1_f32, float c2_f32,
+                                     uint64_t seed, const int64_t* image_index, int64_t first_index, int64_t index_stride,
+                                     int64_t E, natinf_stream_t stream)
+{
+    const int64_t nvec = vec_count(E, 4);
+    const unsigned blocks = quad_blocks(nvec);
+    if (!z || !cond || !hist_x0 || !z_next || !terms_ok(idx_c, val_c, n_c) || !terms_ok(idx_b, val_b, n_b) ||
+        k < 0 || n_b > (int64_t)k + 2 || !nvec || !image_ok(sample_elems, E) || eps_sample_stride < sample_elems ||
+        (eps_sample_stride & 3) || ((sample_elems / 4) >> 32) || !blocks ||
+        !cfg_image || !uncond_slot || n_uncond < 0 || (n_uncond > 0 && !uncond))
+        return NATINF_EINVAL;
+    const int row = noise_row_ok(idx_b, n_b, k, noise != nullptr);
+    if (row <= 0) return row < 0 ? NATINF_ELAUNCH : NATINF_EINVAL;
+    const int slots = slots_ok(uncond_slot, E / sample_elems, n_uncond);
+    if (slots <= 0) return slots < 0 ? NATINF_ELAUNCH : NATINF_EINVAL;
+    hipLaunchKernelGGL(k_step_guided_f32prod, dim3(blocks), dim3(kBlock), 0, (hipStream_t)stream,
+                       (const float4*)z, cond, uncond, cfg_image, uncond_slot, sample_elems / 4, eps_sample_stride,
                        hist_x0, (const float4*)noise, (float4*)z_next, idx_c, val_c, n_c, c_diag, idx_b, val_b, n_b,
                        image_index, first_index, index_stride, (uint32_t)seed, (uint32_t)(seed >> 32),
                        k, c1_f32, c2_f32, nvec, E);

@@ -154,7 +154,8 @@ class ValidateNI:
     global image indices and draws eps_j, j >= 1, in the kernel from Philox(``seed``, global image index, column j)
     (include/natinf.h, natinf_step_f32prod_noise) -- the bytes of the slab path on a slab filled by ``philox_noise(column=j)``,
     for stochastic (``ddpm_*``) and deterministic (``ddim_*``: column 0 only) matrices alike.  ``elems_per_image`` pins the
-    per-image size ``step`` must be called with (None: whatever ``sample_elems`` each call gives)."""
+    per-image size ``step`` must be called with (None: whatever ``sample_elems`` each call gives).  The seeded ``step`` also takes
+    per-image guidance (``cfg`` a tensor with ``uncond_slot``: natinf_step_f32prod_noise_guided)."""
 
     def __init__(self, C: np.ndarray, B: np.ndarray, node: np.ndarray, c1: np.ndarray, c2: np.ndarray, n_elem: int,
                  device="cuda:0", dense: bool = False, *, seed: Optional[int] = None, elems_per_image: Optional[int] = None):
@@ -180,13 +181,25 @@ class ValidateNI:
         self.hist_eps = None if self.seed is not None else torch.empty((self.n_step + 1, self.E), dtype=torch.float32, device=self.device)
         self._z = [torch.empty(self.E, dtype=torch.float32, device=self.device) for _ in range(2)]
 
-    def step(self, k: int, z: torch.Tensor, cond: torch.Tensor, uncond: Optional[torch.Tensor], cfg: float,
+    def step(self, k: int, z: torch.Tensor, cond: torch.Tensor, uncond: Optional[torch.Tensor], cfg,
              sample_elems: Optional[int] = None, eps_sample_stride: Optional[int] = None, *,
-             noise: Optional[torch.Tensor] = None, index=None) -> torch.Tensor:
+             noise: Optional[torch.Tensor] = None, index=None, uncond_slot: Optional[torch.Tensor] = None,
+             n_uncond: Optional[int] = None) -> torch.Tensor:
         """``noise`` / ``index`` (seeded form only): the initial noise eps_0 ([E] fp32, contiguous) and the batch's global image
-        indices in one of ``image_index_args``' forms; an image is one sample of ``sample_elems`` elements."""
+        indices in one of ``image_index_args``' forms; an image is one sample of ``sample_elems`` elements.
+
+        ``cfg`` a float: one scale for the launch, ``uncond`` row i belongs to image i (None: eps = cond).  ``cfg`` a tensor (seeded
+        form only; natinf_step_f32prod_noise_guided): the per-image scales, fp32 ``[n]`` on the device, with ``uncond_slot`` int32 ``[n]``
+        on the device -- image i's row in ``uncond``, or -1 for an unguided image (eps = cond, its scale is not read).  ``uncond`` then
+        holds ``n_uncond`` samples at ``eps_sample_stride`` (default: ``uncond.numel() // eps_sample_stride``; None = no row).  The entry
+        reads ``uncond_slot`` back before it launches: fill it before the call, once per batch."""
         se = self.E if sample_elems is None else int(sample_elems)
         st = se if eps_sample_stride is None else int(eps_sample_stride)
+        guided = isinstance(cfg, torch.Tensor)
+        if guided and (self.seed is None or noise is None):
+            raise ValueError("a tensor cfg (per-image scales) belongs to the seeded form with noise= / index=: the slab form takes one float")
+        if not guided and (uncond_slot is not None or n_uncond is not None):
+            raise ValueError("uncond_slot / n_uncond go with a tensor cfg (per-image scales)")
         z_next = _pingpong(self._z, k, z)
         ic, vc, nc = self.rows_c.ptrs(k)
         ib, vb, nb = self.rows_b.ptrs(k)
@@ -205,6 +218,20 @@ class ValidateNI:
             raise ValueError("sample_elems must be the per-image element count: a multiple of 4 dividing the element count"
                              + ("" if self.epi is None else f" (elems_per_image = {self.epi})"))
         index, first, stride = image_index_args(index, self.E // se, z.device)
+        if guided:
+            n = self.E // se
+            if cfg.dtype != torch.float32 or cfg.device != z.device or not cfg.is_contiguous() or cfg.numel() != n:
+                raise ValueError("a tensor cfg must be a contiguous fp32 tensor on the sampler's device, one scale per image")
+            if (not isinstance(uncond_slot, torch.Tensor) or uncond_slot.dtype != torch.int32 or uncond_slot.device != z.device
+                    or not uncond_slot.is_contiguous() or uncond_slot.numel() != n):
+                raise ValueError("a tensor cfg needs uncond_slot: a contiguous int32 tensor on the sampler's device, one slot per image")
+            if n_uncond is None:
+                n_uncond = 0 if uncond is None else uncond.numel() // st
+            check(lib.natinf_step_f32prod_noise_guided(ptr(z), ptr(cond), ptr(uncond), ptr(cfg), ptr(uncond_slot), int(n_uncond), se, st,
+                                                       ptr(self.hist_x0), ptr(noise), ptr(z_next), ic, vc, nc, self.rows_c.rows[k].diag,
+                                                       ib, vb, nb, k, self.c1[k], self.c2[k], self.seed, ptr(index), first, stride,
+                                                       self.E, stream_ptr()), "natinf_step_f32prod_noise_guided")
+            return z_next
         check(lib.natinf_step_f32prod_noise(ptr(z), ptr(cond), ptr(uncond), float(cfg), se, st, ptr(self.hist_x0), ptr(noise),
                                             ptr(z_next), ic, vc, nc, self.rows_c.rows[k].diag, ib, vb, nb, k, self.c1[k],
                                             self.c2[k], self.seed, ptr(index), first, stride, self.E, stream_ptr()),

@@ -4,6 +4,7 @@ One JSON object on stdout.  Every row: one untimed warm-up job, then ``--reps`` 
 sides; images/s from the median, the spread (min / max seconds) beside it.  GPU box; run from the repository root:
 
     python tools/dit_job.py [--input-size 64] [--batches 8,16,32,64] [--reps 5] [--fp8] [--guard | --stream16 auto] [--no-baseline]
+                            [--guidance-interval LO HI] [--cfg-scales FILE | 4,1,2.5,...]
 
 ``--fp8``: every generate_sharded row is measured twice in the same process -- the bf16 engine, then the engine with fp8 projections (NATINF_DIT_FP8), alternating row by
 row -- and carries ``"fp8": false / true``; each (batch size, mode) also gets a ``forwards`` entry: ms per denoiser forward of 2 x batch samples (HIP events over 20
@@ -12,6 +13,11 @@ forwards) and the per-shape GEMM table of one forward (natinf_gemm_profile_read:
 ``--guard`` (= ``--stream16 auto``): the cost of the stream guard (NATINF_DIT_STREAM_GUARD).  Every generate_sharded row is measured, alternating in this process, on three
 engines per projection mode -- the half stream unguarded (``"stream": "half"``: the default path), the guarded half stream run as ``generate_sharded(stream16="auto")``
 (``"half_guarded"``; the synthetic weights stay in range, so no batch reruns -- ``"reruns"`` says so) and the fp32 stream (``"fp32"``: what a rerun costs).
+
+``--guidance-interval LO HI`` / ``--cfg-scales``: the job's guidance arguments (``generate_sharded(guidance_interval=, cfg_scale=<sequence>)``: guide only at the steps whose
+timestep lies in LO..HI; one scale per image, 1 = unguided; a list shorter than the batch is cycled over the global index).  Every generate_sharded row is then measured twice,
+alternating in this process: ``"guidance": "full"`` -- the default call, [z; z] at every step -- and ``"guidance": "planned"`` -- the job with those arguments; the result's
+``guidance`` entry gives, per batch size, the denoiser forward's sample count at each step of the planned job and how many steps guide at all.
 """
 import argparse
 import json
@@ -90,6 +96,9 @@ def main():
     ap.add_argument("--fp8", action="store_true", help="measure the fp8-projection engine beside the bf16 one, alternating, in this process")
     ap.add_argument("--guard", action="store_true", help="measure the guarded half stream (stream16='auto') and the fp32 stream beside the unguarded half stream, alternating")
     ap.add_argument("--stream16", choices=("auto",), default=None, help="'auto': the same as --guard")
+    ap.add_argument("--guidance-interval", type=int, nargs=2, metavar=("LO", "HI"), default=None,
+                    help="measure the job with guidance_interval=(LO, HI) beside the full-guidance job, alternating, in this process")
+    ap.add_argument("--cfg-scales", default=None, help="per-image CFG scales for the planned job: a file (one number per line or comma separated) or a comma list; cycled over the global index")
     ap.add_argument("--algs", default="ddim,ddpm")
     ap.add_argument("--no-baseline", action="store_true", help="skip the natural_inference (slab) baseline rows")
     a = ap.parse_args()
@@ -99,10 +108,21 @@ def main():
     flat = flatten_state_dict(synthetic_dit_state_dict(input_size=S), XL2["depth"], XL2["hidden"], S)
     vae = None if a.no_decode else VAEDecoder(synthetic_vae_flat(4), max_batch=8, latent_ch=4, latent_res=S)
     rows = []
+    planned = a.guidance_interval is not None or a.cfg_scales is not None
+    scale_list = None
+    if a.cfg_scales is not None:
+        text = Path(a.cfg_scales).read_text() if Path(a.cfg_scales).is_file() else a.cfg_scales
+        scale_list = [float(v) for v in text.replace(",", " ").split()]
+    interval = None if a.guidance_interval is None else tuple(a.guidance_interval)
+    guidance = []
+
+    def plan_kw(bs):
+        """the planned job's arguments for a batch of bs images"""
+        return dict(guidance_interval=interval, cfg_scale=4.0 if scale_list is None else [scale_list[i % len(scale_list)] for i in range(bs)])
 
     forwards = []
 
-    def row(path, alg, bs, decode, ws, sec, fp8=False, stream=None, reruns=None):
+    def row(path, alg, bs, decode, ws, sec, fp8=False, stream=None, reruns=None, mode=None):
         med, lo, hi = sec
         rows.append({"path": path, "alg": alg, "batch_size": bs, "forward_samples": 2 * bs, "decode": decode, "images_per_s": round(bs / med, 2),
                      "median_s": round(med, 4), "min_s": round(lo, 4), "max_s": round(hi, 4), "engine_workspace_bytes": int(ws)})
@@ -110,6 +130,8 @@ def main():
             rows[-1]["fp8"] = fp8
         if stream is not None:
             rows[-1].update(stream=stream, reruns=reruns)
+        if mode is not None:
+            rows[-1]["guidance"] = mode                                  # "planned": forward_samples is the largest forward; the per-step sizes are in res["guidance"]
 
     # the baseline: natural_inference as it stands (eight demo labels, torch.randn_like copied into the noise slab, natinf_step_f32prod)
     eng = DiTEngine(flat, max_batch=16, input_size=S, **XL2)
@@ -130,9 +152,35 @@ def main():
                 for fp8, stream, eng in engines:                              # the modes alternate, row by row
                     rep = {}
                     auto = dict(stream16="auto", fallback=lambda: wide[fp8], report=rep) if stream == "half_guarded" else {}
-                    job = lambda: V.generate_sharded(bs, None, alg_name=alg, num_step=a.steps, batch_size=bs, seed=0, decode=decode, decode_batch=8,
-                                                     model=eng, decoder=vae, **auto)
-                    row("generate_sharded", alg, bs, decode, eng.workspace_bytes, timed(job, a.reps), fp8, stream, len(rep["rerun_batches"]) if auto else None)
+                    job = lambda **kw: V.generate_sharded(bs, None, alg_name=alg, num_step=a.steps, batch_size=bs, seed=0, decode=decode, decode_batch=8,
+                                                          model=eng, decoder=vae, **auto, **kw)
+                    if not planned:
+                        row("generate_sharded", alg, bs, decode, eng.workspace_bytes, timed(job, a.reps), fp8, stream, len(rep["rerun_batches"]) if auto else None)
+                        continue
+                    # full guidance and the planned job, alternating job by job: one warm-up each, then reps pairs
+                    modes = (("full", {}), ("planned", plan_kw(bs)))
+                    secs = {name: [] for name, _ in modes}
+                    for name, kw in modes:
+                        job(**kw)
+                    for _ in range(a.reps):
+                        for name, kw in modes:
+                            torch.cuda.synchronize()
+                            t0 = time.perf_counter()
+                            job(**kw)
+                            torch.cuda.synchronize()
+                            secs[name].append(time.perf_counter() - t0)
+                    for name, _ in modes:
+                        ts = secs[name]
+                        row("generate_sharded", alg, bs, decode, eng.workspace_bytes, (statistics.median(ts), min(ts), max(ts)), fp8, stream,
+                            len(rep["rerun_batches"]) if auto else None, mode=name)
+            if planned:
+                C, B, node = V.load_coeff_npz(V.root_path / ("results/%s/%s_%03d.npz" % (alg.replace("_sympy", ""), alg, a.steps)))
+                kw = plan_kw(bs)
+                guided, slots, _ = V.guidance_plan(node, B.shape[0], V.job_scales(kw["cfg_scale"], bs), interval)
+                g = sum(s >= 0 for s in slots)
+                guidance.append({"alg": alg, "batch_size": bs, "guided_images": g, "steps_guided": sum(guided), "steps": len(guided),
+                                 "timesteps": [int(node[kk, 0]) for kk in range(len(guided))],
+                                 "forward_samples_per_step": {"full": [2 * bs] * len(guided), "planned": [bs + g if ok else bs for ok in guided]}})
         if a.fp8 or a.guard:
             for fp8, stream, eng in engines:
                 forwards.append(dict(fp8=fp8, batch_size=bs, **({"stream": stream} if stream else {}), **forward_profile(eng, 2 * bs, S)))
@@ -142,6 +190,8 @@ def main():
            "device": torch.cuda.get_device_name(0), "rows": rows}
     if a.fp8 or a.guard:
         res["forwards"] = forwards
+    if planned:
+        res.update(guidance_interval=interval, cfg_scales=scale_list, guidance=guidance)
     print(json.dumps(res))
 
 
