@@ -239,6 +239,9 @@ int natinf_weighted_sum_f32prod(const float* hist, float* out,
  * Every product / sum / quotient is formed in fp32 from fp16 operands and rounded to fp16, as
  * eager PyTorch does; scalars are fp32 (`sig`, `sig_next`, `one_minus_sig_next` must already hold
  * the fp16-rounded value of the 0-d tensor the reference multiplies with).  E % 8 == 0.
+ *
+ * Two entries share this arithmetic: natinf_step_f16chain (one cfg, v_null image i for image i) and
+ * natinf_step_f16chain_guided (a scale and a null-prompt row PER IMAGE: guidance intervals and mixed-scale batches).
  * ------------------------------------------------------------------------------------------ */
 #define NATINF_SD3_CFG_ON_VELOCITY 1
 int natinf_step_f16chain(const void* x, const void* v_text, const void* v_null, const void* noise,
@@ -246,6 +249,40 @@ int natinf_step_f16chain(const void* x, const void* v_text, const void* v_null, 
                          const int32_t* idx, const float* val, int n_terms, float c_diag, float w_total,
                          int k, float sig, float sig_next, float one_minus_sig_next, float cfg,
                          int flags, int64_t E, natinf_stream_t stream);
+
+/* natinf_step_f16chain with per-image guidance (a guidance interval, a scale sweep, guided and unguided images in one
+ * batch): every image carries its own CFG scale, and the null-prompt velocities are compacted to the images that are
+ * guided.  An image is sample_elems consecutive elements; with n_images = E / sample_elems, the fused x0 of image i is
+ *
+ *   uncond_slot[i] < 0 : f = x - sig*v_text                                   (either flag value)
+ *   otherwise          : u = v_null[uncond_slot[i]] ; cfg = cfg_image[i] ;
+ *                        default:  x0n = x - sig*u ; x0t = x - sig*v_text ; f = x0n + cfg*(x0t - x0n)
+ *                        velocity: v = u + cfg*(v_text - u) ; f = x - sig*v
+ *
+ * (every operation rounded to fp16, the roundings of the launch-wide form in the same order); hist[k], acc, mean and
+ * x_next are those of natinf_step_f16chain.  cfg_image: device [n_images] fp32.  uncond_slot: device [n_images] int32,
+ * each -1 or a row 0..n_uncond-1 of `v_null`; rows may repeat or be left out.  `v_null` holds n_uncond images of
+ * sample_elems fp16 elements, contiguous, so it may be the tail of a transformer output [n_images + n_uncond, C, H, W]; it
+ * may be NULL when n_uncond == 0.  `x` and `v_text` hold all n_images.  Neither cfg_image[i] nor any element of v_null is
+ * read for an image without a slot.
+ *
+ * Identity rule: with cfg_image[i] == cfg and uncond_slot[i] == i for every i, hist[k], mean_out and x_next are byte for
+ * byte those of natinf_step_f16chain(..., v_null, ..., cfg, flags, ...).  A step is a per-image function, so a mixed launch
+ * gives each image the bytes of that entry run on the images that share its scale.
+ *
+ * NATINF_EINVAL, nothing launched: every refusal of natinf_step_f16chain (except that v_null may be NULL when
+ * n_uncond == 0); cfg_image or uncond_slot NULL; n_uncond < 0; n_uncond > 0 with `v_null` NULL; sample_elems not a
+ * positive multiple of 8 dividing E; a slot outside -1..n_uncond-1.  The slots are checked the way
+ * natinf_step_f32prod_noise_guided checks them: read back on the same private stream before the launch, so uncond_slot
+ * must be complete when the call is made (a table uploaded once per batch) and the call cannot be part of a stream
+ * capture.  The VALUES of cfg_image are not inspected (any fp32, NaN included, goes into the arithmetic above), and it
+ * is read by the kernel only, in stream order. */
+int natinf_step_f16chain_guided(const void* x, const void* v_text, const void* v_null,
+                                const float* cfg_image, const int32_t* uncond_slot, int n_uncond, int64_t sample_elems,
+                                const void* noise, void* hist, void* mean_out, void* x_next,
+                                const int32_t* idx, const float* val, int n_terms, float c_diag, float w_total,
+                                int k, float sig, float sig_next, float one_minus_sig_next,
+                                int flags, int64_t E, natinf_stream_t stream);
 
 /* src/SD3NaturalInference.py:209 on its own: out = sig*noise + one_minus_sig*mean (fp16 ops; mean may be
  * NULL = zeros, the k = 0 case of :207). */

@@ -160,31 +160,161 @@ def _velocities(pipe, x, ts, emb):
     return vt.contiguous(), vn.contiguous()
 
 
+def job_prompts(prompts, sample_count):
+    """The prompt of every image of a job, by GLOBAL index: None is ``PROMPT`` for every image, a string is every image's prompt, a
+    sequence must hold exactly ``sample_count`` strings (image i carries ``prompts[i]`` whatever the rank, world or batch split).
+    Pure host code."""
+    sample_count = int(sample_count)
+    if prompts is None or isinstance(prompts, str):
+        return [PROMPT if prompts is None else prompts] * sample_count
+    table = list(prompts)
+    if len(table) != sample_count or not all(isinstance(p, str) for p in table):
+        raise ValueError(f"{len(table)} prompts for {sample_count} images: a prompt sequence has one string per image of the job")
+    return table
+
+
+def _check_interval(interval):
+    if interval is not None and (len(interval) != 2 or float(interval[0]) > float(interval[1])):
+        raise ValueError(f"guidance_interval must be (s_lo, s_hi) with s_lo <= s_hi, got {interval!r}")
+
+
+def sd_guidance_plan(sigmas, n_step, scales, interval=None):
+    """The guidance of one batch -> (guided, slots, scales).  ``scales``: the batch's per-image CFG scales (``job_scales`` taken at
+    the batch's global indices); ``interval`` None or ``(s_lo, s_hi)`` on the sigma scale: step kk is inside when
+    ``s_lo <= float(sigmas[kk]) <= s_hi``, the fp32 value of the schedule the step multiplies by, both ends inclusive.
+
+    ``slots[i]``: the row of image i among the batch's null-prompt sequences, or -1 for an image whose scale is exactly 1.0
+    (unguided: f = x - sig*v_text, no null-prompt sequence); the images that are guided take rows 0, 1, ... in batch order.
+    ``guided[kk]``: whether step kk runs the null-prompt sequences at all -- its sigma lies in the interval and at least one
+    image has a slot.  A step that is not guided is unguided for every image.  ``scales`` comes back as the fp32 values.
+    Pure host code: at most two forward shapes per batch, n + max(slots) + 1 sequences and n."""
+    _check_interval(interval)
+    n_step = int(n_step)
+    if len(sigmas) < n_step:
+        raise ValueError(f"{len(sigmas)} sigmas for {n_step} steps")
+    scales = [float(np.float32(v)) for v in scales]
+    slots, g = [], 0
+    for v in scales:
+        slots.append(-1 if v == 1.0 else g)
+        g += v != 1.0
+    if interval is None:
+        inside = [True] * n_step
+    else:
+        s_lo, s_hi = (float(v) for v in interval)
+        inside = [s_lo <= float(sigmas[kk]) <= s_hi for kk in range(n_step)]
+    return [bool(g) and ok for ok in inside], slots, scales
+
+
+def _velocity(pipe, x, ts, text, pooled, joint):
+    """one denoiser call on the sequences given: the engine's own ``forward`` when it holds them (``joint``), the reference's call shape otherwise"""
+    if joint:
+        return pipe.transformer.forward(x, ts, text, pooled)
+    return pipe.transformer(hidden_states=x, timestep=ts, encoder_hidden_states=text, pooled_projections=pooled, return_dict=False)[0]
+
+
+def _planned_trajectory(pipe, ni, noises, timesteps, num_step, emb, plan):
+    """The loop of ``sd_generate_sharded`` under an ``sd_guidance_plan``: a guided step forwards [x; x[G]] with [pe; ne[G]] and [ppe; npe[G]] (one call
+    when the transformer is the engine and takes n + |G| sequences, two otherwise) and makes the per-image step; every other step forwards the n text
+    sequences alone and makes the per-image step with every slot -1."""
+    from .mmdit import MMDiTEngine
+    guided, pick, slots_t, none_t, scales_t = plan
+    pe, ne, ppe, npe = emb
+    nb, g, per = noises.shape[0], pick.numel(), noises[0].numel()
+    engine = isinstance(pipe.transformer, MMDiTEngine)
+    joint = engine and pipe.transformer.max_batch >= nb + g
+    alone = engine and pipe.transformer.max_batch >= nb
+    if g:
+        ne_g, npe_g = (ne, npe) if g == nb else (ne[pick], npe[pick])
+        text_g, pooled_g = torch.cat([pe, ne_g]), torch.cat([ppe, npe_g])
+    flat_noise = noises.reshape(-1)
+    x = ni.first_input(flat_noise)
+    for kk in range(num_step):
+        xs, want = x.view(noises.shape), kk + 1 < num_step
+        if not guided[kk]:
+            vt = _velocity(pipe, xs, timesteps[kk].expand(nb), pe, ppe, alone).contiguous()
+            mean, x = ni.step(kk, x, vt.reshape(-1), None, flat_noise, want_next=want, cfg=scales_t, uncond_slot=none_t, n_uncond=0, sample_elems=per)
+            continue
+        xg = xs if g == nb else xs[pick]
+        if joint:
+            v = pipe.transformer.forward(torch.cat([xs, xg]), timesteps[kk].expand(nb + g), text_g, pooled_g)
+            vt, vn = v[:nb].contiguous(), v[nb:].contiguous()
+        else:
+            vt = _velocity(pipe, xs, timesteps[kk].expand(nb), pe, ppe, alone).contiguous()
+            vn = _velocity(pipe, xg, timesteps[kk].expand(g), ne_g, npe_g, engine and pipe.transformer.max_batch >= g).contiguous()
+        mean, x = ni.step(kk, x, vt.reshape(-1), vn.reshape(-1), flat_noise, want_next=want, cfg=scales_t, uncond_slot=slots_t, n_uncond=g, sample_elems=per)
+    return mean
+
+
 @torch.no_grad()
 def sd_generate_sharded(pipe, sample_count: int, n: int = 4, rank: int = 0, world: int = 1, seed: int = 10, num_step: int = 28,
-                        weight_name: str = "sd3_step_28_weight.csv", device="cuda:0", latent_shape=(16, 128, 128)):
+                        weight_name: str = "sd3_step_28_weight.csv", device="cuda:0", latent_shape=(16, 128, 128), *,
+                        prompts=None, negative_prompt: str = "", cfg_scale=7.0, guidance_interval=None):
     """Batch-sharded SD3 generation (BASELINE configs 4 / 5): this rank runs the reference's loop (:198-223) for the images
     whose GLOBAL index is rank, rank + world, ... in batches of ``n`` -- no collective on the data path, Philox noise keyed by the global index
     (``philox_noise_f16``), so image i is the same bytes whatever the GPU count or batch split.  ``pipe`` as in ``sd_natural_inference_tx``
     (``encode_prompt`` is asked for ``n`` prompts once; a ragged last batch uses the first rows).
+
+    Prompts.  ``prompts`` None (the default) is the reference's one ``PROMPT`` for every image, encoded once as above.  A string gives every image that
+    prompt; a sequence must hold exactly ``sample_count`` strings, by GLOBAL image index (``job_prompts``).  With either, ``encode_prompt`` is called once
+    per batch with that batch's prompts.  ``negative_prompt`` is what ``encode_prompt`` is given for the null side (one string for the job).
+
+    Guidance.  ``cfg_scale`` a number and ``guidance_interval`` None (the defaults' form) is the reference's one hard-wired form and makes exactly the calls
+    it always made: every step a forward of [x; x] and natinf_step_f16chain with the one scale -- byte-identical latents.  Two arguments go beyond it
+    (``sd_guidance_plan``, natinf_step_f16chain_guided):
+
+    * ``cfg_scale`` a sequence of ``sample_count`` numbers, by GLOBAL image index (``ValidateNaturalInference.job_scales``): image i carries its own scale
+      whatever the rank, world or batch split.  A scale exactly 1.0 means unguided: no null-prompt sequence for that image at any step, f = x - sig*v_text.
+    * ``guidance_interval=(s_lo, s_hi)`` on the sigma scale: guide only at the steps kk with ``s_lo <= float(sigmas[kk]) <= s_hi`` (the fp32 value of the
+      schedule), both ends inclusive; every other step is unguided for every image (Kynkaanniemi et al., 2024).  With it a scalar ``cfg_scale == 1.0``
+      means unguided as well.
+
+    With G the guided images of a batch at a step: G empty -> ONE forward of the n text sequences and the guided step with every slot -1 (``v_null=None``,
+    ``n_uncond=0``); otherwise one forward of [x; x[G]] with [pe; ne[G]] and [ppe; npe[G]] -- n + |G| <= 2n sequences, within the engine's ``max_batch`` --
+    and the guided step, slots 0..|G|-1 at the positions in G and -1 elsewhere.  A transformer that is not the ``MMDiTEngine``, or one too small, gets two
+    calls.  Slot and scale tensors are built once per batch; nothing in the loop waits for the GPU beyond the slot read-back the C entry makes.
+    Contract: with either new argument image i is still a function of (seed, global index, its prompt, its scale, the interval) up to the engine's own
+    batch dependence -- the same function, not the same bytes as the default form: the engine picks GEMM tile variants by row count, so a forward of
+    n + |G| sequences and one of 2n may differ by bf16 rounding flips.  Only when n + |G| == 2n at every step (every image guided, no interval) are the
+    forward shapes those of the default form, and then the kernel's identity rule makes the latents byte-identical to it.
+
     Returns (final latents [n_local, *latent_shape] fp16 on the device, their global indices [n_local] int64 on the CPU)."""
     from .shard import rank_batches
+    from .ValidateNaturalInference import job_scales
+    planned = guidance_interval is not None or not isinstance(cfg_scale, (int, float, np.floating, np.integer))   # False: the reference's form, today's calls
+    _check_interval(guidance_interval)
+    scale_of = job_scales(cfg_scale, sample_count) if planned else None
+    prompt_of = None if prompts is None else job_prompts(prompts, sample_count)
     _lib.require_gpu()
     dev = torch.device(device)
     batches = list(rank_batches(sample_count, n, rank, world))
     if not batches:
         return torch.empty((0,) + tuple(latent_shape), dtype=torch.float16, device=dev), torch.empty(0, dtype=torch.int64)
-    emb = pipe.encode_prompt(prompt=[PROMPT] * n, prompt_2=None, prompt_3=None, negative_prompt="")
+    if prompt_of is None:
+        emb = pipe.encode_prompt(prompt=[PROMPT] * n, prompt_2=None, prompt_3=None, negative_prompt=negative_prompt)
     pipe.scheduler.set_timesteps(num_step, device=dev)
     timesteps, sigmas = pipe.scheduler.timesteps.to(dev), pipe.scheduler.sigmas.to(dev)
     weights = load_sd3_csv(os.path.join(root_path / "weights", weight_name))
     samplers, outs = {}, []
+    if planned:
+        sigmas_host = sigmas.detach().to("cpu", torch.float32)
     for batch in batches:
         nb = len(batch)
         noises = philox_noise_f16(batch, latent_shape, seed, dev)
         if nb not in samplers:                                          # (a ragged last batch gets its own history slabs)
-            samplers[nb] = SD3NI(weights, sigmas, noises.numel(), device=dev, cfg=7.0)
-        ni, e = samplers[nb], tuple(t[:nb] for t in emb)
+            samplers[nb] = SD3NI(weights, sigmas, noises.numel(), device=dev, cfg=float(cfg_scale) if not planned else 7.0,
+                                 elems_per_image=noises[0].numel() if planned else None)
+        if prompt_of is None:
+            ni, e = samplers[nb], tuple(t[:nb] for t in emb)
+        else:                                                           # this batch's prompts, by global index
+            ni, e = samplers[nb], tuple(pipe.encode_prompt(prompt=[prompt_of[i] for i in batch], prompt_2=None, prompt_3=None,
+                                                           negative_prompt=negative_prompt))
+        if planned:                                                     # slot and scale tensors once per batch
+            guided, slots, scales = sd_guidance_plan(sigmas_host, num_step, [scale_of[i] for i in batch], guidance_interval)
+            plan = (guided, torch.tensor([i for i, sl in enumerate(slots) if sl >= 0], dtype=torch.int64, device=dev),
+                    torch.tensor(slots, dtype=torch.int32, device=dev), torch.full((nb,), -1, dtype=torch.int32, device=dev),
+                    torch.tensor(scales, dtype=torch.float32, device=dev))
+            outs.append(_planned_trajectory(pipe, ni, noises, timesteps, num_step, e, plan).view(noises.shape).clone())
+            continue
         flat_noise = noises.reshape(-1)
         x = ni.first_input(flat_noise)
         for kk in range(num_step):
@@ -197,12 +327,15 @@ def sd_generate_sharded(pipe, sample_count: int, n: int = 4, rank: int = 0, worl
 @torch.no_grad()
 def sd_natural_inference_tx(pipe=None, device="cuda", noises: Optional[torch.Tensor] = None, n: int = 4, seed: int = 10,
                             num_step: int = 28, weight_names=("sd3_step_28_weight.csv", "sd3_step_28_weight_sharp.csv"),
-                            decode: bool = True, rank: int = 0, world: int = 1, sample_count: Optional[int] = None, latent_shape=None):
+                            decode: bool = True, rank: int = 0, world: int = 1, sample_count: Optional[int] = None, latent_shape=None, *,
+                            prompts=None, negative_prompt: str = "", cfg_scale=7.0, guidance_interval=None):
     """Reference :172-245.  Returns the final latents per weight file (and writes ``results/sd3/sgl_*.png``
     when ``decode``).  With ``sample_count`` (not in the reference: its job is one batch of four) the job is ``sample_count`` images sharded by
     global index over ``world`` ranks (``sd_generate_sharded``): returns [(latents of this rank, global indices)] per weight file and, when
     ``decode``, writes this rank's images to ``results/sd3/sgl_<weights>_<index>.png``.  ``latent_shape`` of the sharded job: the native
-    transformer's own (in_ch, 2 grid, 2 grid) when ``pipe.transformer`` is the HIP engine, the reference's (16, 128, 128) otherwise."""
+    transformer's own (in_ch, 2 grid, 2 grid) when ``pipe.transformer`` is the HIP engine, the reference's (16, 128, 128) otherwise.
+    ``prompts``, ``negative_prompt``, ``cfg_scale`` and ``guidance_interval`` belong to the sharded job and go to ``sd_generate_sharded`` as they are
+    (per-image prompts and CFG scales by global index, a guidance interval on the sigma scale); without ``sample_count`` they are refused."""
     dtype = torch.float16
     pipe = _load_pipe(pipe, device, dtype, n)
     if sample_count is not None:
@@ -216,7 +349,8 @@ def sd_natural_inference_tx(pipe=None, device="cuda", noises: Optional[torch.Ten
         if dev_r.type == "cuda" and dev_r.index is None:
             dev_r = torch.device("cuda", torch.cuda.current_device())
         for weight_name in weight_names:
-            lat, idx = sd_generate_sharded(pipe, sample_count, n, rank, world, seed, num_step, weight_name, dev_r, latent_shape=tuple(latent_shape))
+            lat, idx = sd_generate_sharded(pipe, sample_count, n, rank, world, seed, num_step, weight_name, dev_r, latent_shape=tuple(latent_shape),
+                                           prompts=prompts, negative_prompt=negative_prompt, cfg_scale=cfg_scale, guidance_interval=guidance_interval)
             finals.append((lat, idx))
             if decode:
                 for s0 in range(0, lat.shape[0], n):
@@ -225,6 +359,8 @@ def sd_natural_inference_tx(pipe=None, device="cuda", noises: Optional[torch.Ten
         return finals
     if world != 1 or rank != 0:
         raise ValueError("rank / world need sample_count (the reference's job is one batch: nothing to shard)")
+    if prompts is not None or negative_prompt != "" or guidance_interval is not None or not isinstance(cfg_scale, (int, float, np.floating, np.integer)) or cfg_scale != 7.0:
+        raise ValueError("prompts / negative_prompt / cfg_scale / guidance_interval need sample_count (the reference's job hard-wires one prompt and cfg 7)")
     noises, emb, timesteps, sigmas = _prepare(pipe, device, dtype, n, seed, num_step, noises)
     shape, finals = noises.shape, []
     for weight_name in weight_names:

@@ -48,6 +48,8 @@ SIGNATURES = {
     "natinf_weighted_sum_f32prod": (C.c_int, [_p, _p, _p, _p, _i32, _i64, _p]),
     "natinf_step_f16chain": (C.c_int, [_p, _p, _p, _p, _p, _p, _p, _p, _p, _i32, _f32, _f32, _i32, _f32, _f32, _f32,
                                        _f32, _i32, _i64, _p]),
+    "natinf_step_f16chain_guided": (C.c_int, [_p, _p, _p, _p, _p, _i32, _i64, _p, _p, _p, _p, _p, _p, _i32, _f32, _f32, _i32, _f32, _f32,
+                                              _f32, _i32, _i64, _p]),
     "natinf_weighted_mean_f16": (C.c_int, [_p, _p, _p, _p, _i32, _f32, _i64, _p]),
     "natinf_flow_input_f16": (C.c_int, [_p, _p, _p, _f32, _f32, _i64, _p]),
     # include/natinf_ncsnpp.h

@@ -106,6 +106,40 @@ __device__ __forceinline__ h8 flow_input(h8 nz, h8 m, float sig, float oms) {
     return r;
 }
 
+// ---- piece of the SD3 form with per-image guidance (fp16 chain) ----
+// the fused x0 of one 8-vector: image img's null-prompt velocity is row uncond_slot[img] of the compacted v_null (quad q of it) and
+// its scale cfg_image[img]; a negative slot = an unguided image, f = x - sig*v_text for both flag values (neither v_null nor
+// cfg_image[img] is read then).  With a slot it is the arithmetic of k_step_f16chain for the flag, in its order of fp16 roundings.
+// Both per-image values are uniform over the svec consecutive threads of an image: plain vector loads, served by one cache line.
+template <bool kVelocityCfg>
+__device__ __forceinline__ h8 x0_cfg_image(h8 xv, h8 tv, const h8* v_null, const float* cfg_image, const int32_t* uncond_slot,
+                                           int64_t img, int64_t q, int64_t svec, float sig)
+{
+    const int32_t slot = uncond_slot[img];
+    h8 f;
+    if (slot < 0) {
+#pragma unroll
+        for (int i = 0; i < 8; ++i) f.v[i] = hsub(xv.v[i], hmulf(sig, tv.v[i]));
+        return f;
+    }
+    const float cfg = cfg_image[img];
+    const h8 uv = v_null[(int64_t)slot * svec + q];
+#pragma unroll
+    for (int i = 0; i < 8; ++i) {
+        if (kVelocityCfg) {
+            const h16 d = hsub(tv.v[i], uv.v[i]);
+            const h16 vv = hadd(uv.v[i], hmulf(cfg, d));
+            f.v[i] = hsub(xv.v[i], hmulf(sig, vv));
+        } else {
+            const h16 x0n = hsub(xv.v[i], hmulf(sig, uv.v[i]));
+            const h16 x0t = hsub(xv.v[i], hmulf(sig, tv.v[i]));
+            const h16 d = hsub(x0t, x0n);
+            f.v[i] = hadd(x0n, hmulf(cfg, d));
+        }
+    }
+    return f;
+}
+
 // ---- pieces of the CIFAR10 form (fp64 history) ----
 // x0 = ((-out/std) * sigma^2 + x) / alpha: the score in fp32, then three fp64 roundings; stored as quad v of the slab row
 __device__ __forceinline__ void x0_from_score_f64(double (&x0)[4], float4 xv, float4 ov, float stdv, double sigma2,
@@ -355,6 +389,35 @@ __global__ __launch_bounds__(kBlock) void k_step_f16chain(
     }
 }
 
+// ------------------------------------------------------------------------------------------
+// k_step_f16chain with per-image guidance (x0_cfg_image in place of the launch-wide fuse): the null-prompt velocities are
+// compacted to the images that are guided, each image carries its own scale.  Everything behind f is the same composition, so
+// with uncond_slot[i] == i and cfg_image[i] == cfg the two kernels give the same bytes.  No Philox state here, so the
+// grid-stride loop stays.
+// ------------------------------------------------------------------------------------------
+template <bool kVelocityCfg>
+__global__ __launch_bounds__(kBlock) void k_step_f16chain_guided(
+    const h8* __restrict__ x, const h8* __restrict__ v_text, const h8* __restrict__ v_null,
+    const float* __restrict__ cfg_image, const int32_t* __restrict__ uncond_slot, int64_t svec,
+    const h8* __restrict__ noise, h16* __restrict__ hist, h8* __restrict__ mean_out, h8* __restrict__ x_next,
+    const int32_t* __restrict__ idx, const float* __restrict__ val, int n_terms, float c_diag, float w_total,
+    int k, float sig, float sig_next, float oms_next, int64_t nvec, int64_t E)
+{
+    for (int64_t v = first_vec(); v < nvec; v += vec_stride()) {
+        const int64_t img = v / svec, q = v - img * svec;            // an image is svec 8-vectors
+        const h8 f = x0_cfg_image<kVelocityCfg>(x[v], v_text[v], v_null, cfg_image, uncond_slot, img, q, svec, sig);
+        reinterpret_cast<h8*>(hist + (int64_t)k * E)[v] = f;
+
+        h8 acc = h8_zero();
+        chain_terms(acc, hist, idx, val, n_terms, v, E);
+#pragma unroll
+        for (int i = 0; i < 8; ++i) acc.v[i] = hadd(acc.v[i], hmulf(c_diag, f.v[i]));
+        const h8 mean = mean_of(acc, w_total);
+        if (mean_out) mean_out[v] = mean;
+        if (x_next) x_next[v] = flow_input(noise[v], mean, sig_next, oms_next);
+    }
+}
+
 __global__ __launch_bounds__(kBlock) void k_flow_input_f16(
     const h8* __restrict__ noise, const h8* __restrict__ mean, h8* __restrict__ out, float sig, float oms, int64_t nvec)
 {
@@ -539,8 +602,8 @@ inline bool terms_ok(const void* idx, const void* val, int n) { return n >= 0 &&
 // E / lanes vectors when E is a positive multiple of lanes (4 or 8); 0 = refuse
 inline int64_t vec_count(int64_t E, int lanes) { return E > 0 && !(E & (lanes - 1)) ? E / lanes : 0; }
 
-// a per-image (per-sample) element count: a positive multiple of 4 dividing E
-inline bool image_ok(int64_t elems, int64_t E) { return elems > 0 && !(elems & 3) && !(E % elems); }
+// a per-image (per-sample) element count: a positive multiple of lanes (4 or 8) dividing E
+inline bool image_ok(int64_t elems, int64_t E, int lanes = 4) { return elems > 0 && !(elems & (lanes - 1)) && !(E % elems); }
 
 // blocks of a one-quad-per-thread launch (k_step_noise_f64, k_step_noise_f32prod); 0 = more than a grid holds
 inline unsigned quad_blocks(int64_t nvec) {
@@ -549,7 +612,7 @@ inline unsigned quad_blocks(int64_t nvec) {
 }
 
 // Host-side check of a small device int32 array before a launch (the noise row of natinf_step_f32prod_noise, the slots of
-// natinf_step_f32prod_noise_guided): every one of the n values lies in lo..hi.  They are read back, kRowChunk at a time into
+// natinf_step_f32prod_noise_guided and natinf_step_f16chain_guided): every one of the n values lies in lo..hi.  They are read back, kRowChunk at a time into
 // one pinned buffer, on a private non-blocking stream of the current device: the host waits for those small copies only,
 // never for the caller's stream.  1 = fine, 0 = a value outside the range, -1 = a HIP call failed.
 constexpr int kRowChunk = 1024, kMaxDevices = 64;
@@ -807,6 +870,28 @@ int natinf_step_f16chain(const void* x, const void* v_text, const void* v_null, 
                        (const h8*)x, (const h8*)v_text, (const h8*)v_null, (const h8*)noise, (h16*)hist,
                        (h8*)mean_out, (h8*)x_next, idx, val, n_terms, c_diag, w_total, k, sig, sig_next,
                        one_minus_sig_next, cfg, nvec, E);
+    return launched();
+}
+
+int natinf_step_f16chain_guided(const void* x, const void* v_text, const void* v_null,
+                                const float* cfg_image, const int32_t* uncond_slot, int n_uncond, int64_t sample_elems,
+                                const void* noise, void* hist, void* mean_out, void* x_next,
+                                const int32_t* idx, const float* val, int n_terms, float c_diag, float w_total,
+                                int k, float sig, float sig_next, float one_minus_sig_next,
+                                int flags, int64_t E, natinf_stream_t stream)
+{
+    const int64_t nvec = vec_count(E, 8);
+    if (!x || !v_text || !hist || !terms_ok(idx, val, n_terms) || k < 0 || !nvec ||
+        (x_next && !noise) || (flags & ~NATINF_SD3_CFG_ON_VELOCITY) || !image_ok(sample_elems, E, 8) ||
+        !cfg_image || !uncond_slot || n_uncond < 0 || (n_uncond > 0 && !v_null))
+        return NATINF_EINVAL;
+    const int slots = slots_ok(uncond_slot, E / sample_elems, n_uncond);
+    if (slots <= 0) return slots < 0 ? NATINF_ELAUNCH : NATINF_EINVAL;
+    const auto kern = (flags & NATINF_SD3_CFG_ON_VELOCITY) ? k_step_f16chain_guided<true> : k_step_f16chain_guided<false>;
+    hipLaunchKernelGGL(kern, dim3(grid_for(nvec)), dim3(kBlock), 0, (hipStream_t)stream,
+                       (const h8*)x, (const h8*)v_text, (const h8*)v_null, cfg_image, uncond_slot, sample_elems / 8,
+                       (const h8*)noise, (h16*)hist, (h8*)mean_out, (h8*)x_next, idx, val, n_terms, c_diag, w_total,
+                       k, sig, sig_next, one_minus_sig_next, nvec, E);
     return launched();
 }
 

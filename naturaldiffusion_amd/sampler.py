@@ -52,9 +52,9 @@ def _pingpong(bufs, k: int, src: torch.Tensor) -> torch.Tensor:
     return bufs[(k + 1) & 1] if out.data_ptr() == src.data_ptr() else out
 
 
-def _check_elems_per_image(epi: Optional[int], E: int) -> None:
-    if epi is not None and (epi <= 0 or epi % 4 or E % epi):
-        raise ValueError("elems_per_image must be a positive multiple of 4 dividing the element count")
+def _check_elems_per_image(epi: Optional[int], E: int, lanes: int = 4) -> None:
+    if epi is not None and (epi <= 0 or epi % lanes or E % epi):
+        raise ValueError(f"elems_per_image must be a positive multiple of {lanes} dividing the element count")
 
 
 class CifarNI:
@@ -240,14 +240,20 @@ class ValidateNI:
 
 
 class SD3NI:
-    """Row-normalised fp16 weighted mean + CFG + next flow input (SD3NaturalInference.py:157-168,198-223)."""
+    """Row-normalised fp16 weighted mean + CFG + next flow input (SD3NaturalInference.py:157-168,198-223).
+
+    ``elems_per_image`` pins the per-image size the per-image-guidance form of ``step`` must be called with (None: whatever
+    ``sample_elems`` each call gives).  ``step`` takes per-image guidance as ``cfg=<tensor>`` with ``uncond_slot``
+    (natinf_step_f16chain_guided); without them it is natinf_step_f16chain with the one ``cfg`` given here."""
 
     def __init__(self, weights: np.ndarray, sigmas: torch.Tensor, n_elem: int, device="cuda:0", cfg: float = 7.0,
-                 dense: bool = False, euler: bool = False):
+                 dense: bool = False, euler: bool = False, elems_per_image: Optional[int] = None):
         _lib.require_gpu()
         if n_elem % 8:
             raise ValueError("element count must be a multiple of 8")
         self.E = int(n_elem)
+        self.epi = None if elems_per_image is None else int(elems_per_image)
+        _check_elems_per_image(self.epi, self.E, 8)
         self.device = torch.device(device)
         self.cfg = float(cfg)
         self.euler = bool(euler)
@@ -295,12 +301,40 @@ class SD3NI:
               "natinf_flow_input_f16")
         return out
 
-    def step(self, k: int, x: torch.Tensor, v_text: torch.Tensor, v_null: torch.Tensor, noises: torch.Tensor,
-             want_next: bool = True):
+    def step(self, k: int, x: torch.Tensor, v_text: torch.Tensor, v_null: Optional[torch.Tensor], noises: torch.Tensor,
+             want_next: bool = True, *, cfg=None, uncond_slot: Optional[torch.Tensor] = None, n_uncond: Optional[int] = None,
+             sample_elems: Optional[int] = None):
+        """``cfg`` None: one scale for the launch (the constructor's), ``v_null`` image i belongs to image i.  ``cfg`` a tensor
+        (natinf_step_f16chain_guided): the per-image scales, fp32 ``[n]`` on the device, with ``uncond_slot`` int32 ``[n]`` on the
+        device -- image i's row in ``v_null``, or -1 for an unguided image (f = x - sig*v_text, its scale is not read); an image is
+        ``sample_elems`` elements (default: ``elems_per_image``).  ``v_null`` then holds ``n_uncond`` images, contiguous (default:
+        ``v_null.numel() // sample_elems``; None = no row).  The entry reads ``uncond_slot`` back before it launches: fill it
+        before the call, once per batch."""
+        guided = isinstance(cfg, torch.Tensor)
+        if not guided and (cfg is not None or uncond_slot is not None or n_uncond is not None or sample_elems is not None):
+            raise ValueError("uncond_slot / n_uncond / sample_elems go with a tensor cfg (per-image scales); the launch-wide scale is the constructor's")
         x_next = _pingpong(self._x, k, x)
         idx, val, n = self.rows.ptrs(k)
         r = self.rows.rows[k]
         flags = _lib.SD3_CFG_ON_VELOCITY if self.euler else 0
+        if guided:
+            se = self.epi if sample_elems is None else int(sample_elems)
+            if se is None or se <= 0 or se % 8 or self.E % se or (self.epi is not None and se != self.epi):
+                raise ValueError("sample_elems must be the per-image element count: a multiple of 8 dividing the element count"
+                                 + ("" if self.epi is None else f" (elems_per_image = {self.epi})"))
+            m = self.E // se
+            if cfg.dtype != torch.float32 or cfg.device != x.device or not cfg.is_contiguous() or cfg.numel() != m:
+                raise ValueError("a tensor cfg must be a contiguous fp32 tensor on the sampler's device, one scale per image")
+            if (not isinstance(uncond_slot, torch.Tensor) or uncond_slot.dtype != torch.int32 or uncond_slot.device != x.device
+                    or not uncond_slot.is_contiguous() or uncond_slot.numel() != m):
+                raise ValueError("a tensor cfg needs uncond_slot: a contiguous int32 tensor on the sampler's device, one slot per image")
+            if n_uncond is None:
+                n_uncond = 0 if v_null is None else v_null.numel() // se
+            check(lib.natinf_step_f16chain_guided(ptr(x), ptr(v_text), ptr(v_null), ptr(cfg), ptr(uncond_slot), int(n_uncond), se,
+                                                  ptr(noises), ptr(self.hist), ptr(self.mean), ptr(x_next) if want_next else None,
+                                                  idx, val, n, r.diag, self.totals[k], k, self.sig[k], self.sig[k + 1],
+                                                  self.oms[k + 1], flags, self.E, stream_ptr()), "natinf_step_f16chain_guided")
+            return self.mean, (x_next if want_next else None)
         check(lib.natinf_step_f16chain(ptr(x), ptr(v_text), ptr(v_null), ptr(noises), ptr(self.hist), ptr(self.mean),
                                        ptr(x_next) if want_next else None, idx, val, n, r.diag, self.totals[k], k,
                                        self.sig[k], self.sig[k + 1], self.oms[k + 1], self.cfg, flags, self.E,
