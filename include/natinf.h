@@ -103,6 +103,44 @@ int natinf_step_f64hist_noise(const float* x_k, const float* model_out, const fl
                               uint64_t seed, const int64_t* image_index, int64_t first_index, int64_t index_stride,
                               int64_t elems_per_image, int64_t E, natinf_stream_t stream);
 
+/* Inpainting on the CIFAR10 form: known pixels overwritten with the data diffused to the current noise level
+ * (deps/score_sde_pytorch/controllable_generation.py:44-52, get_pc_inpainter).  The blend on its own, element e of image i:
+ *
+ *   out[e] = mask[e] ? fp32( fp32(known[e]*known_alpha_f32) + fp32(z[e]*known_std_f32) ) : x_in[e]
+ *
+ * z is what natinf_randn_philox_col_f32(..., seed, column = known_column) returns for that image and element (the same
+ * generator call, bit for bit); the two products and the sum are three fp32 roundings.  known_std_f32 == 0.0f: no draw is made
+ * and out = fp32(known*known_alpha_f32).  The blend is a SELECT, not the reference's x*(1-mask) + md*mask: for a 0/1 mask and
+ * finite values the two agree except for the sign of a zero, and a NaN of the unknown side stays out of the known pixels.
+ * `known`: device fp32.  `mask`: device uint8, one byte per element, non-zero = known, 4-byte aligned (read as one 32-bit
+ * word per element quad).  known_image_stride / mask_image_stride: elems_per_image (one row per image of the call) or 0 (one
+ * row shared by every image).  known_column >= 2^31: the noise columns of a matrix are at most N + 1, so the replacement
+ * draws never collide with them.  x_in and out may be the same buffer.  image_index / first_index / index_stride /
+ * elems_per_image as natinf_step_f64hist_noise.  NATINF_EINVAL, nothing launched: a NULL pointer, E % 4, elems_per_image not a
+ * multiple of 4 dividing E or with 2^32 quads or more, a stride that is neither 0 nor elems_per_image, `mask` not 4-byte aligned,
+ * known_column < 2^31.  The values of known_alpha_f32 and known_std_f32 are not inspected. */
+int natinf_known_blend_f32(const float* x_in, float* out, const float* known, const uint8_t* mask,
+                           int64_t known_image_stride, int64_t mask_image_stride,
+                           float known_alpha_f32, float known_std_f32, uint32_t known_column,
+                           uint64_t seed, const int64_t* image_index, int64_t first_index, int64_t index_stride,
+                           int64_t elems_per_image, int64_t E, natinf_stream_t stream);
+
+/* natinf_step_f64hist_noise with that blend applied to x_next in registers, before its one store: one launch per step, no
+ * second pass over x and no noise slab.  hist[k] and the unblended x_next are operation for operation those of
+ * natinf_step_f64hist_noise; x_next equals, byte for byte, natinf_step_f64hist_noise followed by natinf_known_blend_f32 with
+ * the same known / mask / strides / known_* / seed / index arguments, and hist[k] equals that of natinf_step_f64hist_noise.
+ * A deterministic matrix goes through as a one-term noise row (column 0, val_b[0] = fp32(B[k,0])): natinf_step_f64hist's bytes.
+ * NATINF_EINVAL, nothing launched: every refusal of natinf_step_f64hist_noise and of natinf_known_blend_f32. */
+int natinf_step_f64hist_inpaint(const float* x_k, const float* model_out, const float* noise,
+                                double* hist, float* x_next,
+                                const int32_t* idx, const double* val, int n_terms, double c_diag,
+                                const int32_t* idx_b, const float* val_b, int n_b,
+                                int k, double alpha, double sigma, float std_f32,
+                                uint64_t seed, const int64_t* image_index, int64_t first_index, int64_t index_stride,
+                                int64_t elems_per_image, int64_t E,
+                                const float* known, const uint8_t* mask, int64_t known_image_stride, int64_t mask_image_stride,
+                                float known_alpha_f32, float known_std_f32, uint32_t known_column, natinf_stream_t stream);
+
 /* src/CIFAR10NaturalInference.py:233-238 on its own: out = (float) sum_t hist[idx[t]]*val[t]. */
 int natinf_weighted_sum_f64(const double* hist, float* out,
                             const int32_t* idx, const double* val, int n_terms,

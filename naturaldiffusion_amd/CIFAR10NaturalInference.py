@@ -96,6 +96,47 @@ def philox_noise(indices, shape_per_image, seed: int, device="cuda:0", column: i
     return out
 
 
+def u8_to_centered(v) -> torch.Tensor:
+    """uint8 pixel values -> the centred fp32 value at the middle of the pixel's bin, fp32((v + 0.5)/255*2 - 1) evaluated in fp64: all 256
+    values come back exactly through ``to_pixel_from_centered`` (trunc((x+1)/2*255) sits half a level from either neighbour; v/255*2 - 1, the
+    bin's lower edge, would fall to v - 1 on a last-bit rounding).  255 maps to 1 + 1/255 and comes back through the clamp."""
+    v = torch.as_tensor(v)
+    return ((v.to(torch.float64) + 0.5) / 255.0 * 2.0 - 1.0).to(torch.float32)
+
+
+def prepare_known(known, mask, sample_count: int, known_final: str = "mean"):
+    """The inpainting arguments of ``generate_sharded`` -> (known fp32 [K, 3072] centred NCHW, mask uint8 [K', 3072]) on the CPU, K and K'
+    each ``sample_count`` (row i belongs to global image index i) or 1 (shared by every image).  ``known``: uint8 [K, 32, 32, 3] (the job's own
+    output format, mapped by ``u8_to_centered``) or fp32 [K, 3, 32, 32] centred.  ``mask``: bool / uint8 [K', 32, 32] (a pixel: broadcast over
+    the channels) or [K', 3, 32, 32]; non-zero = known.  Pure host code: every refusal comes before any GPU call."""
+    if known is None or mask is None:
+        raise ValueError("inpainting needs both known= and mask=")
+    if known_final not in ("mean", "data"):
+        raise ValueError('known_final must be "mean" or "data"')
+    known, mask = torch.as_tensor(known).cpu(), torch.as_tensor(mask).cpu()
+    if known.dtype == torch.uint8 and known.dim() == 4 and tuple(known.shape[1:]) == (32, 32, 3):
+        kf = u8_to_centered(known.permute(0, 3, 1, 2))
+    elif known.dtype == torch.float32 and known.dim() == 4 and tuple(known.shape[1:]) == (3, 32, 32):
+        kf = known
+    else:
+        raise ValueError("known must be uint8 [K, 32, 32, 3] or fp32 [K, 3, 32, 32] (centred)")
+    if mask.dtype not in (torch.bool, torch.uint8):
+        raise ValueError("mask must be bool or uint8")
+    if mask.dim() == 3 and tuple(mask.shape[1:]) == (32, 32):
+        mask = mask[:, None].expand(-1, 3, -1, -1)
+    elif not (mask.dim() == 4 and tuple(mask.shape[1:]) == (3, 32, 32)):
+        raise ValueError("mask must be [K, 32, 32] or [K, 3, 32, 32]")
+    for name, t in (("known", kf), ("mask", mask)):
+        if t.shape[0] not in (1, int(sample_count)):
+            raise ValueError(f"{name} must hold sample_count ({sample_count}) images or 1, not {t.shape[0]}")
+    return kf.reshape(kf.shape[0], -1).contiguous(), (mask != 0).to(torch.uint8).reshape(mask.shape[0], -1).contiguous()
+
+
+def gather_known(rows: torch.Tensor, batch: Sequence[int]) -> torch.Tensor:
+    """The rows of a ``prepare_known`` table a batch takes, flat: the rows at the batch's global indices, or the one shared row."""
+    return (rows[0] if rows.shape[0] == 1 else rows[torch.as_tensor(list(batch), dtype=torch.int64)]).reshape(-1)
+
+
 class BatchLanes:
     """The batch pipeline of ``natural_inference_tx`` / ``generate_sharded``: the batches of a generation job are independent
     trajectories (reference loop :287-309), so consecutive batches go to ``len(models)`` lanes -- one HIP stream, one denoiser handle and
@@ -124,11 +165,13 @@ class BatchLanes:
             self.samplers[k][n] = CifarNI(*self.coeff, n * 3 * 32 * 32, device=self.device, seed=self.seed, elems_per_image=3 * 32 * 32)
         return self.samplers[k][n]
 
-    def submit(self, n: int, noise=None, noise_fn=None, index=None) -> torch.Tensor:
+    def submit(self, n: int, noise=None, noise_fn=None, index=None, known=None, mask=None, known_final: str = "mean") -> torch.Tensor:
         """One batch of ``n`` images: ``noise`` (drawn on the CALLER's current stream) or ``noise_fn()`` (called on the lane's stream).
         ``index``: the images' global indices, which key the noise a stochastic matrix injects -- an int64 device tensor made on the
-        caller's stream, the int index of the first image, or ``(first, stride)`` (``CifarNI.step``).  Returns the uint8 [n, 32, 32, 3] DEVICE tensor the lane will fill."""
+        caller's stream, the int index of the first image, or ``(first, stride)`` (``CifarNI.step``).  ``known`` / ``mask`` (inpainting): device
+        tensors made on the caller's stream, forwarded to ``CifarNI.run``.  Returns the uint8 [n, 32, 32, 3] DEVICE tensor the lane will fill."""
         idx_t = isinstance(index, torch.Tensor)
+        inpaint = [t for t in (known, mask) if t is not None]
         k = self.count % len(self.models)
         self.count += 1
         st = self.streams[k]
@@ -138,17 +181,21 @@ class BatchLanes:
             # A lane's first launch is ordered behind everything the caller's stream has queued: the engine's workspace and packed weights (and
             # the blocks clone() got from the caching allocator, which may be recycled ones with work pending) were allocated THERE, and a
             # still-queued forward of lane 0's engine on the caller's stream would otherwise race with the lane's.  With `noise` every submit waits.
-            if st is not None and (noise is not None or idx_t or not self.joined[k]):
+            if st is not None and (noise is not None or idx_t or inpaint or not self.joined[k]):
                 st.wait_stream(torch.cuda.current_stream())
                 self.joined[k] = True
             if st is not None and noise is not None:
                 noise.record_stream(st)
             if st is not None and idx_t:
                 index.record_stream(st)
+            if st is not None:
+                for t in inpaint:
+                    t.record_stream(st)
             with torch.cuda.stream(st):
                 ni = self._sampler(k, n)                                # (first use allocates on the lane's stream)
                 z = noise if noise is not None else noise_fn()
-                pix = _to_pixel(ni.run(self.models[k], z, index=index), 1, to_cpu=False)
+                kw = dict(known=known, mask=mask, known_final=known_final) if inpaint else {}
+                pix = _to_pixel(ni.run(self.models[k], z, index=index, **kw), 1, to_cpu=False)
                 ev = torch.cuda.Event()
                 ev.record()
         self.pending[k].append(ev)
@@ -185,7 +232,8 @@ def _lane_models(model_fn, streams: int, n_batches: int):
 
 @torch.no_grad()
 def generate_sharded(model_fn, weight_path, sample_count: int, batch_size: int, rank: int = 0, world: int = 1,
-                     seed: int = 888, device="cuda:0", streams: int = 3, to_cpu: bool = True, coeff=None):
+                     seed: int = 888, device="cuda:0", streams: int = 3, to_cpu: bool = True, coeff=None,
+                     known=None, mask=None, known_final: str = "mean"):
     """Batch-sharded generation (BASELINE config 3): this rank generates the images whose
     global index is rank, rank+world, ... in batches of ``batch_size`` -- no collective on the data path -- on the two-lane pipeline
     of ``natural_inference_tx`` (``BatchLanes``): Philox noise keyed by the GLOBAL image index drawn on the lane's own stream, uint8 images
@@ -193,16 +241,33 @@ def generate_sharded(model_fn, weight_path, sample_count: int, batch_size: int, 
     ``model_fn``: an ``NCSNppEngine`` (cloned per lane), a sequence of callables (one lane each) or one callable (one lane).
     ``coeff``: (C, B, node_coeff) instead of a file (matrices from ``coeffgen``).  A stochastic matrix draws the noise it injects after each
     step from the same (seed, global index) key, column j of B as counter word 3: an image's whole noise is Philox(seed, global index, column).
+    ``known`` / ``mask`` (inpainting, ``prepare_known``): the pixels of image i that are given -- row i of each, or its only row -- come back as
+    ``known`` at the last level (``known_final="mean"``: alpha_N * known, the reference's ``x_mean``) or exactly as given (``"data"``), and the rest
+    of the image is generated around them: every step overwrites them with the data diffused to the step's level.
     Returns (uint8 images [n_local, 32, 32, 3], their global indices [n_local] int64 on the CPU)."""
     from .shard import rank_batches
+    inpaint = known is not None or mask is not None
+    if inpaint:
+        known, mask = prepare_known(known, mask, sample_count, known_final)
     C, B, node = coeff if coeff is not None else load_coeff_npz(weight_path)
     batches = list(rank_batches(sample_count, batch_size, rank, world))
     dev = torch.device(device)
     if not batches:
         return torch.empty((0, 32, 32, 3), dtype=torch.uint8, device="cpu" if to_cpu else dev), torch.empty(0, dtype=torch.int64)
     lanes = BatchLanes(_lane_models(model_fn, streams, len(batches)), C, B, node, dev, seed=seed)
+    shared = {}                                                          # a one-row table is uploaded once
     for batch in batches:
-        lanes.submit(len(batch), noise_fn=lambda b=batch: philox_noise(b, (3, 32, 32), seed, dev), index=(batch[0], world))   # = batch
+        kw = {}
+        if inpaint:
+            for name, rows in (("known", known), ("mask", mask)):
+                if rows.shape[0] == 1:
+                    if name not in shared:
+                        shared[name] = gather_known(rows, batch).to(dev)
+                    kw[name] = shared[name]
+                else:
+                    kw[name] = gather_known(rows, batch).to(dev)
+            kw["known_final"] = known_final
+        lanes.submit(len(batch), noise_fn=lambda b=batch: philox_noise(b, (3, 32, 32), seed, dev), index=(batch[0], world), **kw)   # = batch
     imgs = torch.cat(lanes.finish())
     idxs = torch.cat([torch.tensor(b, dtype=torch.int64) for b in batches])
     return (imgs.cpu() if to_cpu else imgs), idxs

@@ -536,6 +536,78 @@ __global__ __launch_bounds__(kBlock) void k_step_noise_f64(
     }
 }
 
+// ---- piece of the inpainting forms: known pixels re-noised to the level of the step's output ----
+// quad q of image img, xv the unconditioned value: element i with a non-zero mask byte becomes fp32(fp32(known*alpha) + fp32(z*std)), z the
+// Philox normals of column `column` (what natinf_randn_philox_col_f32 returns); the others keep xv.  A SELECT, not x*(1-mask) + md*mask: a NaN
+// of the unknown side stays out of the known pixels.  std == 0 (wave-uniform): no draw, fp32(known*alpha).  The draw is also skipped by the
+// lanes whose mask word is 0 (a wave without a known pixel branches over it).  The mask is read as one 32-bit word per quad.
+__device__ __forceinline__ float4 known_blend(float4 xv, const float* known, const uint8_t* mask, int64_t kstride, int64_t mstride,
+                                              int64_t img, int64_t q, int64_t qpi, float alpha, float stdv, uint32_t column,
+                                              uint64_t gi, uint32_t k0, uint32_t k1)
+{
+    // a stride is 0 or 4*qpi: the word index of the quad within the mask, the quad index within known
+    const int64_t mq = (mstride ? img * qpi : 0) + q, kq = (kstride ? img * qpi : 0) + q;
+    const uint32_t m = reinterpret_cast<const uint32_t*>(mask)[mq];
+    const float4 kv = reinterpret_cast<const float4*>(known)[kq];
+    float md[4] = {kv.x * alpha, kv.y * alpha, kv.z * alpha, kv.w * alpha};
+    if (stdv != 0.0f && m != 0u) {
+        const float4 z = philox_normals(gi, (uint64_t)q, column, k0, k1);
+        const float n0 = z.x * stdv, n1 = z.y * stdv, n2 = z.z * stdv, n3 = z.w * stdv;
+        md[0] = md[0] + n0; md[1] = md[1] + n1; md[2] = md[2] + n2; md[3] = md[3] + n3;
+    }
+    return make_float4((m & 0x000000FFu) ? md[0] : xv.x, (m & 0x0000FF00u) ? md[1] : xv.y,
+                       (m & 0x00FF0000u) ? md[2] : xv.z, (m & 0xFF000000u) ? md[3] : xv.w);
+}
+
+// the blend on its own: the first model input of an inpainting trajectory, and the definition the fused step is tested against.
+// x_in and out may be the same buffer (a thread reads its quad before it writes it): no __restrict__ on them.
+__global__ __launch_bounds__(kBlock) void k_known_blend(
+    const float4* x_in, float4* out, const float* __restrict__ known, const uint8_t* __restrict__ mask,
+    int64_t kstride, int64_t mstride, float kalpha, float kstd, uint32_t kcolumn,
+    const int64_t* __restrict__ index, int64_t first_index, int64_t index_stride, int64_t quads_per_image,
+    uint32_t k0, uint32_t k1, int64_t nvec)
+{
+    // one element quad per thread, no grid-stride loop (k_step_noise_f64)
+    const int64_t v = first_vec();
+    if (v < nvec) {
+        const int64_t img = v / quads_per_image, q = v - img * quads_per_image;
+        out[v] = known_blend(x_in[v], known, mask, kstride, mstride, img, q, quads_per_image, kalpha, kstd, kcolumn,
+                             global_index(index, first_index, index_stride, img), k0, k1);
+    }
+}
+
+// ------------------------------------------------------------------------------------------
+// CIFAR10 form, inpainting: k_step_noise_f64 operation for operation (hist[k] and the unblended x_next are its bytes), then known_blend in
+// registers before the one 16-byte store of x_next: no second pass over x, no noise slab.  x_next equals k_step_noise_f64 followed by
+// k_known_blend, byte for byte.
+// ------------------------------------------------------------------------------------------
+__global__ __launch_bounds__(kBlock) void k_step_inpaint_f64(
+    const float4* __restrict__ x_k, const float4* __restrict__ mout, const float4* __restrict__ noise,
+    double* __restrict__ hist, float4* __restrict__ x_next,
+    const int32_t* __restrict__ idx, const double* __restrict__ val, int n_terms, double c_diag,
+    const int32_t* __restrict__ idx_b, const float* __restrict__ val_b, int n_b,
+    const int64_t* __restrict__ index, int64_t first_index, int64_t index_stride, int64_t quads_per_image,
+    uint32_t k0, uint32_t k1, int k, double alpha, double sigma2, float stdv,
+    const float* __restrict__ known, const uint8_t* __restrict__ mask, int64_t kstride, int64_t mstride,
+    float kalpha, float kstd, uint32_t kcolumn, int64_t nvec, int64_t E)
+{
+    // one element quad per thread, no grid-stride loop (k_step_noise_f64: the loop's carried scalars make the hoisted
+    // Philox round keys spill SGPRs)
+    const int64_t v = first_vec();
+    if (v < nvec) {
+        double x0[4], acc[4] = {0.0, 0.0, 0.0, 0.0}, nacc[4] = {0.0, 0.0, 0.0, 0.0};
+        x0_from_score_f64(x0, x_k[v], mout[v], stdv, sigma2, alpha, hist + (int64_t)k * E, v);
+        wsum_f64(acc, hist, idx, val, n_terms, v, E);
+        acc_f64(acc, x0[0], x0[1], x0[2], x0[3], c_diag);
+
+        const int64_t img = v / quads_per_image, q = v - img * quads_per_image;
+        const uint64_t gi = global_index(index, first_index, index_stride, img);
+        noise_row_sum(nacc, noise, idx_b, val_b, n_b, v, gi, q, k0, k1);
+        x_next[v] = known_blend(combine(acc, nacc), known, mask, kstride, mstride, img, q, quads_per_image, kalpha, kstd, kcolumn,
+                                gi, k0, k1);
+    }
+}
+
 // ------------------------------------------------------------------------------------------
 // Validate form with the noise row generated in registers: k_step_f32prod with noise_row_sum in place of the row sum over a
 // hist_eps slab, so the two kernels give the same bytes and the (N+1) x E slab is gone.
@@ -609,6 +681,13 @@ inline bool image_ok(int64_t elems, int64_t E, int lanes = 4) { return elems > 0
 inline unsigned quad_blocks(int64_t nvec) {
     const int64_t blocks = (nvec + kBlock - 1) / kBlock;
     return blocks > INT32_MAX ? 0u : (unsigned)blocks;
+}
+
+// the known pixels of an inpainting call: both arrays given, each per-image stride 0 (one row shared by every image) or elems_per_image,
+// the mask readable as 32-bit words, and a replacement column no noise column of a matrix (<= N + 1) can collide with
+inline bool known_ok(const float* known, const uint8_t* mask, int64_t kstride, int64_t mstride, uint32_t column, int64_t elems_per_image) {
+    return known && mask && (kstride == 0 || kstride == elems_per_image) && (mstride == 0 || mstride == elems_per_image) &&
+           !((uintptr_t)mask & 3) && column >= 0x80000000u;
 }
 
 // Host-side check of a small device int32 array before a launch (the noise row of natinf_step_f32prod_noise, the slots of
@@ -748,6 +827,49 @@ int natinf_step_f64hist_noise(const float* x_k, const float* model_out, const fl
                        (const float4*)x_k, (const float4*)model_out, (const float4*)noise, hist, (float4*)x_next,
                        idx, val, n_terms, c_diag, idx_b, val_b, n_b, image_index, first_index, index_stride,
                        elems_per_image / 4, (uint32_t)seed, (uint32_t)(seed >> 32), k, alpha, sigma * sigma, std_f32,
+                       nvec, E);
+    return launched();
+}
+
+int natinf_known_blend_f32(const float* x_in, float* out, const float* known, const uint8_t* mask,
+                           int64_t known_image_stride, int64_t mask_image_stride,
+                           float known_alpha_f32, float known_std_f32, uint32_t known_column,
+                           uint64_t seed, const int64_t* image_index, int64_t first_index, int64_t index_stride,
+                           int64_t elems_per_image, int64_t E, natinf_stream_t stream)
+{
+    const int64_t nvec = vec_count(E, 4);
+    const unsigned blocks = quad_blocks(nvec);
+    if (!x_in || !out || !nvec || !image_ok(elems_per_image, E) || ((elems_per_image / 4) >> 32) || !blocks ||
+        !known_ok(known, mask, known_image_stride, mask_image_stride, known_column, elems_per_image))
+        return NATINF_EINVAL;
+    hipLaunchKernelGGL(k_known_blend, dim3(blocks), dim3(kBlock), 0, (hipStream_t)stream,
+                       (const float4*)x_in, (float4*)out, known, mask, known_image_stride, mask_image_stride,
+                       known_alpha_f32, known_std_f32, known_column, image_index, first_index, index_stride,
+                       elems_per_image / 4, (uint32_t)seed, (uint32_t)(seed >> 32), nvec);
+    return launched();
+}
+
+int natinf_step_f64hist_inpaint(const float* x_k, const float* model_out, const float* noise,
+                                double* hist, float* x_next,
+                                const int32_t* idx, const double* val, int n_terms, double c_diag,
+                                const int32_t* idx_b, const float* val_b, int n_b,
+                                int k, double alpha, double sigma, float std_f32,
+                                uint64_t seed, const int64_t* image_index, int64_t first_index, int64_t index_stride,
+                                int64_t elems_per_image, int64_t E,
+                                const float* known, const uint8_t* mask, int64_t known_image_stride, int64_t mask_image_stride,
+                                float known_alpha_f32, float known_std_f32, uint32_t known_column, natinf_stream_t stream)
+{
+    const int64_t nvec = vec_count(E, 4);
+    const unsigned blocks = quad_blocks(nvec);
+    if (!x_k || !model_out || !noise || !hist || !x_next || !terms_ok(idx, val, n_terms) || !terms_ok(idx_b, val_b, n_b) ||
+        k < 0 || !nvec || !image_ok(elems_per_image, E) || ((elems_per_image / 4) >> 32) || !blocks ||
+        !known_ok(known, mask, known_image_stride, mask_image_stride, known_column, elems_per_image))
+        return NATINF_EINVAL;
+    hipLaunchKernelGGL(k_step_inpaint_f64, dim3(blocks), dim3(kBlock), 0, (hipStream_t)stream,
+                       (const float4*)x_k, (const float4*)model_out, (const float4*)noise, hist, (float4*)x_next,
+                       idx, val, n_terms, c_diag, idx_b, val_b, n_b, image_index, first_index, index_stride,
+                       elems_per_image / 4, (uint32_t)seed, (uint32_t)(seed >> 32), k, alpha, sigma * sigma, std_f32,
+                       known, mask, known_image_stride, mask_image_stride, known_alpha_f32, known_std_f32, known_column,
                        nvec, E);
     return launched();
 }

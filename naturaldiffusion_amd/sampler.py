@@ -57,13 +57,61 @@ def _check_elems_per_image(epi: Optional[int], E: int, lanes: int = 4) -> None:
         raise ValueError(f"elems_per_image must be a positive multiple of {lanes} dividing the element count")
 
 
+KNOWN_COLUMN0 = 2 ** 31      # Philox column of the known-pixel draw at level 0; level j draws column KNOWN_COLUMN0 + j (a matrix's noise columns are <= N + 1)
+
+
+def known_schedule(node: np.ndarray, known_final: str = "mean"):
+    """The inpainting schedule of a node table [N+1, 3] (t, alpha, sigma) -> N + 1 triples (alpha fp32, std fp32, Philox column), as Python
+    floats / ints.  Entry 0 is the level of the first model input; entry k + 1 is what step k blends with: the level of x_{k+1}, the node
+    table's own.  The last entry draws nothing: ``known_final="mean"`` gives alpha_N * known (the reference returns
+    ``x_mean``), ``"data"`` gives the known pixels back as they were given (alpha 1)."""
+    if known_final not in ("mean", "data"):
+        raise ValueError('known_final must be "mean" or "data"')
+    node = np.asarray(node, np.float64)
+    n = node.shape[0] - 1
+    out = [(float(np.float32(node[j, 1])), float(np.float32(node[j, 2])), KNOWN_COLUMN0 + j) for j in range(n + 1)]
+    out[n] = (out[n][0] if known_final == "mean" else 1.0, 0.0, KNOWN_COLUMN0 + n)
+    return out
+
+
+def check_known(known, mask, n_elem: int, elems_per_image: Optional[int], *, seed, fast_f32: bool = False, device=None):
+    """The argument checks of an inpainting call, made before anything is launched -> (known image stride, mask image stride).
+    ``known``: flat contiguous fp32, ``mask``: flat contiguous uint8 (non-zero = known), each of ``n_elem`` elements (one row per image:
+    stride ``elems_per_image``) or ``elems_per_image`` elements (one row shared by every image: stride 0).  ``device`` None skips the
+    device check (host-side callers)."""
+    if known is None or mask is None:
+        raise ValueError("inpainting needs both known= and mask=")
+    if fast_f32:
+        raise ValueError("inpainting: the fast_f32 mode has no blend")
+    if seed is None:
+        raise ValueError("inpainting: the known pixels are re-noised at every level, which needs a seed (deterministic matrices too)")
+    if elems_per_image is None:
+        raise ValueError("inpainting: elems_per_image is needed to key the known-pixel noise")
+    epi = int(elems_per_image)
+    _check_elems_per_image(epi, n_elem)
+    strides = []
+    for name, t, dt in (("known", known, torch.float32), ("mask", mask, torch.uint8)):
+        if not isinstance(t, torch.Tensor) or t.dtype != dt or t.dim() != 1 or not t.is_contiguous():
+            raise ValueError(f"{name} must be a flat contiguous {str(dt).split('.')[-1]} tensor")
+        if t.numel() not in (n_elem, epi):
+            raise ValueError(f"{name} must have n_elem ({n_elem}) or elems_per_image ({epi}) elements, not {t.numel()}")
+        if device is not None and t.device != device:
+            raise ValueError(f"{name} must be on the sampler's device")
+        strides.append(epi if t.numel() == n_elem and n_elem != epi else 0)
+    return strides[0], strides[1]
+
+
 class CifarNI:
     """x_{k+1} = fp32(sum_j C[k,j]*x0_j) + fp32(B[k,0])*noise with x0_k = ((-out/std)*sigma^2 + x_k)/alpha.
 
     A stochastic matrix (``coeff.is_stochastic``: some B[k, j >= 1] != 0) adds the noise injected after each step,
     fp32(sum_j fp32(B[k,j]*eps_j)) in fp64 accumulation, eps_0 = ``noise`` and eps_j (j >= 1) drawn in the kernel from
     Philox(``seed``, global image index, column j) (include/natinf.h, natinf_step_f64hist_noise).  It needs ``seed``;
-    ``elems_per_image`` defaults to the per-image size of the noise ``run`` gets; the fp32 fast mode does not take it."""
+    ``elems_per_image`` defaults to the per-image size of the noise ``run`` gets; the fp32 fast mode does not take it.
+
+    Inpainting (``known=`` / ``mask=`` of ``step`` and ``run``; natinf_step_f64hist_inpaint): after every update the known pixels are
+    overwritten, inside the step's launch, with the data diffused to the level of the step's output (``known_schedule``).  It needs a
+    ``seed`` and ``elems_per_image`` for any matrix; a deterministic one goes through as a one-term noise row."""
 
     def __init__(self, C: np.ndarray, B: np.ndarray, node: np.ndarray, n_elem: int, device="cuda:0",
                  dense: bool = False, fast_f32: bool = False, stds=None, *, seed: Optional[int] = None,
@@ -97,13 +145,55 @@ class CifarNI:
         # (torch.exp on CPU differs in the last ulp between hosts -- so does the reference's own value)
         self.std = [vp_std_f32(self.node[k, 0]) for k in range(self.n_step)] if stds is None else [float(v) for v in stds]
         self.labels = [float(np.float32(self.node[k, 0]) * np.float32(999)) for k in range(self.n_step)]
+        self._rows_b0 = None
+        self._known_levels = {}
+
+    def _noise_rows(self) -> SparseRows:
+        """The noise rows an inpainting step passes: B's own for a stochastic matrix, else column 0 alone as a one-term row
+        (val_b[0] = fp32(B[k,0]): natinf_step_f64hist's bytes), made on first use."""
+        if self.stochastic:
+            return self.rows_b
+        if self._rows_b0 is None:
+            self._rows_b0 = SparseRows(self.B[:, :1], lambda k: 1, torch.float32, self.device, diag=False, dense=True)
+        return self._rows_b0
+
+    def _known_level(self, j: int, known_final: str):
+        if known_final not in self._known_levels:
+            self._known_levels[known_final] = known_schedule(self.node, known_final)
+        return self._known_levels[known_final][j]
+
+    def first_input(self, noise: torch.Tensor, known: torch.Tensor, mask: torch.Tensor, index=None,
+                    elems_per_image: Optional[int] = None, known_final: str = "mean") -> torch.Tensor:
+        """The first model input of an inpainting trajectory: ``noise`` with the known pixels at level 0 (natinf_known_blend_f32,
+        column 2^31) -> a new flat tensor; ``noise`` itself (eps_0 of every step) is left as it is."""
+        epi = self.epi if elems_per_image is None else int(elems_per_image)
+        noise = noise.reshape(-1)
+        if noise.dtype != torch.float32 or noise.numel() != self.E or not noise.is_contiguous():
+            raise ValueError("noise must be a contiguous fp32 tensor of n_elem elements")
+        ks, ms = check_known(known, mask, self.E, epi, seed=self.seed, fast_f32=self.fast, device=noise.device)
+        ka, kstd, kcol = self._known_level(0, known_final)
+        index, first, stride = image_index_args(index, self.E // epi, noise.device)
+        out = torch.empty_like(noise)
+        check(lib.natinf_known_blend_f32(ptr(noise), ptr(out), ptr(known), ptr(mask), ks, ms, ka, kstd, kcol, self.seed,
+                                         ptr(index), first, stride, epi, self.E, stream_ptr()), "natinf_known_blend_f32")
+        return out
 
     def step(self, k: int, x_k: torch.Tensor, model_out: torch.Tensor, noise: torch.Tensor,
-             x_next: Optional[torch.Tensor] = None, index=None, elems_per_image: Optional[int] = None) -> torch.Tensor:
+             x_next: Optional[torch.Tensor] = None, index=None, elems_per_image: Optional[int] = None, *,
+             known: Optional[torch.Tensor] = None, mask: Optional[torch.Tensor] = None, known_final: str = "mean") -> torch.Tensor:
         """``index`` (stochastic matrices): the batch's global image indices -- an int64 device tensor with one entry per
         image, an int ``first`` (image i is ``first + i``) or a pair ``(first, stride)`` (image i is ``first + i*stride``);
-        None = 0.  ``elems_per_image`` overrides the constructor's value for this call."""
+        None = 0.  ``elems_per_image`` overrides the constructor's value for this call.
+
+        ``known`` / ``mask`` (inpainting): flat fp32 / uint8 device tensors of ``n_elem`` elements (one row per image) or
+        ``elems_per_image`` elements (one row for every image); a non-zero mask byte marks a known element, which leaves the step as
+        ``known`` diffused to the level of x_{k+1} (``known_schedule``; ``known_final`` says what the last step leaves).  ``index`` keys
+        that noise too."""
         epi = self.epi if elems_per_image is None else int(elems_per_image)
+        inpaint = known is not None or mask is not None
+        if inpaint:                                                       # refusals first: nothing below touches the GPU before them
+            ks, ms = check_known(known, mask, self.E, epi, seed=self.seed, fast_f32=self.fast, device=x_k.device)
+            ka, kstd, kcol = self._known_level(k + 1, known_final)
         if x_next is None:
             x_next = _pingpong(self._x, k, x_k)
         for t in (x_k, model_out, noise):
@@ -112,6 +202,14 @@ class CifarNI:
         idx, val, n = self.rows.ptrs(k)
         r = self.rows.rows[k]
         a, s = float(self.node[k, 1]), float(self.node[k, 2])
+        if inpaint:
+            ib, vb, nb = self._noise_rows().ptrs(k)
+            index, first, stride = image_index_args(index, self.E // epi, x_k.device)
+            check(lib.natinf_step_f64hist_inpaint(ptr(x_k), ptr(model_out), ptr(noise), ptr(self.hist), ptr(x_next), idx, val, n,
+                                                  r.diag, ib, vb, nb, k, a, s, self.std[k], self.seed, ptr(index), first, stride,
+                                                  epi, self.E, ptr(known), ptr(mask), ks, ms, ka, kstd, kcol, stream_ptr()),
+                  "natinf_step_f64hist_inpaint")
+            return x_next
         if self.stochastic:
             if epi is None:
                 raise ValueError("stochastic NI matrix: elems_per_image is needed to key the injected noise")
@@ -127,11 +225,16 @@ class CifarNI:
                  a, s, self.std[k], b0, self.E, stream_ptr()), "natinf_step_f64hist")
         return x_next
 
-    def run(self, model_fn: Callable, noise: torch.Tensor, return_all: bool = False, index=None):
-        """``model_fn(x [B,...] fp32, labels [B] fp32) -> out`` (raw network output).  ``index``: see ``step``."""
+    def run(self, model_fn: Callable, noise: torch.Tensor, return_all: bool = False, index=None, *,
+            known: Optional[torch.Tensor] = None, mask: Optional[torch.Tensor] = None, known_final: str = "mean"):
+        """``model_fn(x [B,...] fp32, labels [B] fp32) -> out`` (raw network output).  ``index``: see ``step``.
+        ``known`` / ``mask`` (inpainting; any shape holding B or 1 images, ``mask`` uint8 or bool): the first model input is ``noise``
+        with the known pixels at level 0, and every step blends (``step``); with ``return_all`` entry 0 is that first input."""
         shape, B = noise.shape, noise.shape[0]
         noise = noise.contiguous()
         epi = self.epi if self.epi is not None else noise.numel() // B
+        if known is not None or mask is not None:
+            return self._run_inpaint(model_fn, noise, return_all, index, epi, known, mask, known_final)
         x, xs = noise, [noise]
         for k in range(self.n_step):
             labels = torch.full((B,), self.labels[k], dtype=torch.float32, device=self.device)
@@ -140,6 +243,22 @@ class CifarNI:
             # every step goes through self.step (callers wrap it per instance, e.g. bench.py's timed replica); a column-0
             # matrix gets exactly the four positional arguments it always got
             x = self.step(*args, index=index, elems_per_image=epi) if self.stochastic else self.step(*args)
+            if return_all:
+                x = x.clone()
+                xs.append(x.view(shape))
+        return xs if return_all else x.view(shape)
+
+    def _run_inpaint(self, model_fn, noise, return_all, index, epi, known, mask, known_final):
+        shape, B = noise.shape, noise.shape[0]
+        flat = lambda t: t if t is None else (t.view(torch.uint8) if t.dtype == torch.bool else t).reshape(-1)
+        known, mask = flat(known), flat(mask)
+        kw = dict(index=index, elems_per_image=epi, known=known, mask=mask, known_final=known_final)
+        x = self.first_input(noise, **kw)
+        xs = [x.view(shape)]
+        for k in range(self.n_step):
+            labels = torch.full((B,), self.labels[k], dtype=torch.float32, device=self.device)
+            out = model_fn(x.view(shape), labels)
+            x = self.step(k, x.reshape(-1), out.contiguous().reshape(-1), noise.reshape(-1), **kw)
             if return_all:
                 x = x.clone()
                 xs.append(x.view(shape))
