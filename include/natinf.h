@@ -141,6 +141,54 @@ int natinf_step_f64hist_inpaint(const float* x_k, const float* model_out, const 
                                 const float* known, const uint8_t* mask, int64_t known_image_stride, int64_t mask_image_stride,
                                 float known_alpha_f32, float known_std_f32, uint32_t known_column, natinf_stream_t stream);
 
+/* Colorization on the CIFAR10 form: the gray channel of a rotated colour space overwritten with the gray data diffused to the
+ * current noise level (deps/score_sde_pytorch/controllable_generation.py:85-181, get_pc_colorizer; :142 with mask = (1, 0, 0)).
+ * An image is three planes of P = elems_per_image / 3 elements (NCHW).  The blend on its own, pixel p of image i, with
+ * x = (x0, x1, x2) the values of planes 0, 1, 2 at p, M = basis and W = inverse (row-major, M[r][c] = basis[3*r + c]):
+ *
+ *   dot3(a,b,c; p,q,r) = fp32( fp32( fp32(a*p) + fp32(b*q) ) + fp32(c*r) )
+ *   u1    = dot3(x0,x1,x2; M[0][1],M[1][1],M[2][1])
+ *   u2    = dot3(x0,x1,x2; M[0][2],M[1][2],M[2][2])
+ *   u0    = gray_std_f32 != 0 ? fp32( fp32(gray_u[p]*gray_alpha_f32) + fp32(z[p]*gray_std_f32) ) : fp32(gray_u[p]*gray_alpha_f32)
+ *   out_c = dot3(u0,u1,u2; W[0][c],W[1][c],W[2][c])        c = 0, 1, 2
+ *
+ * No product and sum is ever fused.  The old latent channel 0 is fully replaced, so it is never computed.  z is what
+ * natinf_randn_philox_col_f32(..., seed, column = gray_column) returns for PLANE 0 of that image (the same generator call, bit
+ * for bit: the element quad of plane 0 is the pixel quad); gray_std_f32 == 0.0f: no draw is made.  Unlike the inpainting select,
+ * a NaN in x reaches all three outputs of its pixel: that is the rotation.
+ * `gray_u`: device fp32, one value per pixel: latent channel 0 of the known picture, dot3(k0,k1,k2; M[0][0],M[1][0],M[2][0]),
+ * prepared by the caller; read as one 16-byte load per pixel quad.  gray_image_stride: elems_per_image / 3 (one row per image of
+ * the call) or 0 (one picture shared by every image).  `basis`, `inverse`: HOST arrays of 9 floats, read at call time and carried
+ * to the kernel by value; the library hard-codes neither (any orthonormal basis and its inverse will do).
+ * Columns: a matrix's noise columns are 0..N+1, the inpainting draws 2^31 + level, the colorization draws 2^31 + 2^30 + level:
+ * the three families are disjoint for N < 2^30.  x_in and out may be the same buffer.  image_index / first_index / index_stride
+ * / elems_per_image as natinf_step_f64hist_noise.  NATINF_EINVAL, nothing launched: a NULL x_in, out, gray_u, basis or inverse,
+ * E % 4, elems_per_image not a multiple of 4 dividing E or with 2^32 quads or more, elems_per_image % 12 != 0 (three planes of
+ * whole quads), a gray_image_stride that is neither 0 nor elems_per_image / 3, gray_column < 0xC0000000.  The values of
+ * gray_alpha_f32, gray_std_f32 and the matrices are not inspected. */
+int natinf_color_blend_f32(const float* x_in, float* out, const float* gray_u, int64_t gray_image_stride,
+                           const float basis[9], const float inverse[9],
+                           float gray_alpha_f32, float gray_std_f32, uint32_t gray_column,
+                           uint64_t seed, const int64_t* image_index, int64_t first_index, int64_t index_stride,
+                           int64_t elems_per_image, int64_t E, natinf_stream_t stream);
+
+/* natinf_step_f64hist_noise with that blend applied to x_next in registers: one launch per step, one thread per pixel quad, which
+ * runs natinf_step_f64hist_noise's arithmetic on the element quad of each plane in turn, blends the three results and stores them.
+ * hist[k] and the unblended x_next are operation for operation those of natinf_step_f64hist_noise; x_next equals, byte for byte,
+ * natinf_step_f64hist_noise followed by natinf_color_blend_f32 with the same gray_* / basis / inverse / seed / index arguments, and
+ * hist[k] equals that of natinf_step_f64hist_noise.  A deterministic matrix goes through as a one-term noise row (column 0,
+ * val_b[0] = fp32(B[k,0])).  NATINF_EINVAL, nothing launched: every refusal of natinf_step_f64hist_noise and of
+ * natinf_color_blend_f32. */
+int natinf_step_f64hist_colorize(const float* x_k, const float* model_out, const float* noise,
+                                 double* hist, float* x_next,
+                                 const int32_t* idx, const double* val, int n_terms, double c_diag,
+                                 const int32_t* idx_b, const float* val_b, int n_b,
+                                 int k, double alpha, double sigma, float std_f32,
+                                 uint64_t seed, const int64_t* image_index, int64_t first_index, int64_t index_stride,
+                                 int64_t elems_per_image, int64_t E,
+                                 const float* gray_u, int64_t gray_image_stride, const float basis[9], const float inverse[9],
+                                 float gray_alpha_f32, float gray_std_f32, uint32_t gray_column, natinf_stream_t stream);
+
 /* src/CIFAR10NaturalInference.py:233-238 on its own: out = (float) sum_t hist[idx[t]]*val[t]. */
 int natinf_weighted_sum_f64(const double* hist, float* out,
                             const int32_t* idx, const double* val, int n_terms,

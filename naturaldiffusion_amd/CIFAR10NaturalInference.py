@@ -18,7 +18,7 @@ import torch
 from . import _lib
 from ._lib import lib, check, ptr, stream_ptr
 from .coeff import load_coeff_npz, SparseRows
-from .sampler import CifarNI, vp_std_f32
+from .sampler import CifarNI, decouple0_host, vp_std_f32
 
 root_path = Path(__file__).resolve().parent.parent
 
@@ -132,6 +132,27 @@ def prepare_known(known, mask, sample_count: int, known_final: str = "mean"):
     return kf.reshape(kf.shape[0], -1).contiguous(), (mask != 0).to(torch.uint8).reshape(mask.shape[0], -1).contiguous()
 
 
+def prepare_gray(gray, sample_count: int, known_final: str = "mean") -> torch.Tensor:
+    """The colorization argument of ``generate_sharded`` -> gray_u fp32 [K, 1024] on the CPU: latent channel 0 (``sampler.decouple0_host``) of the
+    known pictures, K ``sample_count`` (row i belongs to global image index i) or 1 (shared by every image).  ``gray``: uint8 [K, 32, 32] (a gray
+    picture, taken as (g, g, g)), uint8 [K, 32, 32, 3] or fp32 [K, 3, 32, 32] centred (of a colour picture its gray channel is taken).  uint8
+    values go through ``u8_to_centered``.  Pure host code: every refusal comes before any GPU call."""
+    if known_final not in ("mean", "data"):
+        raise ValueError('known_final must be "mean" or "data"')
+    gray = torch.as_tensor(gray).cpu()
+    if gray.dtype == torch.uint8 and gray.dim() == 3 and tuple(gray.shape[1:]) == (32, 32):
+        gf = u8_to_centered(gray)[:, None].expand(-1, 3, -1, -1)
+    elif gray.dtype == torch.uint8 and gray.dim() == 4 and tuple(gray.shape[1:]) == (32, 32, 3):
+        gf = u8_to_centered(gray.permute(0, 3, 1, 2))
+    elif gray.dtype == torch.float32 and gray.dim() == 4 and tuple(gray.shape[1:]) == (3, 32, 32):
+        gf = gray
+    else:
+        raise ValueError("gray must be uint8 [K, 32, 32], uint8 [K, 32, 32, 3] or fp32 [K, 3, 32, 32] (centred)")
+    if gf.shape[0] not in (1, int(sample_count)):
+        raise ValueError(f"gray must hold sample_count ({sample_count}) images or 1, not {gf.shape[0]}")
+    return torch.from_numpy(np.ascontiguousarray(decouple0_host(gf.contiguous().numpy()))).reshape(gf.shape[0], -1)
+
+
 def gather_known(rows: torch.Tensor, batch: Sequence[int]) -> torch.Tensor:
     """The rows of a ``prepare_known`` table a batch takes, flat: the rows at the batch's global indices, or the one shared row."""
     return (rows[0] if rows.shape[0] == 1 else rows[torch.as_tensor(list(batch), dtype=torch.int64)]).reshape(-1)
@@ -165,13 +186,13 @@ class BatchLanes:
             self.samplers[k][n] = CifarNI(*self.coeff, n * 3 * 32 * 32, device=self.device, seed=self.seed, elems_per_image=3 * 32 * 32)
         return self.samplers[k][n]
 
-    def submit(self, n: int, noise=None, noise_fn=None, index=None, known=None, mask=None, known_final: str = "mean") -> torch.Tensor:
+    def submit(self, n: int, noise=None, noise_fn=None, index=None, known=None, mask=None, known_final: str = "mean", gray_u=None) -> torch.Tensor:
         """One batch of ``n`` images: ``noise`` (drawn on the CALLER's current stream) or ``noise_fn()`` (called on the lane's stream).
         ``index``: the images' global indices, which key the noise a stochastic matrix injects -- an int64 device tensor made on the
         caller's stream, the int index of the first image, or ``(first, stride)`` (``CifarNI.step``).  ``known`` / ``mask`` (inpainting): device
-        tensors made on the caller's stream, forwarded to ``CifarNI.run``.  Returns the uint8 [n, 32, 32, 3] DEVICE tensor the lane will fill."""
+        tensors made on the caller's stream, forwarded to ``CifarNI.run``; ``gray_u`` (colorization) likewise.  Returns the uint8 [n, 32, 32, 3] DEVICE tensor the lane will fill."""
         idx_t = isinstance(index, torch.Tensor)
-        inpaint = [t for t in (known, mask) if t is not None]
+        inpaint = [t for t in (known, mask, gray_u) if t is not None]       # the lane is ordered behind their upload
         k = self.count % len(self.models)
         self.count += 1
         st = self.streams[k]
@@ -194,7 +215,9 @@ class BatchLanes:
             with torch.cuda.stream(st):
                 ni = self._sampler(k, n)                                # (first use allocates on the lane's stream)
                 z = noise if noise is not None else noise_fn()
-                kw = dict(known=known, mask=mask, known_final=known_final) if inpaint else {}
+                kw = dict(known=known, mask=mask, known_final=known_final) if known is not None or mask is not None else {}
+                if gray_u is not None:
+                    kw.update(gray_u=gray_u, known_final=known_final)
                 pix = _to_pixel(ni.run(self.models[k], z, index=index, **kw), 1, to_cpu=False)
                 ev = torch.cuda.Event()
                 ev.record()
@@ -233,7 +256,7 @@ def _lane_models(model_fn, streams: int, n_batches: int):
 @torch.no_grad()
 def generate_sharded(model_fn, weight_path, sample_count: int, batch_size: int, rank: int = 0, world: int = 1,
                      seed: int = 888, device="cuda:0", streams: int = 3, to_cpu: bool = True, coeff=None,
-                     known=None, mask=None, known_final: str = "mean"):
+                     known=None, mask=None, known_final: str = "mean", gray=None):
     """Batch-sharded generation (BASELINE config 3): this rank generates the images whose
     global index is rank, rank+world, ... in batches of ``batch_size`` -- no collective on the data path -- on the two-lane pipeline
     of ``natural_inference_tx`` (``BatchLanes``): Philox noise keyed by the GLOBAL image index drawn on the lane's own stream, uint8 images
@@ -244,9 +267,16 @@ def generate_sharded(model_fn, weight_path, sample_count: int, batch_size: int, 
     ``known`` / ``mask`` (inpainting, ``prepare_known``): the pixels of image i that are given -- row i of each, or its only row -- come back as
     ``known`` at the last level (``known_final="mean"``: alpha_N * known, the reference's ``x_mean``) or exactly as given (``"data"``), and the rest
     of the image is generated around them: every step overwrites them with the data diffused to the step's level.
+    ``gray`` (colorization, ``prepare_gray``): the gray picture of image i -- row i, or the only row -- comes back as the gray channel of the result
+    (at the last level for ``known_final="mean"``, as given for ``"data"``) and the colours are generated around it: every step overwrites latent
+    channel 0 of a rotated colour space with the gray data diffused to the step's level.  Not together with ``known`` / ``mask``.
     Returns (uint8 images [n_local, 32, 32, 3], their global indices [n_local] int64 on the CPU)."""
     from .shard import rank_batches
     inpaint = known is not None or mask is not None
+    if gray is not None:
+        if inpaint:
+            raise ValueError("gray (colorization) does not go with known / mask (inpainting)")
+        gray = prepare_gray(gray, sample_count, known_final)
     if inpaint:
         known, mask = prepare_known(known, mask, sample_count, known_final)
     C, B, node = coeff if coeff is not None else load_coeff_npz(weight_path)
@@ -266,6 +296,14 @@ def generate_sharded(model_fn, weight_path, sample_count: int, batch_size: int, 
                     kw[name] = shared[name]
                 else:
                     kw[name] = gather_known(rows, batch).to(dev)
+            kw["known_final"] = known_final
+        if gray is not None:
+            if gray.shape[0] == 1:
+                if "gray_u" not in shared:
+                    shared["gray_u"] = gather_known(gray, batch).to(dev)
+                kw["gray_u"] = shared["gray_u"]
+            else:
+                kw["gray_u"] = gather_known(gray, batch).to(dev)
             kw["known_final"] = known_final
         lanes.submit(len(batch), noise_fn=lambda b=batch: philox_noise(b, (3, 32, 32), seed, dev), index=(batch[0], world), **kw)   # = batch
     imgs = torch.cat(lanes.finish())

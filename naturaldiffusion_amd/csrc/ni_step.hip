@@ -608,6 +608,117 @@ __global__ __launch_bounds__(kBlock) void k_step_inpaint_f64(
     }
 }
 
+// ---- pieces of the colorization forms: the gray channel of a rotated colour space re-noised to the level of the step's output ----
+// a 3x3 fp32 matrix carried to the kernel by value, row-major m[3*i + j] = M[i][j]: the caller's basis or its inverse, neither is hard-coded here
+struct mat3 { float m[9]; };
+
+// fp32( fp32( fp32(a*p) + fp32(b*q) ) + fp32(c*r) ): three products, two sums, five roundings in this order (deps/score_sde_pytorch/
+// controllable_generation.py:115,119 is an einsum over the channel index; this is its ascending-index evaluation)
+__device__ __forceinline__ float dot3(float a, float b, float c, float p, float q, float r) {
+    const float ap = a * p, bq = b * q, cr = c * r;
+    const float s = ap + bq;
+    return s + cr;
+}
+
+// pixel quad pq of image img, x[c] the unconditioned values of plane c (one pixel per lane): rotate (x0, x1, x2) with M, replace latent channel 0
+// by fp32(fp32(gray_u*alpha) + fp32(z*std)), z the Philox normals of column `column` for plane 0 (the element quad of plane 0 IS the pixel quad:
+// what natinf_randn_philox_col_f32 returns there), rotate back with W.  The old channel 0 is fully replaced, so it is never computed.
+// std == 0 (wave-uniform): no draw, fp32(gray_u*alpha).  Unlike known_blend's select, a NaN of x reaches all three outputs of its pixel: that is
+// the rotation.  A stride is 0 or the pixel count of an image: gq is the quad index within gray_u.
+__device__ __forceinline__ void color_blend(float4 (&x)[3], const float* gray_u, int64_t gq, const mat3& M, const mat3& W,
+                                            float alpha, float stdv, uint32_t column, uint64_t gi, int64_t pq, uint32_t k0, uint32_t k1)
+{
+    const float4 gv = reinterpret_cast<const float4*>(gray_u)[gq];
+    float u0[4] = {gv.x * alpha, gv.y * alpha, gv.z * alpha, gv.w * alpha};
+    if (stdv != 0.0f) {
+        const float4 z = philox_normals(gi, (uint64_t)pq, column, k0, k1);
+        const float n0 = z.x * stdv, n1 = z.y * stdv, n2 = z.z * stdv, n3 = z.w * stdv;
+        u0[0] = u0[0] + n0; u0[1] = u0[1] + n1; u0[2] = u0[2] + n2; u0[3] = u0[3] + n3;
+    }
+    const float a[4] = {x[0].x, x[0].y, x[0].z, x[0].w}, b[4] = {x[1].x, x[1].y, x[1].z, x[1].w}, c[4] = {x[2].x, x[2].y, x[2].z, x[2].w};
+    float o[3][4];
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+        const float u1 = dot3(a[i], b[i], c[i], M.m[1], M.m[4], M.m[7]);
+        const float u2 = dot3(a[i], b[i], c[i], M.m[2], M.m[5], M.m[8]);
+#pragma unroll
+        for (int j = 0; j < 3; ++j) o[j][i] = dot3(u0[i], u1, u2, W.m[j], W.m[3 + j], W.m[6 + j]);
+    }
+#pragma unroll
+    for (int j = 0; j < 3; ++j) {
+        // the empty asm pins the four results of a plane in VGPRs at one point: without it the backend, which pairs the lanes into packed fp32
+        // operations, stores a quad as two 8-byte halves as each pair becomes ready
+        asm("" : "+v"(o[j][0]), "+v"(o[j][1]), "+v"(o[j][2]), "+v"(o[j][3]));
+        x[j] = make_float4(o[j][0], o[j][1], o[j][2], o[j][3]);
+    }
+}
+
+// the blend on its own: the first model input of a colorization trajectory, and the definition the fused step is tested against.  One pixel quad
+// per thread: its three element quads sit ppq quads apart (NCHW).  x_in and out may be the same buffer (a thread reads its three quads before it
+// writes them, and no other thread touches them): no __restrict__ on them.
+__global__ __launch_bounds__(kBlock) void k_color_blend(
+    const float4* x_in, float4* out, const float* __restrict__ gray_u, int64_t gstride, mat3 M, mat3 W,
+    float galpha, float gstd, uint32_t gcolumn,
+    const int64_t* __restrict__ index, int64_t first_index, int64_t index_stride, int64_t ppq,
+    uint32_t k0, uint32_t k1, int64_t npq)
+{
+    // no grid-stride loop (k_step_noise_f64)
+    const int64_t t = first_vec();
+    if (t < npq) {
+        const int64_t img = t / ppq, pq = t - img * ppq, v0 = img * 3 * ppq + pq;
+        float4 x[3] = {x_in[v0], x_in[v0 + ppq], x_in[v0 + 2 * ppq]};
+        color_blend(x, gray_u, (gstride ? img * ppq : 0) + pq, M, W, galpha, gstd, gcolumn,
+                    global_index(index, first_index, index_stride, img), pq, k0, k1);
+        out[v0] = x[0]; out[v0 + ppq] = x[1]; out[v0 + 2 * ppq] = x[2];
+    }
+}
+
+// the body of k_step_noise_f64 for element quad v (quad q of image img), operation for operation: hist[k] <- x0_k, the unblended x_next returned.
+// Only the float4 leaves: the fp64 accumulators of a plane are dead before the next plane's begin.
+__device__ __forceinline__ float4 noise_step_quad(
+    const float4* x_k, const float4* mout, const float4* noise, double* hist, const int32_t* idx, const double* val, int n_terms, double c_diag,
+    const int32_t* idx_b, const float* val_b, int n_b, uint64_t gi, int64_t q, uint32_t k0, uint32_t k1, int k, double alpha, double sigma2,
+    float stdv, int64_t v, int64_t E)
+{
+    double x0[4], acc[4] = {0.0, 0.0, 0.0, 0.0}, nacc[4] = {0.0, 0.0, 0.0, 0.0};
+    x0_from_score_f64(x0, x_k[v], mout[v], stdv, sigma2, alpha, hist + (int64_t)k * E, v);
+    wsum_f64(acc, hist, idx, val, n_terms, v, E);
+    acc_f64(acc, x0[0], x0[1], x0[2], x0[3], c_diag);
+    noise_row_sum(nacc, noise, idx_b, val_b, n_b, v, gi, q, k0, k1);
+    return combine(acc, nacc);
+}
+
+// ------------------------------------------------------------------------------------------
+// CIFAR10 form, colorization: one thread per PIXEL quad.  For each plane the thread runs k_step_noise_f64's body on that plane's element quad
+// (hist[k] and the unblended values are that kernel's bytes) and keeps the resulting float4 only, then color_blend on the three in registers and
+// three 16-byte stores: x_next equals k_step_noise_f64 followed by k_color_blend, byte for byte.
+// ------------------------------------------------------------------------------------------
+__global__ __launch_bounds__(kBlock) void k_step_colorize_f64(
+    const float4* __restrict__ x_k, const float4* __restrict__ mout, const float4* __restrict__ noise,
+    double* __restrict__ hist, float4* __restrict__ x_next,
+    const int32_t* __restrict__ idx, const double* __restrict__ val, int n_terms, double c_diag,
+    const int32_t* __restrict__ idx_b, const float* __restrict__ val_b, int n_b,
+    const int64_t* __restrict__ index, int64_t first_index, int64_t index_stride, int64_t ppq,
+    uint32_t k0, uint32_t k1, int k, double alpha, double sigma2, float stdv,
+    const float* __restrict__ gray_u, int64_t gstride, mat3 M, mat3 W, float galpha, float gstd, uint32_t gcolumn,
+    int64_t npq, int64_t E)
+{
+    // one pixel quad per thread, no grid-stride loop (k_step_noise_f64: the loop's carried scalars make the hoisted
+    // Philox round keys spill SGPRs)
+    const int64_t t = first_vec();
+    if (t < npq) {
+        const int64_t img = t / ppq, pq = t - img * ppq, v0 = img * 3 * ppq + pq;
+        const uint64_t gi = global_index(index, first_index, index_stride, img);
+        float4 x[3];
+#pragma unroll
+        for (int c = 0; c < 3; ++c)
+            x[c] = noise_step_quad(x_k, mout, noise, hist, idx, val, n_terms, c_diag, idx_b, val_b, n_b, gi, c * ppq + pq, k0, k1, k, alpha,
+                                   sigma2, stdv, v0 + c * ppq, E);
+        color_blend(x, gray_u, (gstride ? img * ppq : 0) + pq, M, W, galpha, gstd, gcolumn, gi, pq, k0, k1);
+        x_next[v0] = x[0]; x_next[v0 + ppq] = x[1]; x_next[v0 + 2 * ppq] = x[2];
+    }
+}
+
 // ------------------------------------------------------------------------------------------
 // Validate form with the noise row generated in registers: k_step_f32prod with noise_row_sum in place of the row sum over a
 // hist_eps slab, so the two kernels give the same bytes and the (N+1) x E slab is gone.
@@ -688,6 +799,17 @@ inline unsigned quad_blocks(int64_t nvec) {
 inline bool known_ok(const float* known, const uint8_t* mask, int64_t kstride, int64_t mstride, uint32_t column, int64_t elems_per_image) {
     return known && mask && (kstride == 0 || kstride == elems_per_image) && (mstride == 0 || mstride == elems_per_image) &&
            !((uintptr_t)mask & 3) && column >= 0x80000000u;
+}
+
+// the gray channel of a colorization call: the array and both matrices given, the image three planes of whole quads, a per-image stride of 0 (one
+// picture shared by every image) or the pixel count, and a column of the colorization family (>= 2^31 + 2^30: above the inpainting draws' levels)
+inline bool gray_ok(const float* gray_u, const float* basis, const float* inverse, int64_t gstride, uint32_t column, int64_t elems_per_image) {
+    return gray_u && basis && inverse && !(elems_per_image % 12) && (gstride == 0 || gstride == elems_per_image / 3) && column >= 0xC0000000u;
+}
+inline mat3 mat3_of(const float* p) {
+    mat3 r;
+    for (int i = 0; i < 9; ++i) r.m[i] = p[i];
+    return r;
 }
 
 // Host-side check of a small device int32 array before a launch (the noise row of natinf_step_f32prod_noise, the slots of
@@ -871,6 +993,51 @@ int natinf_step_f64hist_inpaint(const float* x_k, const float* model_out, const 
                        elems_per_image / 4, (uint32_t)seed, (uint32_t)(seed >> 32), k, alpha, sigma * sigma, std_f32,
                        known, mask, known_image_stride, mask_image_stride, known_alpha_f32, known_std_f32, known_column,
                        nvec, E);
+    return launched();
+}
+
+int natinf_color_blend_f32(const float* x_in, float* out, const float* gray_u, int64_t gray_image_stride,
+                           const float basis[9], const float inverse[9],
+                           float gray_alpha_f32, float gray_std_f32, uint32_t gray_column,
+                           uint64_t seed, const int64_t* image_index, int64_t first_index, int64_t index_stride,
+                           int64_t elems_per_image, int64_t E, natinf_stream_t stream)
+{
+    const int64_t nvec = vec_count(E, 4);
+    if (!x_in || !out || !nvec || !image_ok(elems_per_image, E) || ((elems_per_image / 4) >> 32) ||
+        !gray_ok(gray_u, basis, inverse, gray_image_stride, gray_column, elems_per_image))
+        return NATINF_EINVAL;
+    const int64_t npq = nvec / 3;                                   // pixel quads: one thread each
+    const unsigned blocks = quad_blocks(npq);
+    if (!blocks) return NATINF_EINVAL;
+    hipLaunchKernelGGL(k_color_blend, dim3(blocks), dim3(kBlock), 0, (hipStream_t)stream,
+                       (const float4*)x_in, (float4*)out, gray_u, gray_image_stride, mat3_of(basis), mat3_of(inverse),
+                       gray_alpha_f32, gray_std_f32, gray_column, image_index, first_index, index_stride,
+                       elems_per_image / 12, (uint32_t)seed, (uint32_t)(seed >> 32), npq);
+    return launched();
+}
+
+int natinf_step_f64hist_colorize(const float* x_k, const float* model_out, const float* noise,
+                                 double* hist, float* x_next,
+                                 const int32_t* idx, const double* val, int n_terms, double c_diag,
+                                 const int32_t* idx_b, const float* val_b, int n_b,
+                                 int k, double alpha, double sigma, float std_f32,
+                                 uint64_t seed, const int64_t* image_index, int64_t first_index, int64_t index_stride,
+                                 int64_t elems_per_image, int64_t E,
+                                 const float* gray_u, int64_t gray_image_stride, const float basis[9], const float inverse[9],
+                                 float gray_alpha_f32, float gray_std_f32, uint32_t gray_column, natinf_stream_t stream)
+{
+    const int64_t nvec = vec_count(E, 4);
+    if (!x_k || !model_out || !noise || !hist || !x_next || !terms_ok(idx, val, n_terms) || !terms_ok(idx_b, val_b, n_b) ||
+        k < 0 || !nvec || !image_ok(elems_per_image, E) || ((elems_per_image / 4) >> 32) || !quad_blocks(nvec) ||
+        !gray_ok(gray_u, basis, inverse, gray_image_stride, gray_column, elems_per_image))
+        return NATINF_EINVAL;
+    const int64_t npq = nvec / 3;                                   // pixel quads: one thread each
+    hipLaunchKernelGGL(k_step_colorize_f64, dim3(quad_blocks(npq)), dim3(kBlock), 0, (hipStream_t)stream,
+                       (const float4*)x_k, (const float4*)model_out, (const float4*)noise, hist, (float4*)x_next,
+                       idx, val, n_terms, c_diag, idx_b, val_b, n_b, image_index, first_index, index_stride,
+                       elems_per_image / 12, (uint32_t)seed, (uint32_t)(seed >> 32), k, alpha, sigma * sigma, std_f32,
+                       gray_u, gray_image_stride, mat3_of(basis), mat3_of(inverse), gray_alpha_f32, gray_std_f32, gray_column,
+                       npq, E);
     return launched();
 }
 

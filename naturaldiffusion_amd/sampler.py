@@ -101,6 +101,84 @@ def check_known(known, mask, n_elem: int, elems_per_image: Optional[int], *, see
     return strides[0], strides[1]
 
 
+# Colorization.  COLOR_M: the orthonormal basis of deps/score_sde_pytorch/controllable_generation.py:107-109, fp32, whose column 0 is the
+# gray direction: latent channel j of a pixel (R, G, B) is sum_i x_i * M[i][j].  COLOR_W = fp32(inv(fp64(COLOR_M))), as shortest round-trip literals
+# (it differs from fp32 torch.inverse(M) in one entry by one ulp; max |M W - I| = 2.6e-8 in fp64).  The library takes both as arguments.
+COLOR_M = np.array([[5.7735014e-01, -8.1649649e-01, 4.7008697e-08],
+                    [5.7735026e-01, 4.0824834e-01, 7.0710671e-01],
+                    [5.7735026e-01, 4.0824822e-01, -7.0710683e-01]], dtype=np.float32)
+COLOR_W = np.array([[5.7735032e-01, 5.7735032e-01, 5.7735026e-01],
+                    [-8.1649673e-01, 4.0824834e-01, 4.0824822e-01],
+                    [6.8825528e-08, 7.0710677e-01, -7.0710683e-01]], dtype=np.float32)
+COLOR_COLUMN0 = 2 ** 31 + 2 ** 30      # Philox column of the gray-channel draw at level 0; level j draws COLOR_COLUMN0 + j: disjoint from the matrix's columns and from KNOWN_COLUMN0 + j for N < 2^30
+
+
+def color_schedule(node: np.ndarray, known_final: str = "mean"):
+    """``known_schedule``'s levels with the colorization columns: N + 1 triples (alpha fp32, std fp32, COLOR_COLUMN0 + j); the last entry draws
+    nothing ("mean": alpha_N * gray_u, "data": gray_u as given)."""
+    return [(a, s, c - KNOWN_COLUMN0 + COLOR_COLUMN0) for a, s, c in known_schedule(node, known_final)]
+
+
+def _dot3(a, b, c, p, q, r):
+    """fp32(fp32(fp32(a*p) + fp32(b*q)) + fp32(c*r)) on fp32 numpy arrays and fp32 scalars: numpy rounds every operation to fp32"""
+    return (a * p + b * q) + c * r
+
+
+def decouple0_host(known) -> np.ndarray:
+    """Latent channel 0 (the gray value) of centred fp32 pictures [..., 3, H, W] -> fp32 [..., H, W]: dot3(k0, k1, k2; M[0][0], M[1][0], M[2][0])."""
+    k = np.asarray(known, dtype=np.float32)
+    if k.ndim < 3 or k.shape[-3] != 3:
+        raise ValueError("decouple0_host takes [..., 3, H, W]")
+    M = COLOR_M
+    return _dot3(k[..., 0, :, :], k[..., 1, :, :], k[..., 2, :, :], M[0, 0], M[1, 0], M[2, 0])
+
+
+def color_blend_host(x, gray_u, alpha, std, z0=None, M=COLOR_M, W=COLOR_W) -> np.ndarray:
+    """The colorization blend in numpy fp32, operation for operation the library's (include/natinf.h, natinf_color_blend_f32): ``x`` fp32 [..., 3, P],
+    ``gray_u`` and ``z0`` (the normals of plane 0; not read when std == 0) fp32 broadcastable to [..., P] -> fp32 [..., 3, P].  The CPU replay of a
+    GPU step, and what the GPU is compared against bit for bit."""
+    x = np.asarray(x, dtype=np.float32)
+    a, s = np.float32(alpha), np.float32(std)
+    x0, x1, x2 = x[..., 0, :], x[..., 1, :], x[..., 2, :]
+    u1 = _dot3(x0, x1, x2, M[0, 1], M[1, 1], M[2, 1])
+    u2 = _dot3(x0, x1, x2, M[0, 2], M[1, 2], M[2, 2])
+    u0 = np.asarray(gray_u, dtype=np.float32) * a
+    if s != 0:
+        u0 = u0 + np.asarray(z0, dtype=np.float32) * s
+    out = np.stack([_dot3(u0, u1, u2, W[0, i], W[1, i], W[2, i]) for i in range(3)], axis=-2)
+    assert out.dtype == np.float32
+    return out
+
+
+def _f9(m):
+    """a 3x3 matrix as the ``const float[9]`` host array the colorization entries read at call time (row-major)"""
+    import ctypes
+    return (ctypes.c_float * 9)(*np.asarray(m, dtype=np.float32).reshape(-1).tolist())
+
+
+def check_gray(gray_u, n_elem: int, elems_per_image: Optional[int], *, seed, fast_f32: bool = False, device=None) -> int:
+    """The argument checks of a colorization call, made before anything is launched -> the gray image stride.  ``gray_u``: flat contiguous fp32,
+    one value per pixel: ``n_elem / 3`` elements (one row per image: stride ``elems_per_image / 3``) or ``elems_per_image / 3`` (one picture shared by
+    every image: stride 0).  ``device`` None skips the device check (host-side callers)."""
+    if fast_f32:
+        raise ValueError("colorization: the fast_f32 mode has no blend")
+    if seed is None:
+        raise ValueError("colorization: the gray channel is re-noised at every level, which needs a seed (deterministic matrices too)")
+    if elems_per_image is None:
+        raise ValueError("colorization: elems_per_image is needed to key the gray-channel noise")
+    epi = int(elems_per_image)
+    _check_elems_per_image(epi, n_elem)
+    if epi % 12:
+        raise ValueError("colorization: an image is three planes of whole quads (elems_per_image % 12 == 0)")
+    if not isinstance(gray_u, torch.Tensor) or gray_u.dtype != torch.float32 or gray_u.dim() != 1 or not gray_u.is_contiguous():
+        raise ValueError("gray_u must be a flat contiguous float32 tensor")
+    if gray_u.numel() not in (n_elem // 3, epi // 3):
+        raise ValueError(f"gray_u must have n_elem / 3 ({n_elem // 3}) or elems_per_image / 3 ({epi // 3}) elements, not {gray_u.numel()}")
+    if device is not None and gray_u.device != device:
+        raise ValueError("gray_u must be on the sampler's device")
+    return epi // 3 if gray_u.numel() == n_elem // 3 and n_elem != epi else 0
+
+
 class CifarNI:
     """x_{k+1} = fp32(sum_j C[k,j]*x0_j) + fp32(B[k,0])*noise with x0_k = ((-out/std)*sigma^2 + x_k)/alpha.
 
@@ -111,7 +189,11 @@ class CifarNI:
 
     Inpainting (``known=`` / ``mask=`` of ``step`` and ``run``; natinf_step_f64hist_inpaint): after every update the known pixels are
     overwritten, inside the step's launch, with the data diffused to the level of the step's output (``known_schedule``).  It needs a
-    ``seed`` and ``elems_per_image`` for any matrix; a deterministic one goes through as a one-term noise row."""
+    ``seed`` and ``elems_per_image`` for any matrix; a deterministic one goes through as a one-term noise row.
+
+    Colorization (``gray_u=`` of ``first_input``, ``step`` and ``run``; natinf_step_f64hist_colorize): the same, on one channel of a rotated colour
+    space instead of a subset of the pixels -- after every update latent channel 0 of every pixel (``COLOR_M``) is overwritten with ``gray_u``
+    diffused to the level of the step's output (``color_schedule``).  ``gray_u`` together with ``known`` or ``mask`` is a ValueError."""
 
     def __init__(self, C: np.ndarray, B: np.ndarray, node: np.ndarray, n_elem: int, device="cuda:0",
                  dense: bool = False, fast_f32: bool = False, stds=None, *, seed: Optional[int] = None,
@@ -147,6 +229,7 @@ class CifarNI:
         self.labels = [float(np.float32(self.node[k, 0]) * np.float32(999)) for k in range(self.n_step)]
         self._rows_b0 = None
         self._known_levels = {}
+        self._color_levels = {}
 
     def _noise_rows(self) -> SparseRows:
         """The noise rows an inpainting step passes: B's own for a stochastic matrix, else column 0 alone as a one-term row
@@ -162,14 +245,30 @@ class CifarNI:
             self._known_levels[known_final] = known_schedule(self.node, known_final)
         return self._known_levels[known_final][j]
 
-    def first_input(self, noise: torch.Tensor, known: torch.Tensor, mask: torch.Tensor, index=None,
-                    elems_per_image: Optional[int] = None, known_final: str = "mean") -> torch.Tensor:
+    def _color_level(self, j: int, known_final: str):
+        if known_final not in self._color_levels:
+            self._color_levels[known_final] = color_schedule(self.node, known_final)
+        return self._color_levels[known_final][j]
+
+    def first_input(self, noise: torch.Tensor, known: Optional[torch.Tensor] = None, mask: Optional[torch.Tensor] = None, index=None,
+                    elems_per_image: Optional[int] = None, known_final: str = "mean", *, gray_u: Optional[torch.Tensor] = None) -> torch.Tensor:
         """The first model input of an inpainting trajectory: ``noise`` with the known pixels at level 0 (natinf_known_blend_f32,
-        column 2^31) -> a new flat tensor; ``noise`` itself (eps_0 of every step) is left as it is."""
+        column 2^31) -> a new flat tensor; ``noise`` itself (eps_0 of every step) is left as it is.  With ``gray_u`` (colorization) it is
+        ``noise`` with its gray channel at level 0 (natinf_color_blend_f32, column ``COLOR_COLUMN0``)."""
         epi = self.epi if elems_per_image is None else int(elems_per_image)
         noise = noise.reshape(-1)
         if noise.dtype != torch.float32 or noise.numel() != self.E or not noise.is_contiguous():
             raise ValueError("noise must be a contiguous fp32 tensor of n_elem elements")
+        if gray_u is not None:
+            if known is not None or mask is not None:
+                raise ValueError("gray_u (colorization) does not go with known / mask (inpainting)")
+            gs = check_gray(gray_u, self.E, epi, seed=self.seed, fast_f32=self.fast, device=noise.device)
+            ga, gstd, gcol = self._color_level(0, known_final)
+            index, first, stride = image_index_args(index, self.E // epi, noise.device)
+            out = torch.empty_like(noise)
+            check(lib.natinf_color_blend_f32(ptr(noise), ptr(out), ptr(gray_u), gs, _f9(COLOR_M), _f9(COLOR_W), ga, gstd, gcol, self.seed,
+                                             ptr(index), first, stride, epi, self.E, stream_ptr()), "natinf_color_blend_f32")
+            return out
         ks, ms = check_known(known, mask, self.E, epi, seed=self.seed, fast_f32=self.fast, device=noise.device)
         ka, kstd, kcol = self._known_level(0, known_final)
         index, first, stride = image_index_args(index, self.E // epi, noise.device)
@@ -180,7 +279,8 @@ class CifarNI:
 
     def step(self, k: int, x_k: torch.Tensor, model_out: torch.Tensor, noise: torch.Tensor,
              x_next: Optional[torch.Tensor] = None, index=None, elems_per_image: Optional[int] = None, *,
-             known: Optional[torch.Tensor] = None, mask: Optional[torch.Tensor] = None, known_final: str = "mean") -> torch.Tensor:
+             known: Optional[torch.Tensor] = None, mask: Optional[torch.Tensor] = None, known_final: str = "mean",
+             gray_u: Optional[torch.Tensor] = None) -> torch.Tensor:
         """``index`` (stochastic matrices): the batch's global image indices -- an int64 device tensor with one entry per
         image, an int ``first`` (image i is ``first + i``) or a pair ``(first, stride)`` (image i is ``first + i*stride``);
         None = 0.  ``elems_per_image`` overrides the constructor's value for this call.
@@ -188,9 +288,18 @@ class CifarNI:
         ``known`` / ``mask`` (inpainting): flat fp32 / uint8 device tensors of ``n_elem`` elements (one row per image) or
         ``elems_per_image`` elements (one row for every image); a non-zero mask byte marks a known element, which leaves the step as
         ``known`` diffused to the level of x_{k+1} (``known_schedule``; ``known_final`` says what the last step leaves).  ``index`` keys
-        that noise too."""
+        that noise too.
+
+        ``gray_u`` (colorization): a flat fp32 device tensor of ``n_elem / 3`` elements (one row per image) or ``elems_per_image / 3`` (one
+        picture for every image): latent channel 0 of the known picture (``decouple0_host``), which leaves the step, in every pixel's latent
+        channel 0, diffused to the level of x_{k+1} (``color_schedule``).  Not together with ``known`` / ``mask``."""
         epi = self.epi if elems_per_image is None else int(elems_per_image)
         inpaint = known is not None or mask is not None
+        if gray_u is not None:                                            # refusals first, as for inpainting
+            if inpaint:
+                raise ValueError("gray_u (colorization) does not go with known / mask (inpainting)")
+            gs = check_gray(gray_u, self.E, epi, seed=self.seed, fast_f32=self.fast, device=x_k.device)
+            ga, gstd, gcol = self._color_level(k + 1, known_final)
         if inpaint:                                                       # refusals first: nothing below touches the GPU before them
             ks, ms = check_known(known, mask, self.E, epi, seed=self.seed, fast_f32=self.fast, device=x_k.device)
             ka, kstd, kcol = self._known_level(k + 1, known_final)
@@ -210,6 +319,14 @@ class CifarNI:
                                                   epi, self.E, ptr(known), ptr(mask), ks, ms, ka, kstd, kcol, stream_ptr()),
                   "natinf_step_f64hist_inpaint")
             return x_next
+        if gray_u is not None:
+            ib, vb, nb = self._noise_rows().ptrs(k)
+            index, first, stride = image_index_args(index, self.E // epi, x_k.device)
+            check(lib.natinf_step_f64hist_colorize(ptr(x_k), ptr(model_out), ptr(noise), ptr(self.hist), ptr(x_next), idx, val, n,
+                                                   r.diag, ib, vb, nb, k, a, s, self.std[k], self.seed, ptr(index), first, stride,
+                                                   epi, self.E, ptr(gray_u), gs, _f9(COLOR_M), _f9(COLOR_W), ga, gstd, gcol, stream_ptr()),
+                  "natinf_step_f64hist_colorize")
+            return x_next
         if self.stochastic:
             if epi is None:
                 raise ValueError("stochastic NI matrix: elems_per_image is needed to key the injected noise")
@@ -226,13 +343,19 @@ class CifarNI:
         return x_next
 
     def run(self, model_fn: Callable, noise: torch.Tensor, return_all: bool = False, index=None, *,
-            known: Optional[torch.Tensor] = None, mask: Optional[torch.Tensor] = None, known_final: str = "mean"):
+            known: Optional[torch.Tensor] = None, mask: Optional[torch.Tensor] = None, known_final: str = "mean",
+            gray_u: Optional[torch.Tensor] = None):
         """``model_fn(x [B,...] fp32, labels [B] fp32) -> out`` (raw network output).  ``index``: see ``step``.
         ``known`` / ``mask`` (inpainting; any shape holding B or 1 images, ``mask`` uint8 or bool): the first model input is ``noise``
-        with the known pixels at level 0, and every step blends (``step``); with ``return_all`` entry 0 is that first input."""
+        with the known pixels at level 0, and every step blends (``step``); with ``return_all`` entry 0 is that first input.
+        ``gray_u`` (colorization; any shape holding B or 1 gray pictures of one value per pixel): the same with the gray-channel blend."""
         shape, B = noise.shape, noise.shape[0]
         noise = noise.contiguous()
         epi = self.epi if self.epi is not None else noise.numel() // B
+        if gray_u is not None:
+            if known is not None or mask is not None:
+                raise ValueError("gray_u (colorization) does not go with known / mask (inpainting)")
+            return self._run_colorize(model_fn, noise, return_all, index, epi, gray_u, known_final)
         if known is not None or mask is not None:
             return self._run_inpaint(model_fn, noise, return_all, index, epi, known, mask, known_final)
         x, xs = noise, [noise]
@@ -249,10 +372,17 @@ class CifarNI:
         return xs if return_all else x.view(shape)
 
     def _run_inpaint(self, model_fn, noise, return_all, index, epi, known, mask, known_final):
-        shape, B = noise.shape, noise.shape[0]
         flat = lambda t: t if t is None else (t.view(torch.uint8) if t.dtype == torch.bool else t).reshape(-1)
-        known, mask = flat(known), flat(mask)
-        kw = dict(index=index, elems_per_image=epi, known=known, mask=mask, known_final=known_final)
+        return self._run_blended(model_fn, noise, return_all, dict(index=index, elems_per_image=epi, known=flat(known), mask=flat(mask),
+                                                                   known_final=known_final))
+
+    def _run_colorize(self, model_fn, noise, return_all, index, epi, gray_u, known_final):
+        return self._run_blended(model_fn, noise, return_all, dict(index=index, elems_per_image=epi, gray_u=gray_u.reshape(-1),
+                                                                   known_final=known_final))
+
+    def _run_blended(self, model_fn, noise, return_all, kw):
+        """the loop of a conditioned trajectory: the first input and every step blend with the same arguments ``kw``"""
+        shape, B = noise.shape, noise.shape[0]
         x = self.first_input(noise, **kw)
         xs = [x.view(shape)]
         for k in range(self.n_step):
