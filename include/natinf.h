@@ -161,7 +161,8 @@ int natinf_step_f64hist_inpaint(const float* x_k, const float* model_out, const 
  * the call) or 0 (one picture shared by every image).  `basis`, `inverse`: HOST arrays of 9 floats, read at call time and carried
  * to the kernel by value; the library hard-codes neither (any orthonormal basis and its inverse will do).
  * Columns: a matrix's noise columns are 0..N+1, the inpainting draws 2^31 + level, the colorization draws 2^31 + 2^30 + level:
- * the three families are disjoint for N < 2^30.  x_in and out may be the same buffer.  image_index / first_index / index_stride
+ * the three families are disjoint for N < 2^30.  The AutoencoderKL posterior draw (natinf_vae.h) uses the one column 0xE0000000
+ * = 2^31 + 2^30 + 2^29: outside all three for level < 2^29.  x_in and out may be the same buffer.  image_index / first_index / index_stride
  * / elems_per_image as natinf_step_f64hist_noise.  NATINF_EINVAL, nothing launched: a NULL x_in, out, gray_u, basis or inverse,
  * E % 4, elems_per_image not a multiple of 4 dividing E or with 2^32 quads or more, elems_per_image % 12 != 0 (three planes of
  * whole quads), a gray_image_stride that is neither 0 nor elems_per_image / 3, gray_column < 0xC0000000.  The values of

@@ -206,6 +206,18 @@ def _setup(seed):
     return model, labels, len(labels)
 
 
+def _read_vae_weights(path):
+    """state dict of an AutoencoderKL: ``path`` is the model directory (``diffusion_pytorch_model.safetensors`` / ``.bin``) or a weights file"""
+    p = Path(path)
+    if p.is_dir():
+        cand = [p / "diffusion_pytorch_model.safetensors", p / "diffusion_pytorch_model.bin"]
+        p = next((c for c in cand if c.exists()), cand[0])
+    if p.suffix == ".safetensors":
+        from safetensors.torch import load_file
+        return load_file(str(p))
+    return torch.load(p, map_location="cpu", weights_only=True)
+
+
 def load_vae_decoder(path, max_batch=8, latent_res=32):
     """Reference :212-214 (``AutoencoderKL.from_pretrained(vae_path)``) on the gfx950 decoder engine (include/natinf_vae.h):
     ``path`` is the model directory (``diffusion_pytorch_model.safetensors`` / ``.bin``) or a weights file; one engine
@@ -213,16 +225,18 @@ def load_vae_decoder(path, max_batch=8, latent_res=32):
     from .vae import VAEDecoder, flatten_state_dict
     key = ("vae", str(path), max_batch, latent_res)
     if key not in _engine_cache:
-        p = Path(path)
-        if p.is_dir():
-            cand = [p / "diffusion_pytorch_model.safetensors", p / "diffusion_pytorch_model.bin"]
-            p = next((c for c in cand if c.exists()), cand[0])
-        if p.suffix == ".safetensors":
-            from safetensors.torch import load_file
-            sd = load_file(str(p))
-        else:
-            sd = torch.load(p, map_location="cpu", weights_only=True)
-        _engine_cache[key] = VAEDecoder(flatten_state_dict(sd, 4, prefix="decoder."), max_batch, latent_ch=4, latent_res=latent_res, device=device)
+        _engine_cache[key] = VAEDecoder(flatten_state_dict(_read_vae_weights(path), 4, prefix="decoder."), max_batch, latent_ch=4, latent_res=latent_res, device=device)
+    return _engine_cache[key]
+
+
+def load_vae_encoder(path, max_batch=16, latent_res=32):
+    """The other half of the same AutoencoderKL weights file on the gfx950 encoder engine (``vae.encode`` of
+    src/AnalyzeWeightedSumDegradation.py:56): ``path`` as for ``load_vae_decoder``; one engine per latent resolution
+    (32: 256x256 images, 64: 512x512)."""
+    from .vae import VAEEncoder, flatten_encoder_state_dict
+    key = ("vae_enc", str(path), max_batch, latent_res)
+    if key not in _engine_cache:
+        _engine_cache[key] = VAEEncoder(flatten_encoder_state_dict(_read_vae_weights(path), 4, prefix="encoder."), max_batch, latent_ch=4, latent_res=latent_res, device=device)
     return _engine_cache[key]
 
 

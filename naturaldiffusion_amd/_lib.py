@@ -161,6 +161,14 @@ SIGNATURES = {
     "natinf_vae_workspace_bytes": (C.c_int64, [_p, _i32]),
     "natinf_vae_load": (C.c_int, [_p, _p, _i64, _p, _i64, _p]),
     "natinf_vae_decode": (C.c_int, [_p, _p, _p, _i32, _p, _i64, _p]),
+    "natinf_vae_enc_create": (C.c_int, [C.POINTER(_p), _i32, _i32]),
+    "natinf_vae_enc_destroy": (C.c_int, [_p]),
+    "natinf_vae_enc_param_count": (C.c_int64, [_p]),
+    "natinf_vae_enc_packed_bytes": (C.c_int64, [_p]),
+    "natinf_vae_enc_workspace_bytes": (C.c_int64, [_p, _i32]),
+    "natinf_vae_enc_load": (C.c_int, [_p, _p, _i64, _p, _i64, _p]),
+    "natinf_vae_posterior_f32": (C.c_int, [_p, _p, _i64, _i32, _i64, _i32, _f32, _f32, C.c_uint64, _p, _i64, _i64, _p]),
+    "natinf_vae_encode": (C.c_int, [_p, _p, _p, _p, _i32, _i32, _f32, _f32, C.c_uint64, _p, _i64, _i64, _p, _i64, _p]),
 }
 
 for _name, (_res, _args) in SIGNATURES.items():

@@ -260,8 +260,9 @@ int choose_variant(const GemmArgs& g) {
         if (w128_ok(g) && (!g.gn_part || (1 << g.logHW) % 256 == 0)) return V_W128;
     }
     else if (g_force_variant > V_GENERIC && g_force_variant != V_CONV_GN && g_force_variant != V_FP8_256x256) {
-        // a forced tile must keep GroupNorm partial tiles inside one sample (e.g. 512-row tiles on the 16x16 level do not)
-        if (!g.gn_part || (g.taps == 9 && (1 << g.logHW) % variant_bm(g_force_variant) == 0)) return g_force_variant;
+        // a forced tile must keep GroupNorm partial tiles inside one sample (e.g. 512-row tiles on the 16x16 level do not): the launch has to say what a
+        // sample is -- a 3x3 launch always does, a plain GEMM when its caller sets logHW (the im2col'ed stride-2 convolutions; the V_W128 rule above reads the same field)
+        if (!g.gn_part || ((g.taps == 9 || g.logHW > 0) && (1 << g.logHW) % variant_bm(g_force_variant) == 0)) return g_force_variant;
     }
     // measured on the engine's layer shapes (tools/bench_gemm.py, profiles/r01): 256x256 two-stage for wide-N,
     // long-K layers; the 4-wave 256x128 ring (wave tile 128x64, 2 blocks/CU) for N = 128 and short-K layers;

@@ -23,6 +23,7 @@
 #include <stdint.h>
 #include <mutex>
 #include "natinf.h"
+#include "natinf_vae.h"
 
 #pragma clang fp contract(off)
 
@@ -778,6 +779,36 @@ __global__ __launch_bounds__(kBlock) void k_step_guided_f32prod(
     }
 }
 
+// ------------------------------------------------------------------------------------------
+// AutoencoderKL posterior (include/natinf_vae.h, natinf_vae_posterior_f32; the last launch of natinf_vae_encode): one thread per element quad
+// of the latents.  An image's moments are [mean: C*hw][logvar: C*hw], so quad q of the latents reads quad q of each half: two 16-byte loads, one
+// 16-byte store.  std*eps, mean + that, z - shift and its product with scale are four fp32 roundings; eps = philox_normals of the posterior
+// column, what natinf_randn_philox_col_f32 returns for (seed, global index, element).  sample == 0 (wave-uniform): no draw, the logvar half is not read.
+// ------------------------------------------------------------------------------------------
+__global__ __launch_bounds__(kBlock) void k_vae_posterior(
+    const float4* __restrict__ moments, float4* __restrict__ latents, int sample, float scale, float shift,
+    const int64_t* __restrict__ index, int64_t first_index, int64_t index_stride, int64_t quads_per_image,
+    uint32_t k0, uint32_t k1, int64_t nvec)
+{
+    // one element quad per thread, no grid-stride loop (k_step_noise_f64)
+    const int64_t v = first_vec();
+    if (v < nvec) {
+        const int64_t img = v / quads_per_image, q = v - img * quads_per_image;
+        const float4 mu = moments[2 * img * quads_per_image + q];
+        float z[4] = {mu.x, mu.y, mu.z, mu.w};
+        if (sample) {
+            const float4 lv = moments[(2 * img + 1) * quads_per_image + q];
+            const float4 e = philox_normals(global_index(index, first_index, index_stride, img), (uint64_t)q, NATINF_VAE_POSTERIOR_COLUMN, k0, k1);
+            const float s0 = expf(0.5f * fminf(fmaxf(lv.x, -30.0f), 20.0f)), s1 = expf(0.5f * fminf(fmaxf(lv.y, -30.0f), 20.0f));
+            const float s2 = expf(0.5f * fminf(fmaxf(lv.z, -30.0f), 20.0f)), s3 = expf(0.5f * fminf(fmaxf(lv.w, -30.0f), 20.0f));
+            const float n0 = s0 * e.x, n1 = s1 * e.y, n2 = s2 * e.z, n3 = s3 * e.w;
+            z[0] = z[0] + n0; z[1] = z[1] + n1; z[2] = z[2] + n2; z[3] = z[3] + n3;
+        }
+        const float d0 = z[0] - shift, d1 = z[1] - shift, d2 = z[2] - shift, d3 = z[3] - shift;
+        latents[v] = make_float4(d0 * scale, d1 * scale, d2 * scale, d3 * scale);
+    }
+}
+
 // ---- host side: argument checks and launch geometry shared by the ABI entries ----
 inline int launched() { return hipGetLastError() == hipSuccess ? NATINF_OK : NATINF_ELAUNCH; }
 inline bool terms_ok(const void* idx, const void* val, int n) { return n >= 0 && (n == 0 || (idx && val)); }
@@ -1201,6 +1232,22 @@ int natinf_weighted_mean_f16(const void* hist, void* out, const int32_t* idx, co
     if (!hist || !out || !terms_ok(idx, val, n_terms) || !nvec) return NATINF_EINVAL;
     hipLaunchKernelGGL(k_wmean_f16, dim3(grid_for(nvec)), dim3(kBlock), 0, (hipStream_t)stream,
                        (const h16*)hist, (h8*)out, idx, val, n_terms, w_total, nvec, E);
+    return launched();
+}
+
+int natinf_vae_posterior_f32(const float* moments, float* latents, int64_t n_images, int latent_ch, int64_t hw,
+                             int sample, float scale, float shift,
+                             uint64_t seed, const int64_t* image_index, int64_t first_index, int64_t index_stride,
+                             natinf_stream_t stream)
+{
+    if (!moments || !latents || n_images < 1 || latent_ch < 1 || hw < 1 || hw > (INT64_MAX >> 1) / latent_ch) return NATINF_EINVAL;
+    const int64_t qpi = vec_count((int64_t)latent_ch * hw, 4);
+    if (!qpi || (qpi >> 32) || n_images > INT64_MAX / (2 * qpi)) return NATINF_EINVAL;      // counter word 3 carries the column: the quad must fit word 2
+    const int64_t nvec = qpi * n_images;
+    const unsigned blocks = quad_blocks(nvec);
+    if (!blocks) return NATINF_EINVAL;
+    hipLaunchKernelGGL(k_vae_posterior, dim3(blocks), dim3(kBlock), 0, (hipStream_t)stream, (const float4*)moments, (float4*)latents,
+                       sample != 0, scale, shift, image_index, first_index, index_stride, qpi, (uint32_t)seed, (uint32_t)(seed >> 32), nvec);
     return launched();
 }
 

@@ -1,4 +1,4 @@
-// vae_engine.inc -- AutoencoderKL decoder engine (C ABI of include/natinf_vae.h); included after mmdit_engine.inc.
+// vae_engine.inc -- AutoencoderKL decoder and encoder engines (C ABI of include/natinf_vae.h); included after mmdit_engine.inc.
 //
 // The same building blocks as the NCSN++ engine: NHWC bf16 activations, 3x3 convolutions as LDS-DMA implicit GEMMs over
 // zero-bordered inputs (written by the GroupNorm-apply pass, which also does the nearest 2x up-sampling), 1x1 shortcut
@@ -6,8 +6,15 @@
 // GroupNorm statistics come from the producing GEMM's epilogue (per-tile quad partials, folded by k_gn_fold when a sample
 // has more than 64 tiles, then k_gn_finalize); below 16x16 the streaming kernel (one block per sample).  The mid-block
 // attention (single head, C = 512) runs as batched GEMMs with the scores materialised (1 GiB per sample at r = 128).
+//
+// The encoder (VaeEncBuilder) is the same blocks the other way: k_vae_images writes the zero-bordered 64-channel picture conv_in reads, the stride-2
+// convolutions run as k_inc_im2col + one GEMM (the `ddpm` plan's emit_downconv), conv_out leaves fp32 NCHW moments, k_vae_quant (vae_quant.hip) applies quant_conv,
+// and natinf_vae_encode ends with the posterior kernel of ni_step.hip.
 #include "natinf_vae.h"
 #include "engine_core.h"
+
+// the encoder's quant_conv pass k_vae_quant: vae_quant.hip
+namespace ncsn_vq { void launch(const float* m, const float* W, const float* bias, float* out, int N, int hw, int64_t total, void* stream); }
 
 namespace ncsn {
 
@@ -27,6 +34,27 @@ __global__ void k_vae_latents(const float* __restrict__ z, const float* __restri
         for (int k = 0; k < C; ++k) v += W[c * C + k] * z[(((int64_t)b * C + k) * r + yy - 1) * r + xx - 1];
     }
     y[i] = (bf16)v;
+}
+// encoder input: images fp32 [B][3][R][R] -> bf16 [B][R+2][R+2][64] with a zero border and zero channels >= 3 (what the padded K = 576 conv_in reads).
+// One thread per pixel of the padded output: eight 16-byte stores (its 128 bytes); consecutive threads read consecutive x of each plane.
+__global__ __launch_bounds__(256) void k_vae_images(const float* __restrict__ img, bf16* __restrict__ y, int R, int64_t total)
+{
+    const int64_t pix = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;       // over the padded output's pixels
+    if (pix >= total) return;
+    const int rp = R + 2;
+    const int xx = (int)(pix % rp), yy = (int)((pix / rp) % rp); const int64_t b = pix / ((int64_t)rp * rp);
+    uint4 v = make_uint4(0u, 0u, 0u, 0u);
+    if (xx >= 1 && xx <= R && yy >= 1 && yy <= R) {
+        const int64_t plane = (int64_t)R * R;
+        const float* p = img + (b * 3 * R + yy - 1) * R + xx - 1;
+        const bf16 c0 = (bf16)p[0], c1 = (bf16)p[plane], c2 = (bf16)p[2 * plane];
+        v.x = (uint32_t)__builtin_bit_cast(unsigned short, c0) | ((uint32_t)__builtin_bit_cast(unsigned short, c1) << 16);
+        v.y = (uint32_t)__builtin_bit_cast(unsigned short, c2);
+    }
+    uint4* d = reinterpret_cast<uint4*>(y + pix * 64);
+    d[0] = v;
+#pragma unroll
+    for (int k = 1; k < 8; ++k) d[k] = make_uint4(0u, 0u, 0u, 0u);
 }
 // (k_fill_f32: ncsnpp_kernels.h)
 // partial GroupNorm tables P [B][tps][quads] (float2 = sum, sum of squares) -> [B][tps / fold][quads]; grid (tps / fold, B).
@@ -71,12 +99,16 @@ __global__ __launch_bounds__(256) void k_softmax_rows_wide(const float* __restri
 struct natinf_vae : EngineCore {
     int Cl = 0, r = 0;
 };
+struct natinf_vae_enc : EngineCore {
+    int Cl = 0, r = 0;
+    int64_t mom_off = 0;                 // the moments' place in the workspace (bytes per image) when the caller passes none
+};
 
 namespace {
 
-struct VaeBuilder : PlanBuilder {
-    natinf_vae& E;
-    explicit VaeBuilder(natinf_vae& e) : PlanBuilder(e), E(e) {}
+// what the decoder's and the encoder's plans share: GroupNorm tables, ResnetBlock, mid-block attention
+struct VaeBase : PlanBuilder {
+    explicit VaeBase(EngineCore& e) : PlanBuilder(e) {}
 
     struct GNp { int64_t gamma, beta; };
     GNp take_gn(int C) { const int64_t g = take(C), b = take(C); return GNp{pack_f32(g, C), pack_f32(b, C)}; }
@@ -84,7 +116,6 @@ struct VaeBuilder : PlanBuilder {
         TRef t; t.off = arena.alloc((int64_t)(res + 2 * pad) * (res + 2 * pad) * C * 2); t.C = C; t.ld = C; t.res = res; t.pad = pad;
         return t;
     }
-    int64_t ident_sc = -1, ident_sh = -1;                 // scale 1 / shift 0 per (sample, channel): the plain up-sampling pass
     void pack_conv3(int64_t src, int64_t dst, int N, int Cin, int dst_ld) {
         E.packs.push_back([=](const PackCtx& p) {
             const int64_t n = (int64_t)N * Cin * 9;
@@ -250,9 +281,15 @@ struct VaeBuilder : PlanBuilder {
         arena.release(sc); arena.release(sh);
         return y;
     }
+};
+
+struct VaeBuilder : VaeBase {
+    natinf_vae& V;
+    explicit VaeBuilder(natinf_vae& e) : VaeBase(e), V(e) {}
+    int64_t ident_sc = -1, ident_sh = -1;                 // scale 1 / shift 0 per (sample, channel): the plain up-sampling pass
 
     void build() {
-        const int Cl = E.Cl, r = E.r;
+        const int Cl = V.Cl, r = V.r;
         // post_quant_conv (1x1 on the latents), then conv_in: latents -> zero-bordered 64-channel NHWC, 3x3 conv to 512
         const int64_t p_qw = take((int64_t)Cl * Cl), p_qb = take(Cl);
         const int64_t wq = pack_f32(p_qw, (int64_t)Cl * Cl), bq = pack_f32(p_qb, Cl);
@@ -327,6 +364,104 @@ struct VaeBuilder : PlanBuilder {
     void gn_apply_ident(const TRef& x, const TRef& u) { gn_apply(x, ident_sc, ident_sh, u, ACT_NONE, RS_UP); }
 };
 
+// images -> moments: conv_in, four down blocks of two ResnetBlocks (128, 256, 512, 512; a stride-2 convolution after the first three), the mid block,
+// GroupNorm + SiLU + conv_out, quant_conv.  The posterior is natinf_vae_encode's own last launch.
+struct VaeEncBuilder : VaeBase {
+    natinf_vae_enc& V;
+    explicit VaeEncBuilder(natinf_vae_enc& e) : VaeBase(e), V(e) {}
+
+    // diffusers' Downsample2D(padding = 0) after F.pad(x, (0, 1, 0, 1)): 3x3, stride 2, one zero row / column at the bottom / right.  As the `ddpm` plan's
+    // emit_downconv: an im2col pass (k_inc_im2col, K order tap-major) + one GEMM, whose epilogue writes the partial table the next norm1 consumes.
+    TRef downconv(const TRef& x, int C, Part& yp) {
+        const int rin = x.res, ro = rin / 2, Kd = 9 * C;
+        const int64_t pw = take((int64_t)C * C * 9), pb = take(C);
+        const int64_t w = wres((int64_t)C * Kd * 2);
+        E.packs.push_back([=](const PackCtx& p) {              // k = tap * C + c (the im2col order)
+            const int64_t n = (int64_t)C * C * 9;
+            hipLaunchKernelGGL(k_pack_conv, dim3(grid1d(n, 256, 1 << 30)), dim3(256), 0, p.stream, p.params + pw, reinterpret_cast<bf16*>(p.packed + w), C, C, 9, Kd, 0, C, 0, 1.0f);
+        });
+        const int64_t b = pack_f32(pb, C);
+        const int64_t col = arena.alloc((int64_t)ro * ro * Kd * 2);
+        TRef y = new_act(ro, C);
+        const Part pt = new_part(ro, C);
+        op([=](const Ctx& c) {
+            const int64_t M = (int64_t)c.B * ro * ro, total = M * (Kd / 8);
+            hipLaunchKernelGGL(k_inc_im2col, dim3(grid1d(total, 256, 1 << 30)), dim3(256), 0, c.stream, c.act(x), rin, rin, x.ld, C, 3, 3, 2, 0, 0, ro, ro, Kd,
+                               c.at<bf16>(col), total);
+            GemmArgs g = gemm_defaults();
+            g.a0 = c.at<bf16>(col); g.a0_ld = Kd; g.a0_C = Kd; g.M = (int)M; g.N = C; g.b = c.w<bf16>(w); g.b_ld = Kd; g.bias_n = c.w<float>(b);
+            g.log_rows_per_sample = 2 * ilog2(ro); g.logHW = 2 * ilog2(ro); g.logW = ilog2(ro);
+            g.c = c.act(y); g.c_ld = y.ld;
+            if (pt.valid()) { g.gn_part = c.at<float>(pt.off); g.gn_quads = pt.quads; }
+            const int bm = launch_gemm(g, c.stream);
+            if (pt.valid()) c.part_bm[pt.id] = bm;
+        });
+        arena.release(col);
+        yp = pt;
+        return y;
+    }
+
+    void build() {
+        const int Cl = V.Cl, r = V.r, R = 8 * r, N2 = 2 * Cl;
+        // the moments' workspace copy first: at offset 0 of the arena and never released (natinf_vae_encode hands it to the posterior launch)
+        V.mom_off = arena.alloc((int64_t)N2 * r * r * 4);
+        // conv_in: the picture as a zero-bordered 64-channel NHWC tensor, 3x3 conv (K padded to 576) to 128
+        const int64_t p_iw = take((int64_t)128 * 3 * 9), p_ib = take(128);
+        const int64_t wi = wres((int64_t)128 * 576 * 2);
+        E.packs.push_back([=](const PackCtx& p) {
+            const int64_t n = (int64_t)128 * 576;
+            hipLaunchKernelGGL(k_fill_bf16_zero, dim3(grid1d(n, 256, 1 << 30)), dim3(256), 0, p.stream, reinterpret_cast<bf16*>(p.packed + wi), n);
+        });
+        pack_conv3(p_iw, wi, 128, 3, 576);
+        const int64_t bi = pack_f32(p_ib, 128);
+        TRef z = new_act(R, 64, 1);
+        op([=](const Ctx& c) {
+            const int64_t tot = (int64_t)c.B * (R + 2) * (R + 2);
+            hipLaunchKernelGGL(k_vae_images, dim3(grid1d(tot, 256, 1 << 30)), dim3(256), 0, c.stream, c.x, c.act(z), R, tot);
+        });
+        TRef x = new_act(R, 128);
+        Part xp = conv(z, 64, 128, wi, 576, bi, x, nullptr, 0, nullptr), np;
+        arena.release(z.off);
+        auto step = [&](TRef nx) { arena.release(x.off); x = nx; free_part(xp); xp = np; np = Part(); };
+        const int chans[4] = {128, 256, 512, 512};
+        int cin = 128;
+        for (int i = 0; i < 4; ++i) {
+            const int cout = chans[i];
+            for (int j = 0; j < 2; ++j) step(resnet(x, xp, j == 0 ? cin : cout, cout, np));
+            if (i < 3) step(downconv(x, cout, np));
+            cin = cout;
+        }
+        step(resnet(x, xp, 512, 512, np));
+        step(attention(x, xp, np));
+        step(resnet(x, xp, 512, 512, np));
+        // conv_norm_out + SiLU + conv_out -> fp32 NCHW moments in the workspace, quant_conv on them -> the caller's moments (c.out)
+        const GNp gno = take_gn(512);
+        const int64_t p_ow = take((int64_t)N2 * 512 * 9), p_ob = take(N2);
+        const int64_t wo = wres((int64_t)N2 * 4608 * 2);
+        pack_conv3(p_ow, wo, N2, 512, 4608);
+        const int64_t bo = pack_f32(p_ob, N2);
+        const int64_t p_qw = take((int64_t)N2 * N2), p_qb = take(N2);
+        const int64_t wq = pack_f32(p_qw, (int64_t)N2 * N2), bq = pack_f32(p_qb, N2);
+        const int64_t sc = arena.alloc((int64_t)512 * 4), sh = arena.alloc((int64_t)512 * 4);
+        gn_stats(x, gno, sc, sh, xp);
+        TRef u = new_act(r, 512, 1);
+        gn_apply(x, sc, sh, u, ACT_SILU, RS_NONE);
+        const int64_t raw = arena.alloc((int64_t)N2 * r * r * 4);
+        const int logW = ilog2(r);
+        op([=](const Ctx& c) {
+            GemmArgs g = gemm_defaults();
+            g.a0 = c.act(u); g.a0_ld = u.ld; g.a0_C = 512; g.taps = 9; g.logW = logW; g.logHW = 2 * logW; g.a0_padded = 1;
+            g.M = c.B * r * r; g.N = N2; g.b = c.w<bf16>(wo); g.b_ld = 4608; g.bias_n = c.w<float>(bo);
+            g.c = c.at<float>(raw); g.c_mode = OUT_F32_NCHW;
+            launch_gemm(g, c.stream);
+            const int64_t tot = (int64_t)c.B * N2 * r * r;
+            ncsn_vq::launch(c.at<float>(raw), c.w<float>(wq), c.w<float>(bq), c.out, N2, r * r, tot, (void*)c.stream);
+        });
+        E.part_bm.assign(n_parts > 0 ? n_parts : 1, 128);
+        finish();
+    }
+};
+
 }  // namespace
 
 extern "C" {
@@ -350,6 +485,35 @@ int natinf_vae_load(natinf_vae_t h, const float* params_f32, int64_t n_params, v
 int natinf_vae_decode(natinf_vae_t h, const float* latents, float* images, int B, void* workspace, int64_t workspace_bytes, natinf_stream_t stream) {
     if (!h) return NATINF_EINVAL;
     return h->run(latents, latents, images, B, workspace, workspace_bytes, (hipStream_t)stream);
+}
+
+int natinf_vae_enc_create(natinf_vae_enc_t* out, int latent_ch, int latent_res) {
+    // (latent_res 128 -- 1024^2 images -- is the next size: include/natinf_vae.h)
+    if (!out || latent_ch < 1 || latent_ch > 32 || (latent_res != 8 && latent_res != 16 && latent_res != 32 && latent_res != 64)) return NATINF_EINVAL;
+    natinf_vae_enc* e = new natinf_vae_enc();
+    e->Cl = latent_ch; e->r = latent_res;
+    VaeEncBuilder b(*e);
+    b.build();
+    *out = e;
+    return NATINF_OK;
+}
+int natinf_vae_enc_destroy(natinf_vae_enc_t h) { if (!h) return NATINF_EINVAL; delete h; return NATINF_OK; }
+int64_t natinf_vae_enc_param_count(natinf_vae_enc_t h) { return h ? h->n_params : NATINF_EINVAL; }
+int64_t natinf_vae_enc_packed_bytes(natinf_vae_enc_t h) { return h ? h->packed_bytes : NATINF_EINVAL; }
+int64_t natinf_vae_enc_workspace_bytes(natinf_vae_enc_t h, int max_batch) { return h && max_batch > 0 ? h->ws_per_image * (int64_t)max_batch : NATINF_EINVAL; }
+int natinf_vae_enc_load(natinf_vae_enc_t h, const float* params_f32, int64_t n_params, void* packed, int64_t packed_bytes, natinf_stream_t stream) {
+    return h ? h->load(params_f32, n_params, packed, packed_bytes, (hipStream_t)stream) : NATINF_EINVAL;
+}
+int natinf_vae_encode(natinf_vae_enc_t h, const float* images, float* moments, float* latents, int B, int sample, float scale, float shift,
+                      uint64_t seed, const int64_t* image_index, int64_t first_index, int64_t index_stride,
+                      void* workspace, int64_t workspace_bytes, natinf_stream_t stream) {
+    if (!h || !images || (!moments && !latents) || !workspace || B < 1) return NATINF_EINVAL;
+    const int64_t hw = (int64_t)h->r * h->r;
+    if (((int64_t)h->Cl * hw) % 4 || (((int64_t)h->Cl * hw / 4) >> 32)) return NATINF_EINVAL;      // the posterior's refusals, before anything is launched
+    float* mom = moments ? moments : reinterpret_cast<float*>(reinterpret_cast<unsigned char*>(workspace) + h->mom_off * B);
+    const int rc = h->run(images, images, mom, B, workspace, workspace_bytes, (hipStream_t)stream);
+    if (rc != NATINF_OK || !latents) return rc;
+    return natinf_vae_posterior_f32(mom, latents, B, h->Cl, hw, sample, scale, shift, seed, image_index, first_index, index_stride, stream);
 }
 
 }  // extern "C"

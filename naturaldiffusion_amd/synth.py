@@ -126,3 +126,24 @@ def synthetic_vae_flat(latent_ch: int = 4, seed: int = 0) -> torch.Tensor:
             fan = int(np.prod(shape[1:]))
             parts.append((torch.randn(shape, generator=g) / fan ** 0.5).reshape(-1))
     return torch.cat(parts)
+
+
+def synthetic_vae_encoder_flat(latent_ch: int = 4, seed: int = 0) -> torch.Tensor:
+    """Stand-in AutoencoderKL encoder weights in ``vae.encoder_param_layout`` order with an identity ``quant_conv`` behind them: norm
+    scales 1, biases small, filters / matrices ~ N(0, 1 / fan_in)."""
+    from .vae import encoder_param_layout
+    g = torch.Generator().manual_seed(3000 + seed)
+    parts = []
+    for name, shape in encoder_param_layout(latent_ch):
+        if name == "quant_conv.weight":
+            parts.append(torch.eye(2 * latent_ch).reshape(-1))
+        elif name == "quant_conv.bias":
+            parts.append(torch.zeros(shape))
+        elif name.endswith(("norm1.weight", "norm2.weight", "norm.weight", "norm_out.weight")):
+            parts.append(torch.ones(shape).reshape(-1))
+        elif len(shape) == 1:
+            parts.append(0.01 * torch.randn(shape, generator=g))
+        else:
+            fan = int(np.prod(shape[1:]))
+            parts.append((torch.randn(shape, generator=g) / fan ** 0.5).reshape(-1))
+    return torch.cat(parts)
