@@ -195,6 +195,22 @@ int natinf_set_conv_gn_regw(int on);
 /* 1 (default; read when a plan is built): the up-sampling blocks at 16x16 / 32x32 read their half-resolution input inside the fused
  * convolution (nearest up-sampling in the patch fetch and in the residual fetch); 0: through the separate GroupNorm-apply + up-sample pass. */
 int natinf_set_fuse_up(int on);
+/* Read when a plan is built, needs natinf_set_fuse_up(1): Conv_0 of the 16 -> 32 up-sampling res-block, conv3x3(nearest_up_2x(act(GroupNorm(x)))), runs as the four 2x2
+ * convolutions over the 16x16 tensor it is equal to -- one per output parity, weights folded in fp32 at load (k_fold_up_conv), 4/9 of the multiply-accumulates: a
+ * GroupNorm-apply pass at 16x16 and one implicit-GEMM launch that natinf_ncsnpp_describe_gemms lists as `conv_gn_upfold` with its issued shape (M = B * 256, N = 1024,
+ * K = 4 * cin).  0: the nine-tap fused launch with the up-sampling in its fetch -- the plan, packed buffer and bytes of natinf_set_fuse_up alone. */
+int natinf_set_fuse_up_fold(int on);
+/* k_fold_up_conv on its own: w fp32 [N][cin][3][3] -> out_f32 (or NULL) fp32 [2][2][N][cin][2][2] = [a][b][n][c][ty][tx], the phase kernels times w_mul BEFORE the bf16
+ * rounding, summed rows first, then columns, each pair as (W[lo] + W[hi]); out_packed (or NULL; cin % 64 == 0) bf16 [4 N][4 cin], phase-major, K order
+ * ((c / 64) * 4 + 2 ty + tx) * 64 + c % 64. */
+int natinf_debug_fold_up_weights(const float* w, int N, int cin, float w_mul, float* out_f32, void* out_packed, natinf_stream_t stream);
+/* Conv_0 of the 16 -> 32 up-sampling block as a natinf_set_fuse_up_fold(1) plan runs it: k_fold_up_conv, the GroupNorm-apply + SiLU pass at 16x16, the up-fold launch.
+ *   out = (conv3x3(nearest_up_2x(silu(x * scale + shift)), w, zero padding) + bias_n + rowvec[sample]) * out_scale
+ * x: raw bf16 [B][16][16][cin], cin % 64 == 0; scale, shift: fp32 [B][cin], PLAIN (not times -log2 e); w: fp32 [N][cin][3][3], N = 256; w_packed: scratch, bf16 [4 N][4 cin];
+ * h_scratch: bf16 [B][18][18][cin]; bias_n: NULL or [N]; rowvec: NULL or fp32 [B][N]; out: bf16 [B * 1024][N]; gn_part: NULL or fp32 [4 B][N / 4][2] -- row 4 s + 2 a + b
+ * holds (sum, sum of squares) per 4-channel quad of sample s's 256 outputs of parity (a, b), i.e. of pixels (2 i + a, 2 j + b). */
+int natinf_debug_conv_up_fold(int B, int N, int cin, const void* x, const float* scale, const float* shift, const float* w, void* w_packed, void* h_scratch,
+                              const float* bias_n, const float* rowvec, float out_scale, void* out, float* gn_part, int iters, natinf_stream_t stream);
 /* 1 (default; read when a plan is built): the output head -- GroupNorm + SiLU + the 128 -> 3 convolution, fp32 NCHW -- is ONE launch
  * (k_head_conv); 0: GroupNorm-apply pass + implicit GEMM on an N = 3 column tile. */
 int natinf_set_fuse_head(int on);

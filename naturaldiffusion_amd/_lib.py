@@ -89,6 +89,9 @@ SIGNATURES = {
     "natinf_set_conv_gn_w128_min_k": (C.c_int, [_i32, _i32]),
     "natinf_set_conv_gn_regw": (C.c_int, [_i32]),
     "natinf_set_fuse_up": (C.c_int, [_i32]),
+    "natinf_set_fuse_up_fold": (C.c_int, [_i32]),
+    "natinf_debug_fold_up_weights": (C.c_int, [_p, _i32, _i32, _f32, _p, _p, _p]),
+    "natinf_debug_conv_up_fold": (C.c_int, [_i32, _i32, _i32, _p, _p, _p, _p, _p, _p, _p, _p, _f32, _p, _p, _i32, _p]),
     "natinf_set_fuse_head": (C.c_int, [_i32]),
     "natinf_set_fuse_gn8": (C.c_int, [_i32]),
     "natinf_set_fuse_gn4": (C.c_int, [_i32]),

@@ -115,17 +115,18 @@ __device__ __forceinline__ float4 gload_f4(const void* p) { const gf32x4 t = *as
 __device__ __forceinline__ void gstore_u4(void* p, uint4 v) { *as_global(reinterpret_cast<gu32x4*>(p)) = gu32x4{v.x, v.y, v.z, v.w}; }
 // slab -> global copy of sweeps SW .. NSW-1: all LDS reads first, then the stores (template recursion instead of an array of
 // kept values: hipcc left a 16-entry uint4 array in scratch memory here)
-template <int SW, int NSW, int RPS, int PROW, bool EDGE>
+// DSTEP: destination rows between two sweeps (RPS: the tile's rows are consecutive rows of the output; the up-fold epilogue -- UPW below -- scatters them)
+template <int SW, int NSW, int RPS, int PROW, bool EDGE, int DSTEP = RPS>
 struct SlabCopy {
     template <class T>
     static __device__ __forceinline__ void run(const unsigned char* src, T* dst, int64_t ld, int m, int M) {
         const uint4 v = *reinterpret_cast<const uint4*>(src + SW * RPS * PROW);
-        SlabCopy<SW + 1, NSW, RPS, PROW, EDGE>::run(src, dst, ld, m, M);
-        if (!EDGE || m + SW * RPS < M) gstore_u4(dst + (int64_t)(SW * RPS) * ld, v);
+        SlabCopy<SW + 1, NSW, RPS, PROW, EDGE, DSTEP>::run(src, dst, ld, m, M);
+        if (!EDGE || m + SW * RPS < M) gstore_u4(dst + (int64_t)(SW * DSTEP) * ld, v);
     }
 };
-template <int NSW, int RPS, int PROW, bool EDGE>
-struct SlabCopy<NSW, NSW, RPS, PROW, EDGE> {
+template <int NSW, int RPS, int PROW, bool EDGE, int DSTEP>
+struct SlabCopy<NSW, NSW, RPS, PROW, EDGE, DSTEP> {
     template <class T> static __device__ __forceinline__ void run(const unsigned char*, T*, int64_t, int, int) {}
 };
 // DEQ (fp8 operands): acc * (deq_m[row] * deq_n[col]) first, and a row bias (bias_m) next to the column terms.
@@ -139,10 +140,15 @@ struct SlabCopy<NSW, NSW, RPS, PROW, EDGE> {
 // rows 4 q + e a lane holds of both tiles are EIGHT consecutive channels 32 p + 8 q .. + 7 -- 16-byte residual loads and 16-byte slab writes instead of 8-byte ones.
 // SCALE_ALWAYS (k_conv_gn3: one block per CU, nothing hides the epilogue): the output scale is applied without the wave-uniform `scale != 1` branch around it -- 64 taken-or-not
 // branches per tile cost more than 64 packed multiplies by 1.0 (exact: the same bytes).
-template <int WM, int WN, int TM, int TN, class Cfg, int ACT, bool GN, bool RES, bool DEQ = false, bool OUT8 = false, int NSAMP = 1, bool FIN = false, bool PAIR = false, bool SCALE_ALWAYS = false>
+// UPW > 0 (k_conv_gn_upfold: Conv_0 of an up-sampling res-block as four 2x2 phase convolutions over its UPW x UPW input): the tile is ONE whole low-resolution image
+// and `z` carries its output parity (a, b) = (z >> 1, z & 1) instead of a batch index: tile row (i, j) is stored at pixel (2 i + a, 2 j + b) of the 2 UPW x 2 UPW output, the
+// GroupNorm partials go to row 4 (m0 / BM_) + z of the table (four phase tiles = four partial rows per sample); n0 is the column inside the phase.
+template <int WM, int WN, int TM, int TN, class Cfg, int ACT, bool GN, bool RES, bool DEQ = false, bool OUT8 = false, int NSAMP = 1, bool FIN = false, bool PAIR = false, bool SCALE_ALWAYS = false, int UPW = 0>
 __device__ __forceinline__ void packed_tile_epilogue(const GemmArgs& g, unsigned char* smem, f32x4 (&acc)[TM][TN],
                                                      int m0, int n0, int z, int tid, int lane, int wm, int wn)
 {
+    const int phase = UPW > 0 ? z : 0;
+    if constexpr (UPW > 0) z = 0;
     constexpr int BN_ = WN * TN * 16, BM_ = WM * TM * 16, THREADS = WM * WN * 64, PROW = OUT8 ? BN_ + 16 : Cfg::PROW;
     static_assert(!OUT8 || (!GN && !RES && TN % 2 == 0), "fp8 output: plain column terms only");
     static_assert(!PAIR || (TN % 2 == 0 && !OUT8 && !DEQ), "interleaved n-tile pairs: bf16 output");
@@ -373,6 +379,11 @@ __device__ __forceinline__ void packed_tile_epilogue(const GemmArgs& g, unsigned
             uint8_t* dst = reinterpret_cast<uint8_t*>(g.c) + (int64_t)z * g.c_bs + (int64_t)(m0 + rsub) * g.c_ld + n;
             if (m0 + BM_ <= g.M) SlabCopy<0, NSW, RPS, PROW, false>::run(src, dst, g.c_ld, m0 + rsub, g.M);
             else SlabCopy<0, NSW, RPS, PROW, true>::run(src, dst, g.c_ld, m0 + rsub, g.M);
+        } else if constexpr (UPW > 0) {
+            // a sweep is one row of the input image (RPS == UPW rows of the tile x all columns): its pixel (SW, rsub) -> output pixel (2 SW + a, 2 rsub + b)
+            static_assert(RPS == UPW && BM_ == UPW * UPW && NSAMP == 1 && !RES && !FIN, "up-fold epilogue: one UPW x UPW image per tile, one image row per sweep");
+            bf16* dst = reinterpret_cast<bf16*>(g.c) + ((int64_t)(m0 / BM_) * (4 * BM_) + (phase >> 1) * (2 * UPW) + (phase & 1) + 2 * rsub) * g.c_ld + n;
+            SlabCopy<0, NSW, RPS, PROW, false, 4 * UPW>::run(src, dst, g.c_ld, 0, 0);
         } else {
             bf16* dst = reinterpret_cast<bf16*>(g.c) + (int64_t)z * g.c_bs + (int64_t)(m0 + rsub) * g.c_ld + n;
             if (m0 + BM_ <= g.M) SlabCopy<0, NSW, RPS, PROW, false>::run(src, dst, g.c_ld, m0 + rsub, g.M);
@@ -391,7 +402,7 @@ __device__ __forceinline__ void packed_tile_epilogue(const GemmArgs& g, unsigned
                 float s = 0.f, qq = 0.f;
 #pragma unroll
                 for (int w = 0; w < WM; ++w) { s += sred[w * (BN_ / 4) + tid].x; qq += sred[w * (BN_ / 4) + tid].y; }
-                reinterpret_cast<float2*>(g.gn_part)[(int64_t)(m0 / BM_) * g.gn_quads + (n0 >> 2) + tid] = make_float2(s, qq);
+                reinterpret_cast<float2*>(g.gn_part)[(int64_t)(UPW > 0 ? (m0 / BM_) * 4 + phase : m0 / BM_) * g.gn_quads + (n0 >> 2) + tid] = make_float2(s, qq);
             }
         }
         if constexpr (FIN) {
@@ -770,17 +781,18 @@ __device__ __forceinline__ void direct_f32_epilogue(const GemmArgs& g, f32x4 (&a
 // 7 = the direct fp32 residual-stream epilogue (10 = its guarded form, GemmArgs::stream_guard); 8 = packed with row terms (a row bias: the V^T = W h^T + b GEMMs).  One epilogue per kernel: with both in one
 // kernel behind a run-time branch hipcc spilled inside the packed register phase (measured: isolated GEMMs +15..23 %, the
 // network 8 % SLOWER).
-template <int WM, int WN, int TM, int TN, class Cfg, int EPI, int NSAMP = 1, bool FIN = false, bool PAIR = false>
+template <int WM, int WN, int TM, int TN, class Cfg, int EPI, int NSAMP = 1, bool FIN = false, bool PAIR = false, int UPW = 0>
 __device__ __forceinline__ void tile_epilogue(const GemmArgs& g, unsigned char* smem, f32x4 (&acc)[TM][TN],
                                               int m0, int n0, int z, int tid, int lane, int wm, int wn)
 {
+    static_assert(UPW == 0 || EPI == 1 || EPI == 2, "up-fold tiles: the plain packed epilogue, with or without GroupNorm partials");
     if constexpr (EPI == 0) dma_tile_epilogue<WM, WN, TM, TN, Cfg>(g, smem, acc, m0, n0, z, tid, lane, wm, wn);
     else if constexpr (EPI == 7) direct_f32_epilogue<WM, WN, TM, TN>(g, acc, m0, n0, z, lane, wm, wn);
     else if constexpr (EPI == 10) direct_f32_epilogue<WM, WN, TM, TN, false, 0, true>(g, acc, m0, n0, z, lane, wm, wn);
     else {
         static_assert(Cfg::PACK_OK, "packed epilogue needs the whole bf16 tile in LDS");
         NATINF_TS(2);
-        packed_tile_epilogue<WM, WN, TM, TN, Cfg, EPI == 3 ? ACT_SILU : (EPI == 4 ? ACT_GELU_TANH : ACT_NONE), EPI == 2 || EPI == 6, EPI == 5 || EPI == 6, EPI == 8, false, NSAMP, FIN && (EPI == 2 || EPI == 6), PAIR>(
+        packed_tile_epilogue<WM, WN, TM, TN, Cfg, EPI == 3 ? ACT_SILU : (EPI == 4 ? ACT_GELU_TANH : ACT_NONE), EPI == 2 || EPI == 6, EPI == 5 || EPI == 6, EPI == 8, false, NSAMP, FIN && (EPI == 2 || EPI == 6), PAIR, false, UPW>(
             g, smem, acc, m0, n0, z, tid, lane, wm, wn);
     }
 }
@@ -834,12 +846,21 @@ struct PipeStep {
 // SPREAD = 2: the hand-counted LDS fragment pipeline (PipeStep), every wave issuing its own LDS-DMA pieces of tile k+1 in one burst after
 // the barrier; SPREAD = 6: the same loop with the burst issued by one wave per SIMD.  (The plain two-stage loop, SPREAD 0, the spread issue, 1,
 // and the two K-loop ablations, 3 / 4, are retired: git history before the commit that removed them.)
-template <int WM, int WN, int TM, int TN, int SPREAD = 0, int EPI = 0>
-__global__ __launch_bounds__(WM * WN * 64, 2) void k_gemm_dma(const GemmArgs g)
+// UPW > 0 (GemmArgs::taps == 4): Conv_0 of an up-sampling res-block, conv3x3(nearest_up_2x(h)), as the four 2x2 convolutions over the UPW x UPW image h it is equal
+// to -- one per output parity (a, b): output pixel (2 i + a, 2 j + b) reads input rows i + a - 1 + ty, columns j + b - 1 + tx (ty, tx in {0, 1}) with the row / column sums of
+// the 3x3 kernel as weights (k_fold_up_conv, up_fold.h): 4/9 of the multiply-accumulates.  a0 is the zero-bordered ACTIVATED input at the low resolution
+// (logW = log2 UPW; the border is the up-sampled image's zero padding: output row -1 is input row -1, output row 2 UPW is input row UPW), M its pixel count, N = four column
+// tiles of BN_ = cout: column tile nt IS the phase 2 a + b; b holds the phase-major folded weights [4 cout][4 cin] in K order ((c / 64) * 4 + 2 ty + tx) * 64 + c % 64; the
+// epilogue scatters the tile to its parity (packed_tile_epilogue, UPW).
+// (the body of both kernels below: k_gemm_dma keeps its six template parameters -- the names the ISA tests and the profiles know -- and k_conv_gn_upfold, up_fold.h, adds UPW)
+template <int WM, int WN, int TM, int TN, int SPREAD, int EPI, int UPW>
+__device__ __forceinline__ void gemm_dma_tile(const GemmArgs& g)
 {
     static_assert(SPREAD == 2 || SPREAD == 6, "the shipped K loops: hand pipeline (2), one issuing wave per SIMD (6)");
     using Cfg = DmaCfg<WM, WN, TM, TN>;
     constexpr int BM_ = Cfg::BM_, BN_ = Cfg::BN_, THREADS = Cfg::THREADS;
+    constexpr bool UPF = UPW > 0;
+    static_assert(!UPF || BM_ == UPW * UPW, "up-fold: a tile is one low-resolution image");
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     lds_poison();
     const int tid = threadIdx.x, lane = tid & 63;
@@ -852,6 +873,7 @@ __global__ __launch_bounds__(WM * WN * 64, 2) void k_gemm_dma(const GemmArgs g)
     tile_coords(tile, nM, nN, g.raster_g, mt_, nt_);
     const int m0 = mt_ * BM_, n0 = nt_ * BN_;
     const int z = blockIdx.z;
+    const int up_a = UPF ? (nt_ >> 1) & 1 : 0, up_b = UPF ? nt_ & 1 : 0;      // output parity of this column tile
 
     const bf16* a0 = g.a0 + (int64_t)z * g.a_bs;
     const bf16* a1 = g.a1 ? g.a1 + (int64_t)z * g.a_bs : nullptr;
@@ -868,14 +890,14 @@ __global__ __launch_bounds__(WM * WN * 64, 2) void k_gemm_dma(const GemmArgs g)
     uint64_t a_row[PAI], a_delta[PAI], b_row[PBI];
     // the first K-tile's pieces are requested as soon as each address exists (kt = 0: tap (-1, -1) of chunk 0, or column 0)
     typedef __attribute__((address_space(3))) void lds_void;
-    const int64_t ashift0 = g.taps == 9 ? (int64_t)(-Wp - 1) * g.a0_ld * 2 : 0;
+    const int64_t ashift0 = UPF ? (int64_t)((up_a - 1) * Wp + up_b - 1) * g.a0_ld * 2 : (g.taps == 9 ? (int64_t)(-Wp - 1) * g.a0_ld * 2 : 0);
 #pragma unroll
     for (int j = 0; j < PAI; ++j) {
         const int r = (wave * PAI + j) * 8 + (lane >> 3);
         const int lchunk = ((lane & 7) ^ ((r >> 1) & 7)) << 3;
         const int m = min(m0 + r, g.M - 1);
         int64_t off0;
-        if (g.taps == 9) {
+        if (UPF || g.taps == 9) {
             const int b = m >> g.logHW, p = m & ((1 << g.logHW) - 1), y = p >> g.logW, x = p & ((1 << g.logW) - 1);
             off0 = ((int64_t)(b * Hp + y + 1) * Wp + x + 1) * g.a0_ld;
         } else {
@@ -917,8 +939,9 @@ __global__ __launch_bounds__(WM * WN * 64, 2) void k_gemm_dma(const GemmArgs g)
         int64_t ashiftn; int kkn;
         if (seg0n) {
             int tap = 0, c0 = kn * BK;
-            if (g.taps == 9) { const int cch = kn / 9; tap = kn - 9 * cch; c0 = cch * BK; }
-            const int dy = g.taps == 9 ? tap / 3 - 1 : 0, dx = g.taps == 9 ? tap % 3 - 1 : 0;
+            if (UPF) { tap = kn & 3; c0 = (kn >> 2) * BK; }
+            else if (g.taps == 9) { const int cch = kn / 9; tap = kn - 9 * cch; c0 = cch * BK; }
+            const int dy = UPF ? up_a - 1 + (tap >> 1) : (g.taps == 9 ? tap / 3 - 1 : 0), dx = UPF ? up_b - 1 + (tap & 1) : (g.taps == 9 ? tap % 3 - 1 : 0);
             ashiftn = ((int64_t)(dy * Wp + dx) * g.a0_ld + c0) * 2; kkn = kn * BK;
         } else {
             ashiftn = (int64_t)(kn - nk0) * BK * 2; kkn = K0 + (kn - nk0) * BK;
@@ -955,8 +978,11 @@ __global__ __launch_bounds__(WM * WN * 64, 2) void k_gemm_dma(const GemmArgs g)
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // next tile's LDS-DMA has landed (explicit: not left to the compiler's tracking)
         __syncthreads();
     }
-    tile_epilogue<WM, WN, TM, TN, typename Cfg::Epi, EPI>(g, smem, acc, m0, n0, z, tid, lane, wm, wn);
+    if constexpr (UPF) tile_epilogue<WM, WN, TM, TN, typename Cfg::Epi, EPI, 1, false, false, UPW>(g, smem, acc, m0, 0, 2 * up_a + up_b, tid, lane, wm, wn);
+    else tile_epilogue<WM, WN, TM, TN, typename Cfg::Epi, EPI>(g, smem, acc, m0, n0, z, tid, lane, wm, wn);
 }
+template <int WM, int WN, int TM, int TN, int SPREAD = 0, int EPI = 0>
+__global__ __launch_bounds__(WM * WN * 64, 2) void k_gemm_dma(const GemmArgs g) { gemm_dma_tile<WM, WN, TM, TN, SPREAD, EPI, 0>(g); }
 
 
 // ------------------------------------------------------------------------------------------------

@@ -32,6 +32,8 @@ namespace { bool configure_ncsnpp_kernels();         // ncsnpp.hip: the output h
 namespace ncsn_sg { bool configure(); bool has_tile(int variant); void launch_tile(const void* gemm_args, int variant, int raster, void* stream);
                     void launch_fp8(const void* gemm_args, int mxa, int w128, int raster, void* stream); void launch_splitk_reduce(const void* gemm_args, int slices, void* stream);
                     void launch_patch_embed(const float* z, const float* Wt, const float* bias, const float* pos, float* x, int C, int g, int D, int64_t rows, int x_f16, uint32_t* guard, void* stream); }
+// the up-fold launch and its weight fold (up_fold.hip, a translation unit of its own as well): Conv_0 of the 16 -> 32 up-sampling block as four 2x2 phase convolutions
+namespace ncsn_upf { bool configure(); void launch(const void* gemm_args, int epi, void* stream); void fold(const float* w, void* dst_bf16, float* dst_f32, int N, int Cin, float wmul, void* stream); }
 namespace ncsn_cg3 { bool configure(); int tile_rows(int shape); int tile_cols(int shape); void launch(const void* gemm_args, int shape, int epi, void* stream); }
 
 namespace {
@@ -181,6 +183,10 @@ template <class... S> void launch_conv_gn2(FamList<S...>, int res, int bm, int e
     ((S::takes(res, bm) && (launch_family<S>(e, g, s), true)) || ...);
 }
 
+// (2b) Conv_0 of the 16 -> 32 up-sampling res-block as four 2x2 phase convolutions over its 16x16 input (GemmArgs::taps == 4; up_fold.h, ncsn_upf): the hand-pipelined
+// 256 x 256 tile -- one input image x one phase (256 output channels) -- with the packed epilogues 1 / 2 scattering to the phase's output parity
+constexpr int UPFOLD_W = 16, UPFOLD_BM = UPFOLD_W * UPFOLD_W, UPFOLD_BN = 256;
+
 // (3) fp8 operands: the eight-wave 256 x 256 tile (gemm_fp8.h) and the four-wave one (gemm_w128.h), each with plain or E8M0-scaled A x four epilogues
 constexpr unsigned EPI_FP8 = 0xF;
 template <bool MXA> struct FamF8     { using Cfg = CfgD256x256; static constexpr unsigned EPI = EPI_FP8; template <int E> static constexpr auto kernel() { return &k_gemm_fp8<MXA, E>; } };
@@ -191,7 +197,7 @@ bool configure_gemm_kernels() {
     bool ok = hipFuncSetAttribute(reinterpret_cast<const void*>(&k_gemm_bf16), hipFuncAttributeMaxDynamicSharedMemorySize,
                                   GEMM_LDS_BYTES) == hipSuccess;
     ok = ok && set_lds<CfgR128x128>(&k_gemm_ring<2, 2, 4, 4, 4, 9>) && set_lds<W128Cfg>(&k_gemm_w128<9>) &&
-         configure_families(GemmFamilies{}) && configure_families(ConvGnShapes{}) && configure_families(Fp8Families{}) &&
+         configure_families(GemmFamilies{}) && configure_families(ConvGnShapes{}) && ncsn_upf::configure() && configure_families(Fp8Families{}) &&
          ncsn_cg3::configure() && ncsn_sg::configure() && ::configure_conv_ring() && configure_ncsnpp_kernels() && configure_dit_attention() && configure_flash_attention();
     if (!ok) (void)hipGetLastError();
     return ok;
@@ -426,7 +432,23 @@ int launch_gemm(const GemmArgs& g0, hipStream_t s) {
     g_gemm_prof.end(r, s);
     return bm;
 }
+// the up-fold launch (ncsn_upf::launch): the zero-bordered activated 16x16 input, N = 4 phases x 256 channels, column terms and GroupNorm partials only.  Returns its epilogue, 0 = not one
+inline int up_fold_epi(const GemmArgs& g) {
+    if (g.taps != 4 || !g.a0_padded || g.a1 || g.gn_scale || g.batch != 1 || g.logW != 4 || g.logHW != 8 || g.log_rows_per_sample != 8 || g.a0_C <= 0 || g.a0_C % BK ||
+        g.N != 4 * UPFOLD_BN || g.M <= 0 || g.M % UPFOLD_BM || g.b_ld != 4 * g.a0_C || g.resid || g.c_ld % 8) return 0;
+    GemmArgs t = g; t.epi_fp32_slab = 0;
+    const int e = packed_epi(t, UPFOLD_BM);
+    return (e == 1 || e == 2) ? e : 0;
+}
 int launch_gemm_run(const GemmArgs& g0, hipStream_t s) {
+    if (g0.taps == 4) {
+        // four phase tiles per sample = four GroupNorm partial rows per sample of the 32x32 output: 256 output pixels per row
+        const int e = up_fold_epi(g0);
+        if (!e) { if (g_record) record_gemm(g0, "invalid_conv_gn_upfold", 0); else g_launch_error = 1; return 256; }
+        if (g_record) { record_gemm(g0, "conv_gn_upfold", e); return 256; }      // the ISSUED shape: low-resolution M, N = 4 x 256, K = 4 cin
+        ncsn_upf::launch(&g0, e, (void*)s);
+        return 256;
+    }
     if (g_force_variant == V_AUTO) {
         const int S8 = w128_splitk_slices(g0);
         if (S8 > 1) {

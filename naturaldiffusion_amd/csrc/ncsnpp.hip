@@ -64,6 +64,9 @@ int g_fuse_fin = 3;                // natinf_set_fuse_fin (read when a plan is B
 int g_fuse_gn4 = 1;                // natinf_set_fuse_gn4 (read when a plan is BUILT): the 4x4 level on the fused kernel too (four images per 64-pixel tile) instead of
                                    // k_gn_apply + split-K GEMM + k_splitk_reduce + k_gn_stats
 int g_fuse_gn = 1;                 // natinf_set_fuse_gn (read when a plan is BUILT): GroupNorm-apply + SiLU inside the consuming 3x3 conv
+constexpr int UP_FOLD_DEFAULT = 1;
+int g_fuse_up_fold = UP_FOLD_DEFAULT;   // natinf_set_fuse_up_fold (read when a plan is BUILT): Conv_0 of the 16 -> 32 up-sampling block as four 2x2 phase convolutions over its 16x16 input
+                                   // (k_fold_up_conv + k_gn_apply at 16x16 + k_conv_gn_upfold: 4/9 of the multiply-accumulates) instead of a nine-tap launch with the up-sampling in its fetch
 int g_fuse_up = 1;                 // natinf_set_fuse_up (read when a plan is BUILT): up blocks at 16x16 / 32x32 fetch their input up-sampled inside k_conv_gn2
 
 }  // namespace
@@ -183,6 +186,11 @@ struct Builder : PlanBuilder {        // (wtop: the packed-weight bump pointer i
                                reinterpret_cast<bf16*>(p.packed + dst), N, ld, cin, c1);
         });
     }
+    void pack_fold_up(int64_t src, int64_t dst, int N, int Cin, float wmul) {      // [N][Cin][3][3] fp32 -> the phase-major folded 2x2 kernels [4 N][4 Cin] bf16 (k_fold_up_conv)
+        E.packs.push_back([=](const PackCtx& p) {
+            ncsn_upf::fold(p.params + src, p.packed + dst, nullptr, N, Cin, wmul, (void*)p.stream);
+        });
+    }
     void pack_transpose(int64_t src, int64_t dst, int K, int N, int dst_ld) {
         E.packs.push_back([=](const PackCtx& p) {
             hipLaunchKernelGGL(k_pack_transpose, dim3(grid1d((int64_t)K * N, 256, 1 << 30)), dim3(256), 0, p.stream,
@@ -247,11 +255,15 @@ struct Builder : PlanBuilder {        // (wtop: the packed-weight bump pointer i
         const bool fusable_res = g_fuse_gn && (ro == 32 || ro == 16 || (ro == 8 && g_fuse_gn8 && cout % 256 == 0) || (ro == 4 && g_fuse_gn4 && cout % 256 == 0));
         const bool fuse1 = fusable_res && cout % BK == 0;                               // Conv_1
         const bool fuse_up = fuse1 && ro > 8 && g_fuse_up && m.up && cin % BK == 0 && cout % 128 == 0;   // up block: the 2x up-sampling of both branches happens in the fetches
-        const bool fuse = (fusable_res && !m.up && !m.down && cin % BK == 0) || fuse_up;            // Conv_0
+        // ... or (natinf_set_fuse_up_fold, the 16 -> 32 block) not at all: Conv_0 runs as four 2x2 phase convolutions over the ACTIVATED 16x16 tensor -- a k_gn_apply pass at the low
+        // resolution, then the up-fold launch (gemm_launch.h, up_fold.h) with the folded weights; Conv_1 and its shortcut segment keep the up-sampling fetch (a1_up)
+        const bool fold_up = fuse_up && g_fuse_up_fold && !ddpm && ro == 2 * UPFOLD_W && cout == UPFOLD_BN;
+        const bool fuse = (fusable_res && !m.up && !m.down && cin % BK == 0) || (fuse_up && !fold_up);            // Conv_0
         const float LOG2E = 1.4426950408889634f, LN2 = 0.6931471805599453f;
         const float gn_mul = fuse ? -LOG2E : 1.0f, w_mul = fuse ? -LN2 : 1.0f, gn_mul1 = fuse1 ? -LOG2E : 1.0f, w_mul1 = fuse1 ? -LN2 : 1.0f;
-        const int64_t w0 = wres((int64_t)cout * K0a * 2), w1 = wres((int64_t)cout * K1tot * 2);
-        pack_conv(p_c0w, w0, cout, cin, 9, K0a, 0, cin, w_mul);
+        const int64_t w0 = wres((int64_t)cout * (fold_up ? 16 * cin : K0a) * 2), w1 = wres((int64_t)cout * K1tot * 2);
+        if (fold_up) pack_fold_up(p_c0w, w0, cout, cin, w_mul);
+        else pack_conv(p_c0w, w0, cout, cin, 9, K0a, 0, cin, w_mul);
         pack_conv(p_c1w, w1, cout, cout, 9, K1tot, 0, cout, w_mul1);
         if (shortcut && !ddpm) pack_conv(p_c2w, w1, cout, cin, 1, K1tot, 9 * cout, cin);
         if (shortcut && ddpm) pack_transpose(p_c2w, w1 + (int64_t)9 * cout * 2, cin, cout, K1tot);      // NIN_0.W is [in][out] (layers.py:546-555)
@@ -270,7 +282,10 @@ struct Builder : PlanBuilder {        // (wtop: the packed-weight bump pointer i
         int64_t sc = own_sc, sh = own_sh;                 // GroupNorm_0's table: this block's buffers, or the one x's producer wrote
         emit_gn_stats(x, gn0, sc, sh, gn_mul);
         TRef h, xr;
-        if (!fuse) {
+        if (fold_up) {
+            h = new_act(m.res, cin, 1);                   // activated, zero-bordered, at the INPUT resolution
+            emit_gn_apply(x, sc, sh, h, nullptr, ACT_SILU, RS_NONE);
+        } else if (!fuse) {
             h = new_act(ro, cin, 1);
             if (m.up || m.down) xr = new_act(ro, cin);
             emit_gn_apply(x, sc, sh, h, (m.up || m.down) ? &xr : nullptr, ACT_SILU, m.up ? RS_UP : (m.down ? RS_DOWN : RS_NONE));
@@ -283,8 +298,18 @@ struct Builder : PlanBuilder {        // (wtop: the packed-weight bump pointer i
         const Part pt = register_output(t, fuse);
         const int logW = ilog2(ro), logHW = 2 * logW, HWo = ro * ro;
         const int dtotal = dense_total; const int64_t dout = dense_out;
-        op(fuse ? (ro <= 8 ? CLS_CONV_GN8 : CLS_CONV_GN) : CLS_GEMM, [=](const Ctx& c) {
+        op((fuse || fold_up) ? (ro <= 8 ? CLS_CONV_GN8 : CLS_CONV_GN) : CLS_GEMM, [=](const Ctx& c) {
             GemmArgs g = gemm_defaults();
+            if (fold_up) {
+                g.a0 = c.act(h); g.a0_ld = h.ld; g.a0_padded = 1; g.a0_C = cin; g.taps = 4; g.logW = logW - 1; g.logHW = logHW - 2;
+                g.M = c.B * (HWo / 4); g.N = 4 * cout; g.b = c.w<bf16>(w0); g.b_ld = 4 * cin; g.bias_n = c.w<float>(b0);
+                g.rowvec = c.at<float>(dout) + drow; g.rowvec_ld = dtotal; g.log_rows_per_sample = logHW - 2;
+                g.c = c.act(t); g.c_ld = t.ld;
+                if (pt.valid) { g.gn_part = c.at<float>(pt.off); g.gn_quads = pt.quads; }
+                const int bm = launch_gemm(g, c.stream);
+                if (pt.valid) c.part_bm[pt.id] = bm;
+                return;
+            }
             if (fuse) { g.a0 = c.act(x); g.a0_ld = x.ld; g.gn_scale = c.at<float>(sc); g.gn_shift = c.at<float>(sh); g.gn_ld = cin; g.gn_folded = 1; g.a0_up = fuse_up; }
             else { g.a0 = c.act(h); g.a0_ld = h.ld; g.a0_padded = 1; }
             g.a0_C = cin; g.taps = 9; g.logW = logW; g.logHW = logHW;
@@ -901,7 +926,10 @@ const natinf_ncsnpp& reference_engine() {
         int saved[sizeof(knobs) / sizeof(knobs[0])];
         for (size_t i = 0; i < sizeof(knobs) / sizeof(knobs[0]); ++i) { saved[i] = *knobs[i]; *knobs[i] = 1; }
         g_fuse_fin = 3;                                      // (a bit mask: both levels' producer-written tables)
+        const int saved_fold = g_fuse_up_fold;
+        g_fuse_up_fold = 0;                                  // (the folded 2x2 kernels, 16 cin cout, REPLACE the packed and the fragment-major nine-tap copies, 18 cin cout: off is the larger plan)
         natinf_ncsnpp* r = make_engine(0);
+        g_fuse_up_fold = saved_fold;
         for (size_t i = 0; i < sizeof(knobs) / sizeof(knobs[0]); ++i) *knobs[i] = saved[i];
         return r;
     }();
@@ -926,7 +954,7 @@ int64_t natinf_ncsnpp_workspace_bytes(natinf_ncsnpp_t h, int max_batch) {
 // every switch a plan builder reads (layout of the packed weights included), one byte each
 static uint64_t plan_signature() {
     const int k[] = {g_fuse_head, g_attn_qkv, g_attn_w8, g_attn_proj, g_fuse_gn8, g_fuse_fin, g_fuse_gn4, g_fuse_gn, g_cg_wide, g_fuse_up,
-                     g_attn_blk /* (2: the folded attention weights are packed too) */, g_cg3 /* read by the plan builders (which launches exist; which tables a producer may write) */};
+                     g_attn_blk /* (2: the folded attention weights are packed too) */, g_fuse_up_fold, g_cg3 /* read by the plan builders (which launches exist; which tables a producer may write) */};
     uint64_t h = 1469598103934665603ull;
     for (int v : k) h = (h ^ (uint64_t)(v & 0xff)) * 1099511628211ull;
     return h;
@@ -1142,6 +1170,40 @@ int natinf_debug_conv_gn(int res, int B, int N, int cin, int c1, const void* x, 
     return hipGetLastError() == hipSuccess ? NATINF_OK : NATINF_ELAUNCH;
 }
 
+// k_fold_up_conv on its own (tests/test_gpu_up_fold.py): w [N][cin][3][3] fp32 -> out_f32 (may be NULL) [2][2][N][cin][2][2], the folded phase kernels times w_mul before the
+// bf16 rounding, and out_packed (may be NULL) bf16 [4 N][4 cin], what the up-fold launch multiplies with
+int natinf_debug_fold_up_weights(const float* w, int N, int cin, float w_mul, float* out_f32, void* out_packed, natinf_stream_t stream) {
+    if (!w || N <= 0 || cin <= 0 || (!out_f32 && !out_packed) || (out_packed && cin % 64)) return NATINF_EINVAL;
+    ncsn_upf::fold(w, out_packed, out_f32, N, cin, w_mul, stream);
+    return hipGetLastError() == hipSuccess ? NATINF_OK : NATINF_ELAUNCH;
+}
+// Conv_0 of the 16 -> 32 up-sampling block as the plan with natinf_set_fuse_up_fold(1) runs it (tests/test_gpu_up_fold.py): k_fold_up_conv, k_gn_apply at 16x16, the up-fold launch.
+//   out[pixel (2 i + a, 2 j + b) of sample s, n] = (sum_{ty, tx, c} silu(x[s, i + a - 1 + ty, j + b - 1 + tx, c] * scale[s, c] + shift[s, c]) * Wp[a][b][n, c, ty, tx] + bias[n] + rowvec[s, n]) * out_scale
+//   = conv3x3(nearest_up_2x(silu(x * scale + shift)), w, zero padding) + ...   x: raw bf16 [B][16][16][cin]; scale / shift [B][cin] PLAIN (this form does not fold -log2 e into
+// them); w: fp32 [N][cin][3][3], N = 256; w_packed: scratch, bf16 [4 N][4 cin]; h_scratch: bf16 [B][18][18][cin]; rowvec: NULL or [B][N]; out: bf16 [B * 1024][N];
+// gn_part: NULL or [4 B][N / 4] float2 -- row 4 s + 2 a + b = the (sum, sum of squares) of sample s's outputs of parity (a, b).
+int natinf_debug_conv_up_fold(int B, int N, int cin, const void* x, const float* scale, const float* shift, const float* w, void* w_packed, void* h_scratch,
+                              const float* bias_n, const float* rowvec, float out_scale, void* out, float* gn_part, int iters, natinf_stream_t stream) {
+    if (B <= 0 || N != UPFOLD_BN || cin <= 0 || cin % 64 || !x || !scale || !shift || !w || !w_packed || !h_scratch || !out || iters <= 0) return NATINF_EINVAL;
+    static bool configured = false;
+    if (!configured) { if (!configure_gemm_kernels()) return NATINF_ENODEV; configured = true; }
+    hipStream_t s = (hipStream_t)stream;
+    constexpr int W = UPFOLD_W, logW = 4;
+    ncsn_upf::fold(w, w_packed, nullptr, N, cin, 1.0f, stream);
+    hipLaunchKernelGGL(k_gn_apply, dim3((unsigned)((W + 2 + GN_ROWS - 1) / GN_ROWS), (unsigned)B), dim3(256), 0, s, (const bf16*)x, cin, cin, logW, 2 * logW, scale, shift,
+                       (bf16*)h_scratch, (bf16*)nullptr, ACT_SILU, RS_NONE, 1);
+    GemmArgs g = gemm_defaults();
+    g.a0 = (const bf16*)h_scratch; g.a0_ld = cin; g.a0_padded = 1; g.a0_C = cin; g.taps = 4; g.logW = logW; g.logHW = 2 * logW;
+    g.M = B * W * W; g.N = 4 * N; g.b = (const bf16*)w_packed; g.b_ld = 4 * cin; g.bias_n = bias_n;
+    g.rowvec = rowvec; g.rowvec_ld = N; g.log_rows_per_sample = 2 * logW; g.scale = out_scale;
+    g.c = out; g.c_ld = N; g.gn_part = gn_part; g.gn_quads = N / 4;
+    if (!up_fold_epi(g)) return NATINF_EINVAL;
+    g_launch_error = 0;
+    for (int i = 0; i < iters; ++i) launch_gemm(g, s);
+    if (g_launch_error) { g_launch_error = 0; return NATINF_EINVAL; }
+    return hipGetLastError() == hipSuccess ? NATINF_OK : NATINF_ELAUNCH;
+}
+
 // One 16x16 attention block on caller-supplied operands (tests/test_gpu_attn_block_alone.py): the engine's own packs and launches (pack_attn_* / launch_attn_*
 // above), nothing else.  bias [4][256]: rows 0, 1 ARE the engine's bqk table (q then k), rows 2, 3 its bv and b3.
 int natinf_debug_attn_block(int plan, int B, const void* x, int x_ld, const float* scale, const float* shift, const float* w, const float* bias,
@@ -1230,6 +1292,7 @@ int natinf_set_conv_gn_w128_min_k(int shape, int k) { if (shape < 0 || shape > 2
 int natinf_set_conv_gn_wide(int mask) { if (mask < 0 || mask > 3) return NATINF_EINVAL; g_cg_wide = mask; return NATINF_OK; }
 int natinf_set_conv_gn_regw(int on) { return on ? NATINF_OK : NATINF_ESTATE; }      // (0: k_conv_gn, the LDS-ring form, retired)
 int natinf_set_fuse_up(int on) { g_fuse_up = on != 0; return NATINF_OK; }
+int natinf_set_fuse_up_fold(int on) { g_fuse_up_fold = on < 0 ? UP_FOLD_DEFAULT : on != 0; return NATINF_OK; }      // (negative: the library's default)
 int natinf_set_gemm_splitk(int on) { g_splitk = on != 0; return NATINF_OK; }
 int natinf_debug_set_splitk_workspace(float* ws, int max_slices) { g_dbg_splitk_ws = ws; g_dbg_splitk_max = ws ? max_slices : 0; return NATINF_OK; }
 int natinf_set_gemm_half_issue(int on) { return on ? NATINF_OK : NATINF_ESTATE; }      // (0: the every-wave-issues pipelines, retired)
