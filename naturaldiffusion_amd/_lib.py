@@ -172,6 +172,11 @@ SIGNATURES = {
     "natinf_vae_enc_load": (C.c_int, [_p, _p, _i64, _p, _i64, _p]),
     "natinf_vae_posterior_f32": (C.c_int, [_p, _p, _i64, _i32, _i64, _i32, _f32, _f32, C.c_uint64, _p, _i64, _i64, _p]),
     "natinf_vae_encode": (C.c_int, [_p, _p, _p, _p, _i32, _i32, _f32, _f32, C.c_uint64, _p, _i64, _i64, _p, _i64, _p]),
+    # include/natinf_posterior.h
+    "natinf_posterior_workspace_bytes": (C.c_int64, [_i32, _i32]),
+    "natinf_posterior_samples": (C.c_int, [_p, _p, _f32, _f32, C.c_uint64, _p, _i64, _i64, _i32, _i32, _p, _p]),
+    "natinf_posterior_stats": (C.c_int, [_p, _f64, _i32, _i32, _p, _p, _p, _p]),
+    "natinf_posterior_debug_planes": (C.c_int, [_p, _i32, _i32, _p]),
 }
 
 for _name, (_res, _args) in SIGNATURES.items():

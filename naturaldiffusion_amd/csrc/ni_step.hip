@@ -24,6 +24,7 @@
 #include <mutex>
 #include "natinf.h"
 #include "natinf_vae.h"
+#include "posterior_ws.h"
 
 #pragma clang fp contract(off)
 
@@ -809,6 +810,49 @@ __global__ __launch_bounds__(kBlock) void k_vae_posterior(
     }
 }
 
+// ------------------------------------------------------------------------------------------
+// Posterior statistics (include/natinf_posterior.h, natinf_posterior_samples): block (x, row) takes 8 elements of row `row` per thread.  One 16-byte load
+// of f (bf16), eps from two 16-byte loads of the caller's slab or two philox_normals quads of column 0 (what natinf_randn_philox_f32 returns for the
+// row's global index, elems_per_image = d), s = fl(fl(f*a) + fl(eps*b)), then the exact split s = hi + mid + lo into bf16 (round to nearest even; each
+// residual is exact in fp32): three 16-byte stores, one per plane.  The row is uniform over the block, so its global index is a scalar load.
+// ------------------------------------------------------------------------------------------
+typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
+
+__global__ __launch_bounds__(kBlock) void k_post_samples(
+    const bf16x8* __restrict__ f, const float4* __restrict__ noise, float a, float b,
+    const int64_t* __restrict__ index, int64_t first_index, int64_t index_stride, uint32_t k0, uint32_t k1,
+    int d8, int64_t plane_vecs, bf16x8* __restrict__ planes)
+{
+    const int c = blockIdx.x * kBlock + threadIdx.x, row = blockIdx.y;
+    if (c < d8) {
+        const int64_t v = (int64_t)row * d8 + c;
+        const bf16x8 fv = f[v];
+        float4 e0, e1;
+        if (noise) {
+            e0 = noise[2 * v]; e1 = noise[2 * v + 1];
+        } else {
+            const uint64_t gi = global_index(index, first_index, index_stride, row);
+            e0 = philox_normals(gi, (uint64_t)(2 * c), 0u, k0, k1);
+            e1 = philox_normals(gi, (uint64_t)(2 * c + 1), 0u, k0, k1);
+        }
+        const float eps[8] = {e0.x, e0.y, e0.z, e0.w, e1.x, e1.y, e1.z, e1.w};
+        bf16x8 hi, mid, lo;
+#pragma unroll
+        for (int i = 0; i < 8; ++i) {
+            const float fa = (float)fv[i] * a, eb = eps[i] * b;
+            const float s = fa + eb;
+            hi[i] = (__bf16)s;
+            const float r1 = s - (float)hi[i];
+            mid[i] = (__bf16)r1;
+            const float r2 = r1 - (float)mid[i];
+            lo[i] = (__bf16)r2;
+        }
+        planes[v] = hi;
+        planes[plane_vecs + v] = mid;
+        planes[2 * plane_vecs + v] = lo;
+    }
+}
+
 // ---- host side: argument checks and launch geometry shared by the ABI entries ----
 inline int launched() { return hipGetLastError() == hipSuccess ? NATINF_OK : NATINF_ELAUNCH; }
 inline bool terms_ok(const void* idx, const void* val, int n) { return n >= 0 && (n == 0 || (idx && val)); }
@@ -1248,6 +1292,21 @@ int natinf_vae_posterior_f32(const float* moments, float* latents, int64_t n_ima
     if (!blocks) return NATINF_EINVAL;
     hipLaunchKernelGGL(k_vae_posterior, dim3(blocks), dim3(kBlock), 0, (hipStream_t)stream, (const float4*)moments, (float4*)latents,
                        sample != 0, scale, shift, image_index, first_index, index_stride, qpi, (uint32_t)seed, (uint32_t)(seed >> 32), nvec);
+    return launched();
+}
+
+int natinf_posterior_samples(const void* feats_bf16, const float* noise_or_null, float a, float b,
+                             uint64_t seed, const int64_t* index, int64_t first_index, int64_t index_stride,
+                             int n, int d, void* workspace, natinf_stream_t stream)
+{
+    if (!feats_bf16 || !workspace || !post::shape_ok(n, d)) return NATINF_EINVAL;
+    if (((uintptr_t)feats_bf16 & 15) || ((uintptr_t)noise_or_null & 15) || ((uintptr_t)workspace & 255)) return NATINF_EINVAL;
+    const post::Layout L = post::layout(n, d);
+    const int d8 = d / 8;
+    hipLaunchKernelGGL(k_post_samples, dim3((d8 + kBlock - 1) / kBlock, n), dim3(kBlock), 0, (hipStream_t)stream,
+                       (const bf16x8*)feats_bf16, (const float4*)noise_or_null, a, b, index, first_index, index_stride,
+                       (uint32_t)seed, (uint32_t)(seed >> 32), d8, (int64_t)n * d8,
+                       reinterpret_cast<bf16x8*>(static_cast<unsigned char*>(workspace) + L.planes));
     return launched();
 }
 
