@@ -68,10 +68,20 @@ int natinf_mmdit_forward(natinf_mmdit_t h, const float* latents, const float* ti
 /* The attention kernel on its own: o = softmax(q k^T * scale) v per (sequence, head), head_dim 64, bf16.
  * q, k: [B][Tp][ld_qk] (head h at columns 64h..64h+63; per-sequence stride qk_bs elements); vT: [B][64*H][Tp] (V
  * TRANSPOSED: keys contiguous; must be finite at keys >= T); o: [B][Tp][ld_o].  Tp % 128 == 0, Tp - 128 < T <= Tp (the padding
- * must fit inside the last 128-key tile, the only one the kernel masks; anything else is NATINF_EINVAL); keys >= T are ignored,
- * query rows >= T produce unspecified values. */
+ * must fit inside the last 128-key tile, the only one the kernel masks; anything else is NATINF_EINVAL); keys >= T are ignored
+ * whatever the k rows >= T hold, NaN included (their scores are replaced before the softmax sees them; tests/test_gpu_attention_exact.py) -- only vT has to be
+ * finite there, because a probability of exactly 0 still multiplies it; query rows >= T produce unspecified values. */
 int natinf_attention_hd64_bf16(const void* q, const void* k, int ld_qk, int64_t qk_bs, const void* vT, void* o, int ld_o,
                                int64_t o_bs, int B, int H, int Tp, int T, float scale, natinf_stream_t stream);
+
+/* Test hook: the same kernel (the current natinf_set_flash_mode) with its fp8 output epilogue, as the NATINF_MMDIT_FP8 engine launches it in front of
+ * the attention output projection.  q, k, vT, Tp, T, scale: as above.  Outputs, both contiguous:
+ *   o8  [B][Tp][64*H] bytes: e4m3 codes of o / 2^e, one scale per query row and 32 channels (block kb = 2*h + (channel of head h >= 32));
+ *   omx [B][H/2][Tp][4] bytes: the E8M0 scales e + 127, K-tile major (one plane per 128 channels = a pair of heads): the scale of row t of sequence b,
+ *       block kb sits at  b*Tp*2*H + ((kb >> 2)*Tp + t)*4 + (kb & 3).  2^e is the smallest power of two with amax * 2^-e <= 448; an all-zero block gets 127.
+ * Rows >= T of both hold unspecified values.  The refusals of natinf_attention_hd64_bf16, plus NULL o8 / omx and an odd H (a plane pairs heads): NATINF_EINVAL. */
+int natinf_debug_attention_hd64_fp8out(const void* q, const void* k, int ld_qk, int64_t qk_bs, const void* vT, void* o8, void* omx, int B, int H,
+                                       int Tp, int T, float scale, natinf_stream_t stream);
 
 /* 1 (read when an engine is CREATED): the image tokens' residual stream x [Tx][D] is kept in IEEE half instead of fp32 -- the reference's SD3 pipeline is
  * fp16 end to end (src/SD3NaturalInference.py:175-176) --: every update x += gate * (W h + b) is computed in fp32 from the half row and rounded to half once

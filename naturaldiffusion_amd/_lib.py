@@ -138,6 +138,7 @@ SIGNATURES = {
     "natinf_mmdit_stream_status_reset": (C.c_int, [_p, _p, _p]),
     "natinf_mmdit_stream_status": (C.c_int, [_p, _p, _p, _p]),
     "natinf_attention_hd64_bf16": (C.c_int, [_p, _p, _i32, _i64, _p, _p, _i32, _i64, _i32, _i32, _i32, _i32, C.c_float, _p]),
+    "natinf_debug_attention_hd64_fp8out": (C.c_int, [_p, _p, _i32, _i64, _p, _p, _p, _i32, _i32, _i32, _i32, C.c_float, _p]),
     "natinf_inception_create": (C.c_int, [_p, _i32, _i32]),
     "natinf_inception_destroy": (C.c_int, [_p]),
     "natinf_set_inception_conv": (C.c_int, [_i32]),

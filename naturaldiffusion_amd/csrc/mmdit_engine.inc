@@ -394,6 +394,16 @@ int natinf_attention_hd64_bf16(const void* q, const void* k, int ld_qk, int64_t 
     return hipGetLastError() == hipSuccess ? NATINF_OK : NATINF_ELAUNCH;
 }
 
+// test hook: the fp8 output epilogue of the current flash mode's kernel on its own (what the fp8 engine hands to its output projection)
+int natinf_debug_attention_hd64_fp8out(const void* q, const void* k, int ld_qk, int64_t qk_bs, const void* vT, void* o8, void* omx, int B, int H, int Tp,
+                                       int T, float scale, natinf_stream_t stream) {
+    if (!q || !k || !vT || !o8 || !omx || B <= 0 || H <= 0 || H % 2 || Tp <= 0 || Tp % 128 || T <= 0 || T > Tp || Tp - T >= 128 || ld_qk % 8) return NATINF_EINVAL;      // (H: a scale plane pairs heads)
+    if (!configure_gemm_kernels()) return NATINF_ENODEV;
+    launch_flash((const bf16*)q, (const bf16*)k, ld_qk, qk_bs, (const bf16*)vT, nullptr, 64 * H, (int64_t)Tp * 64 * H, B, H, Tp, T, scale, (hipStream_t)stream,
+                 (uint8_t*)o8, (uint8_t*)omx);
+    return hipGetLastError() == hipSuccess ? NATINF_OK : NATINF_ELAUNCH;
+}
+
 int natinf_set_flash_mode(int mode) {
     if (mode < 0 || mode > 3) return NATINF_EINVAL;
     if (mode == 1 || mode == 2) return NATINF_ESTATE;       // the intermediate forms (vector-pipe row sums; 128-key tiles): retired

@@ -199,6 +199,22 @@ def test_attention_abi_rejects_padding_beyond_the_masked_tile():
     assert lib.natinf_attention_hd64_bf16(dummy, dummy, 64, 256 * 64, dummy, dummy, 64, 256 * 64, 1, 1, 256, 300, 0.125, None) == -1
 
 
+def test_attention_fp8out_hook_rejects_bad_arguments():
+    """natinf_debug_attention_hd64_fp8out (include/natinf_mmdit.h): the refusals of natinf_attention_hd64_bf16, plus NULL o8 / omx and an odd head count (a scale
+    plane pairs heads) -- NATINF_EINVAL before anything is configured or launched (there is no GPU here)."""
+    from naturaldiffusion_amd._lib import lib
+    d = 4096                                                # a non-NULL dummy: never dereferenced by the argument check
+    names = ("q", "k", "ld_qk", "qk_bs", "vT", "o8", "omx", "B", "H", "Tp", "T", "scale", "stream")
+    call = lambda **kw: lib.natinf_debug_attention_hd64_fp8out(*[{**dict(q=d, k=d, ld_qk=128, qk_bs=256 * 128, vT=d, o8=d, omx=d, B=1, H=2, Tp=256, T=200, scale=0.125,
+                                                                         stream=None), **kw}[n] for n in names])
+    assert call(T=128) == -1 and call(T=300) == -1          # padding beyond the masked tile; more keys than rows
+    for name in ("q", "k", "vT", "o8", "omx"):
+        assert call(**{name: None}) == -1
+    for H in (1, 3, 0, -2):
+        assert call(H=H) == -1
+    assert call(B=0) == -1 and call(Tp=200) == -1 and call(Tp=0) == -1 and call(T=0) == -1 and call(ld_qk=132) == -1
+
+
 def test_attention_block_hook_rejects_bad_arguments():
     """natinf_debug_attn_block (include/natinf_ncsnpp.h): every argument error is NATINF_EINVAL before anything is configured or launched (there is no GPU here)."""
     from naturaldiffusion_amd._lib import lib
