@@ -234,9 +234,10 @@ int natinf_to_pixel_u8(const float* x, uint8_t* out, int B, int C, int H, int W,
  * holds every noise the row refers to (slot 0 = initial noise, slot j = the draw after step j-1).
  * E % 4 == 0, sample_elems % 4 == 0.
  *
- * Three entries share this arithmetic: natinf_step_f32prod (noises read from the hist_eps slab), natinf_step_f32prod_noise
- * (noises drawn in the kernel; one cfg and uncond row i for image i) and natinf_step_f32prod_noise_guided (the same with
- * a scale and an unconditional row PER IMAGE: guidance intervals and mixed-scale batches).
+ * Four entries share this arithmetic: natinf_step_f32prod (noises read from the hist_eps slab), natinf_step_f32prod_noise
+ * (noises drawn in the kernel; one cfg and uncond row i for image i), natinf_step_f32prod_noise_guided (the same with
+ * a scale and an unconditional row PER IMAGE: guidance intervals and mixed-scale batches) and natinf_step_f32prod_inpaint
+ * (the per-image form with the known latents blended into z_next before its store: latent-space inpainting).
  * ------------------------------------------------------------------------------------------ */
 int natinf_step_f32prod(const float* z, const float* cond, const float* uncond, float cfg,
                         int64_t sample_elems, int64_t eps_sample_stride,
@@ -305,6 +306,41 @@ int natinf_step_f32prod_noise_guided(const float* z, const float* cond, const fl
                                      int k, float c1_f32, float c2_f32,
                                      uint64_t seed, const int64_t* image_index, int64_t first_index, int64_t index_stride,
                                      int64_t E, natinf_stream_t stream);
+
+/* natinf_step_f32prod_noise_guided with the blend of natinf_known_blend_f32 applied to z_next in registers, before its one
+ * store: latent-space inpainting in one launch per step, no second pass over z and no noise slab.  An image of the blend is one
+ * sample (elems_per_image = sample_elems), and the blend shares the step's seed and global image indices:
+ *
+ *   z_next[e] = mask[e] ? fp32( fp32(known[e]*known_alpha_f32) + fp32(n[e]*known_std_f32) ) : (float)a + (float)b
+ *
+ * n = what natinf_randn_philox_col_f32(..., seed, column = known_column) returns for that image and element; known_std_f32 ==
+ * 0.0f draws nothing.  `known` (device fp32), `mask` (device uint8, ONE BYTE PER LATENT ELEMENT, non-zero = known, 4-byte
+ * aligned: a per-pixel mask is broadcast over the channels by the caller), the two strides (sample_elems, or 0 for one row
+ * shared by every image) and known_column (>= 2^31) are natinf_known_blend_f32's.
+ *
+ * Contract: z_next equals, byte for byte, natinf_step_f32prod_noise_guided followed by natinf_known_blend_f32 with the same
+ * known / mask / strides / known_* / seed / index arguments and elems_per_image = sample_elems; hist_x0[k] is that of
+ * natinf_step_f32prod_noise_guided (the unblended entry's: the history never sees the blend).  Through that entry's identity
+ * rule, cfg_image[i] == cfg with uncond_slot[i] == i gives the bytes of natinf_step_f32prod_noise + blend, every slot -1 those
+ * of natinf_step_f32prod_noise with uncond == NULL + blend.  A select, so a NaN of the unblended side stays out of the known
+ * elements.
+ *
+ * NATINF_EINVAL, nothing launched: every refusal of natinf_step_f32prod_noise_guided, and every refusal of
+ * natinf_known_blend_f32 with elems_per_image = sample_elems (known or mask NULL, a stride that is neither 0 nor
+ * sample_elems, `mask` not 4-byte aligned, known_column < 2^31).  All the pure argument checks, the blend's included, are made
+ * before idx_b and uncond_slot are read back, so such a refusal touches no device.  The read-backs are those of the guided
+ * entry (same private stream, same rules for captures). */
+int natinf_step_f32prod_inpaint(const float* z, const float* cond, const float* uncond,
+                                const float* cfg_image, const int32_t* uncond_slot, int n_uncond,
+                                int64_t sample_elems, int64_t eps_sample_stride,
+                                float* hist_x0, const float* noise, float* z_next,
+                                const int32_t* idx_c, const float* val_c, int n_c, float c_diag,
+                                const int32_t* idx_b, const float* val_b, int n_b,
+                                int k, float c1_f32, float c2_f32,
+                                uint64_t seed, const int64_t* image_index, int64_t first_index, int64_t index_stride,
+                                int64_t E,
+                                const float* known, const uint8_t* mask, int64_t known_image_stride, int64_t mask_image_stride,
+                                float known_alpha_f32, float known_std_f32, uint32_t known_column, natinf_stream_t stream);
 
 /* src/ValidateNaturalInference.py:198-204 on its own. */
 int natinf_weighted_sum_f32prod(const float* hist, float* out,

@@ -443,10 +443,88 @@ def to_pixels_u8(images: torch.Tensor) -> torch.Tensor:
     return ((((x.clamp(-1, 1) + 1) * 0.5) * 255 + 0.5).clamp(0, 255)).to(torch.uint8).permute(0, 2, 3, 1).contiguous()
 
 
+def latent_mask(mask_px, erode: int = 1) -> torch.Tensor:
+    """A pixel mask [K, 8S, 8S] (bool / uint8, non-zero = known) reduced to latent cells -> uint8 [K, S, S] on the CPU.  A cell is known iff
+    every pixel of the (8 + 16*erode)-pixel square centred on it that lies inside the image is known: its own 8 x 8 pixels and ``erode`` rings
+    of neighbouring cells (``max_pool2d`` of the UNKNOWN pixels over 8, then over 2*erode + 1 cells; the pooling pads with -inf, so what lies
+    outside the image never makes a cell unknown).  Pure host code."""
+    m = torch.as_tensor(mask_px).cpu()
+    erode = int(erode)
+    if m.dtype not in (torch.bool, torch.uint8) or m.dim() != 3 or m.shape[1] % 8 or m.shape[2] % 8 or not m.shape[1] or not m.shape[2]:
+        raise ValueError("a pixel mask must be bool or uint8 [K, H, W] with H and W positive multiples of 8")
+    if erode < 0:
+        raise ValueError("mask_erode must be >= 0")
+    u = torch.nn.functional.max_pool2d(1.0 - (m != 0).to(torch.float32)[:, None], 8)
+    if erode:
+        u = torch.nn.functional.max_pool2d(u, 2 * erode + 1, 1, erode)
+    return (1.0 - u)[:, 0].to(torch.uint8)
+
+
+def prepare_known_latents(known_latents, known_images, mask, sample_count: int, known_final: str = "mean", mask_erode: int = 1):
+    """The inpainting arguments of ``generate_sharded``, checked and brought to one form -> None (inpainting off) or a dict: ``S`` (the latent
+    side they imply), ``mask`` (uint8 [K', 4*S*S] per latent ELEMENT, the form the step takes), and either ``latents`` (fp32 [K, 4*S*S]) or
+    ``images`` (the caller's uint8 [K, 8S, 8S, 3] / fp32 [K, 3, 8S, 8S], still to be encoded) with ``mask_px`` (bool [K', 8S, 8S]); K and K' each
+    ``sample_count`` (row i belongs to global image index i) or 1 (shared by every image).  Pure host code: every refusal comes before any GPU
+    call."""
+    if known_latents is None and known_images is None and mask is None:
+        return None
+    if known_latents is not None and known_images is not None:
+        raise ValueError("inpainting takes known_latents= or known_images=, not both")
+    if mask is None:
+        raise ValueError("inpainting needs mask= beside known_latents= / known_images=")
+    if known_latents is None and known_images is None:
+        raise ValueError("mask= needs known_latents= or known_images=")
+    if known_final not in ("mean", "data"):
+        raise ValueError('known_final must be "mean" or "data"')
+    sample_count = int(sample_count)
+    mask = torch.as_tensor(mask).cpu()
+    if mask.dtype not in (torch.bool, torch.uint8):
+        raise ValueError("mask must be bool or uint8")
+
+    def rows_ok(name, t):
+        if t.shape[0] not in (1, sample_count):
+            raise ValueError(f"{name} must hold 1 row (shared) or sample_count ({sample_count}) rows, not {t.shape[0]}")
+    if known_latents is not None:
+        kl = torch.as_tensor(known_latents).cpu()
+        if kl.dtype != torch.float32 or kl.dim() != 4 or kl.shape[1] != 4 or kl.shape[2] != kl.shape[3] or kl.shape[2] % 2 or not kl.shape[2]:
+            raise ValueError("known_latents must be fp32 [K, 4, S, S] in the denoiser's scale")
+        S = int(kl.shape[2])
+        rows_ok("known_latents", kl)
+        if mask.dim() == 3 and tuple(mask.shape[1:]) == (S, S):
+            mask = mask[:, None].expand(-1, 4, -1, -1)
+        elif not (mask.dim() == 4 and tuple(mask.shape[1:]) == (4, S, S)):
+            raise ValueError(f"with known_latents the mask must be [K', {S}, {S}] (a latent cell: every channel) or [K', 4, {S}, {S}]")
+        rows_ok("mask", mask)
+        return dict(S=S, latents=kl.reshape(kl.shape[0], -1).contiguous(), mask=(mask != 0).to(torch.uint8).reshape(mask.shape[0], -1).contiguous())
+    ki = torch.as_tensor(known_images).cpu()
+    if ki.dtype == torch.uint8 and ki.dim() == 4 and ki.shape[3] == 3 and ki.shape[1] == ki.shape[2]:
+        R = int(ki.shape[1])
+    elif ki.dtype == torch.float32 and ki.dim() == 4 and ki.shape[1] == 3 and ki.shape[2] == ki.shape[3]:
+        R = int(ki.shape[2])
+    else:
+        raise ValueError("known_images must be uint8 [K, 8S, 8S, 3] or fp32 [K, 3, 8S, 8S] in [-1, 1]")
+    if not R or R % 16:
+        raise ValueError("known_images must be 8S pixels on a side, S even")
+    rows_ok("known_images", ki)
+    if not (mask.dim() == 3 and tuple(mask.shape[1:]) == (R, R)):
+        raise ValueError(f"with known_images the mask must be a pixel mask [K', {R}, {R}]")
+    rows_ok("mask", mask)
+    cells = latent_mask(mask, mask_erode)
+    S = R // 8
+    return dict(S=S, images=ki, mask_px=mask != 0, mask=cells[:, None].expand(-1, 4, -1, -1).reshape(cells.shape[0], -1).contiguous())
+
+
+def gather_rows(rows: torch.Tensor, batch) -> torch.Tensor:
+    """The rows of a per-image table a batch takes, by global index, or the one shared row (``CIFAR10NaturalInference.gather_known``'s pattern,
+    the leading dimension kept)."""
+    return rows[:1] if rows.shape[0] == 1 else rows[torch.as_tensor(list(batch), dtype=torch.int64)]
+
+
 @torch.no_grad()
 def generate_sharded(sample_count, labels=None, alg_name="ddpm", num_step=24, batch_size=32, rank=0, world=1, seed=0,
                      cfg_scale=4.0, decode=True, decode_batch=8, model=None, decoder=None, image_sink=None, fp8=False, stream16=None,
-                     fallback=None, report=None, guidance_interval=None):
+                     fallback=None, report=None, guidance_interval=None, known_latents=None, known_images=None, mask=None,
+                     known_final="mean", mask_erode=1, paste=True, encoder=None):
     """A class-conditional generation job on the loop of ``natural_inference`` (reference :311-372): ``sample_count`` images,
     image i of class ``job_batches``' label of i, sharded by global index over ``world`` ranks with no collective on the data
     path.  The noise is counter-based: z_0 = eps_0 = ``philox_noise(indices, column=0)`` and the noise a stochastic matrix
@@ -486,12 +564,33 @@ def generate_sharded(sample_count, labels=None, alg_name="ddpm", num_step=24, ba
     records the same caveat for the VAE).  ``stream16="auto"``, ``fp8``, ``image_sink``, ``report`` and ``fallback`` compose unchanged; the rerun of a clamped
     batch uses the same plan.
 
+    Inpainting in latent space.  Exactly one of ``known_latents`` / ``known_images``, together with ``mask``, switches it on; without
+    them the job makes exactly the calls described above.  The first model input is the noise with the known latents diffused to level 0
+    (``ValidateNI.first_input``), and every step overwrites the known latent elements, inside its one launch (natinf_step_f32prod_inpaint), with the known
+    latents diffused to the level of its output: ``known_schedule`` of the node table, the draws keyed by (seed, global index, column 2^31 + level).
+    ``known_final``: ``"mean"`` leaves alpha_N * known behind the last step (alpha_N is 1 in the DiT tables), ``"data"`` the known latents as given.
+
+    * ``known_latents``: fp32 ``[K, 4, S, S]`` in the denoiser's scale (already x 0.18215), K 1 (shared) or ``sample_count`` (row i belongs to global index
+      i).  ``mask``: bool / uint8 ``[K', S, S]`` (a cell: all four channels) or ``[K', 4, S, S]``, K' 1 or ``sample_count``; non-zero = known.  No encoder.
+    * ``known_images``: uint8 ``[K, 8S, 8S, 3]`` (the job's own output format) or fp32 ``[K, 3, 8S, 8S]`` in [-1, 1], encoded once per job (the rows this
+      rank generates, in chunks of the encoder's ``max_batch``) by ``encoder``, else ``load_vae_encoder(vae_path, latent_res=S)``, to the posterior MEAN x
+      0.18215.  ``mask`` is then a pixel mask ``[K', 8S, 8S]``, reduced to cells by ``latent_mask(mask, mask_erode)``: a cell is known iff every pixel of the
+      (8 + 16*mask_erode)-pixel square around it is.  The encoder's receptive field is wider than a cell, so the known cells next to the hole still carry
+      some of whatever the caller left IN the hole; ``mask_erode`` trades known area for less of that.  It is a knob, not a guarantee.
+    * ``paste`` (uint8 ``known_images`` only; ignored with ``known_latents`` or fp32 images): the decoded uint8 images get the caller's known pixels back,
+      ``where(mask, known, decoded)`` on the caller's PIXEL mask, before ``image_sink`` / collection.
+
+    Contract: image i is a function of (seed, global index, label, scale, its known row and mask row) up to the denoiser's own batch dependence.  Both the
+    default and the planned (guidance) form take it, the ``stream16="auto"`` rerun uses the same known rows, and ``fp8``, ``image_sink``, ``report`` and
+    ``guidance_interval`` compose unchanged.
+
     -> (latents [n_local, 4, S, S] fp32 on the device, labels [n_local] int64 CPU, global indices [n_local] int64 CPU,
         images [n_local, 8S, 8S, 3] uint8 CPU or None)"""
     from .CIFAR10NaturalInference import philox_noise
     torch.set_grad_enabled(False)
     batch_size = int(batch_size)
     batches = job_batches(sample_count, batch_size, rank, world, labels)
+    inpaint = prepare_known_latents(known_latents, known_images, mask, sample_count, known_final, mask_erode)   # refusals before any GPU call
     planned = guidance_interval is not None or not isinstance(cfg_scale, (int, float, np.floating, np.integer))   # False: the reference's form, today's calls
     scale_of = job_scales(cfg_scale, sample_count) if planned else None
     if guidance_interval is not None and (len(guidance_interval) != 2 or int(guidance_interval[0]) > int(guidance_interval[1])):
@@ -536,14 +635,36 @@ def generate_sharded(sample_count, labels=None, alg_name="ddpm", num_step=24, ba
     per = 4 * S * S
     samplers = {}                                                     # batch size -> ValidateNI (the ragged last batch gets its own)
     out_z, out_img = [], []
+    blend = {}                                                        # the current batch's known= / mask= / known_final= ({}: no inpainting, today's calls)
+    if inpaint is not None:
+        if inpaint["S"] != S:
+            raise ValueError(f"the known data is for latents of side {inpaint['S']}, the denoiser's are {S}")
+        if "images" in inpaint:                                       # encode this rank's rows once: the posterior mean in the denoiser's scale, kept on the host
+            from .AnalyzeWeightedSumDegradation import preprocess
+            if encoder is None:
+                if vae_path is None:
+                    raise RuntimeError("known_images= needs encoder= or ValidateNaturalInference.vae_path (load_vae_encoder)")
+                encoder = load_vae_encoder(vae_path, latent_res=S)
+            imgs = inpaint["images"]
+            rows = [0] if imgs.shape[0] == 1 else [i for idx, _ in batches for i in idx]
+            mb, lat = max(1, int(getattr(encoder, "max_batch", 1))), []
+            for s0 in range(0, len(rows), mb):
+                chunk = imgs[torch.as_tensor(rows[s0:s0 + mb], dtype=torch.int64)]
+                x = (preprocess(chunk) if chunk.dtype == torch.uint8 else chunk).to(device)
+                lat.append(encoder.encode(x, sample=False, scale=0.18215, index=rows[s0:s0 + mb]).reshape(len(chunk), -1).cpu())
+            inpaint["latents"] = torch.cat(lat) if lat else torch.empty((0, per), dtype=torch.float32)
+            if imgs.shape[0] != 1:                                    # the table holds this rank's rows only, in the rank's order
+                inpaint["row_of"] = {i: r for r, i in enumerate(rows)}
 
     def trajectory(denoiser, ni, noise, index, steps_t, classlabels, classnulls):
         n = noise.shape[0]
         input_z, flat_noise = noise, noise.reshape(-1)
+        if blend:                                                     # inpainting: the known latents at level 0; `noise` stays eps_0
+            input_z = ni.first_input(flat_noise, index=index, **blend).view(n, 4, S, S)
         for kk in range(n_step):
             cond, uncond = _cond_uncond(denoiser, input_z, steps_t[kk], classlabels, classnulls)   # [n, 8, S, S] each; first 4 channels used
             z = ni.step(kk, input_z.reshape(-1), cond.contiguous(), uncond.contiguous(), float(cfg_scale), per, cond.shape[1] * S * S,
-                        noise=flat_noise, index=index)
+                        noise=flat_noise, index=index, **blend)
             input_z = z.view(n, 4, S, S)
         return input_z.clone()
 
@@ -555,10 +676,12 @@ def generate_sharded(sample_count, labels=None, alg_name="ddpm", num_step=24, ba
         joint = getattr(denoiser, "max_batch", 0) >= n + g
         nulls = labels_g[n:]
         input_z, flat_noise = noise, noise.reshape(-1)
+        if blend:
+            input_z = ni.first_input(flat_noise, index=index, **blend).view(n, 4, S, S)
         for kk in range(n_step):
             if not guided[kk]:
                 cond = denoiser.forward(input_z, steps_t[kk], classlabels).contiguous()
-                z = ni.step(kk, input_z.reshape(-1), cond, None, 1.0, per, cond.shape[1] * S * S, noise=flat_noise, index=index)
+                z = ni.step(kk, input_z.reshape(-1), cond, None, 1.0, per, cond.shape[1] * S * S, noise=flat_noise, index=index, **blend)
             else:
                 zg = input_z if g == n else input_z[pick]
                 if joint:
@@ -568,7 +691,7 @@ def generate_sharded(sample_count, labels=None, alg_name="ddpm", num_step=24, ba
                     cond = denoiser.forward(input_z, steps_t[kk], classlabels).contiguous()
                     uncond = denoiser.forward(zg, steps_g[kk][n:], nulls).contiguous()
                 z = ni.step(kk, input_z.reshape(-1), cond, uncond, scales_t, per, cond.shape[1] * S * S, noise=flat_noise, index=index,
-                            uncond_slot=slots_t, n_uncond=g)
+                            uncond_slot=slots_t, n_uncond=g, **blend)
             input_z = z.view(n, 4, S, S)
         return input_z.clone()
 
@@ -583,6 +706,10 @@ def generate_sharded(sample_count, labels=None, alg_name="ddpm", num_step=24, ba
         classnulls = torch.full((n,), 1000, dtype=torch.int64, device=device)
         steps_t = [torch.full((n,), int(node[kk, 0]), dtype=torch.int32, device=device) for kk in range(n_step)]
         noise = philox_noise(indices, (4, S, S), seed, device, column=0)
+        if inpaint is not None:                                       # the batch's rows by global index, gathered on the host, uploaded on the caller's stream
+            rows_b = [inpaint["row_of"][i] for i in indices] if "row_of" in inpaint else indices
+            blend.update(known=gather_rows(inpaint["latents"], rows_b).reshape(-1).to(device),
+                         mask=gather_rows(inpaint["mask"], indices).reshape(-1).to(device), known_final=known_final)
         run = (samplers[n], noise, index, steps_t, classlabels, classnulls)
         if planned:                                                   # slot and scale tensors once per batch; the rerun of a clamped batch uses the same plan
             guided, slots, scales = guidance_plan(node, n_step, [scale_of[i] for i in indices], guidance_interval)
@@ -614,6 +741,9 @@ def generate_sharded(sample_count, labels=None, alg_name="ddpm", num_step=24, ba
         db = max(1, int(decode_batch))
         for s0 in range(0, len(all_idx), db):
             u8 = to_pixels_u8(decoder(latents[s0:s0 + db] / 0.18215))
+            if paste and inpaint is not None and "images" in inpaint and inpaint["images"].dtype == torch.uint8:   # the caller's known pixels back
+                u8 = torch.where(gather_rows(inpaint["mask_px"], all_idx[s0:s0 + db]).to(device)[..., None],
+                                 gather_rows(inpaint["images"], all_idx[s0:s0 + db]).to(device), u8)
             if image_sink is not None:
                 image_sink(u8, all_idx[s0:s0 + db], all_lab[s0:s0 + db])
             else:

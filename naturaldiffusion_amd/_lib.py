@@ -51,6 +51,9 @@ SIGNATURES = {
                                             _i32, _f32, _f32, C.c_uint64, _p, _i64, _i64, _i64, _p]),
     "natinf_step_f32prod_noise_guided": (C.c_int, [_p, _p, _p, _p, _p, _i32, _i64, _i64, _p, _p, _p, _p, _p, _i32, _f32, _p, _p, _i32,
                                                    _i32, _f32, _f32, C.c_uint64, _p, _i64, _i64, _i64, _p]),
+    "natinf_step_f32prod_inpaint": (C.c_int, [_p, _p, _p, _p, _p, _i32, _i64, _i64, _p, _p, _p, _p, _p, _i32, _f32, _p, _p, _i32,
+                                              _i32, _f32, _f32, C.c_uint64, _p, _i64, _i64, _i64,
+                                              _p, _p, _i64, _i64, _f32, _f32, C.c_uint32, _p]),
     "natinf_weighted_sum_f32prod": (C.c_int, [_p, _p, _p, _p, _i32, _i64, _p]),
     "natinf_step_f16chain": (C.c_int, [_p, _p, _p, _p, _p, _p, _p, _p, _p, _i32, _f32, _f32, _i32, _f32, _f32, _f32,
                                        _f32, _i32, _i64, _p]),

@@ -781,6 +781,39 @@ __global__ __launch_bounds__(kBlock) void k_step_guided_f32prod(
 }
 
 // ------------------------------------------------------------------------------------------
+// Validate form, inpainting: k_step_guided_f32prod operation for operation (hist_x0[k] and the unblended z_next are its bytes), then known_blend
+// in registers before the one 16-byte store of z_next: no second pass over z, no noise slab.  The blend's quads-per-image is the sample's svec, and
+// it shares the step's global index and Philox key.  z_next equals k_step_guided_f32prod followed by k_known_blend, byte for byte.
+// ------------------------------------------------------------------------------------------
+__global__ __launch_bounds__(kBlock) void k_step_inpaint_f32prod(
+    const float4* __restrict__ z, const float* __restrict__ cond, const float* __restrict__ uncond,
+    const float* __restrict__ cfg_image, const int32_t* __restrict__ uncond_slot, int64_t svec, int64_t sstride,
+    float* __restrict__ hist_x0, const float4* __restrict__ noise, float4* __restrict__ z_next,
+    const int32_t* __restrict__ idx_c, const float* __restrict__ val_c, int n_c, float c_diag,
+    const int32_t* __restrict__ idx_b, const float* __restrict__ val_b, int n_b,
+    const int64_t* __restrict__ index, int64_t first_index, int64_t index_stride,
+    uint32_t k0, uint32_t k1, int k, float c1, float c2,
+    const float* __restrict__ known, const uint8_t* __restrict__ mask, int64_t kstride, int64_t mstride,
+    float kalpha, float kstd, uint32_t kcolumn, int64_t nvec, int64_t E)
+{
+    // one element quad per thread, no grid-stride loop (k_step_noise_f64: the loop's carried scalars make the hoisted
+    // Philox round keys spill SGPRs)
+    const int64_t v = first_vec();
+    if (v < nvec) {
+        const int64_t img = v / svec, q = v - img * svec;            // an image is one sample: svec quads
+        const float4 x0 = x0_f32prod(c1, z[v], c2, cfg_eps_image(cond, uncond, cfg_image, uncond_slot, img, q, sstride));
+        reinterpret_cast<float4*>(hist_x0 + (int64_t)k * E)[v] = x0;
+
+        double a[4] = {0.0, 0.0, 0.0, 0.0}, b[4] = {0.0, 0.0, 0.0, 0.0};
+        wsum_f32prod(a, hist_x0, idx_c, val_c, n_c, v, E);
+        acc_prod(a, x0, c_diag);
+        const uint64_t gi = global_index(index, first_index, index_stride, img);
+        noise_row_sum(b, noise, idx_b, val_b, n_b, v, gi, q, k0, k1);
+        z_next[v] = known_blend(combine(a, b), known, mask, kstride, mstride, img, q, svec, kalpha, kstd, kcolumn, gi, k0, k1);
+    }
+}
+
+// ------------------------------------------------------------------------------------------
 // AutoencoderKL posterior (include/natinf_vae.h, natinf_vae_posterior_f32; the last launch of natinf_vae_encode): one thread per element quad
 // of the latents.  An image's moments are [mean: C*hw][logvar: C*hw], so quad q of the latents reads quad q of each half: two 16-byte loads, one
 // 16-byte store.  std*eps, mean + that, z - shift and its product with scale are four fp32 roundings; eps = philox_normals of the posterior
@@ -1206,6 +1239,40 @@ int natinf_step_f32prod_noise_guided(const float* z, const float* cond, const fl
                        hist_x0, (const float4*)noise, (float4*)z_next, idx_c, val_c, n_c, c_diag, idx_b, val_b, n_b,
                        image_index, first_index, index_stride, (uint32_t)seed, (uint32_t)(seed >> 32),
                        k, c1_f32, c2_f32, nvec, E);
+    return launched();
+}
+
+int natinf_step_f32prod_inpaint(const float* z, const float* cond, const float* uncond,
+                                const float* cfg_image, const int32_t* uncond_slot, int n_uncond,
+                                int64_t sample_elems, int64_t eps_sample_stride,
+                                float* hist_x0, const float* noise, float* z_next,
+                                const int32_t* idx_c, const float* val_c, int n_c, float c_diag,
+                                const int32_t* idx_b, const float* val_b, int n_b,
+                                int k, float c1_f32, float c2_f32,
+                                uint64_t seed, const int64_t* image_index, int64_t first_index, int64_t index_stride,
+                                int64_t E,
+                                const float* known, const uint8_t* mask, int64_t known_image_stride, int64_t mask_image_stride,
+                                float known_alpha_f32, float known_std_f32, uint32_t known_column, natinf_stream_t stream)
+{
+    const int64_t nvec = vec_count(E, 4);
+    const unsigned blocks = quad_blocks(nvec);
+    // every pure argument check, the blend's included, before the first read-back: a refusal of these touches no device
+    if (!z || !cond || !hist_x0 || !z_next || !terms_ok(idx_c, val_c, n_c) || !terms_ok(idx_b, val_b, n_b) ||
+        k < 0 || n_b > (int64_t)k + 2 || !nvec || !image_ok(sample_elems, E) || eps_sample_stride < sample_elems ||
+        (eps_sample_stride & 3) || ((sample_elems / 4) >> 32) || !blocks ||
+        !cfg_image || !uncond_slot || n_uncond < 0 || (n_uncond > 0 && !uncond) ||
+        !known_ok(known, mask, known_image_stride, mask_image_stride, known_column, sample_elems))
+        return NATINF_EINVAL;
+    const int row = noise_row_ok(idx_b, n_b, k, noise != nullptr);
+    if (row <= 0) return row < 0 ? NATINF_ELAUNCH : NATINF_EINVAL;
+    const int slots = slots_ok(uncond_slot, E / sample_elems, n_uncond);
+    if (slots <= 0) return slots < 0 ? NATINF_ELAUNCH : NATINF_EINVAL;
+    hipLaunchKernelGGL(k_step_inpaint_f32prod, dim3(blocks), dim3(kBlock), 0, (hipStream_t)stream,
+                       (const float4*)z, cond, uncond, cfg_image, uncond_slot, sample_elems / 4, eps_sample_stride,
+                       hist_x0, (const float4*)noise, (float4*)z_next, idx_c, val_c, n_c, c_diag, idx_b, val_b, n_b,
+                       image_index, first_index, index_stride, (uint32_t)seed, (uint32_t)(seed >> 32),
+                       k, c1_f32, c2_f32, known, mask, known_image_stride, mask_image_stride,
+                       known_alpha_f32, known_std_f32, known_column, nvec, E);
     return launched();
 }
 

@@ -404,7 +404,11 @@ class ValidateNI:
     (include/natinf.h, natinf_step_f32prod_noise) -- the bytes of the slab path on a slab filled by ``philox_noise(column=j)``,
     for stochastic (``ddpm_*``) and deterministic (``ddim_*``: column 0 only) matrices alike.  ``elems_per_image`` pins the
     per-image size ``step`` must be called with (None: whatever ``sample_elems`` each call gives).  The seeded ``step`` also takes
-    per-image guidance (``cfg`` a tensor with ``uncond_slot``: natinf_step_f32prod_noise_guided)."""
+    per-image guidance (``cfg`` a tensor with ``uncond_slot``: natinf_step_f32prod_noise_guided).
+
+    Latent-space inpainting (``known=`` / ``mask=`` of the seeded ``step``, and ``first_input``; natinf_step_f32prod_inpaint): after every update
+    the known latent elements are overwritten, inside the step's launch, with the known latents diffused to the level of the step's output
+    (``known_schedule`` of the node table, whose rows are the marginal (alpha, sigma) of each level).  The slab form has no blend."""
 
     def __init__(self, C: np.ndarray, B: np.ndarray, node: np.ndarray, c1: np.ndarray, c2: np.ndarray, n_elem: int,
                  device="cuda:0", dense: bool = False, *, seed: Optional[int] = None, elems_per_image: Optional[int] = None):
@@ -429,11 +433,45 @@ class ValidateNI:
         # the seeded form draws the noise rows in the kernel: no (N+1) x E slab
         self.hist_eps = None if self.seed is not None else torch.empty((self.n_step + 1, self.E), dtype=torch.float32, device=self.device)
         self._z = [torch.empty(self.E, dtype=torch.float32, device=self.device) for _ in range(2)]
+        self._known_levels = {}
+        self._launch_wide = {}
+
+    def _known_level(self, j: int, known_final: str):
+        if known_final not in self._known_levels:
+            self._known_levels[known_final] = known_schedule(self.node, known_final)
+        return self._known_levels[known_final][j]
+
+    def _launch_wide_guidance(self, n: int, cfg: float, have_uncond: bool):
+        """A launch-wide scale in the per-image form the inpainting entry takes -> (scales fp32 [n], slots int32 [n]), built once per sampler:
+        slots 0..n-1 with every scale ``cfg``, or every slot -1 without an unconditional half.  The guided entry's identity rule makes these the
+        launch-wide form's bytes."""
+        key = (n, float(cfg), bool(have_uncond))
+        if key not in self._launch_wide:
+            slots = torch.arange(n, dtype=torch.int32) if have_uncond else torch.full((n,), -1, dtype=torch.int32)
+            self._launch_wide[key] = (torch.full((n,), float(cfg), dtype=torch.float32).to(self.device), slots.to(self.device))
+        return self._launch_wide[key]
+
+    def first_input(self, noise: torch.Tensor, known: torch.Tensor, mask: torch.Tensor, index=None, known_final: str = "mean",
+                    elems_per_image: Optional[int] = None) -> torch.Tensor:
+        """The first model input of an inpainting trajectory: ``noise`` with the known latents at level 0 (natinf_known_blend_f32, column
+        ``KNOWN_COLUMN0``) -> a new flat tensor; ``noise`` itself (eps_0 of every step) is left as it is."""
+        epi = self.epi if elems_per_image is None else int(elems_per_image)
+        noise = noise.reshape(-1)
+        if noise.dtype != torch.float32 or noise.numel() != self.E or not noise.is_contiguous():
+            raise ValueError("noise must be a contiguous fp32 tensor of n_elem elements")
+        ks, ms = check_known(known, mask, self.E, epi, seed=self.seed, device=noise.device)
+        ka, kstd, kcol = self._known_level(0, known_final)
+        index, first, stride = image_index_args(index, self.E // epi, noise.device)
+        out = torch.empty_like(noise)
+        check(lib.natinf_known_blend_f32(ptr(noise), ptr(out), ptr(known), ptr(mask), ks, ms, ka, kstd, kcol, self.seed,
+                                         ptr(index), first, stride, epi, self.E, stream_ptr()), "natinf_known_blend_f32")
+        return out
 
     def step(self, k: int, z: torch.Tensor, cond: torch.Tensor, uncond: Optional[torch.Tensor], cfg,
              sample_elems: Optional[int] = None, eps_sample_stride: Optional[int] = None, *,
              noise: Optional[torch.Tensor] = None, index=None, uncond_slot: Optional[torch.Tensor] = None,
-             n_uncond: Optional[int] = None) -> torch.Tensor:
+             n_uncond: Optional[int] = None, known: Optional[torch.Tensor] = None, mask: Optional[torch.Tensor] = None,
+             known_final: str = "mean") -> torch.Tensor:
         """``noise`` / ``index`` (seeded form only): the initial noise eps_0 ([E] fp32, contiguous) and the batch's global image
         indices in one of ``image_index_args``' forms; an image is one sample of ``sample_elems`` elements.
 
@@ -441,10 +479,22 @@ class ValidateNI:
         form only; natinf_step_f32prod_noise_guided): the per-image scales, fp32 ``[n]`` on the device, with ``uncond_slot`` int32 ``[n]``
         on the device -- image i's row in ``uncond``, or -1 for an unguided image (eps = cond, its scale is not read).  ``uncond`` then
         holds ``n_uncond`` samples at ``eps_sample_stride`` (default: ``uncond.numel() // eps_sample_stride``; None = no row).  The entry
-        reads ``uncond_slot`` back before it launches: fill it before the call, once per batch."""
+        reads ``uncond_slot`` back before it launches: fill it before the call, once per batch.
+
+        ``known`` / ``mask`` (seeded form only; natinf_step_f32prod_inpaint): flat fp32 / uint8 device tensors of ``n_elem`` elements (one row per
+        image) or ``sample_elems`` elements (one row for every image); a non-zero mask byte marks a known latent element (one byte per ELEMENT:
+        a per-cell mask is repeated over the channels by the caller), which leaves the step as ``known`` diffused to the level of z_{k+1}:
+        level k + 1 of ``known_schedule(node, known_final)``, column ``KNOWN_COLUMN0 + k + 1``; the last level draws nothing.  ``index`` keys that
+        noise too.  A float ``cfg`` goes through the per-image entry as slots 0..n-1 (all -1 for ``uncond=None``) with that scale: the same bytes."""
         se = self.E if sample_elems is None else int(sample_elems)
         st = se if eps_sample_stride is None else int(eps_sample_stride)
         guided = isinstance(cfg, torch.Tensor)
+        inpaint = known is not None or mask is not None
+        if inpaint:                                                       # refusals first: nothing below touches the GPU before them
+            if self.seed is None:
+                raise ValueError("known / mask belong to the seeded form: the slab form has no blend")
+            ks, ms = check_known(known, mask, self.E, se, seed=self.seed, device=z.device)
+            ka, kstd, kcol = self._known_level(k + 1, known_final)
         if guided and (self.seed is None or noise is None):
             raise ValueError("a tensor cfg (per-image scales) belongs to the seeded form with noise= / index=: the slab form takes one float")
         if not guided and (uncond_slot is not None or n_uncond is not None):
@@ -467,7 +517,10 @@ class ValidateNI:
             raise ValueError("sample_elems must be the per-image element count: a multiple of 4 dividing the element count"
                              + ("" if self.epi is None else f" (elems_per_image = {self.epi})"))
         index, first, stride = image_index_args(index, self.E // se, z.device)
-        if guided:
+        if inpaint and not guided:
+            cfg, uncond_slot = self._launch_wide_guidance(self.E // se, float(cfg), uncond is not None)
+            n_uncond = self.E // se if uncond is not None else 0
+        if guided or inpaint:
             n = self.E // se
             if cfg.dtype != torch.float32 or cfg.device != z.device or not cfg.is_contiguous() or cfg.numel() != n:
                 raise ValueError("a tensor cfg must be a contiguous fp32 tensor on the sampler's device, one scale per image")
@@ -476,6 +529,13 @@ class ValidateNI:
                 raise ValueError("a tensor cfg needs uncond_slot: a contiguous int32 tensor on the sampler's device, one slot per image")
             if n_uncond is None:
                 n_uncond = 0 if uncond is None else uncond.numel() // st
+            if inpaint:
+                check(lib.natinf_step_f32prod_inpaint(ptr(z), ptr(cond), ptr(uncond), ptr(cfg), ptr(uncond_slot), int(n_uncond), se, st,
+                                                      ptr(self.hist_x0), ptr(noise), ptr(z_next), ic, vc, nc, self.rows_c.rows[k].diag,
+                                                      ib, vb, nb, k, self.c1[k], self.c2[k], self.seed, ptr(index), first, stride,
+                                                      self.E, ptr(known), ptr(mask), ks, ms, ka, kstd, kcol, stream_ptr()),
+                      "natinf_step_f32prod_inpaint")
+                return z_next
             check(lib.natinf_step_f32prod_noise_guided(ptr(z), ptr(cond), ptr(uncond), ptr(cfg), ptr(uncond_slot), int(n_uncond), se, st,
                                                        ptr(self.hist_x0), ptr(noise), ptr(z_next), ic, vc, nc, self.rows_c.rows[k].diag,
                                                        ib, vb, nb, k, self.c1[k], self.c2[k], self.seed, ptr(index), first, stride,
