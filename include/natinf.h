@@ -363,8 +363,9 @@ int natinf_weighted_sum_f32prod(const float* hist, float* out,
  * eager PyTorch does; scalars are fp32 (`sig`, `sig_next`, `one_minus_sig_next` must already hold
  * the fp16-rounded value of the 0-d tensor the reference multiplies with).  E % 8 == 0.
  *
- * Two entries share this arithmetic: natinf_step_f16chain (one cfg, v_null image i for image i) and
- * natinf_step_f16chain_guided (a scale and a null-prompt row PER IMAGE: guidance intervals and mixed-scale batches).
+ * Three entries share this arithmetic: natinf_step_f16chain (one cfg, v_null image i for image i),
+ * natinf_step_f16chain_guided (a scale and a null-prompt row PER IMAGE: guidance intervals and mixed-scale batches) and
+ * natinf_step_f16chain_inpaint (the per-image form with the known latents blended into x_next before its store).
  * ------------------------------------------------------------------------------------------ */
 #define NATINF_SD3_CFG_ON_VELOCITY 1
 int natinf_step_f16chain(const void* x, const void* v_text, const void* v_null, const void* noise,
@@ -406,6 +407,63 @@ int natinf_step_f16chain_guided(const void* x, const void* v_text, const void* v
                                 const int32_t* idx, const float* val, int n_terms, float c_diag, float w_total,
                                 int k, float sig, float sig_next, float one_minus_sig_next,
                                 int flags, int64_t E, natinf_stream_t stream);
+
+/* Latent-space inpainting on the SD3 form: the known latents at the flow level (sig, one_minus_sig), blended into x.
+ *
+ *   out[e] = mask[e] ? fp16( fp16(sig*n[e]) + fp16(one_minus_sig*known[e]) ) : x_in[e]
+ *
+ * the known side is natinf_flow_input_f16 with mean = known, in its order of fp16 roundings; sig and one_minus_sig already hold
+ * fp16-rounded values, as for natinf_step_f16chain.  A select: a NaN of x_in stays out of the known elements.  x_in, out, noise and
+ * known are fp16; out may be x_in.  `mask`: device uint8, ONE BYTE PER LATENT ELEMENT, non-zero = known, 8-byte aligned (one
+ * 64-bit word per 8 elements; a per-cell mask is broadcast over the channels by the caller).  known_image_stride /
+ * mask_image_stride: elems_per_image (one row per image) or 0 (one row shared by every image).  The noise side n is chosen by
+ * known_column:
+ *
+ *   0        ("same"):  n = noise[e], the image's own initial noise ([E] fp16; must not be NULL)
+ *   >= 2^31  ("fresh"): n = what natinf_randn_philox_col_f32(..., seed, column = known_column) returns for that image and element,
+ *                       rounded to fp16 once; `noise` is not read and may be NULL.  Element e of image i = e / elems_per_image draws
+ *                       counter = (global index lo, global index hi, quad (e % elems_per_image) / 4, known_column); the global index
+ *                       is image_index[i] or, when image_index is NULL, first_index + i*index_stride.
+ *
+ * An 8-vector whose mask word is 0 draws nothing and does not read `known`.  NATINF_EINVAL, nothing launched: x_in, out, known or
+ * mask NULL; E % 8; elems_per_image not a positive multiple of 8 dividing E, or elems_per_image / 4 >= 2^32; a stride that is
+ * neither 0 nor elems_per_image; `mask` not 8-byte aligned; known_column in 1..2^31-1; known_column == 0 with `noise` NULL. */
+int natinf_known_blend_f16(const void* x_in, void* out, const void* noise, const void* known, const uint8_t* mask,
+                           int64_t known_image_stride, int64_t mask_image_stride,
+                           float sig, float one_minus_sig, uint32_t known_column, uint64_t seed,
+                           const int64_t* image_index, int64_t first_index, int64_t index_stride,
+                           int64_t elems_per_image, int64_t E, natinf_stream_t stream);
+
+/* natinf_step_f16chain_guided with the blend of natinf_known_blend_f16 applied to x_next in registers, before its one store:
+ * latent-space inpainting in one launch per step, no second pass over x.  An image of the blend is sample_elems elements, and the
+ * blend's level is the step's own (sig_next, one_minus_sig_next):
+ *
+ *   x_next[e]   = mask[e] ? fp16( fp16(sig_next*n[e]) + fp16(one_minus_sig_next*known[e]) ) : sig_next*noise + one_minus_sig_next*mean
+ *   mean_out[e] = (flags & NATINF_SD3_BLEND_MEAN) && mask[e] ? known[e] : mean[e]
+ *
+ * n, known, mask, the two strides, known_column, seed and the index arguments are natinf_known_blend_f16's; in "same" mode n is
+ * the `noise` the flow input reads.  NATINF_SD3_BLEND_MEAN is for the last step of a job, whose result is the mean: the known
+ * elements of the result are then `known` itself.  Both values of NATINF_SD3_CFG_ON_VELOCITY are taken.
+ *
+ * Contract: hist[k] is that of natinf_step_f16chain_guided (the history never sees the blend); x_next equals, byte for byte, that
+ * entry followed by natinf_known_blend_f16(x_next, x_next, noise, known, mask, strides, sig_next, one_minus_sig_next, known_column,
+ * seed, index arguments, elems_per_image = sample_elems); without NATINF_SD3_BLEND_MEAN mean_out is that entry's.  Through its
+ * identity rule, cfg_image[i] == cfg with uncond_slot[i] == i gives the bytes of natinf_step_f16chain on the unknown side.
+ *
+ * NATINF_EINVAL, nothing launched: every refusal of natinf_step_f16chain_guided (NATINF_SD3_BLEND_MEAN is accepted here and
+ * nowhere else) and every refusal of natinf_known_blend_f16 with elems_per_image = sample_elems (known_column == 0 needs `noise`
+ * only when x_next is given).  All the pure argument checks, the blend's included, are made before uncond_slot is read back, so
+ * such a refusal touches no device.  The read-back is that of the guided entry (same private stream, same rules for captures). */
+#define NATINF_SD3_BLEND_MEAN 2
+int natinf_step_f16chain_inpaint(const void* x, const void* v_text, const void* v_null,
+                                 const float* cfg_image, const int32_t* uncond_slot, int n_uncond, int64_t sample_elems,
+                                 const void* noise, void* hist, void* mean_out, void* x_next,
+                                 const int32_t* idx, const float* val, int n_terms, float c_diag, float w_total,
+                                 int k, float sig, float sig_next, float one_minus_sig_next,
+                                 int flags, int64_t E,
+                                 const void* known, const uint8_t* mask, int64_t known_image_stride, int64_t mask_image_stride,
+                                 uint32_t known_column, uint64_t seed,
+                                 const int64_t* image_index, int64_t first_index, int64_t index_stride, natinf_stream_t stream);
 
 /* src/SD3NaturalInference.py:209 on its own: out = sig*noise + one_minus_sig*mean (fp16 ops; mean may be
  * NULL = zeros, the k = 0 case of :207). */

@@ -97,6 +97,95 @@ def use_native_vae(pipe, n: int, latent_side: int = 128, device="cuda:0"):
     return pipe
 
 
+def use_native_vae_encoder(pipe, n: int, latent_side: int = 64, device="cuda:0"):
+    """Encode with the HIP AutoencoderKL encoder engine (include/natinf_vae.h) built from ``pipe.vae``'s own weights; ``pipe.vae`` stays in place for
+    its config.  ``pipe.natinf_vae_encoder`` is the engine, for ``n`` images of ``8 * latent_side`` pixels a side; the engine's own size limit
+    (``latent_side`` <= 64) holds."""
+    from .vae import VAEEncoder, flatten_encoder_state_dict
+    enc = getattr(pipe, "natinf_vae_encoder", None)
+    if enc is None or enc.latent_res != int(latent_side) or enc.max_batch < int(n):
+        lc = int(pipe.vae.config.latent_channels)
+        pipe.natinf_vae_encoder = VAEEncoder(flatten_encoder_state_dict(pipe.vae.state_dict(), lc, prefix="encoder."), max_batch=int(n),
+                                             latent_ch=lc, latent_res=int(latent_side), device=device)
+    return pipe
+
+
+def sd_prepare_known(known_latents, known_images, mask, sample_count, latent_shape, renoise: str = "fresh", mask_erode: int = 1):
+    """The inpainting arguments of ``sd_generate_sharded``, checked and brought to one form -> None (inpainting off) or a dict: ``mask`` (uint8
+    [K', C*H*W], one byte per latent ELEMENT, the form the step takes) and either ``latents`` (fp16 [K, C*H*W]) or ``images`` (the caller's uint8
+    [K, 8H, 8W, 3] / fp32 [K, 3, 8H, 8W], still to be encoded); K and K' each ``sample_count`` (row i belongs to global image index i) or 1 (shared
+    by every image).  Pure host code: every refusal comes before any GPU call."""
+    if known_latents is None and known_images is None and mask is None:
+        if renoise not in ("fresh", "same"):
+            raise ValueError('renoise must be "fresh" or "same"')
+        return None
+    if sample_count is None:
+        raise ValueError("known_latents / known_images / mask need sample_count (the reference's job generates from noise alone)")
+    if known_latents is not None and known_images is not None:
+        raise ValueError("inpainting takes known_latents= or known_images=, not both")
+    if mask is None:
+        raise ValueError("inpainting needs mask= beside known_latents= / known_images=")
+    if known_latents is None and known_images is None:
+        raise ValueError("mask= needs known_latents= or known_images=")
+    if renoise not in ("fresh", "same"):
+        raise ValueError('renoise must be "fresh" or "same"')
+    from .ValidateNaturalInference import latent_mask
+    sample_count = int(sample_count)
+    shape = tuple(int(v) for v in latent_shape)
+    if len(shape) != 3 or shape[1] != shape[2]:
+        raise ValueError(f"inpainting needs a square latent_shape (C, S, S), not {shape}")
+    ch, S, _ = shape
+    per = ch * S * S
+
+    def rows_ok(name, t):
+        if t.shape[0] not in (1, sample_count):
+            raise ValueError(f"{name} must hold 1 row (shared) or sample_count ({sample_count}) rows, not {t.shape[0]}")
+    mask = torch.as_tensor(mask).cpu()
+    if mask.dtype not in (torch.bool, torch.uint8):
+        raise ValueError("mask must be bool or uint8")
+    if mask.dim() == 4 and tuple(mask.shape[1:]) == shape:                       # a latent-element mask: as it is
+        cells = (mask != 0).to(torch.uint8)
+    elif mask.dim() == 3 and tuple(mask.shape[1:]) == (S, S):                    # a latent-cell mask: every channel
+        cells = (mask != 0).to(torch.uint8)[:, None].expand(-1, ch, -1, -1)
+    elif mask.dim() == 3 and tuple(mask.shape[1:]) == (8 * S, 8 * S):            # a pixel mask: reduced to cells, every channel
+        cells = latent_mask(mask, mask_erode)[:, None].expand(-1, ch, -1, -1)
+    else:
+        raise ValueError(f"mask must be a latent-element mask [K', {ch}, {S}, {S}], a cell mask [K', {S}, {S}] or a pixel mask [K', {8 * S}, {8 * S}]")
+    rows_ok("mask", cells)
+    out = dict(mask=cells.reshape(cells.shape[0], per).contiguous())
+    if known_latents is not None:
+        kl = torch.as_tensor(known_latents).cpu()
+        if not kl.is_floating_point() or kl.dim() != 4 or tuple(kl.shape[1:]) != shape:
+            raise ValueError(f"known_latents must be floating point [K, {ch}, {S}, {S}] in the model's space, (z - shift) * scale")
+        rows_ok("known_latents", kl)
+        out["latents"] = kl.to(torch.float16).reshape(kl.shape[0], per).contiguous()
+        return out
+    ki = torch.as_tensor(known_images).cpu()
+    R = 8 * S
+    if S > 64:
+        raise ValueError(f"known_images of {R} pixels a side: the encoder engine stops at 512 (latent side 64); pass known_latents= instead")
+    if not ((ki.dtype == torch.uint8 and ki.dim() == 4 and tuple(ki.shape[1:]) == (R, R, 3)) or
+            (ki.dtype == torch.float32 and ki.dim() == 4 and tuple(ki.shape[1:]) == (3, R, R))):
+        raise ValueError(f"known_images must be uint8 [K, {R}, {R}, 3] or fp32 [K, 3, {R}, {R}] in [-1, 1]")
+    rows_ok("known_images", ki)
+    out["images"] = ki
+    return out
+
+
+def _encode_known(pipe, inpaint, rows, n, S, device):
+    """the rows of ``known_images`` a rank needs -> fp16 [len(rows), C*S*S] on the host: the posterior MEAN in the model's space, (z - shift) * scale,
+    through the encoder engine built from ``pipe.vae`` (``use_native_vae_encoder``), in chunks of its ``max_batch``"""
+    from .AnalyzeWeightedSumDegradation import preprocess
+    enc = use_native_vae_encoder(pipe, n, S, device).natinf_vae_encoder
+    scale, shift = float(pipe.vae.config.scaling_factor), float(getattr(pipe.vae.config, "shift_factor", 0.0) or 0.0)
+    imgs, lat = inpaint["images"], []
+    for s0 in range(0, len(rows), enc.max_batch):
+        chunk = imgs[torch.as_tensor(rows[s0:s0 + enc.max_batch], dtype=torch.int64)]
+        x = (preprocess(chunk) if chunk.dtype == torch.uint8 else chunk).to(device)
+        lat.append(enc.encode(x, sample=False, scale=scale, shift=shift).reshape(len(chunk), -1).to(torch.float16).cpu())
+    return torch.cat(lat)
+
+
 def _load_pipe(pipe, device, dtype, n=4):
     if pipe is not None:
         return pipe
@@ -212,11 +301,13 @@ def _velocity(pipe, x, ts, text, pooled, joint):
     return pipe.transformer(hidden_states=x, timestep=ts, encoder_hidden_states=text, pooled_projections=pooled, return_dict=False)[0]
 
 
-def _planned_trajectory(pipe, ni, noises, timesteps, num_step, emb, plan):
+def _planned_trajectory(pipe, ni, noises, timesteps, num_step, emb, plan, blend=None):
     """The loop of ``sd_generate_sharded`` under an ``sd_guidance_plan``: a guided step forwards [x; x[G]] with [pe; ne[G]] and [ppe; npe[G]] (one call
     when the transformer is the engine and takes n + |G| sequences, two otherwise) and makes the per-image step; every other step forwards the n text
-    sequences alone and makes the per-image step with every slot -1."""
+    sequences alone and makes the per-image step with every slot -1.  ``blend`` (inpainting: ``known``, ``mask``, ``seed``, ``index``, ``renoise`` of
+    ``SD3NI.step``) goes to the first input and to every step; the last step, whose mean is the result, blends the mean."""
     from .mmdit import MMDiTEngine
+    blend = blend or {}
     guided, pick, slots_t, none_t, scales_t = plan
     pe, ne, ppe, npe = emb
     nb, g, per = noises.shape[0], pick.numel(), noises[0].numel()
@@ -227,12 +318,13 @@ def _planned_trajectory(pipe, ni, noises, timesteps, num_step, emb, plan):
         ne_g, npe_g = (ne, npe) if g == nb else (ne[pick], npe[pick])
         text_g, pooled_g = torch.cat([pe, ne_g]), torch.cat([ppe, npe_g])
     flat_noise = noises.reshape(-1)
-    x = ni.first_input(flat_noise)
+    x = ni.first_input(flat_noise, sample_elems=per, **blend) if blend else ni.first_input(flat_noise)
     for kk in range(num_step):
         xs, want = x.view(noises.shape), kk + 1 < num_step
+        step_kw = dict(blend, blend_mean=not want) if blend else {}
         if not guided[kk]:
             vt = _velocity(pipe, xs, timesteps[kk].expand(nb), pe, ppe, alone).contiguous()
-            mean, x = ni.step(kk, x, vt.reshape(-1), None, flat_noise, want_next=want, cfg=scales_t, uncond_slot=none_t, n_uncond=0, sample_elems=per)
+            mean, x = ni.step(kk, x, vt.reshape(-1), None, flat_noise, want_next=want, cfg=scales_t, uncond_slot=none_t, n_uncond=0, sample_elems=per, **step_kw)
             continue
         xg = xs if g == nb else xs[pick]
         if joint:
@@ -241,14 +333,15 @@ def _planned_trajectory(pipe, ni, noises, timesteps, num_step, emb, plan):
         else:
             vt = _velocity(pipe, xs, timesteps[kk].expand(nb), pe, ppe, alone).contiguous()
             vn = _velocity(pipe, xg, timesteps[kk].expand(g), ne_g, npe_g, engine and pipe.transformer.max_batch >= g).contiguous()
-        mean, x = ni.step(kk, x, vt.reshape(-1), vn.reshape(-1), flat_noise, want_next=want, cfg=scales_t, uncond_slot=slots_t, n_uncond=g, sample_elems=per)
+        mean, x = ni.step(kk, x, vt.reshape(-1), vn.reshape(-1), flat_noise, want_next=want, cfg=scales_t, uncond_slot=slots_t, n_uncond=g, sample_elems=per, **step_kw)
     return mean
 
 
 @torch.no_grad()
 def sd_generate_sharded(pipe, sample_count: int, n: int = 4, rank: int = 0, world: int = 1, seed: int = 10, num_step: int = 28,
                         weight_name: str = "sd3_step_28_weight.csv", device="cuda:0", latent_shape=(16, 128, 128), *,
-                        prompts=None, negative_prompt: str = "", cfg_scale=7.0, guidance_interval=None):
+                        prompts=None, negative_prompt: str = "", cfg_scale=7.0, guidance_interval=None,
+                        known_latents=None, known_images=None, mask=None, renoise: str = "fresh", mask_erode: int = 1):
     """Batch-sharded SD3 generation (BASELINE configs 4 / 5): this rank runs the reference's loop (:198-223) for the images
     whose GLOBAL index is rank, rank + world, ... in batches of ``n`` -- no collective on the data path, Philox noise keyed by the global index
     (``philox_noise_f16``), so image i is the same bytes whatever the GPU count or batch split.  ``pipe`` as in ``sd_natural_inference_tx``
@@ -277,11 +370,36 @@ def sd_generate_sharded(pipe, sample_count: int, n: int = 4, rank: int = 0, worl
     n + |G| sequences and one of 2n may differ by bf16 rounding flips.  Only when n + |G| == 2n at every step (every image guided, no interval) are the
     forward shapes those of the default form, and then the kernel's identity rule makes the latents byte-identical to it.
 
+    Inpainting in latent space.  Exactly one of ``known_latents`` / ``known_images``, together with ``mask``, switches it on; without
+    them the job makes exactly the calls described above.  The first model input is the flow input with the known latents at level 0
+    (``SD3NI.first_input``), and every step overwrites the known elements of its ``x_next``, inside its one launch (natinf_step_f16chain_inpaint), with
+    ``sig_next*n + (1 - sig_next)*known`` in the reference's fp16 rounding order (``sd_known_schedule``).  ``renoise="fresh"`` draws n anew at every level,
+    keyed by (seed, global index, column 2^31 + level); ``"same"`` uses the image's own initial noise.  The job's result is the mean, so the last step
+    blends the mean: the returned latents equal ``known`` exactly at the masked elements.
+
+    * ``known_latents``: ``[K, *latent_shape]`` in the model's space, that is already ``(z - shift) * scale``; K 1 (shared) or ``sample_count`` (row i
+      belongs to global index i).  Used as fp16.
+    * ``known_images``: uint8 ``[K, 8S, 8S, 3]`` or fp32 ``[K, 3, 8S, 8S]`` in [-1, 1], encoded once per job, before the loop (the rows this rank
+      generates), by the encoder engine built from ``pipe.vae`` (``use_native_vae_encoder``) to the posterior MEAN, with ``scale=scaling_factor`` and
+      ``shift=shift_factor``.  The encoder engine stops at latent side 64 (512 x 512 images); beyond it pass ``known_latents``.
+    * ``mask`` (bool / uint8, non-zero = known; K' 1 or ``sample_count``): a latent-element mask ``[K', *latent_shape]`` as it is, a cell mask
+      ``[K', S, S]`` for every channel, or a pixel mask ``[K', 8S, 8S]`` reduced by ``ValidateNaturalInference.latent_mask(mask, mask_erode)`` and
+      broadcast over the channels.
+
+    Inpainting always runs the per-image step: a scalar ``cfg_scale`` becomes a uniform scale sequence, whose forwards are those of the default form and
+    whose unknown side is, by the kernel's identity rule, the launch-wide entry's bytes.  Guidance intervals, per-image scales and prompts, fp8 engines and
+    sharding compose unchanged.  Contract: image i is a function of (seed, global index, its prompt, its scale, its known row and mask row), the same
+    bytes for any rank, world or batch split whenever the forward shapes agree (the caveat above).
+
     Returns (final latents [n_local, *latent_shape] fp16 on the device, their global indices [n_local] int64 on the CPU)."""
     from .shard import rank_batches
-    from .ValidateNaturalInference import job_scales
-    planned = guidance_interval is not None or not isinstance(cfg_scale, (int, float, np.floating, np.integer))   # False: the reference's form, today's calls
+    from .ValidateNaturalInference import job_scales, gather_rows
+    inpaint = sd_prepare_known(known_latents, known_images, mask, sample_count, latent_shape, renoise, mask_erode)   # refusals before any GPU call
+    # False: the reference's form, today's calls
+    planned = inpaint is not None or guidance_interval is not None or not isinstance(cfg_scale, (int, float, np.floating, np.integer))
     _check_interval(guidance_interval)
+    if inpaint is not None and isinstance(cfg_scale, (int, float, np.floating, np.integer)):
+        cfg_scale = [float(cfg_scale)] * int(sample_count)               # the uniform sequence: the default form's forwards and, on the unknown side, its bytes
     scale_of = job_scales(cfg_scale, sample_count) if planned else None
     prompt_of = None if prompts is None else job_prompts(prompts, sample_count)
     _lib.require_gpu()
@@ -297,9 +415,19 @@ def sd_generate_sharded(pipe, sample_count: int, n: int = 4, rank: int = 0, worl
     samplers, outs = {}, []
     if planned:
         sigmas_host = sigmas.detach().to("cpu", torch.float32)
+    if inpaint is not None and "images" in inpaint:                      # encode this rank's rows once, before the loop; kept on the host
+        rows = [0] if inpaint["images"].shape[0] == 1 else [i for b in batches for i in b]
+        inpaint["latents"] = _encode_known(pipe, inpaint, rows, n, int(latent_shape[-1]), dev)
+        if inpaint["images"].shape[0] != 1:                              # the table holds this rank's rows only, in the rank's order
+            inpaint["row_of"] = {i: r for r, i in enumerate(rows)}
     for batch in batches:
         nb = len(batch)
         noises = philox_noise_f16(batch, latent_shape, seed, dev)
+        blend = None
+        if inpaint is not None:                                         # the batch's rows by global index, gathered on the host
+            rows_b = [inpaint["row_of"][i] for i in batch] if "row_of" in inpaint else batch
+            blend = dict(known=gather_rows(inpaint["latents"], rows_b).reshape(-1).to(dev), mask=gather_rows(inpaint["mask"], batch).reshape(-1).to(dev),
+                         seed=seed, index=torch.tensor(list(batch), dtype=torch.int64, device=dev), renoise=renoise)
         if nb not in samplers:                                          # (a ragged last batch gets its own history slabs)
             samplers[nb] = SD3NI(weights, sigmas, noises.numel(), device=dev, cfg=float(cfg_scale) if not planned else 7.0,
                                  elems_per_image=noises[0].numel() if planned else None)
@@ -313,7 +441,7 @@ def sd_generate_sharded(pipe, sample_count: int, n: int = 4, rank: int = 0, worl
             plan = (guided, torch.tensor([i for i, sl in enumerate(slots) if sl >= 0], dtype=torch.int64, device=dev),
                     torch.tensor(slots, dtype=torch.int32, device=dev), torch.full((nb,), -1, dtype=torch.int32, device=dev),
                     torch.tensor(scales, dtype=torch.float32, device=dev))
-            outs.append(_planned_trajectory(pipe, ni, noises, timesteps, num_step, e, plan).view(noises.shape).clone())
+            outs.append(_planned_trajectory(pipe, ni, noises, timesteps, num_step, e, plan, blend).view(noises.shape).clone())
             continue
         flat_noise = noises.reshape(-1)
         x = ni.first_input(flat_noise)
@@ -328,15 +456,19 @@ def sd_generate_sharded(pipe, sample_count: int, n: int = 4, rank: int = 0, worl
 def sd_natural_inference_tx(pipe=None, device="cuda", noises: Optional[torch.Tensor] = None, n: int = 4, seed: int = 10,
                             num_step: int = 28, weight_names=("sd3_step_28_weight.csv", "sd3_step_28_weight_sharp.csv"),
                             decode: bool = True, rank: int = 0, world: int = 1, sample_count: Optional[int] = None, latent_shape=None, *,
-                            prompts=None, negative_prompt: str = "", cfg_scale=7.0, guidance_interval=None):
+                            prompts=None, negative_prompt: str = "", cfg_scale=7.0, guidance_interval=None,
+                            known_latents=None, known_images=None, mask=None, renoise: str = "fresh", mask_erode: int = 1):
     """Reference :172-245.  Returns the final latents per weight file (and writes ``results/sd3/sgl_*.png``
     when ``decode``).  With ``sample_count`` (not in the reference: its job is one batch of four) the job is ``sample_count`` images sharded by
     global index over ``world`` ranks (``sd_generate_sharded``): returns [(latents of this rank, global indices)] per weight file and, when
     ``decode``, writes this rank's images to ``results/sd3/sgl_<weights>_<index>.png``.  ``latent_shape`` of the sharded job: the native
     transformer's own (in_ch, 2 grid, 2 grid) when ``pipe.transformer`` is the HIP engine, the reference's (16, 128, 128) otherwise.
     ``prompts``, ``negative_prompt``, ``cfg_scale`` and ``guidance_interval`` belong to the sharded job and go to ``sd_generate_sharded`` as they are
-    (per-image prompts and CFG scales by global index, a guidance interval on the sigma scale); without ``sample_count`` they are refused."""
+    (per-image prompts and CFG scales by global index, a guidance interval on the sigma scale); without ``sample_count`` they are refused.  So are
+    ``known_latents`` / ``known_images``, ``mask``, ``renoise`` and ``mask_erode``: latent-space inpainting, a job argument as well."""
     dtype = torch.float16
+    if sample_count is None and (known_latents is not None or known_images is not None or mask is not None or renoise != "fresh" or mask_erode != 1):
+        raise ValueError("known_latents / known_images / mask / renoise / mask_erode need sample_count (the reference's job generates from noise alone)")
     pipe = _load_pipe(pipe, device, dtype, n)
     if sample_count is not None:
         if latent_shape is None:
@@ -350,7 +482,8 @@ def sd_natural_inference_tx(pipe=None, device="cuda", noises: Optional[torch.Ten
             dev_r = torch.device("cuda", torch.cuda.current_device())
         for weight_name in weight_names:
             lat, idx = sd_generate_sharded(pipe, sample_count, n, rank, world, seed, num_step, weight_name, dev_r, latent_shape=tuple(latent_shape),
-                                           prompts=prompts, negative_prompt=negative_prompt, cfg_scale=cfg_scale, guidance_interval=guidance_interval)
+                                           prompts=prompts, negative_prompt=negative_prompt, cfg_scale=cfg_scale, guidance_interval=guidance_interval,
+                                           known_latents=known_latents, known_images=known_images, mask=mask, renoise=renoise, mask_erode=mask_erode)
             finals.append((lat, idx))
             if decode:
                 for s0 in range(0, lat.shape[0], n):

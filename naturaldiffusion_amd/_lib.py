@@ -59,6 +59,9 @@ SIGNATURES = {
                                        _f32, _i32, _i64, _p]),
     "natinf_step_f16chain_guided": (C.c_int, [_p, _p, _p, _p, _p, _i32, _i64, _p, _p, _p, _p, _p, _p, _i32, _f32, _f32, _i32, _f32, _f32,
                                               _f32, _i32, _i64, _p]),
+    "natinf_known_blend_f16": (C.c_int, [_p, _p, _p, _p, _p, _i64, _i64, _f32, _f32, C.c_uint32, C.c_uint64, _p, _i64, _i64, _i64, _i64, _p]),
+    "natinf_step_f16chain_inpaint": (C.c_int, [_p, _p, _p, _p, _p, _i32, _i64, _p, _p, _p, _p, _p, _p, _i32, _f32, _f32, _i32, _f32, _f32,
+                                               _f32, _i32, _i64, _p, _p, _i64, _i64, C.c_uint32, C.c_uint64, _p, _i64, _i64, _p]),
     "natinf_weighted_mean_f16": (C.c_int, [_p, _p, _p, _p, _i32, _f32, _i64, _p]),
     "natinf_flow_input_f16": (C.c_int, [_p, _p, _p, _f32, _f32, _i64, _p]),
     # include/natinf_ncsnpp.h
@@ -191,6 +194,7 @@ for _name, (_res, _args) in SIGNATURES.items():
     _fn.restype, _fn.argtypes = _res, _args
 
 SD3_CFG_ON_VELOCITY = 1
+SD3_BLEND_MEAN = 2                                      # natinf_step_f16chain_inpaint only
 DIT_UNFUSED_ATTENTION = 1                               # include/natinf_dit.h: flags of natinf_dit_create / natinf_dit_create_sized
 DIT_FP8 = 2
 DIT_STREAM_GUARD = 16

@@ -813,6 +813,115 @@ __global__ __launch_bounds__(kBlock) void k_step_inpaint_f32prod(
     }
 }
 
+// ---- pieces of the SD3 inpainting form: known latents re-noised to the flow level of the step's output (fp16 chain) ----
+// the noise side of 8-vector q of an image in "fresh" mode: the Philox normals of quads 2q and 2q + 1 of column `column` (what
+// natinf_randn_philox_col_f32 returns for those eight elements), each rounded to fp16 once
+__device__ __forceinline__ h8 philox_h8(uint64_t gi, int64_t q, uint32_t column, uint32_t k0, uint32_t k1) {
+    const float4 a = philox_normals(gi, (uint64_t)(2 * q), column, k0, k1), b = philox_normals(gi, (uint64_t)(2 * q + 1), column, k0, k1);
+    h8 r;
+    r.v[0] = (h16)a.x; r.v[1] = (h16)a.y; r.v[2] = (h16)a.z; r.v[3] = (h16)a.w;
+    r.v[4] = (h16)b.x; r.v[5] = (h16)b.y; r.v[6] = (h16)b.z; r.v[7] = (h16)b.w;
+    return r;
+}
+
+// element i of the result is kn where byte i of the mask word m is non-zero, xv elsewhere.  A SELECT, as in known_blend: a NaN of xv stays out of
+// the known elements.
+__device__ __forceinline__ h8 select_known(uint64_t m, h8 kn, h8 xv) {
+    h8 r;
+#pragma unroll
+    for (int i = 0; i < 8; ++i) r.v[i] = ((m >> (8 * i)) & 0xFFull) ? kn.v[i] : xv.v[i];
+    return r;
+}
+
+// 8-vector i of p as ONE 16-byte load: the empty asm pins the four dwords in VGPRs at one point; without it the backend, which pairs the halves
+// the way the selects behind it use them, splits the load of the step's noise vector into 2- and 4-byte pieces
+__device__ __forceinline__ h8 ld_whole(const h8* p, int64_t i) {
+    float4 raw = reinterpret_cast<const float4*>(p)[i];
+    asm("" : "+v"(raw.x), "+v"(raw.y), "+v"(raw.z), "+v"(raw.w));
+    h8 r;
+    __builtin_memcpy(&r, &raw, sizeof(r));
+    return r;
+}
+
+// 8-vector q of an image, xv the unconditioned value, m the 8-vector's mask word (not 0) and kv its known values: an element with a non-zero
+// mask byte becomes flow_input(n, known, sig, oms) = fp16(fp16(sig*n) + fp16(oms*known)), the rounding order of natinf_flow_input_f16 with
+// mean = known.  n is `same` (the image's own initial noise, column == 0) or philox_h8 of the column.  The callers branch over this, and over
+// the load of kv, where the mask word is 0: such a thread draws nothing and does not read `known`.
+__device__ __forceinline__ h8 known_blend_h8(h8 xv, uint64_t m, h8 same, h8 kv, float sig, float oms, uint32_t column,
+                                             uint64_t gi, int64_t q, uint32_t k0, uint32_t k1)
+{
+    const h8 nz = column ? philox_h8(gi, q, column, k0, k1) : same;
+    return select_known(m, flow_input(nz, kv, sig, oms), xv);
+}
+
+// the blend on its own: the first model input of an SD3 inpainting trajectory, and the definition the fused step is tested against.
+// x_in and out may be the same buffer (a thread reads its 8-vector before it writes it): no __restrict__ on them.
+__global__ __launch_bounds__(kBlock) void k_blend_known_f16(
+    const h8* x_in, h8* out, const h8* __restrict__ noise, const h8* __restrict__ known, const uint8_t* __restrict__ mask,
+    int64_t kstride, int64_t mstride, float sig, float oms, uint32_t column,
+    const int64_t* __restrict__ index, int64_t first_index, int64_t index_stride, int64_t svec,
+    uint32_t k0, uint32_t k1, int64_t nvec)
+{
+    // one 8-vector per thread, no grid-stride loop (k_step_noise_f64)
+    const int64_t v = first_vec();
+    if (v < nvec) {
+        const int64_t img = v / svec, q = v - img * svec;
+        // a stride is 0 or 8*svec: the word index of the 8-vector within the mask, the vector index within known
+        const uint64_t m = reinterpret_cast<const uint64_t*>(mask)[(mstride ? img * svec : 0) + q];
+        h8 xv = x_in[v];
+        if (m != 0ull)
+            xv = known_blend_h8(xv, m, column ? h8_zero() : noise[v], ld_whole(known, (kstride ? img * svec : 0) + q), sig, oms, column,
+                                global_index(index, first_index, index_stride, img), q, k0, k1);
+        out[v] = xv;
+    }
+}
+
+// ------------------------------------------------------------------------------------------
+// SD3 form, inpainting: k_step_f16chain_guided operation for operation (hist[k], the mean and the unblended x_next are its bytes), then
+// known_blend_h8 at the step's own next level (sig_next, oms_next) in registers before the one 16-byte store of x_next: no second pass over x.
+// x_next equals k_step_f16chain_guided followed by k_blend_known_f16, byte for byte; "same" mode reuses the noise vector the flow input loaded.
+// blend_mean (wave-uniform; the job's last step): mean_out gets `known` itself at the known elements -- the job returns the mean, not x_next.
+// ------------------------------------------------------------------------------------------
+template <bool kVelocityCfg>
+__global__ __launch_bounds__(kBlock) void k_step_inpaint_f16chain(
+    const h8* __restrict__ x, const h8* __restrict__ v_text, const h8* __restrict__ v_null,
+    const float* __restrict__ cfg_image, const int32_t* __restrict__ uncond_slot, int64_t svec,
+    const h8* __restrict__ noise, h16* __restrict__ hist, h8* __restrict__ mean_out, h8* __restrict__ x_next,
+    const int32_t* __restrict__ idx, const float* __restrict__ val, int n_terms, float c_diag, float w_total,
+    int k, float sig, float sig_next, float oms_next,
+    const h8* __restrict__ known, const uint8_t* __restrict__ mask, int64_t kstride, int64_t mstride, uint32_t column, int blend_mean,
+    const int64_t* __restrict__ index, int64_t first_index, int64_t index_stride, uint32_t k0, uint32_t k1,
+    int64_t nvec, int64_t E)
+{
+    // one 8-vector per thread, no grid-stride loop (k_step_noise_f64: the loop's carried scalars make the hoisted
+    // Philox round keys spill SGPRs)
+    const int64_t v = first_vec();
+    if (v < nvec) {
+        const int64_t img = v / svec, q = v - img * svec;            // an image is svec 8-vectors
+        const h8 f = x0_cfg_image<kVelocityCfg>(x[v], v_text[v], v_null, cfg_image, uncond_slot, img, q, svec, sig);
+        reinterpret_cast<h8*>(hist + (int64_t)k * E)[v] = f;
+
+        h8 acc = h8_zero();
+        chain_terms(acc, hist, idx, val, n_terms, v, E);
+#pragma unroll
+        for (int i = 0; i < 8; ++i) acc.v[i] = hadd(acc.v[i], hmulf(c_diag, f.v[i]));
+        h8 mean = mean_of(acc, w_total);
+
+        const uint64_t m = reinterpret_cast<const uint64_t*>(mask)[(mstride ? img * svec : 0) + q];
+        h8 kv = h8_zero(), xn = h8_zero();
+        if (m != 0ull) kv = ld_whole(known, (kstride ? img * svec : 0) + q);
+        if (x_next) {
+            const h8 nv = ld_whole(noise, v);
+            xn = flow_input(nv, mean, sig_next, oms_next);
+            if (m != 0ull)
+                xn = known_blend_h8(xn, m, nv, kv, sig_next, oms_next, column, global_index(index, first_index, index_stride, img), q, k0, k1);
+        }
+        if (blend_mean) mean = select_known(m, kv, mean);
+        if (mean_out) mean_out[v] = mean;
+        if (x_next) x_next[v] = xn;
+    }
+}
+
 // ------------------------------------------------------------------------------------------
 // AutoencoderKL posterior (include/natinf_vae.h, natinf_vae_posterior_f32; the last launch of natinf_vae_encode): one thread per element quad
 // of the latents.  An image's moments are [mean: C*hw][logvar: C*hw], so quad q of the latents reads quad q of each half: two 16-byte loads, one
@@ -907,6 +1016,15 @@ inline unsigned quad_blocks(int64_t nvec) {
 inline bool known_ok(const float* known, const uint8_t* mask, int64_t kstride, int64_t mstride, uint32_t column, int64_t elems_per_image) {
     return known && mask && (kstride == 0 || kstride == elems_per_image) && (mstride == 0 || mstride == elems_per_image) &&
            !((uintptr_t)mask & 3) && column >= 0x80000000u;
+}
+
+// the known latents of an SD3 inpainting call: both arrays given, each per-image stride 0 or elems_per_image, the mask readable as 64-bit words,
+// an image's quads within counter word 2, and the column 0 ("same": the image's own initial noise, which must be there to read) or a
+// replacement column >= 2^31 ("fresh")
+inline bool known_ok_f16(const void* known, const uint8_t* mask, int64_t kstride, int64_t mstride, uint32_t column, int64_t elems_per_image,
+                         bool have_noise) {
+    return known && mask && (kstride == 0 || kstride == elems_per_image) && (mstride == 0 || mstride == elems_per_image) &&
+           !((uintptr_t)mask & 7) && !((elems_per_image / 4) >> 32) && (column == 0 ? have_noise : column >= 0x80000000u);
 }
 
 // the gray channel of a colorization call: the array and both matrices given, the image three planes of whole quads, a per-image stride of 0 (one
@@ -1323,6 +1441,54 @@ int natinf_step_f16chain_guided(const void* x, const void* v_text, const void* v
                        (const h8*)x, (const h8*)v_text, (const h8*)v_null, cfg_image, uncond_slot, sample_elems / 8,
                        (const h8*)noise, (h16*)hist, (h8*)mean_out, (h8*)x_next, idx, val, n_terms, c_diag, w_total,
                        k, sig, sig_next, one_minus_sig_next, nvec, E);
+    return launched();
+}
+
+int natinf_known_blend_f16(const void* x_in, void* out, const void* noise, const void* known, const uint8_t* mask,
+                           int64_t known_image_stride, int64_t mask_image_stride,
+                           float sig, float one_minus_sig, uint32_t known_column, uint64_t seed,
+                           const int64_t* image_index, int64_t first_index, int64_t index_stride,
+                           int64_t elems_per_image, int64_t E, natinf_stream_t stream)
+{
+    const int64_t nvec = vec_count(E, 8);
+    const unsigned blocks = quad_blocks(nvec);
+    if (!x_in || !out || !nvec || !image_ok(elems_per_image, E, 8) || !blocks ||
+        !known_ok_f16(known, mask, known_image_stride, mask_image_stride, known_column, elems_per_image, noise != nullptr))
+        return NATINF_EINVAL;
+    hipLaunchKernelGGL(k_blend_known_f16, dim3(blocks), dim3(kBlock), 0, (hipStream_t)stream,
+                       (const h8*)x_in, (h8*)out, (const h8*)noise, (const h8*)known, mask, known_image_stride, mask_image_stride,
+                       sig, one_minus_sig, known_column, image_index, first_index, index_stride, elems_per_image / 8,
+                       (uint32_t)seed, (uint32_t)(seed >> 32), nvec);
+    return launched();
+}
+
+int natinf_step_f16chain_inpaint(const void* x, const void* v_text, const void* v_null,
+                                 const float* cfg_image, const int32_t* uncond_slot, int n_uncond, int64_t sample_elems,
+                                 const void* noise, void* hist, void* mean_out, void* x_next,
+                                 const int32_t* idx, const float* val, int n_terms, float c_diag, float w_total,
+                                 int k, float sig, float sig_next, float one_minus_sig_next,
+                                 int flags, int64_t E,
+                                 const void* known, const uint8_t* mask, int64_t known_image_stride, int64_t mask_image_stride,
+                                 uint32_t known_column, uint64_t seed,
+                                 const int64_t* image_index, int64_t first_index, int64_t index_stride, natinf_stream_t stream)
+{
+    const int64_t nvec = vec_count(E, 8);
+    const unsigned blocks = quad_blocks(nvec);
+    // every pure argument check, the blend's included, before the slot read-back: a refusal of these touches no device
+    if (!x || !v_text || !hist || !terms_ok(idx, val, n_terms) || k < 0 || !nvec || !blocks ||
+        (x_next && !noise) || (flags & ~(NATINF_SD3_CFG_ON_VELOCITY | NATINF_SD3_BLEND_MEAN)) || !image_ok(sample_elems, E, 8) ||
+        !cfg_image || !uncond_slot || n_uncond < 0 || (n_uncond > 0 && !v_null) ||
+        !known_ok_f16(known, mask, known_image_stride, mask_image_stride, known_column, sample_elems, noise != nullptr || !x_next))
+        return NATINF_EINVAL;
+    const int slots = slots_ok(uncond_slot, E / sample_elems, n_uncond);
+    if (slots <= 0) return slots < 0 ? NATINF_ELAUNCH : NATINF_EINVAL;
+    const auto kern = (flags & NATINF_SD3_CFG_ON_VELOCITY) ? k_step_inpaint_f16chain<true> : k_step_inpaint_f16chain<false>;
+    hipLaunchKernelGGL(kern, dim3(blocks), dim3(kBlock), 0, (hipStream_t)stream,
+                       (const h8*)x, (const h8*)v_text, (const h8*)v_null, cfg_image, uncond_slot, sample_elems / 8,
+                       (const h8*)noise, (h16*)hist, (h8*)mean_out, (h8*)x_next, idx, val, n_terms, c_diag, w_total,
+                       k, sig, sig_next, one_minus_sig_next,
+                       (const h8*)known, mask, known_image_stride, mask_image_stride, known_column, (flags & NATINF_SD3_BLEND_MEAN) != 0,
+                       image_index, first_index, index_stride, (uint32_t)seed, (uint32_t)(seed >> 32), nvec, E);
     return launched();
 }
 

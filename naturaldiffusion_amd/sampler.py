@@ -101,6 +101,47 @@ def check_known(known, mask, n_elem: int, elems_per_image: Optional[int], *, see
     return strides[0], strides[1]
 
 
+def sd_known_schedule(sig16, oms16, renoise: str = "fresh"):
+    """The inpainting schedule of the SD3 (flow) form -> N + 1 triples (sig, 1 - sig, Philox column) from the sampler's fp16-rounded sigma tables
+    (``SD3NI.sig`` / ``SD3NI.oms``, N + 1 entries each).  Entry 0 is the level of the first model input; entry k + 1 is what step k blends with:
+    the step's own ``sig_next`` / ``one_minus_sig_next``.  ``renoise="fresh"``: level j re-noises the known latents with a new draw, column
+    ``KNOWN_COLUMN0 + j``; ``"same"``: with the image's own initial noise at every level, column 0."""
+    if renoise not in ("fresh", "same"):
+        raise ValueError('renoise must be "fresh" or "same"')
+    if len(sig16) != len(oms16):
+        raise ValueError("sig16 and oms16 must have the same length")
+    return [(float(s), float(o), KNOWN_COLUMN0 + j if renoise == "fresh" else 0) for j, (s, o) in enumerate(zip(sig16, oms16))]
+
+
+def check_known_f16(known, mask, n_elem: int, elems_per_image: Optional[int], *, seed, renoise: str = "fresh", device=None):
+    """``check_known`` for the fp16 form (natinf_known_blend_f16 / natinf_step_f16chain_inpaint), made before anything is launched -> (known image
+    stride, mask image stride).  ``known``: flat contiguous fp16, ``mask``: flat contiguous uint8 (non-zero = known) whose storage is 8-byte
+    aligned, each of ``n_elem`` elements (one row per image) or ``elems_per_image`` elements (one row shared by every image: stride 0).  A seed is
+    needed for ``renoise="fresh"`` only.  ``device`` None skips the device check (host-side callers)."""
+    if known is None or mask is None:
+        raise ValueError("inpainting needs both known= and mask=")
+    if renoise not in ("fresh", "same"):
+        raise ValueError('renoise must be "fresh" or "same"')
+    if renoise == "fresh" and seed is None:
+        raise ValueError('inpainting: renoise="fresh" draws new noise for the known latents at every level, which needs a seed')
+    if elems_per_image is None:
+        raise ValueError("inpainting: elems_per_image (sample_elems) is needed to key the known-latent noise")
+    epi = int(elems_per_image)
+    _check_elems_per_image(epi, n_elem, 8)
+    strides = []
+    for name, t, dt in (("known", known, torch.float16), ("mask", mask, torch.uint8)):
+        if not isinstance(t, torch.Tensor) or t.dtype != dt or t.dim() != 1 or not t.is_contiguous():
+            raise ValueError(f"{name} must be a flat contiguous {str(dt).split('.')[-1]} tensor")
+        if t.numel() not in (n_elem, epi):
+            raise ValueError(f"{name} must have n_elem ({n_elem}) or elems_per_image ({epi}) elements, not {t.numel()}")
+        if device is not None and t.device != device:
+            raise ValueError(f"{name} must be on the sampler's device")
+        strides.append(epi if t.numel() == n_elem and n_elem != epi else 0)
+    if mask.data_ptr() % 8:
+        raise ValueError("mask must be 8-byte aligned: the step reads one 64-bit word per 8 elements")
+    return strides[0], strides[1]
+
+
 # Colorization (DESIGN.md section 3e).  COLOR_M: the orthonormal basis of deps/score_sde_pytorch/controllable_generation.py:107-109, fp32, whose column 0 is the
 # gray direction: latent channel j of a pixel (R, G, B) is sum_i x_i * M[i][j].  COLOR_W = fp32(inv(fp64(COLOR_M))), as shortest round-trip literals
 # (it differs from fp32 torch.inverse(M) in one entry by one ulp; max |M W - I| = 2.6e-8 in fp64).  The library takes both as arguments.
@@ -553,7 +594,11 @@ class SD3NI:
 
     ``elems_per_image`` pins the per-image size the per-image-guidance form of ``step`` must be called with (None: whatever
     ``sample_elems`` each call gives).  ``step`` takes per-image guidance as ``cfg=<tensor>`` with ``uncond_slot``
-    (natinf_step_f16chain_guided); without them it is natinf_step_f16chain with the one ``cfg`` given here."""
+    (natinf_step_f16chain_guided); without them it is natinf_step_f16chain with the one ``cfg`` given here.
+
+    Latent-space inpainting (``known=`` / ``mask=`` of the tensor-``cfg`` ``step``, and of ``first_input``; natinf_step_f16chain_inpaint): the known latent
+    elements of every ``x_next`` are overwritten, inside the step's launch, with ``sig_next*n + (1 - sig_next)*known`` in the chain's fp16 rounding order
+    (``sd_known_schedule``); ``blend_mean`` on the last step puts ``known`` itself into the mean the job returns."""
 
     def __init__(self, weights: np.ndarray, sigmas: torch.Tensor, n_elem: int, device="cuda:0", cfg: float = 7.0,
                  dense: bool = False, euler: bool = False, elems_per_image: Optional[int] = None):
@@ -599,39 +644,82 @@ class SD3NI:
         self.hist = torch.empty((n, self.E), dtype=torch.float16, device=self.device)
         self._x = [torch.empty(self.E, dtype=torch.float16, device=self.device) for _ in range(2)]
         self.mean = torch.empty(self.E, dtype=torch.float16, device=self.device)
+        self._known_levels = {}
 
-    def first_input(self, noises: torch.Tensor) -> torch.Tensor:
-        """x_0 = sigma_0*noise + (1-sigma_0)*0 in fp16 ops (SD3...:207-209 with an empty history)."""
+    def _known_level(self, j: int, renoise: str):
+        if renoise not in self._known_levels:
+            self._known_levels[renoise] = sd_known_schedule(self.sig, self.oms, renoise)
+        return self._known_levels[renoise][j]
+
+    def _sample_elems(self, sample_elems: Optional[int]) -> int:
+        se = self.epi if sample_elems is None else int(sample_elems)
+        if se is None or se <= 0 or se % 8 or self.E % se or (self.epi is not None and se != self.epi):
+            raise ValueError("sample_elems must be the per-image element count: a multiple of 8 dividing the element count"
+                             + ("" if self.epi is None else f" (elems_per_image = {self.epi})"))
+        return se
+
+    def first_input(self, noises: torch.Tensor, known: Optional[torch.Tensor] = None, mask: Optional[torch.Tensor] = None, *,
+                    seed: Optional[int] = None, index=None, renoise: str = "fresh", sample_elems: Optional[int] = None) -> torch.Tensor:
+        """x_0 = sigma_0*noise + (1-sigma_0)*0 in fp16 ops (SD3...:207-209 with an empty history).  With ``known`` / ``mask`` (inpainting:
+        ``step``'s arguments of those names, with ``seed``, ``index``, ``renoise`` and ``sample_elems``) the known elements of x_0 are the known
+        latents at level 0 of ``sd_known_schedule`` (natinf_known_blend_f16); ``noises`` itself is left as it is."""
         n = noises.contiguous().reshape(-1)
+        inpaint = known is not None or mask is not None
+        if inpaint:                                                  # refusals first: nothing below touches the GPU before them
+            se = self._sample_elems(sample_elems)
+            ks, ms = check_known_f16(known, mask, self.E, se, seed=seed, renoise=renoise, device=n.device)
+            sig, oms, col = self._known_level(0, renoise)
+            if n.dtype != torch.float16 or n.numel() != self.E:
+                raise ValueError("noises must be an fp16 tensor of n_elem elements")
+            index, first, stride = image_index_args(index, self.E // se, n.device)
         if self.euler:
-            return n.clone()                                         # SD3...:94: curr_outputs = deepcopy(noises)
-        out = self._x[1]
-        check(lib.natinf_flow_input_f16(ptr(n), None, ptr(out), self.sig[0], self.oms[0], self.E, stream_ptr()),
-              "natinf_flow_input_f16")
+            out = n.clone()                                          # SD3...:94: curr_outputs = deepcopy(noises)
+        else:
+            out = self._x[1]
+            check(lib.natinf_flow_input_f16(ptr(n), None, ptr(out), self.sig[0], self.oms[0], self.E, stream_ptr()),
+                  "natinf_flow_input_f16")
+        if inpaint:
+            check(lib.natinf_known_blend_f16(ptr(out), ptr(out), ptr(n), ptr(known), ptr(mask), ks, ms, sig, oms, col,
+                                             0 if seed is None else int(seed) & (2 ** 64 - 1), ptr(index), first, stride, se, self.E,
+                                             stream_ptr()), "natinf_known_blend_f16")
         return out
 
     def step(self, k: int, x: torch.Tensor, v_text: torch.Tensor, v_null: Optional[torch.Tensor], noises: torch.Tensor,
              want_next: bool = True, *, cfg=None, uncond_slot: Optional[torch.Tensor] = None, n_uncond: Optional[int] = None,
-             sample_elems: Optional[int] = None):
+             sample_elems: Optional[int] = None, known: Optional[torch.Tensor] = None, mask: Optional[torch.Tensor] = None,
+             seed: Optional[int] = None, index=None, renoise: str = "fresh", blend_mean: bool = False):
         """``cfg`` None: one scale for the launch (the constructor's), ``v_null`` image i belongs to image i.  ``cfg`` a tensor
         (natinf_step_f16chain_guided): the per-image scales, fp32 ``[n]`` on the device, with ``uncond_slot`` int32 ``[n]`` on the
         device -- image i's row in ``v_null``, or -1 for an unguided image (f = x - sig*v_text, its scale is not read); an image is
         ``sample_elems`` elements (default: ``elems_per_image``).  ``v_null`` then holds ``n_uncond`` images, contiguous (default:
         ``v_null.numel() // sample_elems``; None = no row).  The entry reads ``uncond_slot`` back before it launches: fill it
-        before the call, once per batch."""
+        before the call, once per batch.
+
+        ``known`` / ``mask`` (tensor-``cfg`` form only; natinf_step_f16chain_inpaint): flat fp16 / uint8 device tensors of ``n_elem`` elements (one
+        row per image) or ``sample_elems`` elements (one row for every image); a non-zero mask byte marks a known latent element (one byte per
+        ELEMENT: a per-cell mask is repeated over the channels by the caller), which leaves the step in ``x_next`` as ``known`` at the step's own
+        next level: entry k + 1 of ``sd_known_schedule``.  ``renoise="fresh"`` draws that level's noise from Philox(``seed``, global image index
+        ``index`` -- one of ``image_index_args``' forms --, column ``KNOWN_COLUMN0 + k + 1``); ``"same"`` uses ``noises``.  ``blend_mean`` (the last
+        step of a job, whose result is the mean): the returned mean holds ``known`` itself at the known elements.  The history never sees either."""
         guided = isinstance(cfg, torch.Tensor)
+        inpaint = known is not None or mask is not None
         if not guided and (cfg is not None or uncond_slot is not None or n_uncond is not None or sample_elems is not None):
             raise ValueError("uncond_slot / n_uncond / sample_elems go with a tensor cfg (per-image scales); the launch-wide scale is the constructor's")
+        if not guided and inpaint:
+            raise ValueError("known / mask go with a tensor cfg (per-image scales): the launch-wide form has no blend")
+        if not inpaint and (seed is not None or index is not None or blend_mean):
+            raise ValueError("seed / index / blend_mean go with known= and mask=")
         x_next = _pingpong(self._x, k, x)
         idx, val, n = self.rows.ptrs(k)
         r = self.rows.rows[k]
         flags = _lib.SD3_CFG_ON_VELOCITY if self.euler else 0
         if guided:
-            se = self.epi if sample_elems is None else int(sample_elems)
-            if se is None or se <= 0 or se % 8 or self.E % se or (self.epi is not None and se != self.epi):
-                raise ValueError("sample_elems must be the per-image element count: a multiple of 8 dividing the element count"
-                                 + ("" if self.epi is None else f" (elems_per_image = {self.epi})"))
+            se = self._sample_elems(sample_elems)
             m = self.E // se
+            if inpaint:                                              # refusals first: nothing below touches the GPU before them
+                ks, ms = check_known_f16(known, mask, self.E, se, seed=seed, renoise=renoise, device=x.device)
+                _, _, col = self._known_level(k + 1, renoise)
+                index, first, stride = image_index_args(index, m, x.device)
             if cfg.dtype != torch.float32 or cfg.device != x.device or not cfg.is_contiguous() or cfg.numel() != m:
                 raise ValueError("a tensor cfg must be a contiguous fp32 tensor on the sampler's device, one scale per image")
             if (not isinstance(uncond_slot, torch.Tensor) or uncond_slot.dtype != torch.int32 or uncond_slot.device != x.device
@@ -639,6 +727,14 @@ class SD3NI:
                 raise ValueError("a tensor cfg needs uncond_slot: a contiguous int32 tensor on the sampler's device, one slot per image")
             if n_uncond is None:
                 n_uncond = 0 if v_null is None else v_null.numel() // se
+            if inpaint:
+                check(lib.natinf_step_f16chain_inpaint(ptr(x), ptr(v_text), ptr(v_null), ptr(cfg), ptr(uncond_slot), int(n_uncond), se,
+                                                       ptr(noises), ptr(self.hist), ptr(self.mean), ptr(x_next) if want_next else None,
+                                                       idx, val, n, r.diag, self.totals[k], k, self.sig[k], self.sig[k + 1],
+                                                       self.oms[k + 1], flags | (_lib.SD3_BLEND_MEAN if blend_mean else 0), self.E,
+                                                       ptr(known), ptr(mask), ks, ms, col, 0 if seed is None else int(seed) & (2 ** 64 - 1),
+                                                       ptr(index), first, stride, stream_ptr()), "natinf_step_f16chain_inpaint")
+                return self.mean, (x_next if want_next else None)
             check(lib.natinf_step_f16chain_guided(ptr(x), ptr(v_text), ptr(v_null), ptr(cfg), ptr(uncond_slot), int(n_uncond), se,
                                                   ptr(noises), ptr(self.hist), ptr(self.mean), ptr(x_next) if want_next else None,
                                                   idx, val, n, r.diag, self.totals[k], k, self.sig[k], self.sig[k + 1],

@@ -2,7 +2,7 @@
 
 One JSON object on stdout.  GPU box; run from the repository root:
 
-    python tools/sd3_job.py [--n 4] [--batches 1] [--reps 3] [--fp8] [--guidance-interval S_LO S_HI] [--cfg-scales 7,1] [--kernel-launches 200] [--blocker-ops 80] [--no-jobs | --no-kernel]
+    python tools/sd3_job.py [--n 4] [--batches 1] [--reps 3] [--fp8] [--guidance-interval S_LO S_HI] [--cfg-scales 7,1] [--kernel-launches 200] [--blocker-ops 80] [--no-jobs | --no-kernel] [--inpaint]
 
 Jobs.  One job = ``--batches`` batches of ``--n`` images through all 28 steps, no decode.  Three forms, alternating job by job in this process after one untimed
 warm-up job each, device-synchronised on both sides; images/s from the median of ``--reps``, the spread (min / max seconds) beside it:
@@ -19,6 +19,12 @@ launch was enqueued; a window where it had is dropped), so the events time the l
 the forms alternate over 5 rounds; microseconds per launch from the median window.  Forms: ``f16chain``; ``guided_identity`` (slots 0..3, one scale: the same
 bytes); ``guided_mixed`` (slots -1, 0, -1, 1); ``guided_none`` (every slot -1, v_null NULL).  The blocker leaves the last-level cache cold for a window's first
 launch; after it the 68 MB a launch touches stay in the 256 MB cache, for every form alike.
+
+``--inpaint`` measures latent-space inpainting instead, the same way.  Jobs: ``"default"`` against ``"inpaint_fresh"`` and ``"inpaint_same"`` --
+``known_latents`` one shared random row, ``mask`` the left half of every channel, ``renoise`` either mode; the forwards are the default form's 2n sequences a step.
+Kernel: ``guided_identity`` (natinf_step_f16chain_guided), ``guided_then_blend`` (that launch followed by natinf_known_blend_f16 on its x_next: the two-launch
+form the fused step replaces), ``inpaint_fresh`` and ``inpaint_same`` (natinf_step_f16chain_inpaint, the half-image mask), after a check that the fused step's
+x_next is the two-launch form's bytes at the timed size.
 """
 import argparse
 import json
@@ -37,6 +43,7 @@ from naturaldiffusion_amd import SD3NaturalInference as S                       
 from naturaldiffusion_amd._lib import lib, check, ptr, stream_ptr                   # noqa: E402
 from naturaldiffusion_amd.coeff import SparseRows, load_sd3_csv                     # noqa: E402
 from naturaldiffusion_amd.mmdit import MMDiTEngine, SD3_MEDIUM                      # noqa: E402
+from naturaldiffusion_amd.sampler import KNOWN_COLUMN0                              # noqa: E402
 from naturaldiffusion_amd.synth import synthetic_mmdit_flat                         # noqa: E402
 
 NSTEP, TC = 28, 333
@@ -107,6 +114,33 @@ def jobs(a, dev):
     return {"images_per_job": count, "batch_size": a.n, "steps": NSTEP, "weights": wname, "guidance_interval": interval, "cfg_scales": scale_list, "rows": rows}
 
 
+def windows(forms, a, dev):
+    """the timed windows of the docstring -> ({form: [microseconds per launch of every window kept]}, windows dropped)"""
+    us, dropped = {name: [] for name in forms}, 0
+    for fn in forms.values():
+        for _ in range(20):
+            fn()
+    big = torch.zeros(1 << 28, dtype=torch.float32, device=dev)
+    for _ in range(5):
+        for name, fn in forms.items():
+            eb, e0, e1 = (torch.cuda.Event(enable_timing=True) for _ in range(3))
+            for _ in range(a.blocker_ops):
+                big.add_(1.0)
+            eb.record()
+            e0.record()
+            for _ in range(a.kernel_launches):
+                fn()
+            e1.record()
+            ahead = not eb.query()                                                   # every launch was enqueued while the GPU was still in the blocker
+            torch.cuda.synchronize()
+            if ahead:
+                us[name].append(e0.elapsed_time(e1) * 1e3 / a.kernel_launches)
+            else:
+                dropped += 1
+    assert all(us.values()), "the host never got ahead of the device: raise --blocker-ops"
+    return us, dropped
+
+
 def kernel(a, dev):
     n, se, k = 4, 16 * 128 * 128, 27
     E = n * se
@@ -135,28 +169,7 @@ def kernel(a, dev):
     forms["guided_identity"]()
     torch.cuda.synchronize()
     assert all(torch.equal(p, q) for p, q in zip(want, (hist[k], mean, xn))), "the guided kernel's identity rule does not hold at the timed size"
-    us, dropped = {name: [] for name in forms}, 0
-    for fn in forms.values():
-        for _ in range(20):
-            fn()
-    big = torch.zeros(1 << 28, dtype=torch.float32, device=dev)
-    for _ in range(5):
-        for name, fn in forms.items():
-            eb, e0, e1 = (torch.cuda.Event(enable_timing=True) for _ in range(3))
-            for _ in range(a.blocker_ops):
-                big.add_(1.0)
-            eb.record()
-            e0.record()
-            for _ in range(a.kernel_launches):
-                fn()
-            e1.record()
-            ahead = not eb.query()                                                   # every launch was enqueued while the GPU was still in the blocker
-            torch.cuda.synchronize()
-            if ahead:
-                us[name].append(e0.elapsed_time(e1) * 1e3 / a.kernel_launches)
-            else:
-                dropped += 1
-    assert all(us.values()), "the host never got ahead of the device: raise --blocker-ops"
+    us, dropped = windows(forms, a, dev)
     # bytes a launch moves: the history rows, x, v_text, noise (and v_null rows) in; hist[k], mean, x_next out
     traffic = lambda rows_null: 2 * (k * E + 3 * E + rows_null * se + 3 * E)
     null_rows = {"f16chain": 4, "guided_identity": 4, "guided_mixed": 2, "guided_none": 0}
@@ -165,6 +178,82 @@ def kernel(a, dev):
             "rows": [{"form": name, "median_us": round(statistics.median(t), 2), "min_us": round(min(t), 2), "max_us": round(max(t), 2), "windows": len(t),
                       "ratio_to_f16chain": round(statistics.median(t) / base, 3), "bytes": traffic(null_rows[name]),
                       "tb_per_s": round(traffic(null_rows[name]) / statistics.median(t) / 1e6, 2)} for name, t in us.items()]}
+
+
+def inpaint_jobs(a, dev):
+    pipe = Pipe(a.n, a.fp8, dev)
+    count = a.n * a.batches
+    wname = "sd3_step_28_weight_sharp.csv" if a.fp8 else "sd3_step_28_weight.csv"
+    gen = torch.Generator().manual_seed(1)
+    known = torch.randn(1, 16, 128, 128, generator=gen).half()
+    mask = torch.zeros(1, 128, 128, dtype=torch.uint8)
+    mask[:, :, :64] = 1                                                              # the left half of every channel is known
+    forms = (("default", {}), ("inpaint_fresh", dict(known_latents=known, mask=mask, renoise="fresh")),
+             ("inpaint_same", dict(known_latents=known, mask=mask, renoise="same")))
+    run = lambda kw: S.sd_generate_sharded(pipe, count, a.n, weight_name=wname, device=dev, **kw)
+    secs = {name: [] for name, _ in forms}
+    for name, kw in forms:                                                           # warm-up, and the result holds the known half
+        lat = run(kw)[0]
+        assert torch.isfinite(lat.float()).all(), name
+        assert not kw or torch.equal(lat[:, :, :, :64], known.to(dev).expand(count, -1, -1, -1)[:, :, :, :64]), name
+    for _ in range(a.reps):
+        for name, kw in forms:
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            run(kw)
+            torch.cuda.synchronize()
+            secs[name].append(time.perf_counter() - t0)
+    base = count / statistics.median(secs["default"])
+    rows = [{"form": name, "images_per_s": round(count / statistics.median(ts), 3), "ratio_to_default": round(count / statistics.median(ts) / base, 3),
+             "median_s": round(statistics.median(ts), 4), "min_s": round(min(ts), 4), "max_s": round(max(ts), 4)} for name, ts in secs.items()]
+    return {"images_per_job": count, "batch_size": a.n, "steps": NSTEP, "weights": wname, "mask": "left half, every channel", "rows": rows}
+
+
+def inpaint_kernel(a, dev):
+    n, se, k = 4, 16 * 128 * 128, 27
+    E = n * se
+    gen = torch.Generator().manual_seed(0)
+    rnd = lambda m: torch.randn(m, generator=gen).half().to(dev)
+    x, vt, vn, noise, known = rnd(E), rnd(E), rnd(E), rnd(E), rnd(se)
+    mask = torch.zeros(16, 128, 128, dtype=torch.uint8)
+    mask[:, :, :64] = 1
+    mask = mask.reshape(-1).to(dev)
+    hist = torch.randn(NSTEP, E, generator=gen).half().to(dev)
+    mean, xn = torch.empty(E, dtype=torch.float16, device=dev), torch.empty(E, dtype=torch.float16, device=dev)
+    rows = SparseRows(load_sd3_csv(S.root_path / "weights" / "sd3_step_28_weight.csv"), lambda j: j + 1, torch.float32, dev, dense=True)
+    idx, val, nt = rows.ptrs(k)
+    r = rows.rows[k]
+    sig = (0.05, 0.25, 0.75)                                                         # sig, sig_next, 1 - sig_next: exact in fp16
+    slots, cfg7, seed = torch.arange(n, dtype=torch.int32, device=dev), torch.full((n,), 7.0, device=dev), 10
+    head = (ptr(x), ptr(vt), ptr(vn), ptr(cfg7), ptr(slots), n, se, ptr(noise), ptr(hist), ptr(mean), ptr(xn), idx, val, nt, r.diag, r.total, k, *sig, 0, E)
+    col = KNOWN_COLUMN0 + k + 1                                                      # the fresh column of the step's own next level
+
+    def guided():
+        check(lib.natinf_step_f16chain_guided(*head, stream_ptr()), "natinf_step_f16chain_guided")
+
+    def blend(column):
+        check(lib.natinf_known_blend_f16(ptr(xn), ptr(xn), ptr(noise), ptr(known), ptr(mask), 0, 0, sig[1], sig[2], column, seed, None, 0, 1, se, E, stream_ptr()),
+              "natinf_known_blend_f16")
+
+    def fused(column):
+        return lambda: check(lib.natinf_step_f16chain_inpaint(*head, ptr(known), ptr(mask), 0, 0, column, seed, None, 0, 1, stream_ptr()), "natinf_step_f16chain_inpaint")
+
+    def two():
+        guided()
+        blend(col)
+    forms = {"guided_identity": guided, "guided_then_blend": two, "inpaint_fresh": fused(col), "inpaint_same": fused(0)}
+    for column in (col, 0):                                                          # the same bytes first, at the timed size
+        guided()
+        blend(column)
+        want = xn.clone()
+        fused(column)()
+        torch.cuda.synchronize()
+        assert torch.equal(want, xn), "the fused step is not the guided step followed by the blend at the timed size"
+    us, dropped = windows(forms, a, dev)
+    base = statistics.median(us["guided_identity"])
+    return {"E": E, "k": k, "history_terms": nt, "launches_per_window": a.kernel_launches, "windows_dropped": dropped, "mask": "left half, every channel, one shared row",
+            "rows": [{"form": name, "median_us": round(statistics.median(t), 2), "min_us": round(min(t), 2), "max_us": round(max(t), 2), "windows": len(t),
+                      "ratio_to_guided": round(statistics.median(t) / base, 3)} for name, t in us.items()]}
 
 
 def main():
@@ -179,13 +268,16 @@ def main():
     ap.add_argument("--blocker-ops", type=int, default=80, help="1 GiB in-place additions queued ahead of a window")
     ap.add_argument("--no-jobs", action="store_true")
     ap.add_argument("--no-kernel", action="store_true")
+    ap.add_argument("--inpaint", action="store_true", help="measure latent-space inpainting (half-image mask, both renoise modes) instead of the guidance forms")
     a = ap.parse_args()
     dev = torch.device("cuda:0")
     res = {"tool": "sd3_job", "model": "SD3-medium synthetic (MMDiT 24 blocks, 4,096 + 333 tokens)", "fp8": a.fp8, "reps": a.reps, "device": torch.cuda.get_device_name(0)}
+    if a.inpaint:
+        res["tool"] = "sd3_job --inpaint"
     if not a.no_kernel:
-        res["kernel"] = kernel(a, dev)
+        res["kernel"] = inpaint_kernel(a, dev) if a.inpaint else kernel(a, dev)
     if not a.no_jobs:
-        res["jobs"] = jobs(a, dev)
+        res["jobs"] = inpaint_jobs(a, dev) if a.inpaint else jobs(a, dev)
     print(json.dumps(res))
 
 
