@@ -18,6 +18,7 @@ import torch
 from . import _lib
 from ._lib import lib, check, ptr, stream_ptr
 from .coeff import load_coeff_npz, SparseRows
+from .jobs import KnownRows, check_row_count, gather_known, host_mask, mask_table  # noqa: F401  (gather_known: importable from here as before)
 from .sampler import CifarNI, decouple0_host, vp_std_f32
 
 root_path = Path(__file__).resolve().parent.parent
@@ -113,23 +114,18 @@ def prepare_known(known, mask, sample_count: int, known_final: str = "mean"):
         raise ValueError("inpainting needs both known= and mask=")
     if known_final not in ("mean", "data"):
         raise ValueError('known_final must be "mean" or "data"')
-    known, mask = torch.as_tensor(known).cpu(), torch.as_tensor(mask).cpu()
+    known = torch.as_tensor(known).cpu()
     if known.dtype == torch.uint8 and known.dim() == 4 and tuple(known.shape[1:]) == (32, 32, 3):
         kf = u8_to_centered(known.permute(0, 3, 1, 2))
     elif known.dtype == torch.float32 and known.dim() == 4 and tuple(known.shape[1:]) == (3, 32, 32):
         kf = known
     else:
         raise ValueError("known must be uint8 [K, 32, 32, 3] or fp32 [K, 3, 32, 32] (centred)")
-    if mask.dtype not in (torch.bool, torch.uint8):
-        raise ValueError("mask must be bool or uint8")
-    if mask.dim() == 3 and tuple(mask.shape[1:]) == (32, 32):
-        mask = mask[:, None].expand(-1, 3, -1, -1)
-    elif not (mask.dim() == 4 and tuple(mask.shape[1:]) == (3, 32, 32)):
+    table = mask_table(host_mask(mask), 3, 32, sample_count, forms=("element", "cell"))      # a pixel of the picture is a cell of its three planes
+    if table is None:
         raise ValueError("mask must be [K, 32, 32] or [K, 3, 32, 32]")
-    for name, t in (("known", kf), ("mask", mask)):
-        if t.shape[0] not in (1, int(sample_count)):
-            raise ValueError(f"{name} must hold sample_count ({sample_count}) images or 1, not {t.shape[0]}")
-    return kf.reshape(kf.shape[0], -1).contiguous(), (mask != 0).to(torch.uint8).reshape(mask.shape[0], -1).contiguous()
+    check_row_count("known", kf, sample_count)
+    return kf.reshape(kf.shape[0], -1).contiguous(), table
 
 
 def prepare_gray(gray, sample_count: int, known_final: str = "mean") -> torch.Tensor:
@@ -148,14 +144,8 @@ def prepare_gray(gray, sample_count: int, known_final: str = "mean") -> torch.Te
         gf = gray
     else:
         raise ValueError("gray must be uint8 [K, 32, 32], uint8 [K, 32, 32, 3] or fp32 [K, 3, 32, 32] (centred)")
-    if gf.shape[0] not in (1, int(sample_count)):
-        raise ValueError(f"gray must hold sample_count ({sample_count}) images or 1, not {gf.shape[0]}")
+    check_row_count("gray", gf, sample_count)
     return torch.from_numpy(np.ascontiguousarray(decouple0_host(gf.contiguous().numpy()))).reshape(gf.shape[0], -1)
-
-
-def gather_known(rows: torch.Tensor, batch: Sequence[int]) -> torch.Tensor:
-    """The rows of a ``prepare_known`` table a batch takes, flat: the rows at the batch's global indices, or the one shared row."""
-    return (rows[0] if rows.shape[0] == 1 else rows[torch.as_tensor(list(batch), dtype=torch.int64)]).reshape(-1)
 
 
 class BatchLanes:
@@ -285,26 +275,9 @@ def generate_sharded(model_fn, weight_path, sample_count: int, batch_size: int, 
     if not batches:
         return torch.empty((0, 32, 32, 3), dtype=torch.uint8, device="cpu" if to_cpu else dev), torch.empty(0, dtype=torch.int64)
     lanes = BatchLanes(_lane_models(model_fn, streams, len(batches)), C, B, node, dev, seed=seed)
-    shared = {}                                                          # a one-row table is uploaded once
-    for batch in batches:
-        kw = {}
-        if inpaint:
-            for name, rows in (("known", known), ("mask", mask)):
-                if rows.shape[0] == 1:
-                    if name not in shared:
-                        shared[name] = gather_known(rows, batch).to(dev)
-                    kw[name] = shared[name]
-                else:
-                    kw[name] = gather_known(rows, batch).to(dev)
-            kw["known_final"] = known_final
-        if gray is not None:
-            if gray.shape[0] == 1:
-                if "gray_u" not in shared:
-                    shared["gray_u"] = gather_known(gray, batch).to(dev)
-                kw["gray_u"] = shared["gray_u"]
-            else:
-                kw["gray_u"] = gather_known(gray, batch).to(dev)
-            kw["known_final"] = known_final
+    rows = KnownRows(dev, known=known, mask=mask) if inpaint else KnownRows(dev, gray_u=gray) if gray is not None else None
+    for batch in batches:                                                # the batch's rows are uploaded here, on the caller's stream, in front of submit
+        kw = dict(rows.batch(batch), known_final=known_final) if rows is not None else {}
         lanes.submit(len(batch), noise_fn=lambda b=batch: philox_noise(b, (3, 32, 32), seed, dev), index=(batch[0], world), **kw)   # = batch
     imgs = torch.cat(lanes.finish())
     idxs = torch.cat([torch.tensor(b, dtype=torch.int64) for b in batches])

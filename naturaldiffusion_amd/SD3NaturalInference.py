@@ -21,6 +21,7 @@ import torch
 from . import _lib
 from ._lib import lib, check, ptr, stream_ptr
 from .coeff import load_sd3_csv, SparseRows
+from .jobs import KnownRows, check_interval, check_row_count, guidance_plan, host_mask, inpainting_on, is_scalar_scale, job_scales, mask_table
 from .sampler import SD3NI
 
 root_path = Path(__file__).resolve().parent.parent
@@ -115,50 +116,28 @@ def sd_prepare_known(known_latents, known_images, mask, sample_count, latent_sha
     [K', C*H*W], one byte per latent ELEMENT, the form the step takes) and either ``latents`` (fp16 [K, C*H*W]) or ``images`` (the caller's uint8
     [K, 8H, 8W, 3] / fp32 [K, 3, 8H, 8W], still to be encoded); K and K' each ``sample_count`` (row i belongs to global image index i) or 1 (shared
     by every image).  Pure host code: every refusal comes before any GPU call."""
-    if known_latents is None and known_images is None and mask is None:
-        if renoise not in ("fresh", "same"):
-            raise ValueError('renoise must be "fresh" or "same"')
-        return None
-    if sample_count is None:
+    given = known_latents is not None or known_images is not None or mask is not None
+    if given and sample_count is None:
         raise ValueError("known_latents / known_images / mask need sample_count (the reference's job generates from noise alone)")
-    if known_latents is not None and known_images is not None:
-        raise ValueError("inpainting takes known_latents= or known_images=, not both")
-    if mask is None:
-        raise ValueError("inpainting needs mask= beside known_latents= / known_images=")
-    if known_latents is None and known_images is None:
-        raise ValueError("mask= needs known_latents= or known_images=")
+    inpainting_on(known_latents, known_images, mask)
     if renoise not in ("fresh", "same"):
         raise ValueError('renoise must be "fresh" or "same"')
-    from .ValidateNaturalInference import latent_mask
+    if not given:
+        return None
     sample_count = int(sample_count)
     shape = tuple(int(v) for v in latent_shape)
     if len(shape) != 3 or shape[1] != shape[2]:
         raise ValueError(f"inpainting needs a square latent_shape (C, S, S), not {shape}")
     ch, S, _ = shape
-    per = ch * S * S
-
-    def rows_ok(name, t):
-        if t.shape[0] not in (1, sample_count):
-            raise ValueError(f"{name} must hold 1 row (shared) or sample_count ({sample_count}) rows, not {t.shape[0]}")
-    mask = torch.as_tensor(mask).cpu()
-    if mask.dtype not in (torch.bool, torch.uint8):
-        raise ValueError("mask must be bool or uint8")
-    if mask.dim() == 4 and tuple(mask.shape[1:]) == shape:                       # a latent-element mask: as it is
-        cells = (mask != 0).to(torch.uint8)
-    elif mask.dim() == 3 and tuple(mask.shape[1:]) == (S, S):                    # a latent-cell mask: every channel
-        cells = (mask != 0).to(torch.uint8)[:, None].expand(-1, ch, -1, -1)
-    elif mask.dim() == 3 and tuple(mask.shape[1:]) == (8 * S, 8 * S):            # a pixel mask: reduced to cells, every channel
-        cells = latent_mask(mask, mask_erode)[:, None].expand(-1, ch, -1, -1)
-    else:
+    out = dict(mask=mask_table(host_mask(mask), ch, S, sample_count, mask_erode))
+    if out["mask"] is None:
         raise ValueError(f"mask must be a latent-element mask [K', {ch}, {S}, {S}], a cell mask [K', {S}, {S}] or a pixel mask [K', {8 * S}, {8 * S}]")
-    rows_ok("mask", cells)
-    out = dict(mask=cells.reshape(cells.shape[0], per).contiguous())
     if known_latents is not None:
         kl = torch.as_tensor(known_latents).cpu()
         if not kl.is_floating_point() or kl.dim() != 4 or tuple(kl.shape[1:]) != shape:
             raise ValueError(f"known_latents must be floating point [K, {ch}, {S}, {S}] in the model's space, (z - shift) * scale")
-        rows_ok("known_latents", kl)
-        out["latents"] = kl.to(torch.float16).reshape(kl.shape[0], per).contiguous()
+        check_row_count("known_latents", kl, sample_count)
+        out["latents"] = kl.to(torch.float16).reshape(kl.shape[0], ch * S * S).contiguous()
         return out
     ki = torch.as_tensor(known_images).cpu()
     R = 8 * S
@@ -167,23 +146,26 @@ def sd_prepare_known(known_latents, known_images, mask, sample_count, latent_sha
     if not ((ki.dtype == torch.uint8 and ki.dim() == 4 and tuple(ki.shape[1:]) == (R, R, 3)) or
             (ki.dtype == torch.float32 and ki.dim() == 4 and tuple(ki.shape[1:]) == (3, R, R))):
         raise ValueError(f"known_images must be uint8 [K, {R}, {R}, 3] or fp32 [K, 3, {R}, {R}] in [-1, 1]")
-    rows_ok("known_images", ki)
+    check_row_count("known_images", ki, sample_count)
     out["images"] = ki
     return out
 
 
-def _encode_known(pipe, inpaint, rows, n, S, device):
-    """the rows of ``known_images`` a rank needs -> fp16 [len(rows), C*S*S] on the host: the posterior MEAN in the model's space, (z - shift) * scale,
-    through the encoder engine built from ``pipe.vae`` (``use_native_vae_encoder``), in chunks of its ``max_batch``"""
+def _known_rows(pipe, inpaint, batches, n, S, device) -> KnownRows:
+    """``sd_prepare_known``'s tables as ``KnownRows``; ``known_images`` are encoded here through the encoder engine built from ``pipe.vae``
+    (``use_native_vae_encoder``) to fp16 on the host: the posterior MEAN in the model's space, (z - shift) * scale."""
+    if "latents" in inpaint:
+        return KnownRows(device, known=inpaint["latents"], mask=inpaint["mask"])
     from .AnalyzeWeightedSumDegradation import preprocess
     enc = use_native_vae_encoder(pipe, n, S, device).natinf_vae_encoder
     scale, shift = float(pipe.vae.config.scaling_factor), float(getattr(pipe.vae.config, "shift_factor", 0.0) or 0.0)
-    imgs, lat = inpaint["images"], []
-    for s0 in range(0, len(rows), enc.max_batch):
-        chunk = imgs[torch.as_tensor(rows[s0:s0 + enc.max_batch], dtype=torch.int64)]
+
+    def encode_chunk(chunk, rows):
         x = (preprocess(chunk) if chunk.dtype == torch.uint8 else chunk).to(device)
-        lat.append(enc.encode(x, sample=False, scale=scale, shift=shift).reshape(len(chunk), -1).to(torch.float16).cpu())
-    return torch.cat(lat)
+        return enc.encode(x, sample=False, scale=scale, shift=shift).reshape(len(chunk), -1).to(torch.float16).cpu()
+    known = KnownRows(device, mask=inpaint["mask"])
+    known.encode("known", inpaint["images"], batches, encode_chunk, enc.max_batch)
+    return known
 
 
 def _load_pipe(pipe, device, dtype, n=4):
@@ -237,16 +219,34 @@ def _write_row(path, images):
     Image.fromarray(np.hstack(images)).save(str(path))
 
 
+def _velocity(pipe, x, ts, text, pooled, joint):
+    """one denoiser call on the sequences given: the engine's own ``forward`` when it holds them (``joint``), the reference's call shape otherwise"""
+    if joint:
+        return pipe.transformer.forward(x, ts, text, pooled)
+    return pipe.transformer(hidden_states=x, timestep=ts, encoder_hidden_states=text, pooled_projections=pooled, return_dict=False)[0]
+
+
 def _velocities(pipe, x, ts, emb):
+    """the text and null velocities of a step: ONE forward when the transformer is the engine and holds 2n sequences, the reference's two calls otherwise"""
     pe, ne, ppe, npe = emb
     from .mmdit import MMDiTEngine
-    if isinstance(pipe.transformer, MMDiTEngine) and pipe.transformer.max_batch >= 2 * x.shape[0]:
-        n = x.shape[0]                                      # text and null prompts of a step in one batched forward
-        v = pipe.transformer.forward(torch.cat([x, x]), torch.cat([ts, ts]), torch.cat([pe, ne]), torch.cat([ppe, npe]))
+    n = x.shape[0]
+    if isinstance(pipe.transformer, MMDiTEngine) and pipe.transformer.max_batch >= 2 * n:
+        v = _velocity(pipe, torch.cat([x, x]), torch.cat([ts, ts]), torch.cat([pe, ne]), torch.cat([ppe, npe]), True)
         return v[:n].contiguous(), v[n:].contiguous()
-    vt = pipe.transformer(hidden_states=x, timestep=ts, encoder_hidden_states=pe, pooled_projections=ppe, return_dict=False)[0]
-    vn = pipe.transformer(hidden_states=x, timestep=ts, encoder_hidden_states=ne, pooled_projections=npe, return_dict=False)[0]
-    return vt.contiguous(), vn.contiguous()
+    return _velocity(pipe, x, ts, pe, ppe, False).contiguous(), _velocity(pipe, x, ts, ne, npe, False).contiguous()
+
+
+def _default_trajectory(pipe, ni, noises, timesteps, num_step, emb):
+    """The reference's loop (:198-223) for one batch in the default form -> the mean behind the last step, ``noises``' shape, the sampler's own
+    buffer: the flow input, then per step the two velocities of [x; x] and one natinf_step_f16chain launch with the sampler's one scale."""
+    shape = noises.shape
+    flat_noise = noises.contiguous().reshape(-1)
+    x = ni.first_input(flat_noise)
+    for kk in range(num_step):
+        vt, vn = _velocities(pipe, x.view(shape), timesteps[kk].expand(shape[0]), emb)
+        mean, x = ni.step(kk, x, vt.reshape(-1), vn.reshape(-1), flat_noise, want_next=kk + 1 < num_step)
+    return mean.view(shape)
 
 
 def job_prompts(prompts, sample_count):
@@ -262,43 +262,15 @@ def job_prompts(prompts, sample_count):
     return table
 
 
-def _check_interval(interval):
-    if interval is not None and (len(interval) != 2 or float(interval[0]) > float(interval[1])):
-        raise ValueError(f"guidance_interval must be (s_lo, s_hi) with s_lo <= s_hi, got {interval!r}")
-
-
 def sd_guidance_plan(sigmas, n_step, scales, interval=None):
-    """The guidance of one batch -> (guided, slots, scales).  ``scales``: the batch's per-image CFG scales (``job_scales`` taken at
-    the batch's global indices); ``interval`` None or ``(s_lo, s_hi)`` on the sigma scale: step kk is inside when
-    ``s_lo <= float(sigmas[kk]) <= s_hi``, the fp32 value of the schedule the step multiplies by, both ends inclusive.
-
-    ``slots[i]``: the row of image i among the batch's null-prompt sequences, or -1 for an image whose scale is exactly 1.0
-    (unguided: f = x - sig*v_text, no null-prompt sequence); the images that are guided take rows 0, 1, ... in batch order.
-    ``guided[kk]``: whether step kk runs the null-prompt sequences at all -- its sigma lies in the interval and at least one
-    image has a slot.  A step that is not guided is unguided for every image.  ``scales`` comes back as the fp32 values.
-    Pure host code: at most two forward shapes per batch, n + max(slots) + 1 sequences and n."""
-    _check_interval(interval)
+    """The guidance of one batch -> (guided, slots, scales): ``jobs.guidance_plan``, which describes the three, on the sigma scale.  ``interval`` None
+    or ``(s_lo, s_hi)``: step kk is inside when ``s_lo <= float(sigmas[kk]) <= s_hi``, the fp32 value of the schedule the step multiplies by, both
+    ends inclusive; an unguided image (scale exactly 1.0, slot -1) is f = x - sig*v_text, with no null-prompt sequence.  Pure host code."""
+    check_interval(interval)
     n_step = int(n_step)
     if len(sigmas) < n_step:
         raise ValueError(f"{len(sigmas)} sigmas for {n_step} steps")
-    scales = [float(np.float32(v)) for v in scales]
-    slots, g = [], 0
-    for v in scales:
-        slots.append(-1 if v == 1.0 else g)
-        g += v != 1.0
-    if interval is None:
-        inside = [True] * n_step
-    else:
-        s_lo, s_hi = (float(v) for v in interval)
-        inside = [s_lo <= float(sigmas[kk]) <= s_hi for kk in range(n_step)]
-    return [bool(g) and ok for ok in inside], slots, scales
-
-
-def _velocity(pipe, x, ts, text, pooled, joint):
-    """one denoiser call on the sequences given: the engine's own ``forward`` when it holds them (``joint``), the reference's call shape otherwise"""
-    if joint:
-        return pipe.transformer.forward(x, ts, text, pooled)
-    return pipe.transformer(hidden_states=x, timestep=ts, encoder_hidden_states=text, pooled_projections=pooled, return_dict=False)[0]
+    return guidance_plan([float(sigmas[kk]) for kk in range(n_step)], n_step, scales, None if interval is None else tuple(float(v) for v in interval))
 
 
 def _planned_trajectory(pipe, ni, noises, timesteps, num_step, emb, plan, blend=None):
@@ -355,7 +327,7 @@ def sd_generate_sharded(pipe, sample_count: int, n: int = 4, rank: int = 0, worl
     it always made: every step a forward of [x; x] and natinf_step_f16chain with the one scale -- byte-identical latents.  Two arguments go beyond it
     (``sd_guidance_plan``, natinf_step_f16chain_guided):
 
-    * ``cfg_scale`` a sequence of ``sample_count`` numbers, by GLOBAL image index (``ValidateNaturalInference.job_scales``): image i carries its own scale
+    * ``cfg_scale`` a sequence of ``sample_count`` numbers, by GLOBAL image index (``jobs.job_scales``): image i carries its own scale
       whatever the rank, world or batch split.  A scale exactly 1.0 means unguided: no null-prompt sequence for that image at any step, f = x - sig*v_text.
     * ``guidance_interval=(s_lo, s_hi)`` on the sigma scale: guide only at the steps kk with ``s_lo <= float(sigmas[kk]) <= s_hi`` (the fp32 value of the
       schedule), both ends inclusive; every other step is unguided for every image (Kynkaanniemi et al., 2024).  With it a scalar ``cfg_scale == 1.0``
@@ -383,7 +355,7 @@ def sd_generate_sharded(pipe, sample_count: int, n: int = 4, rank: int = 0, worl
       generates), by the encoder engine built from ``pipe.vae`` (``use_native_vae_encoder``) to the posterior MEAN, with ``scale=scaling_factor`` and
       ``shift=shift_factor``.  The encoder engine stops at latent side 64 (512 x 512 images); beyond it pass ``known_latents``.
     * ``mask`` (bool / uint8, non-zero = known; K' 1 or ``sample_count``): a latent-element mask ``[K', *latent_shape]`` as it is, a cell mask
-      ``[K', S, S]`` for every channel, or a pixel mask ``[K', 8S, 8S]`` reduced by ``ValidateNaturalInference.latent_mask(mask, mask_erode)`` and
+      ``[K', S, S]`` for every channel, or a pixel mask ``[K', 8S, 8S]`` reduced by ``jobs.latent_mask(mask, mask_erode)`` and
       broadcast over the channels.
 
     Inpainting always runs the per-image step: a scalar ``cfg_scale`` becomes a uniform scale sequence, whose forwards are those of the default form and
@@ -393,12 +365,10 @@ def sd_generate_sharded(pipe, sample_count: int, n: int = 4, rank: int = 0, worl
 
     Returns (final latents [n_local, *latent_shape] fp16 on the device, their global indices [n_local] int64 on the CPU)."""
     from .shard import rank_batches
-    from .ValidateNaturalInference import job_scales, gather_rows
     inpaint = sd_prepare_known(known_latents, known_images, mask, sample_count, latent_shape, renoise, mask_erode)   # refusals before any GPU call
-    # False: the reference's form, today's calls
-    planned = inpaint is not None or guidance_interval is not None or not isinstance(cfg_scale, (int, float, np.floating, np.integer))
-    _check_interval(guidance_interval)
-    if inpaint is not None and isinstance(cfg_scale, (int, float, np.floating, np.integer)):
+    planned = inpaint is not None or guidance_interval is not None or not is_scalar_scale(cfg_scale)   # False: the reference's form, today's calls
+    check_interval(guidance_interval)
+    if inpaint is not None and is_scalar_scale(cfg_scale):
         cfg_scale = [float(cfg_scale)] * int(sample_count)               # the uniform sequence: the default form's forwards and, on the unknown side, its bytes
     scale_of = job_scales(cfg_scale, sample_count) if planned else None
     prompt_of = None if prompts is None else job_prompts(prompts, sample_count)
@@ -415,19 +385,12 @@ def sd_generate_sharded(pipe, sample_count: int, n: int = 4, rank: int = 0, worl
     samplers, outs = {}, []
     if planned:
         sigmas_host = sigmas.detach().to("cpu", torch.float32)
-    if inpaint is not None and "images" in inpaint:                      # encode this rank's rows once, before the loop; kept on the host
-        rows = [0] if inpaint["images"].shape[0] == 1 else [i for b in batches for i in b]
-        inpaint["latents"] = _encode_known(pipe, inpaint, rows, n, int(latent_shape[-1]), dev)
-        if inpaint["images"].shape[0] != 1:                              # the table holds this rank's rows only, in the rank's order
-            inpaint["row_of"] = {i: r for r, i in enumerate(rows)}
+    known = None if inpaint is None else _known_rows(pipe, inpaint, batches, n, int(latent_shape[-1]), dev)   # images are encoded here, before the loop
     for batch in batches:
         nb = len(batch)
         noises = philox_noise_f16(batch, latent_shape, seed, dev)
-        blend = None
-        if inpaint is not None:                                         # the batch's rows by global index, gathered on the host
-            rows_b = [inpaint["row_of"][i] for i in batch] if "row_of" in inpaint else batch
-            blend = dict(known=gather_rows(inpaint["latents"], rows_b).reshape(-1).to(dev), mask=gather_rows(inpaint["mask"], batch).reshape(-1).to(dev),
-                         seed=seed, index=torch.tensor(list(batch), dtype=torch.int64, device=dev), renoise=renoise)
+        # inpainting: the batch's rows by global index, gathered on the host
+        blend = None if known is None else dict(known.batch(batch), seed=seed, index=torch.tensor(list(batch), dtype=torch.int64, device=dev), renoise=renoise)
         if nb not in samplers:                                          # (a ragged last batch gets its own history slabs)
             samplers[nb] = SD3NI(weights, sigmas, noises.numel(), device=dev, cfg=float(cfg_scale) if not planned else 7.0,
                                  elems_per_image=noises[0].numel() if planned else None)
@@ -442,13 +405,8 @@ def sd_generate_sharded(pipe, sample_count: int, n: int = 4, rank: int = 0, worl
                     torch.tensor(slots, dtype=torch.int32, device=dev), torch.full((nb,), -1, dtype=torch.int32, device=dev),
                     torch.tensor(scales, dtype=torch.float32, device=dev))
             outs.append(_planned_trajectory(pipe, ni, noises, timesteps, num_step, e, plan, blend).view(noises.shape).clone())
-            continue
-        flat_noise = noises.reshape(-1)
-        x = ni.first_input(flat_noise)
-        for kk in range(num_step):
-            vt, vn = _velocities(pipe, x.view(noises.shape), timesteps[kk].expand(nb), e)
-            mean, x = ni.step(kk, x, vt.reshape(-1), vn.reshape(-1), flat_noise, want_next=kk + 1 < num_step)
-        outs.append(mean.view(noises.shape).clone())
+        else:
+            outs.append(_default_trajectory(pipe, ni, noises, timesteps, num_step, e).clone())
     return torch.cat(outs), torch.cat([torch.tensor(b, dtype=torch.int64) for b in batches])
 
 
@@ -492,20 +450,14 @@ def sd_natural_inference_tx(pipe=None, device="cuda", noises: Optional[torch.Ten
         return finals
     if world != 1 or rank != 0:
         raise ValueError("rank / world need sample_count (the reference's job is one batch: nothing to shard)")
-    if prompts is not None or negative_prompt != "" or guidance_interval is not None or not isinstance(cfg_scale, (int, float, np.floating, np.integer)) or cfg_scale != 7.0:
+    if prompts is not None or negative_prompt != "" or guidance_interval is not None or not is_scalar_scale(cfg_scale) or cfg_scale != 7.0:
         raise ValueError("prompts / negative_prompt / cfg_scale / guidance_interval need sample_count (the reference's job hard-wires one prompt and cfg 7)")
     noises, emb, timesteps, sigmas = _prepare(pipe, device, dtype, n, seed, num_step, noises)
-    shape, finals = noises.shape, []
+    finals = []
     for weight_name in weight_names:
         weights = load_sd3_csv(os.path.join(root_path / "weights", weight_name))
         ni = SD3NI(weights, sigmas, noises.numel(), device=noises.device, cfg=7.0)
-        flat_noise = noises.contiguous().reshape(-1)
-        x = ni.first_input(flat_noise)
-        for kk in range(num_step):
-            ts = timesteps[kk].expand(shape[0])
-            vt, vn = _velocities(pipe, x.view(shape), ts, emb)
-            mean, x = ni.step(kk, x, vt.reshape(-1), vn.reshape(-1), flat_noise, want_next=kk + 1 < num_step)
-        out = mean.view(shape).clone()
+        out = _default_trajectory(pipe, ni, noises, timesteps, num_step, emb).clone()
         finals.append(out)
         if decode:
             _write_row(results_path / ("results/sd3/sgl_%s.png" % (weight_name[:-4])), _decode(pipe, out))
@@ -519,15 +471,8 @@ def sd_euler_natural_inference_tx(pipe=None, device="cuda", noises: Optional[tor
     dtype = torch.float16
     pipe = _load_pipe(pipe, device, dtype, n)
     noises, emb, timesteps, sigmas = _prepare(pipe, device, dtype, n, seed, num_step, noises)
-    shape = noises.shape
     ni = SD3NI(None, sigmas, noises.numel(), device=noises.device, cfg=7.0, euler=True)
-    flat_noise = noises.contiguous().reshape(-1)
-    x = ni.first_input(flat_noise)
-    for i in range(num_step):
-        ts = timesteps[i].expand(shape[0])
-        vt, vn = _velocities(pipe, x.view(shape), ts, emb)
-        mean, x = ni.step(i, x, vt.reshape(-1), vn.reshape(-1), flat_noise, want_next=i + 1 < num_step)
-    out = mean.view(shape).clone()
+    out = _default_trajectory(pipe, ni, noises, timesteps, num_step, emb).clone()
     if decode:
         _write_row(results_path / "results/sd3/euler_sgl_clip0.png", _decode(pipe, out))
     return out

@@ -19,9 +19,11 @@ from typing import Callable, List, Optional
 import numpy as np
 import torch
 
-from . import _lib
+from . import _lib, jobs
 from ._lib import lib, check, ptr, stream_ptr
 from .coeff import load_coeff_npz, SparseRows
+from .jobs import (KnownRows, check_interval, check_row_count, gather_rows, host_mask, inpainting_on, is_scalar_scale, job_scales,  # noqa: F401
+                   latent_mask, mask_table)                # (job_scales, latent_mask and gather_rows: importable from here as before)
 from .sampler import ValidateNI
 
 root_path = Path(__file__).resolve().parent.parent
@@ -195,13 +197,7 @@ def latent_size(model) -> int:
 def _setup(seed):
     torch.manual_seed(seed)
     torch.set_grad_enabled(False)
-    if denoiser_factory is not None:
-        model = denoiser_factory()
-    elif model_path is not None:
-        model = load_dit_engine(model_path)
-    else:
-        raise RuntimeError("set ValidateNaturalInference.model_path (a DiT-XL/2 state dict, reference :152-154) or "
-                           "ValidateNaturalInference.denoiser_factory; see INTEGRATION.md")
+    model, _ = _resolve_denoiser(None, None, 8, False, None)               # the factory's, or the engine of model_path for 2 x 8 samples
     labels = torch.tensor([207, 360, 387, 974, 88, 979, 417, 279], device=device)
     return model, labels, len(labels)
 
@@ -401,40 +397,11 @@ def job_batches(sample_count, batch_size, rank=0, world=1, labels=None):
     return [(idx, [table[i % len(table)] for i in idx]) for idx in rank_batches(sample_count, batch_size, rank, world)]
 
 
-def job_scales(cfg_scale, sample_count):
-    """The CFG scale of every image of a job, by GLOBAL index: a number is every image's scale, a sequence must have exactly
-    ``sample_count`` entries (image i carries ``cfg_scale[i]`` whatever the rank, world or batch split, like its label).  Each
-    is rounded to fp32, the value the step kernel multiplies by.  Pure host code."""
-    sample_count = int(sample_count)
-    if isinstance(cfg_scale, (int, float, np.floating, np.integer)):
-        return [float(np.float32(cfg_scale))] * sample_count
-    table = [float(np.float32(v)) for v in cfg_scale]
-    if len(table) != sample_count:
-        raise ValueError(f"{len(table)} CFG scales for {sample_count} images: a scale sequence has one entry per image of the job")
-    return table
-
-
 def guidance_plan(node, n_step, scales, interval=None):
-    """The guidance of one batch -> (guided, slots, scales).  ``scales``: the batch's per-image CFG scales (``job_scales``
-    taken at the batch's global indices); ``interval`` None or ``(t_lo, t_hi)``, integers on the scale of the timestep the
-    job feeds the denoiser at step kk, ``int(node[kk, 0])``, both ends inclusive.
-
-    ``slots[i]``: the row of image i among the batch's unconditional samples, or -1 for an image whose scale is exactly 1.0
-    (unguided: eps = cond, no unconditional sample); the images that are guided take rows 0, 1, ... in batch order.
-    ``guided[kk]``: whether step kk runs the unconditional samples at all -- its timestep lies in the interval and at
-    least one image has a slot.  A step that is not guided is unguided for every image.  ``scales`` comes back as the
-    fp32 values.  Pure host code: at most two forward shapes per batch, n + max(slots) + 1 samples and n."""
-    scales = [float(np.float32(v)) for v in scales]
-    slots, g = [], 0
-    for v in scales:
-        slots.append(-1 if v == 1.0 else g)
-        g += v != 1.0
-    if interval is None:
-        inside = [True] * int(n_step)
-    else:
-        t_lo, t_hi = (int(v) for v in interval)
-        inside = [t_lo <= int(node[kk, 0]) <= t_hi for kk in range(int(n_step))]
-    return [bool(g) and ok for ok in inside], slots, scales
+    """The guidance of one batch -> (guided, slots, scales): ``jobs.guidance_plan``, which describes the three, on the timestep scale.  ``interval``
+    None or ``(t_lo, t_hi)``, integers on the scale of the timestep the job feeds the denoiser at step kk, ``int(node[kk, 0])``, both ends
+    inclusive; an unguided image (scale exactly 1.0, slot -1) is eps = cond, with no unconditional sample.  Pure host code."""
+    return jobs.guidance_plan([int(node[kk, 0]) for kk in range(int(n_step))], n_step, scales, None if interval is None else tuple(int(v) for v in interval))
 
 
 def to_pixels_u8(images: torch.Tensor) -> torch.Tensor:
@@ -443,81 +410,182 @@ def to_pixels_u8(images: torch.Tensor) -> torch.Tensor:
     return ((((x.clamp(-1, 1) + 1) * 0.5) * 255 + 0.5).clamp(0, 255)).to(torch.uint8).permute(0, 2, 3, 1).contiguous()
 
 
-def latent_mask(mask_px, erode: int = 1) -> torch.Tensor:
-    """A pixel mask [K, 8S, 8S] (bool / uint8, non-zero = known) reduced to latent cells -> uint8 [K, S, S] on the CPU.  A cell is known iff
-    every pixel of the (8 + 16*erode)-pixel square centred on it that lies inside the image is known: its own 8 x 8 pixels and ``erode`` rings
-    of neighbouring cells (``max_pool2d`` of the UNKNOWN pixels over 8, then over 2*erode + 1 cells; the pooling pads with -inf, so what lies
-    outside the image never makes a cell unknown).  Pure host code."""
-    m = torch.as_tensor(mask_px).cpu()
-    erode = int(erode)
-    if m.dtype not in (torch.bool, torch.uint8) or m.dim() != 3 or m.shape[1] % 8 or m.shape[2] % 8 or not m.shape[1] or not m.shape[2]:
-        raise ValueError("a pixel mask must be bool or uint8 [K, H, W] with H and W positive multiples of 8")
-    if erode < 0:
-        raise ValueError("mask_erode must be >= 0")
-    u = torch.nn.functional.max_pool2d(1.0 - (m != 0).to(torch.float32)[:, None], 8)
-    if erode:
-        u = torch.nn.functional.max_pool2d(u, 2 * erode + 1, 1, erode)
-    return (1.0 - u)[:, 0].to(torch.uint8)
-
-
 def prepare_known_latents(known_latents, known_images, mask, sample_count: int, known_final: str = "mean", mask_erode: int = 1):
     """The inpainting arguments of ``generate_sharded``, checked and brought to one form -> None (inpainting off) or a dict: ``S`` (the latent
     side they imply), ``mask`` (uint8 [K', 4*S*S] per latent ELEMENT, the form the step takes), and either ``latents`` (fp32 [K, 4*S*S]) or
     ``images`` (the caller's uint8 [K, 8S, 8S, 3] / fp32 [K, 3, 8S, 8S], still to be encoded) with ``mask_px`` (bool [K', 8S, 8S]); K and K' each
     ``sample_count`` (row i belongs to global image index i) or 1 (shared by every image).  Pure host code: every refusal comes before any GPU
     call."""
-    if known_latents is None and known_images is None and mask is None:
+    if not inpainting_on(known_latents, known_images, mask):
         return None
-    if known_latents is not None and known_images is not None:
-        raise ValueError("inpainting takes known_latents= or known_images=, not both")
-    if mask is None:
-        raise ValueError("inpainting needs mask= beside known_latents= / known_images=")
-    if known_latents is None and known_images is None:
-        raise ValueError("mask= needs known_latents= or known_images=")
     if known_final not in ("mean", "data"):
         raise ValueError('known_final must be "mean" or "data"')
     sample_count = int(sample_count)
-    mask = torch.as_tensor(mask).cpu()
-    if mask.dtype not in (torch.bool, torch.uint8):
-        raise ValueError("mask must be bool or uint8")
-
-    def rows_ok(name, t):
-        if t.shape[0] not in (1, sample_count):
-            raise ValueError(f"{name} must hold 1 row (shared) or sample_count ({sample_count}) rows, not {t.shape[0]}")
+    mask = host_mask(mask)
     if known_latents is not None:
         kl = torch.as_tensor(known_latents).cpu()
         if kl.dtype != torch.float32 or kl.dim() != 4 or kl.shape[1] != 4 or kl.shape[2] != kl.shape[3] or kl.shape[2] % 2 or not kl.shape[2]:
             raise ValueError("known_latents must be fp32 [K, 4, S, S] in the denoiser's scale")
         S = int(kl.shape[2])
-        rows_ok("known_latents", kl)
-        if mask.dim() == 3 and tuple(mask.shape[1:]) == (S, S):
-            mask = mask[:, None].expand(-1, 4, -1, -1)
-        elif not (mask.dim() == 4 and tuple(mask.shape[1:]) == (4, S, S)):
+        check_row_count("known_latents", kl, sample_count)
+        table = mask_table(mask, 4, S, sample_count, forms=("element", "cell"))
+        if table is None:
             raise ValueError(f"with known_latents the mask must be [K', {S}, {S}] (a latent cell: every channel) or [K', 4, {S}, {S}]")
-        rows_ok("mask", mask)
-        return dict(S=S, latents=kl.reshape(kl.shape[0], -1).contiguous(), mask=(mask != 0).to(torch.uint8).reshape(mask.shape[0], -1).contiguous())
+        return dict(S=S, latents=kl.reshape(kl.shape[0], -1).contiguous(), mask=table)
     ki = torch.as_tensor(known_images).cpu()
-    if ki.dtype == torch.uint8 and ki.dim() == 4 and ki.shape[3] == 3 and ki.shape[1] == ki.shape[2]:
-        R = int(ki.shape[1])
-    elif ki.dtype == torch.float32 and ki.dim() == 4 and ki.shape[1] == 3 and ki.shape[2] == ki.shape[3]:
-        R = int(ki.shape[2])
-    else:
+    if not (ki.dim() == 4 and ((ki.dtype == torch.uint8 and ki.shape[3] == 3 and ki.shape[1] == ki.shape[2]) or
+                               (ki.dtype == torch.float32 and ki.shape[1] == 3 and ki.shape[2] == ki.shape[3]))):
         raise ValueError("known_images must be uint8 [K, 8S, 8S, 3] or fp32 [K, 3, 8S, 8S] in [-1, 1]")
+    R = int(ki.shape[2])                                              # the side, in either form
     if not R or R % 16:
         raise ValueError("known_images must be 8S pixels on a side, S even")
-    rows_ok("known_images", ki)
-    if not (mask.dim() == 3 and tuple(mask.shape[1:]) == (R, R)):
+    check_row_count("known_images", ki, sample_count)
+    table = mask_table(mask, 4, R // 8, sample_count, mask_erode, forms=("pixel",))
+    if table is None:
         raise ValueError(f"with known_images the mask must be a pixel mask [K', {R}, {R}]")
-    rows_ok("mask", mask)
-    cells = latent_mask(mask, mask_erode)
-    S = R // 8
-    return dict(S=S, images=ki, mask_px=mask != 0, mask=cells[:, None].expand(-1, 4, -1, -1).reshape(cells.shape[0], -1).contiguous())
+    return dict(S=R // 8, images=ki, mask_px=mask != 0, mask=table)
 
 
-def gather_rows(rows: torch.Tensor, batch) -> torch.Tensor:
-    """The rows of a per-image table a batch takes, by global index, or the one shared row (``CIFAR10NaturalInference.gather_known``'s pattern,
-    the leading dimension kept)."""
-    return rows[:1] if rows.shape[0] == 1 else rows[torch.as_tensor(list(batch), dtype=torch.int64)]
+def _resolve_denoiser(model, fallback, batch_size, fp8, stream16):
+    """the denoiser of a job or a sampler and, for ``stream16="auto"``, the callable that builds its fp32-stream twin -> (model, fallback)"""
+    auto = stream16 == "auto"
+    if auto and fallback is None and model_path is not None and model is None and denoiser_factory is None:
+        fallback = lambda: load_dit_engine(model_path, max_batch=2 * batch_size, fp8=fp8, stream16=False)
+    if model is None:
+        if denoiser_factory is not None:
+            model = denoiser_factory()
+        elif model_path is not None:
+            model = load_dit_engine(model_path, max_batch=2 * batch_size, fp8=fp8, stream16=stream16)
+        else:
+            raise RuntimeError("set ValidateNaturalInference.model_path (a DiT-XL/2 state dict, reference :152-154) or "
+                               "ValidateNaturalInference.denoiser_factory (generate_sharded also takes model=); see INTEGRATION.md")
+    if fp8 and not getattr(model, "fp8", False):
+        raise ValueError("fp8=True, but the denoiser given is not an fp8 engine (DiTEngine(..., fp8=True))")
+    if auto and not (getattr(model, "guard", False) and hasattr(model, "stream_status")):
+        raise ValueError('stream16="auto" needs a guarded denoiser (DiTEngine(..., guard=True)): an unguarded one cannot say that it overflowed')
+    if auto and fallback is None:
+        raise ValueError('stream16="auto" with a denoiser of the caller\'s needs fallback=: a callable that returns the fp32-stream denoiser')
+    return model, fallback
+
+
+def _resolve_decoder(decoder, decode, decode_batch, S):
+    """the decoder of a job: the one given, else ``decoder_factory()``, else the VAE engine of ``vae_path``; None with none of them or ``decode=False``"""
+    if decode and decoder is None and decoder_factory is not None:
+        return decoder_factory()
+    if decode and decoder is None and vae_path is not None:
+        return load_vae_decoder(vae_path, max_batch=int(decode_batch), latent_res=S)
+    return decoder if decode else None
+
+
+def _known_rows(inpaint, batches, encoder, S) -> KnownRows:
+    """``prepare_known_latents``' tables as ``KnownRows``; ``known_images`` are encoded here, to the posterior mean in the denoiser's scale"""
+    if inpaint["S"] != S:
+        raise ValueError(f"the known data is for latents of side {inpaint['S']}, the denoiser's are {S}")
+    if "latents" in inpaint:
+        return KnownRows(device, known=inpaint["latents"], mask=inpaint["mask"])
+    from .AnalyzeWeightedSumDegradation import preprocess
+    if encoder is None:
+        if vae_path is None:
+            raise RuntimeError("known_images= needs encoder= or ValidateNaturalInference.vae_path (load_vae_encoder)")
+        encoder = load_vae_encoder(vae_path, latent_res=S)
+
+    def encode_chunk(chunk, rows):
+        x = (preprocess(chunk) if chunk.dtype == torch.uint8 else chunk).to(device)
+        return encoder.encode(x, sample=False, scale=0.18215, index=rows).reshape(len(chunk), -1).cpu()
+    known = KnownRows(device, mask=inpaint["mask"])
+    known.encode("known", inpaint["images"], [idx for idx, _ in batches], encode_chunk, getattr(encoder, "max_batch", 1))
+    return known
+
+
+def _first_z(ni, noise, index, blend):
+    """the first model input of a trajectory: the noise, or (inpainting) the noise with the known latents at level 0; ``noise`` stays eps_0"""
+    return ni.first_input(noise.reshape(-1), index=index, **blend).view(noise.shape) if blend else noise
+
+
+def _trajectory(denoiser, ni, noise, index, steps_t, classlabels, classnulls, cfg_scale, blend):
+    """one batch in the default form: [z; z] forwards and the launch-wide step; ``blend``: the batch's known= / mask= / known_final= ({}: none)"""
+    shape, S = noise.shape, noise.shape[-1]
+    per = 4 * S * S
+    input_z, flat_noise = _first_z(ni, noise, index, blend), noise.reshape(-1)
+    for kk in range(len(steps_t)):
+        cond, uncond = _cond_uncond(denoiser, input_z, steps_t[kk], classlabels, classnulls)   # [n, 8, S, S] each; first 4 channels used
+        z = ni.step(kk, input_z.reshape(-1), cond.contiguous(), uncond.contiguous(), cfg_scale, per, cond.shape[1] * S * S,
+                    noise=flat_noise, index=index, **blend)
+        input_z = z.view(shape)
+    return input_z.clone()
+
+
+def _batch_plan(node, n_step, scales, interval, classlabels, classnulls):
+    """the ``guidance_plan`` of a batch with its device tensors, built once per batch (the rerun of a clamped batch uses the same plan)"""
+    dev = classlabels.device
+    guided, slots, scales = guidance_plan(node, n_step, scales, interval)
+    pick = [i for i, s in enumerate(slots) if s >= 0]
+    n, g = len(slots), len(pick)
+    return (guided, torch.tensor(pick, dtype=torch.int64, device=dev), torch.cat([classlabels, classnulls[:g]]),
+            [torch.full((n + g,), int(node[kk, 0]), dtype=torch.int32, device=dev) for kk in range(n_step)],
+            torch.tensor(slots, dtype=torch.int32, device=dev), torch.tensor(scales, dtype=torch.float32, device=dev))
+
+
+def _planned_trajectory(denoiser, ni, noise, index, steps_t, classlabels, plan, blend):
+    """``_trajectory`` under a ``_batch_plan``: a guided step forwards [z; z[G]] (one call when the denoiser takes n + |G| samples) and makes the
+    per-image step, every other step forwards the n conditional samples alone"""
+    guided, pick, labels_g, steps_g, slots_t, scales_t = plan
+    shape, n, g, S = noise.shape, noise.shape[0], len(pick), noise.shape[-1]
+    per = 4 * S * S
+    joint = getattr(denoiser, "max_batch", 0) >= n + g
+    nulls = labels_g[n:]
+    input_z, flat_noise = _first_z(ni, noise, index, blend), noise.reshape(-1)
+    for kk in range(len(steps_t)):
+        if not guided[kk]:
+            cond = denoiser.forward(input_z, steps_t[kk], classlabels).contiguous()
+            z = ni.step(kk, input_z.reshape(-1), cond, None, 1.0, per, cond.shape[1] * S * S, noise=flat_noise, index=index, **blend)
+        else:
+            zg = input_z if g == n else input_z[pick]
+            if joint:
+                both = denoiser.forward(torch.cat([input_z, zg]), steps_g[kk], labels_g).contiguous()
+                cond, uncond = both[:n], both[n:]
+            else:
+                cond = denoiser.forward(input_z, steps_t[kk], classlabels).contiguous()
+                uncond = denoiser.forward(zg, steps_g[kk][n:], nulls).contiguous()
+            z = ni.step(kk, input_z.reshape(-1), cond, uncond, scales_t, per, cond.shape[1] * S * S, noise=flat_noise, index=index,
+                        uncond_slot=slots_t, n_uncond=g, **blend)
+        input_z = z.view(shape)
+    return input_z.clone()
+
+
+def _guarded_batch(trajectory, model, wide, fallback, args, report, bi):
+    """One batch of a ``stream16="auto"`` job -> (latents, the fp32-stream denoiser once built): the status is reset in front of the batch and read
+    once behind it (the job's one wait per batch); a batch that clamped runs again, with the same arguments, on ``wide``."""
+    model.reset_stream_status()
+    latents = trajectory(model, *args)
+    st = model.stream_status()
+    hit = np.flatnonzero(np.asarray(st["clamped"]))
+    if len(hit):
+        if report["first_clamp"] is None:
+            k = int(hit[0])
+            report["first_clamp"] = dict(batch=bi, site=k, site_name=model.site_names[k], max_abs=float(st["max_abs"][k]), clamped=int(st["clamped"][k]))
+        report["rerun_batches"].append(bi)
+        if wide is None:
+            wide = fallback()
+        latents = trajectory(wide, *args)                                 # same noise, same labels, same indices: the fp32-stream job's batch
+    return latents, wide
+
+
+def _decode_images(decoder, latents, indices, labels, decode_batch, image_sink, pasted):
+    """decode in chunks of ``decode_batch`` -> uint8 images on the CPU, or None when ``image_sink`` takes each chunk; ``pasted``: None, or the
+    caller's (pixel mask, uint8 images) by global index, whose known pixels go back into the decoded images first"""
+    db, out = max(1, int(decode_batch)), []
+    for s0 in range(0, len(indices), db):
+        u8 = to_pixels_u8(decoder(latents[s0:s0 + db] / 0.18215))
+        if pasted is not None:
+            u8 = torch.where(gather_rows(pasted[0], indices[s0:s0 + db]).to(device)[..., None], gather_rows(pasted[1], indices[s0:s0 + db]).to(device), u8)
+        if image_sink is not None:
+            image_sink(u8, indices[s0:s0 + db], labels[s0:s0 + db])
+        else:
+            out.append(u8.cpu())
+    if image_sink is not None:
+        return None
+    return torch.cat(out) if out else torch.empty((0, 8 * latents.shape[-1], 8 * latents.shape[-1], 3), dtype=torch.uint8)
 
 
 @torch.no_grad()
@@ -591,41 +659,18 @@ def generate_sharded(sample_count, labels=None, alg_name="ddpm", num_step=24, ba
     batch_size = int(batch_size)
     batches = job_batches(sample_count, batch_size, rank, world, labels)
     inpaint = prepare_known_latents(known_latents, known_images, mask, sample_count, known_final, mask_erode)   # refusals before any GPU call
-    planned = guidance_interval is not None or not isinstance(cfg_scale, (int, float, np.floating, np.integer))   # False: the reference's form, today's calls
+    planned = guidance_interval is not None or not is_scalar_scale(cfg_scale)   # False: the reference's form, today's calls
     scale_of = job_scales(cfg_scale, sample_count) if planned else None
-    if guidance_interval is not None and (len(guidance_interval) != 2 or int(guidance_interval[0]) > int(guidance_interval[1])):
-        raise ValueError(f"guidance_interval must be (t_lo, t_hi) with t_lo <= t_hi, got {guidance_interval!r}")
+    check_interval(guidance_interval, int, "t_lo", "t_hi")
     if stream16 not in (None, True, False, "auto"):
         raise ValueError(f'stream16 must be None, True, False or "auto", got {stream16!r}')
     auto = stream16 == "auto"
-    if auto and fallback is None and model_path is not None and model is None and denoiser_factory is None:
-        fallback = lambda: load_dit_engine(model_path, max_batch=2 * batch_size, fp8=fp8, stream16=False)
-    if model is None:
-        if denoiser_factory is not None:
-            model = denoiser_factory()
-        elif model_path is not None:
-            model = load_dit_engine(model_path, max_batch=2 * batch_size, fp8=fp8, stream16=stream16)
-        else:
-            raise RuntimeError("set ValidateNaturalInference.model_path (a DiT-XL/2 state dict, reference :152-154) or "
-                               "ValidateNaturalInference.denoiser_factory, or pass model=; see INTEGRATION.md")
-    if fp8 and not getattr(model, "fp8", False):
-        raise ValueError("fp8=True, but the denoiser given is not an fp8 engine (DiTEngine(..., fp8=True))")
-    if auto and not (getattr(model, "guard", False) and hasattr(model, "stream_status")):
-        raise ValueError('stream16="auto" needs a guarded denoiser (DiTEngine(..., guard=True)): an unguarded one cannot say that it overflowed')
-    if auto and fallback is None:
-        raise ValueError('stream16="auto" with a denoiser of the caller\'s needs fallback=: a callable that returns the fp32-stream denoiser')
+    model, fallback = _resolve_denoiser(model, fallback, batch_size, fp8, stream16)
     if report is None:
         report = {}
     report.update(batches=len(batches), rerun_batches=[], first_clamp=None)
-    wide = None                                                       # the fp32-stream denoiser: built at the first batch that needs it
     S = latent_size(model)
-    if decode and decoder is None:
-        if decoder_factory is not None:
-            decoder = decoder_factory()
-        elif vae_path is not None:
-            decoder = load_vae_decoder(vae_path, max_batch=int(decode_batch), latent_res=S)
-    if not decode:
-        decoder = None
+    decoder = _resolve_decoder(decoder, decode, decode_batch, S)
     weight_path = root_path / ("results/%s/%s_%03d.npz" % (alg_name.replace("_sympy", ""), alg_name, num_step))
     C, B, node = load_coeff_npz(weight_path)
     n_step = B.shape[0]
@@ -633,70 +678,10 @@ def generate_sharded(sample_count, labels=None, alg_name="ddpm", num_step=24, ba
     c1 = np.asarray(tables[2])[::-1].astype(np.float32)
     c2 = np.asarray(tables[3])[::-1].astype(np.float32)
     per = 4 * S * S
-    samplers = {}                                                     # batch size -> ValidateNI (the ragged last batch gets its own)
-    out_z, out_img = [], []
-    blend = {}                                                        # the current batch's known= / mask= / known_final= ({}: no inpainting, today's calls)
-    if inpaint is not None:
-        if inpaint["S"] != S:
-            raise ValueError(f"the known data is for latents of side {inpaint['S']}, the denoiser's are {S}")
-        if "images" in inpaint:                                       # encode this rank's rows once: the posterior mean in the denoiser's scale, kept on the host
-            from .AnalyzeWeightedSumDegradation import preprocess
-            if encoder is None:
-                if vae_path is None:
-                    raise RuntimeError("known_images= needs encoder= or ValidateNaturalInference.vae_path (load_vae_encoder)")
-                encoder = load_vae_encoder(vae_path, latent_res=S)
-            imgs = inpaint["images"]
-            rows = [0] if imgs.shape[0] == 1 else [i for idx, _ in batches for i in idx]
-            mb, lat = max(1, int(getattr(encoder, "max_batch", 1))), []
-            for s0 in range(0, len(rows), mb):
-                chunk = imgs[torch.as_tensor(rows[s0:s0 + mb], dtype=torch.int64)]
-                x = (preprocess(chunk) if chunk.dtype == torch.uint8 else chunk).to(device)
-                lat.append(encoder.encode(x, sample=False, scale=0.18215, index=rows[s0:s0 + mb]).reshape(len(chunk), -1).cpu())
-            inpaint["latents"] = torch.cat(lat) if lat else torch.empty((0, per), dtype=torch.float32)
-            if imgs.shape[0] != 1:                                    # the table holds this rank's rows only, in the rank's order
-                inpaint["row_of"] = {i: r for r, i in enumerate(rows)}
-
-    def trajectory(denoiser, ni, noise, index, steps_t, classlabels, classnulls):
-        n = noise.shape[0]
-        input_z, flat_noise = noise, noise.reshape(-1)
-        if blend:                                                     # inpainting: the known latents at level 0; `noise` stays eps_0
-            input_z = ni.first_input(flat_noise, index=index, **blend).view(n, 4, S, S)
-        for kk in range(n_step):
-            cond, uncond = _cond_uncond(denoiser, input_z, steps_t[kk], classlabels, classnulls)   # [n, 8, S, S] each; first 4 channels used
-            z = ni.step(kk, input_z.reshape(-1), cond.contiguous(), uncond.contiguous(), float(cfg_scale), per, cond.shape[1] * S * S,
-                        noise=flat_noise, index=index, **blend)
-            input_z = z.view(n, 4, S, S)
-        return input_z.clone()
-
-    def planned_trajectory(denoiser, ni, noise, index, steps_t, classlabels, plan):
-        """``trajectory`` under a ``guidance_plan``: a guided step forwards [z; z[G]] (one call when the denoiser takes n + |G| samples) and makes the per-image
-        step, every other step forwards the n conditional samples alone"""
-        guided, pick, labels_g, steps_g, slots_t, scales_t = plan
-        n, g = noise.shape[0], len(pick)
-        joint = getattr(denoiser, "max_batch", 0) >= n + g
-        nulls = labels_g[n:]
-        input_z, flat_noise = noise, noise.reshape(-1)
-        if blend:
-            input_z = ni.first_input(flat_noise, index=index, **blend).view(n, 4, S, S)
-        for kk in range(n_step):
-            if not guided[kk]:
-                cond = denoiser.forward(input_z, steps_t[kk], classlabels).contiguous()
-                z = ni.step(kk, input_z.reshape(-1), cond, None, 1.0, per, cond.shape[1] * S * S, noise=flat_noise, index=index, **blend)
-            else:
-                zg = input_z if g == n else input_z[pick]
-                if joint:
-                    both = denoiser.forward(torch.cat([input_z, zg]), steps_g[kk], labels_g).contiguous()
-                    cond, uncond = both[:n], both[n:]
-                else:
-                    cond = denoiser.forward(input_z, steps_t[kk], classlabels).contiguous()
-                    uncond = denoiser.forward(zg, steps_g[kk][n:], nulls).contiguous()
-                z = ni.step(kk, input_z.reshape(-1), cond, uncond, scales_t, per, cond.shape[1] * S * S, noise=flat_noise, index=index,
-                            uncond_slot=slots_t, n_uncond=g, **blend)
-            input_z = z.view(n, 4, S, S)
-        return input_z.clone()
-
-    if planned:
-        trajectory = planned_trajectory
+    known = None if inpaint is None else _known_rows(inpaint, batches, encoder, S)
+    trajectory = _planned_trajectory if planned else _trajectory
+    samplers, out_z = {}, []                                          # batch size -> ValidateNI (the ragged last batch gets its own)
+    wide = None                                                       # the fp32-stream denoiser: built at the first batch that needs it
     for bi, (indices, labs) in enumerate(batches):
         n = len(indices)
         if n not in samplers:
@@ -706,51 +691,22 @@ def generate_sharded(sample_count, labels=None, alg_name="ddpm", num_step=24, ba
         classnulls = torch.full((n,), 1000, dtype=torch.int64, device=device)
         steps_t = [torch.full((n,), int(node[kk, 0]), dtype=torch.int32, device=device) for kk in range(n_step)]
         noise = philox_noise(indices, (4, S, S), seed, device, column=0)
-        if inpaint is not None:                                       # the batch's rows by global index, gathered on the host, uploaded on the caller's stream
-            rows_b = [inpaint["row_of"][i] for i in indices] if "row_of" in inpaint else indices
-            blend.update(known=gather_rows(inpaint["latents"], rows_b).reshape(-1).to(device),
-                         mask=gather_rows(inpaint["mask"], indices).reshape(-1).to(device), known_final=known_final)
-        run = (samplers[n], noise, index, steps_t, classlabels, classnulls)
-        if planned:                                                   # slot and scale tensors once per batch; the rerun of a clamped batch uses the same plan
-            guided, slots, scales = guidance_plan(node, n_step, [scale_of[i] for i in indices], guidance_interval)
-            pick = [i for i, s in enumerate(slots) if s >= 0]
-            g = len(pick)
-            plan = (guided, torch.tensor(pick, dtype=torch.int64, device=device), torch.cat([classlabels, classnulls[:g]]),
-                    [torch.full((n + g,), int(node[kk, 0]), dtype=torch.int32, device=device) for kk in range(n_step)],
-                    torch.tensor(slots, dtype=torch.int32, device=device), torch.tensor(scales, dtype=torch.float32, device=device))
-            run = (samplers[n], noise, index, steps_t, classlabels, plan)
+        # the batch's known rows by global index, gathered on the host, uploaded on the caller's stream ({}: no inpainting, today's calls)
+        blend = {} if known is None else dict(known.batch(indices), known_final=known_final)
+        guidance = (_batch_plan(node, n_step, [scale_of[i] for i in indices], guidance_interval, classlabels, classnulls),) if planned else (classnulls, float(cfg_scale))
+        args = (samplers[n], noise, index, steps_t, classlabels) + guidance + (blend,)
         if auto:
-            model.reset_stream_status()
-        latents_b = trajectory(model, *run)
-        if auto:
-            st = model.stream_status()                                # the job's one wait per batch
-            hit = np.flatnonzero(np.asarray(st["clamped"]))
-            if len(hit):
-                if report["first_clamp"] is None:
-                    k = int(hit[0])
-                    report["first_clamp"] = dict(batch=bi, site=k, site_name=model.site_names[k], max_abs=float(st["max_abs"][k]), clamped=int(st["clamped"][k]))
-                report["rerun_batches"].append(bi)
-                if wide is None:
-                    wide = fallback()
-                latents_b = trajectory(wide, *run)                        # same noise, same labels, same indices: the fp32-stream job's batch
+            latents_b, wide = _guarded_batch(trajectory, model, wide, fallback, args, report, bi)
+        else:
+            latents_b = trajectory(model, *args)
         out_z.append(latents_b)
     latents = torch.cat(out_z) if out_z else torch.empty((0, 4, S, S), dtype=torch.float32, device=device)
     all_idx = [i for idx, _ in batches for i in idx]
     all_lab = [l for _, lb in batches for l in lb]
-    if decoder is not None:
-        db = max(1, int(decode_batch))
-        for s0 in range(0, len(all_idx), db):
-            u8 = to_pixels_u8(decoder(latents[s0:s0 + db] / 0.18215))
-            if paste and inpaint is not None and "images" in inpaint and inpaint["images"].dtype == torch.uint8:   # the caller's known pixels back
-                u8 = torch.where(gather_rows(inpaint["mask_px"], all_idx[s0:s0 + db]).to(device)[..., None],
-                                 gather_rows(inpaint["images"], all_idx[s0:s0 + db]).to(device), u8)
-            if image_sink is not None:
-                image_sink(u8, all_idx[s0:s0 + db], all_lab[s0:s0 + db])
-            else:
-                out_img.append(u8.cpu())
     images = None
-    if decoder is not None and image_sink is None:
-        images = torch.cat(out_img) if out_img else torch.empty((0, 8 * S, 8 * S, 3), dtype=torch.uint8)
+    if decoder is not None:
+        pasted = paste and inpaint is not None and "images" in inpaint and inpaint["images"].dtype == torch.uint8   # the caller's known pixels back
+        images = _decode_images(decoder, latents, all_idx, all_lab, decode_batch, image_sink, (inpaint["mask_px"], inpaint["images"]) if pasted else None)
     return latents, torch.tensor(all_lab, dtype=torch.int64), torch.tensor(all_idx, dtype=torch.int64), images
 
 

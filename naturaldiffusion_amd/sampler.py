@@ -57,6 +57,44 @@ def _check_elems_per_image(epi: Optional[int], E: int, lanes: int = 4) -> None:
         raise ValueError(f"elems_per_image must be a positive multiple of {lanes} dividing the element count")
 
 
+def _level_memo(schedule: Callable) -> Callable:
+    """``level(j, mode)`` = entry j of ``schedule(mode)``, each mode's list made on first use and kept (the samplers' known / colour levels)"""
+    made = {}
+
+    def level(j: int, mode: str):
+        if mode not in made:
+            made[mode] = schedule(mode)
+        return made[mode][j]
+    return level
+
+
+def _check_guidance_tensors(cfg, uncond_slot, n: int, device) -> None:
+    """per-image guidance as the guided and inpainting entries take it: fp32 scales and int32 slots, one of each per image, on the sampler's device"""
+    if cfg.dtype != torch.float32 or cfg.device != device or not cfg.is_contiguous() or cfg.numel() != n:
+        raise ValueError("a tensor cfg must be a contiguous fp32 tensor on the sampler's device, one scale per image")
+    if (not isinstance(uncond_slot, torch.Tensor) or uncond_slot.dtype != torch.int32 or uncond_slot.device != device
+            or not uncond_slot.is_contiguous() or uncond_slot.numel() != n):
+        raise ValueError("a tensor cfg needs uncond_slot: a contiguous int32 tensor on the sampler's device, one slot per image")
+
+
+def _flat_noise_f32(noise: torch.Tensor, n_elem: int) -> torch.Tensor:
+    noise = noise.reshape(-1)
+    if noise.dtype != torch.float32 or noise.numel() != n_elem or not noise.is_contiguous():
+        raise ValueError("noise must be a contiguous fp32 tensor of n_elem elements")
+    return noise
+
+
+def _known_blend_f32(noise: torch.Tensor, known, mask, n_elem: int, epi, seed, level: Callable, known_final: str, index, fast_f32: bool = False):
+    """``CifarNI.first_input`` / ``ValidateNI.first_input``: flat ``noise`` with the known elements at level 0 of ``level`` -> a new flat tensor"""
+    ks, ms = check_known(known, mask, n_elem, epi, seed=seed, fast_f32=fast_f32, device=noise.device)
+    ka, kstd, kcol = level(0, known_final)
+    index, first, stride = image_index_args(index, n_elem // epi, noise.device)
+    out = torch.empty_like(noise)
+    check(lib.natinf_known_blend_f32(ptr(noise), ptr(out), ptr(known), ptr(mask), ks, ms, ka, kstd, kcol, seed,
+                                     ptr(index), first, stride, epi, n_elem, stream_ptr()), "natinf_known_blend_f32")
+    return out
+
+
 KNOWN_COLUMN0 = 2 ** 31      # Philox column of the known-pixel draw at level 0; level j draws column KNOWN_COLUMN0 + j (a matrix's noise columns are <= N + 1)
 
 
@@ -74,23 +112,20 @@ def known_schedule(node: np.ndarray, known_final: str = "mean"):
     return out
 
 
-def check_known(known, mask, n_elem: int, elems_per_image: Optional[int], *, seed, fast_f32: bool = False, device=None):
-    """The argument checks of an inpainting call, made before anything is launched -> (known image stride, mask image stride).
-    ``known``: flat contiguous fp32, ``mask``: flat contiguous uint8 (non-zero = known), each of ``n_elem`` elements (one row per image:
-    stride ``elems_per_image``) or ``elems_per_image`` elements (one row shared by every image: stride 0).  ``device`` None skips the
-    device check (host-side callers)."""
+def _check_known(known, mask, n_elem: int, elems_per_image: Optional[int], dtype, lanes: int, own, epi_hint: str, device):
+    """What ``check_known`` and ``check_known_f16`` share -> (known image stride, mask image stride).  ``own``: the caller's own refusals as
+    (condition, message) pairs, raised where they always were: behind the both-or-neither check, in front of everything else."""
     if known is None or mask is None:
         raise ValueError("inpainting needs both known= and mask=")
-    if fast_f32:
-        raise ValueError("inpainting: the fast_f32 mode has no blend")
-    if seed is None:
-        raise ValueError("inpainting: the known pixels are re-noised at every level, which needs a seed (deterministic matrices too)")
+    for bad, message in own:
+        if bad:
+            raise ValueError(message)
     if elems_per_image is None:
-        raise ValueError("inpainting: elems_per_image is needed to key the known-pixel noise")
+        raise ValueError(f"inpainting: {epi_hint}")
     epi = int(elems_per_image)
-    _check_elems_per_image(epi, n_elem)
+    _check_elems_per_image(epi, n_elem, lanes)
     strides = []
-    for name, t, dt in (("known", known, torch.float32), ("mask", mask, torch.uint8)):
+    for name, t, dt in (("known", known, dtype), ("mask", mask, torch.uint8)):
         if not isinstance(t, torch.Tensor) or t.dtype != dt or t.dim() != 1 or not t.is_contiguous():
             raise ValueError(f"{name} must be a flat contiguous {str(dt).split('.')[-1]} tensor")
         if t.numel() not in (n_elem, epi):
@@ -99,6 +134,16 @@ def check_known(known, mask, n_elem: int, elems_per_image: Optional[int], *, see
             raise ValueError(f"{name} must be on the sampler's device")
         strides.append(epi if t.numel() == n_elem and n_elem != epi else 0)
     return strides[0], strides[1]
+
+
+def check_known(known, mask, n_elem: int, elems_per_image: Optional[int], *, seed, fast_f32: bool = False, device=None):
+    """The argument checks of an inpainting call, made before anything is launched -> (known image stride, mask image stride).
+    ``known``: flat contiguous fp32, ``mask``: flat contiguous uint8 (non-zero = known), each of ``n_elem`` elements (one row per image:
+    stride ``elems_per_image``) or ``elems_per_image`` elements (one row shared by every image: stride 0).  ``device`` None skips the
+    device check (host-side callers)."""
+    own = ((fast_f32, "inpainting: the fast_f32 mode has no blend"),
+           (seed is None, "inpainting: the known pixels are re-noised at every level, which needs a seed (deterministic matrices too)"))
+    return _check_known(known, mask, n_elem, elems_per_image, torch.float32, 4, own, "elems_per_image is needed to key the known-pixel noise", device)
 
 
 def sd_known_schedule(sig16, oms16, renoise: str = "fresh"):
@@ -118,28 +163,13 @@ def check_known_f16(known, mask, n_elem: int, elems_per_image: Optional[int], *,
     stride, mask image stride).  ``known``: flat contiguous fp16, ``mask``: flat contiguous uint8 (non-zero = known) whose storage is 8-byte
     aligned, each of ``n_elem`` elements (one row per image) or ``elems_per_image`` elements (one row shared by every image: stride 0).  A seed is
     needed for ``renoise="fresh"`` only.  ``device`` None skips the device check (host-side callers)."""
-    if known is None or mask is None:
-        raise ValueError("inpainting needs both known= and mask=")
-    if renoise not in ("fresh", "same"):
-        raise ValueError('renoise must be "fresh" or "same"')
-    if renoise == "fresh" and seed is None:
-        raise ValueError('inpainting: renoise="fresh" draws new noise for the known latents at every level, which needs a seed')
-    if elems_per_image is None:
-        raise ValueError("inpainting: elems_per_image (sample_elems) is needed to key the known-latent noise")
-    epi = int(elems_per_image)
-    _check_elems_per_image(epi, n_elem, 8)
-    strides = []
-    for name, t, dt in (("known", known, torch.float16), ("mask", mask, torch.uint8)):
-        if not isinstance(t, torch.Tensor) or t.dtype != dt or t.dim() != 1 or not t.is_contiguous():
-            raise ValueError(f"{name} must be a flat contiguous {str(dt).split('.')[-1]} tensor")
-        if t.numel() not in (n_elem, epi):
-            raise ValueError(f"{name} must have n_elem ({n_elem}) or elems_per_image ({epi}) elements, not {t.numel()}")
-        if device is not None and t.device != device:
-            raise ValueError(f"{name} must be on the sampler's device")
-        strides.append(epi if t.numel() == n_elem and n_elem != epi else 0)
+    own = ((renoise not in ("fresh", "same"), 'renoise must be "fresh" or "same"'),
+           (renoise == "fresh" and seed is None, 'inpainting: renoise="fresh" draws new noise for the known latents at every level, which needs a seed'))
+    strides = _check_known(known, mask, n_elem, elems_per_image, torch.float16, 8, own,
+                           "elems_per_image (sample_elems) is needed to key the known-latent noise", device)
     if mask.data_ptr() % 8:
         raise ValueError("mask must be 8-byte aligned: the step reads one 64-bit word per 8 elements")
-    return strides[0], strides[1]
+    return strides
 
 
 # Colorization (DESIGN.md section 3e).  COLOR_M: the orthonormal basis of deps/score_sde_pytorch/controllable_generation.py:107-109, fp32, whose column 0 is the
@@ -269,8 +299,8 @@ class CifarNI:
         self.std = [vp_std_f32(self.node[k, 0]) for k in range(self.n_step)] if stds is None else [float(v) for v in stds]
         self.labels = [float(np.float32(self.node[k, 0]) * np.float32(999)) for k in range(self.n_step)]
         self._rows_b0 = None
-        self._known_levels = {}
-        self._color_levels = {}
+        self._known_level = _level_memo(lambda known_final: known_schedule(self.node, known_final))
+        self._color_level = _level_memo(lambda known_final: color_schedule(self.node, known_final))
 
     def _noise_rows(self) -> SparseRows:
         """The noise rows an inpainting step passes: B's own for a stochastic matrix, else column 0 alone as a one-term row
@@ -281,25 +311,13 @@ class CifarNI:
             self._rows_b0 = SparseRows(self.B[:, :1], lambda k: 1, torch.float32, self.device, diag=False, dense=True)
         return self._rows_b0
 
-    def _known_level(self, j: int, known_final: str):
-        if known_final not in self._known_levels:
-            self._known_levels[known_final] = known_schedule(self.node, known_final)
-        return self._known_levels[known_final][j]
-
-    def _color_level(self, j: int, known_final: str):
-        if known_final not in self._color_levels:
-            self._color_levels[known_final] = color_schedule(self.node, known_final)
-        return self._color_levels[known_final][j]
-
     def first_input(self, noise: torch.Tensor, known: Optional[torch.Tensor] = None, mask: Optional[torch.Tensor] = None, index=None,
                     elems_per_image: Optional[int] = None, known_final: str = "mean", *, gray_u: Optional[torch.Tensor] = None) -> torch.Tensor:
         """The first model input of an inpainting trajectory: ``noise`` with the known pixels at level 0 (natinf_known_blend_f32,
         column 2^31) -> a new flat tensor; ``noise`` itself (eps_0 of every step) is left as it is.  With ``gray_u`` (colorization) it is
         ``noise`` with its gray channel at level 0 (natinf_color_blend_f32, column ``COLOR_COLUMN0``)."""
         epi = self.epi if elems_per_image is None else int(elems_per_image)
-        noise = noise.reshape(-1)
-        if noise.dtype != torch.float32 or noise.numel() != self.E or not noise.is_contiguous():
-            raise ValueError("noise must be a contiguous fp32 tensor of n_elem elements")
+        noise = _flat_noise_f32(noise, self.E)
         if gray_u is not None:
             if known is not None or mask is not None:
                 raise ValueError("gray_u (colorization) does not go with known / mask (inpainting)")
@@ -310,13 +328,7 @@ class CifarNI:
             check(lib.natinf_color_blend_f32(ptr(noise), ptr(out), ptr(gray_u), gs, _f9(COLOR_M), _f9(COLOR_W), ga, gstd, gcol, self.seed,
                                              ptr(index), first, stride, epi, self.E, stream_ptr()), "natinf_color_blend_f32")
             return out
-        ks, ms = check_known(known, mask, self.E, epi, seed=self.seed, fast_f32=self.fast, device=noise.device)
-        ka, kstd, kcol = self._known_level(0, known_final)
-        index, first, stride = image_index_args(index, self.E // epi, noise.device)
-        out = torch.empty_like(noise)
-        check(lib.natinf_known_blend_f32(ptr(noise), ptr(out), ptr(known), ptr(mask), ks, ms, ka, kstd, kcol, self.seed,
-                                         ptr(index), first, stride, epi, self.E, stream_ptr()), "natinf_known_blend_f32")
-        return out
+        return _known_blend_f32(noise, known, mask, self.E, epi, self.seed, self._known_level, known_final, index, fast_f32=self.fast)
 
     def step(self, k: int, x_k: torch.Tensor, model_out: torch.Tensor, noise: torch.Tensor,
              x_next: Optional[torch.Tensor] = None, index=None, elems_per_image: Optional[int] = None, *,
@@ -352,27 +364,24 @@ class CifarNI:
         idx, val, n = self.rows.ptrs(k)
         r = self.rows.rows[k]
         a, s = float(self.node[k, 1]), float(self.node[k, 2])
-        if inpaint:
+        if inpaint or gray_u is not None or self.stochastic:              # the entries that draw noise: B's rows and the images' global indices
+            if epi is None:
+                raise ValueError("stochastic NI matrix: elems_per_image is needed to key the injected noise")
             ib, vb, nb = self._noise_rows().ptrs(k)
             index, first, stride = image_index_args(index, self.E // epi, x_k.device)
+        if inpaint:
             check(lib.natinf_step_f64hist_inpaint(ptr(x_k), ptr(model_out), ptr(noise), ptr(self.hist), ptr(x_next), idx, val, n,
                                                   r.diag, ib, vb, nb, k, a, s, self.std[k], self.seed, ptr(index), first, stride,
                                                   epi, self.E, ptr(known), ptr(mask), ks, ms, ka, kstd, kcol, stream_ptr()),
                   "natinf_step_f64hist_inpaint")
             return x_next
         if gray_u is not None:
-            ib, vb, nb = self._noise_rows().ptrs(k)
-            index, first, stride = image_index_args(index, self.E // epi, x_k.device)
             check(lib.natinf_step_f64hist_colorize(ptr(x_k), ptr(model_out), ptr(noise), ptr(self.hist), ptr(x_next), idx, val, n,
                                                    r.diag, ib, vb, nb, k, a, s, self.std[k], self.seed, ptr(index), first, stride,
                                                    epi, self.E, ptr(gray_u), gs, _f9(COLOR_M), _f9(COLOR_W), ga, gstd, gcol, stream_ptr()),
                   "natinf_step_f64hist_colorize")
             return x_next
         if self.stochastic:
-            if epi is None:
-                raise ValueError("stochastic NI matrix: elems_per_image is needed to key the injected noise")
-            ib, vb, nb = self.rows_b.ptrs(k)
-            index, first, stride = image_index_args(index, self.E // epi, x_k.device)
             check(lib.natinf_step_f64hist_noise(ptr(x_k), ptr(model_out), ptr(noise), ptr(self.hist), ptr(x_next), idx, val, n,
                                                 r.diag, ib, vb, nb, k, a, s, self.std[k], self.seed, ptr(index), first, stride,
                                                 epi, self.E, stream_ptr()), "natinf_step_f64hist_noise")
@@ -393,38 +402,18 @@ class CifarNI:
         shape, B = noise.shape, noise.shape[0]
         noise = noise.contiguous()
         epi = self.epi if self.epi is not None else noise.numel() // B
+        inpaint = known is not None or mask is not None
+        if gray_u is not None and inpaint:
+            raise ValueError("gray_u (colorization) does not go with known / mask (inpainting)")
+        # every step goes through self.step (callers wrap it per instance, e.g. bench.py's timed replica): a column-0 matrix gets exactly the four
+        # positional arguments it always got, a stochastic one index= and elems_per_image=, a conditioned trajectory its blend arguments as well
+        kw = dict(index=index, elems_per_image=epi) if self.stochastic or inpaint or gray_u is not None else {}
         if gray_u is not None:
-            if known is not None or mask is not None:
-                raise ValueError("gray_u (colorization) does not go with known / mask (inpainting)")
-            return self._run_colorize(model_fn, noise, return_all, index, epi, gray_u, known_final)
-        if known is not None or mask is not None:
-            return self._run_inpaint(model_fn, noise, return_all, index, epi, known, mask, known_final)
-        x, xs = noise, [noise]
-        for k in range(self.n_step):
-            labels = torch.full((B,), self.labels[k], dtype=torch.float32, device=self.device)
-            out = model_fn(x.view(shape), labels)
-            args = (k, x.reshape(-1), out.contiguous().reshape(-1), noise.reshape(-1))
-            # every step goes through self.step (callers wrap it per instance, e.g. bench.py's timed replica); a column-0
-            # matrix gets exactly the four positional arguments it always got
-            x = self.step(*args, index=index, elems_per_image=epi) if self.stochastic else self.step(*args)
-            if return_all:
-                x = x.clone()
-                xs.append(x.view(shape))
-        return xs if return_all else x.view(shape)
-
-    def _run_inpaint(self, model_fn, noise, return_all, index, epi, known, mask, known_final):
-        flat = lambda t: t if t is None else (t.view(torch.uint8) if t.dtype == torch.bool else t).reshape(-1)
-        return self._run_blended(model_fn, noise, return_all, dict(index=index, elems_per_image=epi, known=flat(known), mask=flat(mask),
-                                                                   known_final=known_final))
-
-    def _run_colorize(self, model_fn, noise, return_all, index, epi, gray_u, known_final):
-        return self._run_blended(model_fn, noise, return_all, dict(index=index, elems_per_image=epi, gray_u=gray_u.reshape(-1),
-                                                                   known_final=known_final))
-
-    def _run_blended(self, model_fn, noise, return_all, kw):
-        """the loop of a conditioned trajectory: the first input and every step blend with the same arguments ``kw``"""
-        shape, B = noise.shape, noise.shape[0]
-        x = self.first_input(noise, **kw)
+            kw.update(gray_u=gray_u.reshape(-1), known_final=known_final)
+        elif inpaint:
+            flat = lambda t: t if t is None else (t.view(torch.uint8) if t.dtype == torch.bool else t).reshape(-1)
+            kw.update(known=flat(known), mask=flat(mask), known_final=known_final)
+        x = self.first_input(noise, **kw) if inpaint or gray_u is not None else noise
         xs = [x.view(shape)]
         for k in range(self.n_step):
             labels = torch.full((B,), self.labels[k], dtype=torch.float32, device=self.device)
@@ -474,13 +463,8 @@ class ValidateNI:
         # the seeded form draws the noise rows in the kernel: no (N+1) x E slab
         self.hist_eps = None if self.seed is not None else torch.empty((self.n_step + 1, self.E), dtype=torch.float32, device=self.device)
         self._z = [torch.empty(self.E, dtype=torch.float32, device=self.device) for _ in range(2)]
-        self._known_levels = {}
+        self._known_level = _level_memo(lambda known_final: known_schedule(self.node, known_final))
         self._launch_wide = {}
-
-    def _known_level(self, j: int, known_final: str):
-        if known_final not in self._known_levels:
-            self._known_levels[known_final] = known_schedule(self.node, known_final)
-        return self._known_levels[known_final][j]
 
     def _launch_wide_guidance(self, n: int, cfg: float, have_uncond: bool):
         """A launch-wide scale in the per-image form the inpainting entry takes -> (scales fp32 [n], slots int32 [n]), built once per sampler:
@@ -497,16 +481,7 @@ class ValidateNI:
         """The first model input of an inpainting trajectory: ``noise`` with the known latents at level 0 (natinf_known_blend_f32, column
         ``KNOWN_COLUMN0``) -> a new flat tensor; ``noise`` itself (eps_0 of every step) is left as it is."""
         epi = self.epi if elems_per_image is None else int(elems_per_image)
-        noise = noise.reshape(-1)
-        if noise.dtype != torch.float32 or noise.numel() != self.E or not noise.is_contiguous():
-            raise ValueError("noise must be a contiguous fp32 tensor of n_elem elements")
-        ks, ms = check_known(known, mask, self.E, epi, seed=self.seed, device=noise.device)
-        ka, kstd, kcol = self._known_level(0, known_final)
-        index, first, stride = image_index_args(index, self.E // epi, noise.device)
-        out = torch.empty_like(noise)
-        check(lib.natinf_known_blend_f32(ptr(noise), ptr(out), ptr(known), ptr(mask), ks, ms, ka, kstd, kcol, self.seed,
-                                         ptr(index), first, stride, epi, self.E, stream_ptr()), "natinf_known_blend_f32")
-        return out
+        return _known_blend_f32(_flat_noise_f32(noise, self.E), known, mask, self.E, epi, self.seed, self._known_level, known_final, index)
 
     def step(self, k: int, z: torch.Tensor, cond: torch.Tensor, uncond: Optional[torch.Tensor], cfg,
              sample_elems: Optional[int] = None, eps_sample_stride: Optional[int] = None, *,
@@ -562,12 +537,7 @@ class ValidateNI:
             cfg, uncond_slot = self._launch_wide_guidance(self.E // se, float(cfg), uncond is not None)
             n_uncond = self.E // se if uncond is not None else 0
         if guided or inpaint:
-            n = self.E // se
-            if cfg.dtype != torch.float32 or cfg.device != z.device or not cfg.is_contiguous() or cfg.numel() != n:
-                raise ValueError("a tensor cfg must be a contiguous fp32 tensor on the sampler's device, one scale per image")
-            if (not isinstance(uncond_slot, torch.Tensor) or uncond_slot.dtype != torch.int32 or uncond_slot.device != z.device
-                    or not uncond_slot.is_contiguous() or uncond_slot.numel() != n):
-                raise ValueError("a tensor cfg needs uncond_slot: a contiguous int32 tensor on the sampler's device, one slot per image")
+            _check_guidance_tensors(cfg, uncond_slot, self.E // se, z.device)
             if n_uncond is None:
                 n_uncond = 0 if uncond is None else uncond.numel() // st
             if inpaint:
@@ -644,12 +614,7 @@ class SD3NI:
         self.hist = torch.empty((n, self.E), dtype=torch.float16, device=self.device)
         self._x = [torch.empty(self.E, dtype=torch.float16, device=self.device) for _ in range(2)]
         self.mean = torch.empty(self.E, dtype=torch.float16, device=self.device)
-        self._known_levels = {}
-
-    def _known_level(self, j: int, renoise: str):
-        if renoise not in self._known_levels:
-            self._known_levels[renoise] = sd_known_schedule(self.sig, self.oms, renoise)
-        return self._known_levels[renoise][j]
+        self._known_level = _level_memo(lambda renoise: sd_known_schedule(self.sig, self.oms, renoise))
 
     def _sample_elems(self, sample_elems: Optional[int]) -> int:
         se = self.epi if sample_elems is None else int(sample_elems)
@@ -720,11 +685,7 @@ class SD3NI:
                 ks, ms = check_known_f16(known, mask, self.E, se, seed=seed, renoise=renoise, device=x.device)
                 _, _, col = self._known_level(k + 1, renoise)
                 index, first, stride = image_index_args(index, m, x.device)
-            if cfg.dtype != torch.float32 or cfg.device != x.device or not cfg.is_contiguous() or cfg.numel() != m:
-                raise ValueError("a tensor cfg must be a contiguous fp32 tensor on the sampler's device, one scale per image")
-            if (not isinstance(uncond_slot, torch.Tensor) or uncond_slot.dtype != torch.int32 or uncond_slot.device != x.device
-                    or not uncond_slot.is_contiguous() or uncond_slot.numel() != m):
-                raise ValueError("a tensor cfg needs uncond_slot: a contiguous int32 tensor on the sampler's device, one slot per image")
+            _check_guidance_tensors(cfg, uncond_slot, m, x.device)
             if n_uncond is None:
                 n_uncond = 0 if v_null is None else v_null.numel() // se
             if inpaint:
