@@ -141,6 +141,56 @@ int natinf_step_f64hist_inpaint(const float* x_k, const float* model_out, const 
                                 const float* known, const uint8_t* mask, int64_t known_image_stride, int64_t mask_image_stride,
                                 float known_alpha_f32, float known_std_f32, uint32_t known_column, natinf_stream_t stream);
 
+/* x0 correction on the CIFAR10 form: the predicted x0 of every image clipped (DDPM's clip_denoised) or dynamically thresholded (Imagen;
+ * deps/dpm_solver_pytorch.py:416-425, dynamic_thresholding_fn, the reference's correcting_x0_fn="dynamic_thresholding") before the solver
+ * uses it.  The correction on its own, in place on x0 [n_images][elems_per_image] fp64; for one image, x its n = elems_per_image values:
+ *
+ *   NATINF_X0_CLIP    : y[e] = x[e] < -c ? -c : (x[e] > c ? c : x[e])       c = max_val     (a NaN stays NaN; no division)
+ *   NATINF_X0_DYNAMIC : a    = sort(|x|) ascending (NaN last)
+ *                       rank = ratio * (double)(n - 1)                       one fp64 product, on the host
+ *                       lo   = floor(rank), hi = ceil(rank), w = rank - lo
+ *                       d    = a[hi] - a[lo]
+ *                       q    = w < 0.5 ? fma(w, d, a[lo]) : fma(w - 1.0, d, a[hi])       ONE fused multiply-add, fp64
+ *                       s    = any NaN in x ? NaN : max(q, max_val)          (a NaN q, from a[lo] = a[hi] = inf, gives s = NaN)
+ *                       y[e] = s is NaN ? NaN : min(max(x[e], -s), s) / s    IEEE fp64 division
+ *
+ * This is torch.quantile(|x0|, ratio, dim=1), torch.maximum and torch.clamp(...) / s of the reference lines, on fp64, as ATen's CPU
+ * kernels evaluate them (the interpolation inside torch.quantile is a fused multiply-add: the library's only one outside a division).  The
+ * two order statistics are exact: selected on the 64-bit patterns of |x| with integer counts, so the result does not depend on the order in
+ * which threads arrive.  A NaN the correction produces is the quiet NaN 0x7FF8000000000000; a NaN that CLIP passes through keeps its bits.
+ * s_out: NULL or [n_images] fp64, the threshold used (CLIP: max_val).  One workgroup per image; the image lives in LDS, so
+ * elems_per_image <= 8192.  NATINF_EINVAL, nothing launched: x0 NULL, n_images <= 0, elems_per_image not a positive multiple of 4 or
+ * > 8192, mode neither value, ratio outside [0, 1] or NaN, max_val not finite or <= 0 (ratio is checked in CLIP mode too). */
+#define NATINF_X0_CLIP    1
+#define NATINF_X0_DYNAMIC 2
+int natinf_x0_threshold_f64(double* x0, double* s_out, int64_t n_images, int64_t elems_per_image,
+                            int mode, double ratio, double max_val, natinf_stream_t stream);
+
+/* natinf_step_f64hist_noise with that correction between the denoiser and the history, in one launch and without a workspace: one
+ * workgroup per image computes the image's raw x0 into LDS (it is never written to memory), finds the threshold, and then, per element,
+ *
+ *   hist[k] <- y                 byte for byte natinf_x0_threshold_f64 applied to the hist[k] natinf_step_f64hist_noise writes
+ *   acc     = sum over terms t of hist[idx[t]] * val[t], then + y * c_diag      (the diagonal term uses the corrected value)
+ *   x_next  = (float)acc + (float)nacc, then the blend of natinf_known_blend_f32 if known / mask are given
+ *
+ * everything else operation for operation natinf_step_f64hist_noise's.  `known` and `mask` may both be NULL (no blend; the strides and
+ * known_* are then not inspected); with both given they are natinf_step_f64hist_inpaint's.  s_out as above.  A deterministic matrix goes
+ * through as a one-term noise row (column 0, val_b[0] = fp32(B[k,0])).  "Matrix X plus this correction" is the classical solver X with
+ * correcting_x0_fn: every sampler the matrices express is linear in the x0_j.
+ * NATINF_EINVAL, nothing launched: every refusal of natinf_step_f64hist_inpaint (the blend's only when known / mask are given), exactly
+ * one of known / mask NULL, and every refusal of natinf_x0_threshold_f64 for mode / ratio / max_val / elems_per_image.  All of them are
+ * pure argument checks: a refusal touches no device (like natinf_step_f64hist_noise, the entry does not read idx_b back). */
+int natinf_step_f64hist_x0fix(const float* x_k, const float* model_out, const float* noise,
+                              double* hist, float* x_next,
+                              const int32_t* idx, const double* val, int n_terms, double c_diag,
+                              const int32_t* idx_b, const float* val_b, int n_b,
+                              int k, double alpha, double sigma, float std_f32,
+                              uint64_t seed, const int64_t* image_index, int64_t first_index, int64_t index_stride,
+                              int64_t elems_per_image, int64_t E,
+                              const float* known, const uint8_t* mask, int64_t known_image_stride, int64_t mask_image_stride,
+                              float known_alpha_f32, float known_std_f32, uint32_t known_column,
+                              int mode, double ratio, double max_val, double* s_out, natinf_stream_t stream);
+
 /* Colorization on the CIFAR10 form: the gray channel of a rotated colour space overwritten with the gray data diffused to the
  * current noise level (deps/score_sde_pytorch/controllable_generation.py:85-181, get_pc_colorizer; :142 with mask = (1, 0, 0)).
  * An image is three planes of P = elems_per_image / 3 elements (NCHW).  The blend on its own, pixel p of image i, with

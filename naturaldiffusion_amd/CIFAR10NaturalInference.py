@@ -19,7 +19,7 @@ from . import _lib
 from ._lib import lib, check, ptr, stream_ptr
 from .coeff import load_coeff_npz, SparseRows
 from .jobs import KnownRows, check_row_count, gather_known, host_mask, mask_table  # noqa: F401  (gather_known: importable from here as before)
-from .sampler import CifarNI, decouple0_host, vp_std_f32
+from .sampler import CifarNI, check_x0_fix, decouple0_host, vp_std_f32
 
 root_path = Path(__file__).resolve().parent.parent
 
@@ -154,9 +154,14 @@ class BatchLanes:
     one set of history slabs each -- and the under-occupied launches of one batch run under the other's convolutions.
     A batch is enqueued end to end (noise, 15-18 forwards + ni_step launches, ``to_pixel``) without the host waiting for the GPU; the uint8
     images stay on the device until ``finish``; at most ``depth`` batches per lane are enqueued ahead of the GPU.  ``seed`` keys the noise a
-    stochastic matrix injects after each step (``CifarNI``), per image by the global indices ``submit`` gets."""
+    stochastic matrix injects after each step (``CifarNI``), per image by the global indices ``submit`` gets.  ``x0_fix`` / ``x0_ratio`` /
+    ``x0_max``: the x0 correction every lane's sampler applies (``CifarNI``: "clip" or "dynamic" thresholding of each step's predicted x0);
+    a bad value is a ValueError before any GPU call."""
 
-    def __init__(self, models, C, B, node, device, depth: int = 2, seed: Optional[int] = None):
+    def __init__(self, models, C, B, node, device, depth: int = 2, seed: Optional[int] = None,
+                 x0_fix: Optional[str] = None, x0_ratio: float = 0.995, x0_max: float = 1.0):
+        check_x0_fix(x0_fix, x0_ratio, x0_max, seed=seed, elems_per_image=3 * 32 * 32)
+        self.x0 = dict(x0_fix=x0_fix, x0_ratio=x0_ratio, x0_max=x0_max) if x0_fix is not None else {}
         _lib.require_gpu()
         self.device = torch.device(device)
         self.coeff = (C, B, node)
@@ -173,7 +178,7 @@ class BatchLanes:
 
     def _sampler(self, k: int, n: int) -> CifarNI:
         if n not in self.samplers[k]:
-            self.samplers[k][n] = CifarNI(*self.coeff, n * 3 * 32 * 32, device=self.device, seed=self.seed, elems_per_image=3 * 32 * 32)
+            self.samplers[k][n] = CifarNI(*self.coeff, n * 3 * 32 * 32, device=self.device, seed=self.seed, elems_per_image=3 * 32 * 32, **self.x0)
         return self.samplers[k][n]
 
     def submit(self, n: int, noise=None, noise_fn=None, index=None, known=None, mask=None, known_final: str = "mean", gray_u=None) -> torch.Tensor:
@@ -182,6 +187,8 @@ class BatchLanes:
         caller's stream, the int index of the first image, or ``(first, stride)`` (``CifarNI.step``).  ``known`` / ``mask`` (inpainting): device
         tensors made on the caller's stream, forwarded to ``CifarNI.run``; ``gray_u`` (colorization) likewise.  Returns the uint8 [n, 32, 32, 3] DEVICE tensor the lane will fill."""
         idx_t = isinstance(index, torch.Tensor)
+        if gray_u is not None and self.x0:
+            raise ValueError("x0_fix does not go with gray_u (colorization)")
         inpaint = [t for t in (known, mask, gray_u) if t is not None]       # the lane is ordered behind their upload
         k = self.count % len(self.models)
         self.count += 1
@@ -246,7 +253,8 @@ def _lane_models(model_fn, streams: int, n_batches: int):
 @torch.no_grad()
 def generate_sharded(model_fn, weight_path, sample_count: int, batch_size: int, rank: int = 0, world: int = 1,
                      seed: int = 888, device="cuda:0", streams: int = 3, to_cpu: bool = True, coeff=None,
-                     known=None, mask=None, known_final: str = "mean", gray=None):
+                     known=None, mask=None, known_final: str = "mean", gray=None,
+                     x0_fix: Optional[str] = None, x0_ratio: float = 0.995, x0_max: float = 1.0):
     """Batch-sharded generation (BASELINE config 3): this rank generates the images whose
     global index is rank, rank+world, ... in batches of ``batch_size`` -- no collective on the data path -- on the two-lane pipeline
     of ``natural_inference_tx`` (``BatchLanes``): Philox noise keyed by the GLOBAL image index drawn on the lane's own stream, uint8 images
@@ -260,8 +268,13 @@ def generate_sharded(model_fn, weight_path, sample_count: int, batch_size: int, 
     ``gray`` (colorization, ``prepare_gray``): the gray picture of image i -- row i, or the only row -- comes back as the gray channel of the result
     (at the last level for ``known_final="mean"``, as given for ``"data"``) and the colours are generated around it: every step overwrites latent
     channel 0 of a rotated colour space with the gray data diffused to the step's level.  Not together with ``known`` / ``mask``.
+    ``x0_fix`` (x0 correction, DESIGN.md section 3i): ``"clip"`` clamps every step's predicted x0 to [-``x0_max``, ``x0_max``] (DDPM's clip_denoised);
+    ``"dynamic"`` clamps it to, and divides it by, s = max(the ``x0_ratio`` quantile of the image's |x0|, ``x0_max``) (Imagen's dynamic thresholding, the
+    reference's ``correcting_x0_fn="dynamic_thresholding"``), inside the step's launch, before the history and the sum see it.  A per-image function: image
+    i stays the same bytes for any split.  It goes with ``known`` / ``mask``, not with ``gray``; ``None`` (default) is the job without the option.
     Returns (uint8 images [n_local, 32, 32, 3], their global indices [n_local] int64 on the CPU)."""
     from .shard import rank_batches
+    check_x0_fix(x0_fix, x0_ratio, x0_max, seed=seed, elems_per_image=3 * 32 * 32, gray=gray is not None)
     inpaint = known is not None or mask is not None
     if gray is not None:
         if inpaint:
@@ -274,7 +287,7 @@ def generate_sharded(model_fn, weight_path, sample_count: int, batch_size: int, 
     dev = torch.device(device)
     if not batches:
         return torch.empty((0, 32, 32, 3), dtype=torch.uint8, device="cpu" if to_cpu else dev), torch.empty(0, dtype=torch.int64)
-    lanes = BatchLanes(_lane_models(model_fn, streams, len(batches)), C, B, node, dev, seed=seed)
+    lanes = BatchLanes(_lane_models(model_fn, streams, len(batches)), C, B, node, dev, seed=seed, x0_fix=x0_fix, x0_ratio=x0_ratio, x0_max=x0_max)
     rows = KnownRows(dev, known=known, mask=mask) if inpaint else KnownRows(dev, gray_u=gray) if gray is not None else None
     for batch in batches:                                                # the batch's rows are uploaded here, on the caller's stream, in front of submit
         kw = dict(rows.batch(batch), known_final=known_final) if rows is not None else {}
@@ -458,7 +471,8 @@ def natural_inference_tx(batch_size: int = 500,
                          ckpt_filename: Optional[str] = None,
                          weight_path: Optional[str] = None,
                          sample_count: int = 50 * 1000, seed: int = 888, device: str = "cuda:0",
-                         compute_fid: bool = True, flat_params: Optional[torch.Tensor] = None, streams: int = 3):
+                         compute_fid: bool = True, flat_params: Optional[torch.Tensor] = None, streams: int = 3,
+                         x0_fix: Optional[str] = None, x0_ratio: float = 0.995, x0_max: float = 1.0):
     """Reference :242-317: generate ``sample_count`` CIFAR10 images with the NI matrix at ``weight_path``
     and score them.  ``flat_params`` lets a caller supply weights directly (engine order) instead of the
     score_sde checkpoint.
@@ -467,7 +481,11 @@ def natural_inference_tx(batch_size: int = 500,
     (one engine handle + history buffer each), so that the under-occupied launches of one batch -- the 4x4 level, the per-sample GroupNorm
     tables, every launch's last round of blocks -- run under the other batch's convolutions: -6 % per batch at 512 images on one MI355X.
     The noise is drawn in the reference's order and every batch runs the same launches: the images are bit-identical to ``streams=1``,
-    the reference's one-after-the-other order (tests/test_gpu_ncsnpp.py; DESIGN.md section 5 for what that took)."""
+    the reference's one-after-the-other order (tests/test_gpu_ncsnpp.py; DESIGN.md section 5 for what that took).
+
+    ``x0_fix`` / ``x0_ratio`` / ``x0_max``: the x0 correction of ``generate_sharded`` ("clip" or "dynamic" thresholding of every step's predicted x0;
+    DESIGN.md section 3i), refused on the host when a value is bad; ``None`` (default) is the reference's sampler."""
+    check_x0_fix(x0_fix, x0_ratio, x0_max, seed=seed, elems_per_image=3 * 32 * 32)
     from .ncsnpp import NCSNppEngine, load_score_sde_checkpoint
     ckpt_filename = ckpt_filename or str(root_path / "deps/score_sde_pytorch/checkpoint_8.pth")
     weight_path = weight_path or str(root_path / "weights/step_5_weight_00.npz")
@@ -480,7 +498,7 @@ def natural_inference_tx(batch_size: int = 500,
     bz = batch_size
     num = int(np.ceil(sample_count / bz))
     engine = NCSNppEngine(flat_params, max_batch=batch_size, device=device)
-    lanes = BatchLanes(_lane_models(engine, streams, num), C, B, node, device, seed=seed)   # the second lane shares the first's packed weights
+    lanes = BatchLanes(_lane_models(engine, streams, num), C, B, node, device, seed=seed, x0_fix=x0_fix, x0_ratio=x0_ratio, x0_max=x0_max)   # the second lane shares the first's packed weights
     torch.cuda.synchronize(torch.device(device))
     torch.manual_seed(seed)
     for ii in range(num):

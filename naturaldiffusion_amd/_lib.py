@@ -41,6 +41,10 @@ SIGNATURES = {
     "natinf_known_blend_f32": (C.c_int, [_p, _p, _p, _p, _i64, _i64, _f32, _f32, C.c_uint32, C.c_uint64, _p, _i64, _i64, _i64, _i64, _p]),
     "natinf_step_f64hist_inpaint": (C.c_int, [_p, _p, _p, _p, _p, _p, _p, _i32, _f64, _p, _p, _i32, _i32, _f64, _f64, _f32,
                                               C.c_uint64, _p, _i64, _i64, _i64, _i64, _p, _p, _i64, _i64, _f32, _f32, C.c_uint32, _p]),
+    "natinf_x0_threshold_f64": (C.c_int, [_p, _p, _i64, _i64, _i32, _f64, _f64, _p]),
+    "natinf_step_f64hist_x0fix": (C.c_int, [_p, _p, _p, _p, _p, _p, _p, _i32, _f64, _p, _p, _i32, _i32, _f64, _f64, _f32,
+                                            C.c_uint64, _p, _i64, _i64, _i64, _i64, _p, _p, _i64, _i64, _f32, _f32, C.c_uint32,
+                                            _i32, _f64, _f64, _p, _p]),
     "natinf_color_blend_f32": (C.c_int, [_p, _p, _p, _i64, _p, _p, _f32, _f32, C.c_uint32, C.c_uint64, _p, _i64, _i64, _i64, _i64, _p]),
     "natinf_step_f64hist_colorize": (C.c_int, [_p, _p, _p, _p, _p, _p, _p, _i32, _f64, _p, _p, _i32, _i32, _f64, _f64, _f32,
                                                C.c_uint64, _p, _i64, _i64, _i64, _i64, _p, _i64, _p, _p, _f32, _f32, C.c_uint32, _p]),
@@ -193,6 +197,7 @@ for _name, (_res, _args) in SIGNATURES.items():
         raise ImportError(f"{LIB_PATH} does not export {_name}; rebuild it") from e
     _fn.restype, _fn.argtypes = _res, _args
 
+X0_CLIP, X0_DYNAMIC = 1, 2                              # include/natinf.h: mode of natinf_x0_threshold_f64 / natinf_step_f64hist_x0fix
 SD3_CFG_ON_VELOCITY = 1
 SD3_BLEND_MEAN = 2                                      # natinf_step_f16chain_inpaint only
 DIT_UNFUSED_ATTENTION = 1                               # include/natinf_dit.h: flags of natinf_dit_create / natinf_dit_create_sized

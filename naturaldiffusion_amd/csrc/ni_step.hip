@@ -18,9 +18,12 @@
 //
 // Reference lines replaced: src/CIFAR10NaturalInference.py:219-238,299-304;
 // src/ValidateNaturalInference.py:193,198-204,355,362-366; src/SD3NaturalInference.py:61-69,
-// 117-129,157-168,209,215-219; deps/score_sde_pytorch/models/utils.py:157.
+// 117-129,157-168,209,215-219; deps/score_sde_pytorch/models/utils.py:157; deps/dpm_solver_pytorch.py:416-425 (the x0 correction: its
+// quantile interpolation is the one __builtin_fma of this file).
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include <cfloat>
+#include <cmath>
 #include <mutex>
 #include "natinf.h"
 #include "natinf_vae.h"
@@ -143,9 +146,8 @@ __device__ __forceinline__ h8 x0_cfg_image(h8 xv, h8 tv, const h8* v_null, const
 }
 
 // ---- pieces of the CIFAR10 form (fp64 history) ----
-// x0 = ((-out/std) * sigma^2 + x) / alpha: the score in fp32, then three fp64 roundings; stored as quad v of the slab row
-__device__ __forceinline__ void x0_from_score_f64(double (&x0)[4], float4 xv, float4 ov, float stdv, double sigma2,
-                                                  double alpha, double* hist_k, int64_t v)
+// x0 = ((-out/std) * sigma^2 + x) / alpha: the score in fp32, then three fp64 roundings
+__device__ __forceinline__ void x0_score_f64(double (&x0)[4], float4 xv, float4 ov, float stdv, double sigma2, double alpha)
 {
     const float xs[4] = {xv.x, xv.y, xv.z, xv.w};
     const float os[4] = {ov.x, ov.y, ov.z, ov.w};
@@ -154,9 +156,21 @@ __device__ __forceinline__ void x0_from_score_f64(double (&x0)[4], float4 xv, fl
         const float s = (-os[i]) / stdv;                          // score, fp32
         x0[i] = ((double)s * sigma2 + (double)xs[i]) / alpha;     // fp64, three roundings
     }
-    d2* hk = reinterpret_cast<d2*>(hist_k) + 2 * v;
-    hk[0] = d2{x0[0], x0[1]};
-    hk[1] = d2{x0[2], x0[3]};
+}
+
+// four fp64 values as quad v of a slab row: two 16-byte stores
+__device__ __forceinline__ void st_quad_f64(double* row, int64_t v, const double (&x)[4]) {
+    d2* r = reinterpret_cast<d2*>(row) + 2 * v;
+    r[0] = d2{x[0], x[1]};
+    r[1] = d2{x[2], x[3]};
+}
+
+// x0_score_f64, stored as quad v of the slab row
+__device__ __forceinline__ void x0_from_score_f64(double (&x0)[4], float4 xv, float4 ov, float stdv, double sigma2,
+                                                  double alpha, double* hist_k, int64_t v)
+{
+    x0_score_f64(x0, xv, ov, stdv, sigma2, alpha);
+    st_quad_f64(hist_k, v, x0);
 }
 
 // acc <- acc + h*c, four lanes: one fp64 product, one fp64 sum
@@ -610,6 +624,181 @@ __global__ __launch_bounds__(kBlock) void k_step_inpaint_f64(
     }
 }
 
+// ---- pieces of the x0 correction (static clip / dynamic thresholding): one workgroup per image, the image's raw x0 in LDS ----
+// The LDS of a workgroup: the image as four planes (element i of quad q at x[i][q]: a wave's 8-byte accesses are consecutive, conflict-free)
+// and the scratch of the order-statistic search.  kCapQuads is the kernel's capacity; the host picks the instantiation that holds the image.
+constexpr int kFixQuadsSmall = 768, kFixQuadsMax = 2048;             // 32x32x3 (24 KB of fp64) and the ABI's cap of 8192 elements (64 KB)
+constexpr int kWaves = kBlock / 64;
+template <int kCapQuads>
+struct FixLds {
+    double x[4][kCapQuads];
+    unsigned int bins[256];                                         // one radix digit's histogram
+    unsigned int wave_total[kWaves];
+    unsigned int sel_bin, sel_rank, sel_count, any_nan;
+    unsigned long long min_above;
+};
+
+// |x| as its 64-bit pattern: non-negative doubles order as unsigned integers, NaN patterns sort above +inf
+__device__ __forceinline__ uint64_t abs_key(double x) { return (uint64_t)__double_as_longlong(x) & 0x7FFFFFFFFFFFFFFFull; }
+constexpr uint64_t kInfKey = 0x7FF0000000000000ull;
+
+// The dynamic threshold of the image in L.x (qpi quads), for every thread of the workgroup: a[lo] and, with `next`, a[lo + 1] of the ascending
+// |x| by an 8-bit radix select on the keys (most significant digit first; integer LDS counts, so arrival order cannot matter), then
+//   d = a[hi] - a[lo] ; q = w < 0.5 ? fma(w, d, a[lo]) : fma(w - 1, d, a[hi]) ; s = any NaN in x or q NaN ? NaN : max(q, max_val)
+// The fma is the file's one fused operation, asked for by name (torch.quantile's interpolation is one).  Every branch around a barrier is
+// workgroup-uniform: its condition is read from LDS behind a barrier.
+template <int kCapQuads>
+__device__ __forceinline__ double dynamic_threshold(FixLds<kCapQuads>& L, int qpi, unsigned lo, bool next, double w, double max_val)
+{
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    if (tid == 0) { L.any_nan = 0u; L.min_above = ~0ull; }
+    uint64_t prefix = 0;
+    unsigned r = lo, count = 0;
+    for (int shift = 56; shift >= 0; shift -= 8) {
+        L.bins[tid] = 0u;                                           // kBlock == 256 digits
+        __syncthreads();
+        const uint64_t himask = shift == 56 ? 0ull : ~0ull << (shift + 8);
+        bool nan = false;
+        for (int q = tid; q < qpi; q += kBlock) {
+#pragma unroll
+            for (int i = 0; i < 4; ++i) {
+                const uint64_t key = abs_key(L.x[i][q]);
+                nan = nan || key > kInfKey;
+                if ((key & himask) == prefix) atomicAdd(&L.bins[(unsigned)(key >> shift) & 0xFFu], 1u);
+            }
+        }
+        if (shift == 56 && nan) atomicOr(&L.any_nan, 1u);
+        __syncthreads();
+        // the digit whose cumulative count passes r: inclusive scan of the 256 counts (in the wave by lane shifts, across waves through LDS)
+        const unsigned c = L.bins[tid];
+        unsigned incl = c;
+#pragma unroll
+        for (int o = 1; o < 64; o <<= 1) {
+            const unsigned up = __shfl_up(incl, o, 64);
+            if (lane >= o) incl += up;
+        }
+        if (lane == 63) L.wave_total[wave] = incl;
+        __syncthreads();
+        for (int wv = 0; wv < wave; ++wv) incl += L.wave_total[wv];
+        if (incl - c <= r && r < incl) { L.sel_bin = (unsigned)tid; L.sel_rank = r - (incl - c); L.sel_count = c; }      // exactly one thread
+        __syncthreads();
+        prefix |= (uint64_t)L.sel_bin << shift;
+        r = L.sel_rank;
+        count = L.sel_count;                                        // after the last digit: how many elements equal a[lo], r its rank among them
+    }
+    uint64_t hi_key = prefix;
+    if (next && r + 1 >= count) {                                   // a[lo] is the last of its value: a[lo + 1] is the least key above it
+        uint64_t m = ~0ull;
+        for (int q = tid; q < qpi; q += kBlock) {
+#pragma unroll
+            for (int i = 0; i < 4; ++i) {
+                const uint64_t key = abs_key(L.x[i][q]);
+                m = key > prefix && key < m ? key : m;
+            }
+        }
+        if (m != ~0ull) atomicMin(&L.min_above, (unsigned long long)m);
+        __syncthreads();
+        hi_key = L.min_above;
+    }
+    const double a_lo = __longlong_as_double((long long)prefix), a_hi = __longlong_as_double((long long)hi_key);
+    const double d = a_hi - a_lo;
+    const double wm1 = w - 1.0;
+    const double q = w < 0.5 ? __builtin_fma(w, d, a_lo) : __builtin_fma(wm1, d, a_hi);
+    if (L.any_nan != 0u || q != q) return __builtin_nan("");
+    return q > max_val ? q : max_val;
+}
+
+// the threshold of the workgroup's image for the mode: max_val itself (CLIP, nothing searched) or dynamic_threshold
+template <int kCapQuads>
+__device__ __forceinline__ double x0_threshold(FixLds<kCapQuads>& L, int qpi, int mode, unsigned lo, bool next, double w, double max_val) {
+    return mode == NATINF_X0_CLIP ? max_val : dynamic_threshold(L, qpi, lo, next, w, max_val);
+}
+
+// the corrected quad.  CLIP: x < -c ? -c : (x > c ? c : x), a NaN stays as it is, no division.  DYNAMIC: min(max(x, -s), s) / s, one IEEE fp64
+// division; a NaN threshold makes the whole image NaN (both comparisons fail, x / NaN), and every NaN quotient (inf / inf under an infinite
+// threshold too) leaves as the one quiet NaN pattern 0x7FF8000000000000.
+__device__ __forceinline__ void x0_fix(double (&y)[4], const double (&x)[4], int mode, double s) {
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+        const double lo = x[i] < -s ? -s : x[i];
+        const double t = lo > s ? s : lo;
+        const double r = t / s;
+        y[i] = mode == NATINF_X0_CLIP ? t : (r != r ? __builtin_nan("") : r);
+    }
+}
+
+// the correction on its own, in place: the definition the fused step is tested against.  blockIdx.x = image.
+template <int kCapQuads>
+__global__ __launch_bounds__(kBlock) void k_x0fix_f64(double* x0, double* __restrict__ s_out, int qpi, int mode, unsigned lo, int next,
+                                                     double w, double max_val)
+{
+    __shared__ FixLds<kCapQuads> L;
+    const int tid = threadIdx.x;
+    d2* img = reinterpret_cast<d2*>(x0) + 2 * (int64_t)blockIdx.x * qpi;
+    for (int q = tid; q < qpi; q += kBlock) {
+        const d2 a = img[2 * q], b = img[2 * q + 1];
+        L.x[0][q] = a.x; L.x[1][q] = a.y; L.x[2][q] = b.x; L.x[3][q] = b.y;
+    }
+    // (a thread reads back only what it wrote itself; the search's first barrier comes before any other thread's read)
+    const double s = x0_threshold(L, qpi, mode, lo, next != 0, w, max_val);
+    for (int q = tid; q < qpi; q += kBlock) {
+        const double x[4] = {L.x[0][q], L.x[1][q], L.x[2][q], L.x[3][q]};
+        double y[4];
+        x0_fix(y, x, mode, s);
+        img[2 * q] = d2{y[0], y[1]};
+        img[2 * q + 1] = d2{y[2], y[3]};
+    }
+    if (s_out && tid == 0) s_out[blockIdx.x] = s;
+}
+
+// ------------------------------------------------------------------------------------------
+// CIFAR10 form with the x0 correction: k_step_inpaint_f64's composition with one workgroup per image (blockIdx.x = image; a thread owns the
+// quads tid, tid + kBlock, ...).  The raw x0 of the image goes to LDS and nowhere else; after the threshold is known each quad is corrected,
+// stored once as hist[k], and used for the diagonal term; the rest is k_step_noise_f64 operation for operation, then known_blend if there are
+// known pixels.  hist[k] equals k_step_noise_f64 followed by k_x0fix_f64, byte for byte.
+// ------------------------------------------------------------------------------------------
+template <int kCapQuads>
+__global__ __launch_bounds__(kBlock) void k_stepfix_f64(
+    const float4* __restrict__ x_k, const float4* __restrict__ mout, const float4* __restrict__ noise,
+    double* __restrict__ hist, float4* __restrict__ x_next,
+    const int32_t* __restrict__ idx, const double* __restrict__ val, int n_terms, double c_diag,
+    const int32_t* __restrict__ idx_b, const float* __restrict__ val_b, int n_b,
+    const int64_t* __restrict__ index, int64_t first_index, int64_t index_stride, int qpi,
+    uint32_t k0, uint32_t k1, int k, double alpha, double sigma2, float stdv,
+    const float* __restrict__ known, const uint8_t* __restrict__ mask, int64_t kstride, int64_t mstride,
+    float kalpha, float kstd, uint32_t kcolumn,
+    int mode, unsigned lo, int next, double w, double max_val, double* __restrict__ s_out, int64_t E)
+{
+    __shared__ FixLds<kCapQuads> L;
+    const int tid = threadIdx.x;
+    const int64_t img = blockIdx.x, v0 = img * qpi;
+    for (int q = tid; q < qpi; q += kBlock) {
+        double x0[4];
+        x0_score_f64(x0, x_k[v0 + q], mout[v0 + q], stdv, sigma2, alpha);
+        L.x[0][q] = x0[0]; L.x[1][q] = x0[1]; L.x[2][q] = x0[2]; L.x[3][q] = x0[3];
+    }
+    const double s = x0_threshold(L, qpi, mode, lo, next != 0, w, max_val);
+    if (s_out && tid == 0) s_out[img] = s;
+
+    const uint64_t gi = global_index(index, first_index, index_stride, img);
+    // the Philox key pinned in vector registers: left scalar, the 20 round keys the compiler derives from it are hoisted out of this loop into
+    // SGPRs, next to the loop's own carried scalars, and spill (k_step_noise_f64 drops its loop for that; this kernel's loop is its shape)
+    asm("" : "+v"(k0), "+v"(k1));
+    for (int q = tid; q < qpi; q += kBlock) {
+        const int64_t v = v0 + q;
+        const double x[4] = {L.x[0][q], L.x[1][q], L.x[2][q], L.x[3][q]};
+        double y[4], acc[4] = {0.0, 0.0, 0.0, 0.0}, nacc[4] = {0.0, 0.0, 0.0, 0.0};
+        x0_fix(y, x, mode, s);
+        st_quad_f64(hist + (int64_t)k * E, v, y);
+        wsum_f64(acc, hist, idx, val, n_terms, v, E);
+        acc_f64(acc, y[0], y[1], y[2], y[3], c_diag);
+        noise_row_sum(nacc, noise, idx_b, val_b, n_b, v, gi, q, k0, k1);
+        float4 xn = combine(acc, nacc);
+        if (known) xn = known_blend(xn, known, mask, kstride, mstride, img, q, qpi, kalpha, kstd, kcolumn, gi, k0, k1);
+        x_next[v] = xn;
+    }
+}
+
 // ---- pieces of the colorization forms: the gray channel of a rotated colour space re-noised to the level of the step's output ----
 // a 3x3 fp32 matrix carried to the kernel by value, row-major m[3*i + j] = M[i][j]: the caller's basis or its inverse, neither is hard-coded here
 struct mat3 { float m[9]; };
@@ -1038,6 +1227,21 @@ inline mat3 mat3_of(const float* p) {
     return r;
 }
 
+// the x0 correction of a call: a known mode, a ratio in [0, 1] (a NaN fails both comparisons), a positive finite max_val and an image the
+// largest kernel instantiation holds
+inline bool x0fix_ok(int mode, double ratio, double max_val, int64_t elems_per_image) {
+    return (mode == NATINF_X0_CLIP || mode == NATINF_X0_DYNAMIC) && ratio >= 0.0 && ratio <= 1.0 && max_val > 0.0 && max_val <= DBL_MAX &&
+           elems_per_image <= 4 * (int64_t)kFixQuadsMax;
+}
+// where the quantile sits in the ascending |x0| of an image: rank = ratio*(n - 1) is ONE fp64 product; lo = floor(rank), hi = ceil(rank) is lo or
+// lo + 1 (`next`), w = rank - lo (exact)
+struct QuantilePos { unsigned lo; int next; double w; };
+inline QuantilePos quantile_pos(double ratio, int64_t elems_per_image) {
+    const double rank = ratio * (double)(elems_per_image - 1);
+    const double lo = std::floor(rank);
+    return QuantilePos{(unsigned)lo, std::ceil(rank) != lo, rank - lo};
+}
+
 // Host-side check of a small device int32 array before a launch (the noise row of natinf_step_f32prod_noise, the slots of
 // natinf_step_f32prod_noise_guided and natinf_step_f16chain_guided): every one of the n values lies in lo..hi.  They are read back, kRowChunk at a time into
 // one pinned buffer, on a private non-blocking stream of the current device: the host waits for those small copies only,
@@ -1219,6 +1423,48 @@ int natinf_step_f64hist_inpaint(const float* x_k, const float* model_out, const 
                        elems_per_image / 4, (uint32_t)seed, (uint32_t)(seed >> 32), k, alpha, sigma * sigma, std_f32,
                        known, mask, known_image_stride, mask_image_stride, known_alpha_f32, known_std_f32, known_column,
                        nvec, E);
+    return launched();
+}
+
+int natinf_x0_threshold_f64(double* x0, double* s_out, int64_t n_images, int64_t elems_per_image,
+                            int mode, double ratio, double max_val, natinf_stream_t stream)
+{
+    const int64_t qpi = vec_count(elems_per_image, 4);
+    if (!x0 || n_images <= 0 || n_images > INT32_MAX || !qpi || !x0fix_ok(mode, ratio, max_val, elems_per_image)) return NATINF_EINVAL;
+    const QuantilePos p = quantile_pos(ratio, elems_per_image);
+    auto kernel = qpi <= kFixQuadsSmall ? k_x0fix_f64<kFixQuadsSmall> : k_x0fix_f64<kFixQuadsMax>;
+    hipLaunchKernelGGL(kernel, dim3((unsigned)n_images), dim3(kBlock), 0, (hipStream_t)stream,
+                       x0, s_out, (int)qpi, mode, p.lo, p.next, p.w, max_val);
+    return launched();
+}
+
+int natinf_step_f64hist_x0fix(const float* x_k, const float* model_out, const float* noise,
+                              double* hist, float* x_next,
+                              const int32_t* idx, const double* val, int n_terms, double c_diag,
+                              const int32_t* idx_b, const float* val_b, int n_b,
+                              int k, double alpha, double sigma, float std_f32,
+                              uint64_t seed, const int64_t* image_index, int64_t first_index, int64_t index_stride,
+                              int64_t elems_per_image, int64_t E,
+                              const float* known, const uint8_t* mask, int64_t known_image_stride, int64_t mask_image_stride,
+                              float known_alpha_f32, float known_std_f32, uint32_t known_column,
+                              int mode, double ratio, double max_val, double* s_out, natinf_stream_t stream)
+{
+    const int64_t nvec = vec_count(E, 4);
+    if (!x_k || !model_out || !noise || !hist || !x_next || !terms_ok(idx, val, n_terms) || !terms_ok(idx_b, val_b, n_b) ||
+        k < 0 || !nvec || !image_ok(elems_per_image, E) || !x0fix_ok(mode, ratio, max_val, elems_per_image) ||
+        E / elems_per_image > INT32_MAX || (!known != !mask) ||
+        (known && !known_ok(known, mask, known_image_stride, mask_image_stride, known_column, elems_per_image)))
+        return NATINF_EINVAL;
+    // no read-back of the noise row (natinf_step_f64hist_noise): every check above is a pure argument check, no device is touched
+    const QuantilePos p = quantile_pos(ratio, elems_per_image);
+    const int64_t qpi = elems_per_image / 4;
+    auto kernel = qpi <= kFixQuadsSmall ? k_stepfix_f64<kFixQuadsSmall> : k_stepfix_f64<kFixQuadsMax>;
+    hipLaunchKernelGGL(kernel, dim3((unsigned)(E / elems_per_image)), dim3(kBlock), 0, (hipStream_t)stream,
+                       (const float4*)x_k, (const float4*)model_out, (const float4*)noise, hist, (float4*)x_next,
+                       idx, val, n_terms, c_diag, idx_b, val_b, n_b, image_index, first_index, index_stride,
+                       (int)qpi, (uint32_t)seed, (uint32_t)(seed >> 32), k, alpha, sigma * sigma, std_f32,
+                       known, mask, known_image_stride, mask_image_stride, known_alpha_f32, known_std_f32, known_column,
+                       mode, p.lo, p.next, p.w, max_val, s_out, E);
     return launched();
 }
 

@@ -250,6 +250,89 @@ def check_gray(gray_u, n_elem: int, elems_per_image: Optional[int], *, seed, fas
     return epi // 3 if gray_u.numel() == n_elem // 3 and n_elem != epi else 0
 
 
+# x0 correction: the modes of natinf_x0_threshold_f64 / natinf_step_f64hist_x0fix by the names the samplers take
+X0_FIX_MODES = {"clip": _lib.X0_CLIP, "dynamic": _lib.X0_DYNAMIC}
+X0_FIX_MAX_ELEMS = 8192      # one workgroup holds an image's fp64 x0 in LDS
+
+
+def check_x0_fix(x0_fix, x0_ratio, x0_max, *, seed=0, elems_per_image: Optional[int] = 4, fast_f32: bool = False, gray: bool = False,
+                 epi_later: bool = False) -> int:
+    """The argument checks of an x0 correction, made before anything is launched -> the mode (0 for ``x0_fix=None``, which checks nothing
+    else).  ``seed`` / ``elems_per_image``: pass the sampler's own (None is refused; ``epi_later``: a missing ``elems_per_image`` may still come
+    with the step); host-side callers that have neither leave the defaults."""
+    if x0_fix is None:
+        return 0
+    if not isinstance(x0_fix, str) or x0_fix not in X0_FIX_MODES:
+        raise ValueError('x0_fix must be None, "clip" or "dynamic"')
+    try:
+        ratio, mx = float(x0_ratio), float(x0_max)
+    except (TypeError, ValueError):
+        raise ValueError("x0_ratio and x0_max must be numbers") from None
+    if not 0.0 <= ratio <= 1.0:
+        raise ValueError("x0_ratio must be in [0, 1]")
+    if not (mx > 0.0 and math.isfinite(mx)):
+        raise ValueError("x0_max must be positive and finite")
+    if fast_f32:
+        raise ValueError("x0_fix: the fast_f32 mode has no correction")
+    if gray:
+        raise ValueError("x0_fix does not go with gray_u (colorization): its step has one thread per pixel quad, the correction one workgroup per image")
+    if seed is None:
+        raise ValueError("x0_fix: the step takes the noise-drawing form, which needs a seed (deterministic matrices too)")
+    if elems_per_image is None and not epi_later:
+        raise ValueError("x0_fix: elems_per_image is needed, the threshold is a per-image statistic")
+    if elems_per_image is not None and int(elems_per_image) > X0_FIX_MAX_ELEMS:
+        raise ValueError(f"x0_fix: elems_per_image must be <= {X0_FIX_MAX_ELEMS}")
+    return X0_FIX_MODES[x0_fix]
+
+
+def _fma_f64(a: float, b: float, c: float) -> float:
+    """fma(a, b, c) in fp64 with its one rounding: exact rational arithmetic for finite operands; a non-finite operand decides the result
+    without any rounding, so the plain expression is right there"""
+    from fractions import Fraction
+    if not (math.isfinite(a) and math.isfinite(b) and math.isfinite(c)):
+        with np.errstate(invalid="ignore", over="ignore"):
+            return float(np.float64(a) * np.float64(b) + np.float64(c))
+    exact = Fraction(a) * Fraction(b) + Fraction(c)
+    if exact == 0:                                                      # a zero product plus a zero is exact in plain arithmetic, sign included; a cancellation gives +0
+        return float(np.float64(a) * np.float64(b) + np.float64(c)) if a == 0.0 or b == 0.0 else 0.0
+    try:
+        return float(exact)                                             # int / int true division: correctly rounded
+    except OverflowError:
+        return math.inf if exact > 0 else -math.inf
+
+
+def x0_threshold_host(x0, mode, ratio: float = 0.995, max_val: float = 1.0):
+    """The x0 correction in numpy fp64, operation for operation the library's (include/natinf.h, natinf_x0_threshold_f64): ``x0`` fp64
+    [n_images, n] (or [n]: one image), ``mode`` "clip" / "dynamic" (or the ABI's 1 / 2) -> (y like ``x0``, s fp64 [n_images]).  The one fused
+    multiply-add per image is evaluated exactly.  The CPU replay of a GPU step, and what the GPU is compared against byte for byte."""
+    mode = X0_FIX_MODES.get(mode, mode)
+    if mode not in (_lib.X0_CLIP, _lib.X0_DYNAMIC):
+        raise ValueError('mode must be "clip" or "dynamic"')
+    ratio, c = float(ratio), float(max_val)
+    if not 0.0 <= ratio <= 1.0 or not (c > 0.0 and math.isfinite(c)):
+        raise ValueError("ratio must be in [0, 1], max_val positive and finite")
+    x = np.ascontiguousarray(x0, dtype=np.float64)
+    rows = x.reshape(1, -1) if x.ndim == 1 else x.reshape(x.shape[0], -1)
+    n = rows.shape[1]
+    if mode == _lib.X0_CLIP:
+        y = np.where(rows < -c, -c, np.where(rows > c, c, rows))        # a NaN fails both comparisons and stays, bits and all
+        return y.reshape(x.shape), np.full(rows.shape[0], c)
+    rank = ratio * float(n - 1)
+    lo, hi = int(math.floor(rank)), int(math.ceil(rank))
+    w = rank - lo
+    y, s = np.empty_like(rows), np.empty(rows.shape[0])
+    with np.errstate(invalid="ignore"):
+        for i, r in enumerate(rows):
+            a = np.sort(np.abs(r))                                       # NaN last
+            a_lo, a_hi = float(a[lo]), float(a[hi])
+            d = float(np.float64(a_hi) - np.float64(a_lo))
+            q = _fma_f64(w, d, a_lo) if w < 0.5 else _fma_f64(w - 1.0, d, a_hi)
+            s[i] = np.nan if np.isnan(r).any() or math.isnan(q) else max(q, c)
+            y[i] = np.minimum(np.maximum(r, -s[i]), s[i]) / s[i]         # a NaN s makes every element NaN; inf / inf under an infinite s is one
+    y[np.isnan(y)] = np.nan                                              # every NaN the correction produces: the one quiet pattern 0x7FF8000000000000
+    return y.reshape(x.shape), s
+
+
 class CifarNI:
     """x_{k+1} = fp32(sum_j C[k,j]*x0_j) + fp32(B[k,0])*noise with x0_k = ((-out/std)*sigma^2 + x_k)/alpha.
 
@@ -264,11 +347,21 @@ class CifarNI:
 
     Colorization (``gray_u=`` of ``first_input``, ``step`` and ``run``; natinf_step_f64hist_colorize): the same, on one channel of a rotated colour
     space instead of a subset of the pixels -- after every update latent channel 0 of every pixel (``COLOR_M``) is overwritten with ``gray_u``
-    diffused to the level of the step's output (``color_schedule``).  ``gray_u`` together with ``known`` or ``mask`` is a ValueError."""
+    diffused to the level of the step's output (``color_schedule``).  ``gray_u`` together with ``known`` or ``mask`` is a ValueError.
+
+    x0 correction (``x0_fix="clip"`` / ``"dynamic"``; natinf_step_f64hist_x0fix): every step corrects its predicted x0 per image before it enters
+    the history and the sum -- clamped to [-``x0_max``, ``x0_max``] (DDPM's clip_denoised), or clamped to and divided by s = max(the ``x0_ratio``
+    quantile of the image's |x0|, ``x0_max``) (Imagen's dynamic thresholding, the reference's ``correcting_x0_fn="dynamic_thresholding"``).  Matrix
+    X with it is the classical solver X with that ``correcting_x0_fn``.  It needs a ``seed`` and ``elems_per_image`` (<= 8192) like inpainting,
+    goes with ``known`` / ``mask``, and not with ``fast_f32`` or ``gray_u``.  ``x0_s`` [n_step, n_images] fp64 (device) holds the thresholds used
+    (``"clip"``: ``x0_max``), row k written by step k.  ``x0_fix=None`` (default) launches exactly what the class launched without the option."""
 
     def __init__(self, C: np.ndarray, B: np.ndarray, node: np.ndarray, n_elem: int, device="cuda:0",
                  dense: bool = False, fast_f32: bool = False, stds=None, *, seed: Optional[int] = None,
-                 elems_per_image: Optional[int] = None):
+                 elems_per_image: Optional[int] = None, x0_fix: Optional[str] = None, x0_ratio: float = 0.995, x0_max: float = 1.0):
+        # (the correction's refusals come first: they need no GPU; elems_per_image may still come with the step)
+        self.x0_mode = check_x0_fix(x0_fix, x0_ratio, x0_max, seed=seed, elems_per_image=elems_per_image, fast_f32=fast_f32, epi_later=True)
+        self.x0_fix, self.x0_ratio, self.x0_max, self.x0_s = x0_fix, float(x0_ratio), float(x0_max), None
         _lib.require_gpu()
         if n_elem % 4:
             raise ValueError("element count must be a multiple of 4")
@@ -348,6 +441,9 @@ class CifarNI:
         channel 0, diffused to the level of x_{k+1} (``color_schedule``).  Not together with ``known`` / ``mask``."""
         epi = self.epi if elems_per_image is None else int(elems_per_image)
         inpaint = known is not None or mask is not None
+        if self.x0_mode:                                                  # refusals first: gray_u, a missing or oversized elems_per_image
+            check_x0_fix(self.x0_fix, self.x0_ratio, self.x0_max, seed=self.seed, elems_per_image=epi, gray=gray_u is not None)
+            _check_elems_per_image(epi, self.E)
         if gray_u is not None:                                            # refusals first, as for inpainting
             if inpaint:
                 raise ValueError("gray_u (colorization) does not go with known / mask (inpainting)")
@@ -364,11 +460,21 @@ class CifarNI:
         idx, val, n = self.rows.ptrs(k)
         r = self.rows.rows[k]
         a, s = float(self.node[k, 1]), float(self.node[k, 2])
-        if inpaint or gray_u is not None or self.stochastic:              # the entries that draw noise: B's rows and the images' global indices
+        if inpaint or gray_u is not None or self.stochastic or self.x0_mode:    # the entries that draw noise: B's rows and the images' global indices
             if epi is None:
                 raise ValueError("stochastic NI matrix: elems_per_image is needed to key the injected noise")
             ib, vb, nb = self._noise_rows().ptrs(k)
             index, first, stride = image_index_args(index, self.E // epi, x_k.device)
+        if self.x0_mode:                                                  # with or without known pixels: one entry
+            n_images = self.E // epi
+            if self.x0_s is None or self.x0_s.shape[1] != n_images:
+                self.x0_s = torch.zeros((self.n_step, n_images), dtype=torch.float64, device=self.device)
+            kargs = (ptr(known), ptr(mask), ks, ms, ka, kstd, kcol) if inpaint else (0, 0, 0, 0, 0.0, 0.0, 0)
+            check(lib.natinf_step_f64hist_x0fix(ptr(x_k), ptr(model_out), ptr(noise), ptr(self.hist), ptr(x_next), idx, val, n,
+                                                r.diag, ib, vb, nb, k, a, s, self.std[k], self.seed, ptr(index), first, stride,
+                                                epi, self.E, *kargs, self.x0_mode, self.x0_ratio, self.x0_max, ptr(self.x0_s[k]),
+                                                stream_ptr()), "natinf_step_f64hist_x0fix")
+            return x_next
         if inpaint:
             check(lib.natinf_step_f64hist_inpaint(ptr(x_k), ptr(model_out), ptr(noise), ptr(self.hist), ptr(x_next), idx, val, n,
                                                   r.diag, ib, vb, nb, k, a, s, self.std[k], self.seed, ptr(index), first, stride,
@@ -405,9 +511,11 @@ class CifarNI:
         inpaint = known is not None or mask is not None
         if gray_u is not None and inpaint:
             raise ValueError("gray_u (colorization) does not go with known / mask (inpainting)")
+        if self.x0_mode:
+            check_x0_fix(self.x0_fix, self.x0_ratio, self.x0_max, seed=self.seed, elems_per_image=epi, gray=gray_u is not None)
         # every step goes through self.step (callers wrap it per instance, e.g. bench.py's timed replica): a column-0 matrix gets exactly the four
         # positional arguments it always got, a stochastic one index= and elems_per_image=, a conditioned trajectory its blend arguments as well
-        kw = dict(index=index, elems_per_image=epi) if self.stochastic or inpaint or gray_u is not None else {}
+        kw = dict(index=index, elems_per_image=epi) if self.stochastic or inpaint or gray_u is not None or self.x0_mode else {}
         if gray_u is not None:
             kw.update(gray_u=gray_u.reshape(-1), known_final=known_final)
         elif inpaint:
