@@ -455,6 +455,59 @@ def calc_fid_sharded(imgs, ref_path, device, group=None, model=None, timings: Op
     return fid
 
 
+def get_features(imgs, model, device=None) -> torch.Tensor:
+    """``get_activation`` with the pool3 features kept on the device: uint8 [n, H, W, 3] images -> fp32 [n, 2048], the same batching.  The result is on
+    ``device``; with ``device=None`` it stays where the model put it (the engine's own device)."""
+    bs = _fid_batch(model)
+    parts = [model(imgs[ii:ii + bs]).float() for ii in range(0, len(imgs), bs)]
+    if not parts:
+        return torch.empty(0, 2048, dtype=torch.float32, device=device)
+    feats = torch.cat(parts).contiguous()
+    return feats if device is None else feats.to(device)
+
+
+def _ref_features(ref_feats, device) -> torch.Tensor:
+    """``ref_feats``: an fp32-convertible [n, 2048] array / tensor or the path of a ``.npy`` holding one (the real images' pool3 features)"""
+    if isinstance(ref_feats, (str, os.PathLike)):
+        if not os.path.exists(ref_feats):
+            raise FileNotFoundError(f"prdc: blocked -- {ref_feats} (pool3 features of the real CIFAR10 images) is missing")
+        ref_feats = np.load(ref_feats)
+    return torch.as_tensor(ref_feats).to(device=device, dtype=torch.float32)
+
+
+def calc_prdc(imgs, ref_feats, device, model=None, k: int = 3) -> dict:
+    """dict(precision, recall, density, coverage) of the images (uint8 [n, H, W, 3]) against the real images' pool3 features ``ref_feats`` (array or ``.npy``
+    path): k-nearest-neighbour manifold metrics on the features ``calc_fid`` is computed from (prdc.py; include/natinf_prdc.h).  The real CIFAR10 features
+    are a download the image does not hold, like FID's statistics: a missing file raises ``prdc: blocked``."""
+    from . import prdc as P
+    real = _ref_features(ref_feats, device)
+    model = model or fid_inception(device, tuple(imgs.shape[1:3]))
+    counts = P.prdc_counts(P.FeatureSet(real, device=device), P.FeatureSet(get_features(imgs, model, device), device=device), k)
+    return P.prdc_from_sums(P.count_sums(counts), k)                    # this process's images only, whatever process group exists
+
+
+def calc_prdc_sharded(imgs, ref_feats, device, group=None, model=None, k: int = 3) -> dict:
+    """``calc_prdc`` for a batch-sharded run: every rank scores ITS images, the features (8 KB per image) are all-gathered so that every rank holds the whole
+    generated set as columns, each rank measures its row slice of both sets and one all-reduce of six integers gives every rank the same four numbers."""
+    import torch.distributed as dist
+    from . import prdc as P
+    real = _ref_features(ref_feats, device)
+    model = model or fid_inception(device, tuple(imgs.shape[1:3]))
+    feats = get_features(imgs, model, device)
+    if dist.is_available() and dist.is_initialized() and dist.get_world_size(group) > 1:
+        world, host = dist.get_world_size(group), dist.get_backend(group) != "nccl"
+        n = torch.tensor([feats.shape[0]], dtype=torch.int64, device="cpu" if host else feats.device)
+        ns = [torch.zeros_like(n) for _ in range(world)]
+        dist.all_gather(ns, n, group=group)
+        m = max(int(v) for v in ns)
+        pad = torch.zeros(m, feats.shape[1], dtype=torch.float32, device=n.device)
+        pad[:feats.shape[0]] = feats
+        parts = [torch.empty_like(pad) for _ in range(world)]
+        dist.all_gather(parts, pad, group=group)
+        feats = torch.cat([p[:int(c)] for p, c in zip(parts, ns)]).to(device)
+    return P.prdc(P.FeatureSet(real, device=device), P.FeatureSet(feats, device=device), k=k, group=group)
+
+
 class FidBlocked:
     """What ``natural_inference_tx(compute_fid=True)`` returns when the FID assets (Inception weights, ``cifar10_mu_sigma.npz``) are absent:
     the images it generated and the reason -- distinguishable from both a FID value (float) and the ``compute_fid=False`` result (a tensor)."""

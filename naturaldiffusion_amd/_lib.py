@@ -188,6 +188,12 @@ SIGNATURES = {
     "natinf_posterior_samples": (C.c_int, [_p, _p, _f32, _f32, C.c_uint64, _p, _i64, _i64, _i32, _i32, _p, _p]),
     "natinf_posterior_stats": (C.c_int, [_p, _f64, _i32, _i32, _p, _p, _p, _p]),
     "natinf_posterior_debug_planes": (C.c_int, [_p, _i32, _i32, _p]),
+    # include/natinf_prdc.h
+    "natinf_prdc_workspace_bytes": (C.c_int64, [_i64, _i64, _i32, _i32]),
+    "natinf_prdc_planes": (C.c_int, [_p, _i64, _i32, _p, _p, _p]),
+    "natinf_prdc_knn_radius": (C.c_int, [_p, _p, _i64, _p, _p, _i64, _i32, _i32, _i64, _p, _p, _i64, _p]),
+    "natinf_prdc_ball_counts": (C.c_int, [_p, _p, _i64, _p, _p, _i64, _i32, _i64, _p, _p, _p, _p, _p]),
+    "natinf_prdc_debug_dist2": (C.c_int, [_p, _p, _i64, _p, _p, _i64, _i32, _i64, _p, _p]),
 }
 
 for _name, (_res, _args) in SIGNATURES.items():

@@ -1,0 +1,116 @@
+// prdc.hip -- the k-nearest-neighbour manifold metrics' kernels (prdc.h) and their C ABI (include/natinf_prdc.h).
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+#include "natinf.h"
+#include "natinf_prdc.h"
+
+namespace {
+#include "prdc.h"
+
+inline int launched() { return hipGetLastError() == hipSuccess ? NATINF_OK : NATINF_ELAUNCH; }
+
+constexpr int RESIDENT_BLOCKS = 512;     // 256 CUs x 2 blocks (46 KB of LDS, <= 256 VGPRs each)
+constexpr int MAX_SPLITS = 64;
+constexpr int MIN_SPLITS = 8;            // one column range per XCD: the blocks of a row block run beside each other and share its rows of A beyond the L2s
+
+inline bool dims_ok(int d, int k) { return d >= 64 && d <= NATINF_PRDC_MAX_D && d % 64 == 0 && k >= 1 && k <= NATINF_PRDC_MAX_K; }
+inline bool count_ok(int64_t n) { return n >= 1 && n <= NATINF_PRDC_MAX_N; }
+inline bool self_ok(int64_t self_offset, int64_t n_rows, int64_t n_cols) { return self_offset >= -1 && (self_offset < 0 || self_offset + n_rows <= n_cols); }
+inline bool aligned(const void* p, uintptr_t a) { return p && !((uintptr_t)p & (a - 1)); }
+
+inline int64_t row_blocks(int64_t n_rows) { return (n_rows + prdc::BM - 1) / prdc::BM; }
+
+// Blocks over the column tiles: as many as fill one round of resident blocks, eight at least.  A function of the shape only; the result does not depend
+// on it (the k smallest of a set, an integer sum).
+inline int splits_for(int64_t n_rows, int64_t n_cols) {
+    const int64_t ctiles = (n_cols + prdc::BN - 1) / prdc::BN, smax = ctiles < MAX_SPLITS ? ctiles : MAX_SPLITS;
+    const int64_t fill = RESIDENT_BLOCKS / row_blocks(n_rows), s = fill > MIN_SPLITS ? fill : MIN_SPLITS;
+    return (int)(s > smax ? smax : s);
+}
+
+// rows of K_MAX doubles the lists need: splits * n_rows <= max(MIN_SPLITS * n_rows, RESIDENT_BLOCKS * BM), which is monotone (the split count itself is not)
+inline int64_t list_rows(int64_t n_rows) {
+    const int64_t floor_rows = (int64_t)RESIDENT_BLOCKS * prdc::BM, by_min = MIN_SPLITS * n_rows;
+    return by_min > floor_rows ? by_min : floor_rows;
+}
+
+inline bool operands_ok(const void* row_planes, const double* row_norms, int64_t n_rows, const void* col_planes, const double* col_norms, int64_t n_cols,
+                        int d, int k, int64_t self_offset) {
+    return aligned(row_planes, 16) && aligned(col_planes, 16) && aligned(row_norms, 8) && aligned(col_norms, 8) && dims_ok(d, k) && count_ok(n_rows) &&
+           count_ok(n_cols) && self_ok(self_offset, n_rows, n_cols) && k + (self_offset >= 0) <= n_cols;
+}
+
+inline prdc::Operands operands(const void* row_planes, const double* row_norms, int64_t n_rows, const void* col_planes, const double* col_norms, int64_t n_cols,
+                               int d, int64_t self_offset) {
+    prdc::Operands op;
+    op.a = (const __bf16*)row_planes; op.na = row_norms; op.b = (const __bf16*)col_planes; op.nb = col_norms;
+    op.n_rows = (int)n_rows; op.n_cols = (int)n_cols; op.d = d; op.self_offset = self_offset;
+    return op;
+}
+}  // namespace
+
+extern "C" {
+
+int64_t natinf_prdc_workspace_bytes(int64_t n_rows, int64_t n_cols, int d, int k)
+{
+    if (!dims_ok(d, k) || !count_ok(n_rows) || !count_ok(n_cols) || k > n_cols) return NATINF_EINVAL;
+    return list_rows(n_rows) * prdc::K_MAX * (int64_t)sizeof(double);
+}
+
+int natinf_prdc_planes(const float* feats, int64_t n, int d, void* planes_bf16, double* norms, natinf_stream_t stream)
+{
+    if (!aligned(feats, 16) || !aligned(planes_bf16, 16) || !aligned(norms, 8) || !count_ok(n) || !dims_ok(d, 1)) return NATINF_EINVAL;
+    hipLaunchKernelGGL(prdc::k_prdc_planes, dim3((unsigned)n), dim3(prdc::THREADS), 0, (hipStream_t)stream, (const float4*)feats, (prdc::bf16x8*)planes_bf16,
+                       norms, d / 8, n * (d / 8));
+    return launched();
+}
+
+int natinf_prdc_knn_radius(const void* row_planes, const double* row_norms, int64_t n_rows,
+                           const void* col_planes, const double* col_norms, int64_t n_cols,
+                           int d, int k, int64_t self_offset, double* r2_out,
+                           void* workspace, int64_t workspace_bytes, natinf_stream_t stream)
+{
+    if (!operands_ok(row_planes, row_norms, n_rows, col_planes, col_norms, n_cols, d, k, self_offset) || !aligned(r2_out, 8) || !aligned(workspace, 256))
+        return NATINF_EINVAL;
+    if (workspace_bytes < natinf_prdc_workspace_bytes(n_rows, n_cols, d, k)) return NATINF_EINVAL;
+    const prdc::Operands op = operands(row_planes, row_norms, n_rows, col_planes, col_norms, n_cols, d, self_offset);
+    const int splits = splits_for(n_rows, n_cols);
+    hipStream_t s = (hipStream_t)stream;
+    hipLaunchKernelGGL(prdc::k_prdc_knn, dim3(splits, (unsigned)row_blocks(n_rows)), dim3(prdc::THREADS), 0, s, op, splits, (double*)workspace);
+    if (launched() != NATINF_OK) return NATINF_ELAUNCH;
+    hipLaunchKernelGGL(prdc::k_prdc_merge, dim3((unsigned)((n_rows + prdc::THREADS - 1) / prdc::THREADS)), dim3(prdc::THREADS), 0, s,
+                       (const double*)workspace, n_rows, splits, k, r2_out);
+    return launched();
+}
+
+int natinf_prdc_ball_counts(const void* row_planes, const double* row_norms, int64_t n_rows,
+                            const void* col_planes, const double* col_norms, int64_t n_cols,
+                            int d, int64_t self_offset, const double* r2_rows, const double* r2_cols,
+                            int32_t* cnt_row_ball, int32_t* cnt_col_ball, natinf_stream_t stream)
+{
+    if (!operands_ok(row_planes, row_norms, n_rows, col_planes, col_norms, n_cols, d, 1, self_offset)) return NATINF_EINVAL;
+    if (!r2_rows != !cnt_row_ball || !r2_cols != !cnt_col_ball || (!cnt_row_ball && !cnt_col_ball)) return NATINF_EINVAL;
+    if (((uintptr_t)r2_rows & 7) || ((uintptr_t)r2_cols & 7) || ((uintptr_t)cnt_row_ball & 3) || ((uintptr_t)cnt_col_ball & 3)) return NATINF_EINVAL;
+    const prdc::Operands op = operands(row_planes, row_norms, n_rows, col_planes, col_norms, n_cols, d, self_offset);
+    const int splits = splits_for(n_rows, n_cols);
+    hipStream_t s = (hipStream_t)stream;
+    if (cnt_row_ball && hipMemsetAsync(cnt_row_ball, 0, n_rows * sizeof(int32_t), s) != hipSuccess) { (void)hipGetLastError(); return NATINF_ELAUNCH; }
+    if (cnt_col_ball && hipMemsetAsync(cnt_col_ball, 0, n_rows * sizeof(int32_t), s) != hipSuccess) { (void)hipGetLastError(); return NATINF_ELAUNCH; }
+    hipLaunchKernelGGL(prdc::k_prdc_balls, dim3(splits, (unsigned)row_blocks(n_rows)), dim3(prdc::THREADS), 0, s, op, splits, r2_rows, r2_cols,
+                       (int*)cnt_row_ball, (int*)cnt_col_ball);
+    return launched();
+}
+
+int natinf_prdc_debug_dist2(const void* row_planes, const double* row_norms, int64_t n_rows,
+                            const void* col_planes, const double* col_norms, int64_t n_cols,
+                            int d, int64_t self_offset, double* d2_out, natinf_stream_t stream)
+{
+    if (!operands_ok(row_planes, row_norms, n_rows, col_planes, col_norms, n_cols, d, 1, self_offset) || !aligned(d2_out, 8)) return NATINF_EINVAL;
+    if (n_rows * n_cols > ((int64_t)1 << 20)) return NATINF_EINVAL;
+    const prdc::Operands op = operands(row_planes, row_norms, n_rows, col_planes, col_norms, n_cols, d, self_offset);
+    const dim3 grid((unsigned)((n_cols + prdc::BN - 1) / prdc::BN), (unsigned)row_blocks(n_rows));
+    hipLaunchKernelGGL(prdc::k_prdc_dist2, grid, dim3(prdc::THREADS), 0, (hipStream_t)stream, op, d2_out);
+    return launched();
+}
+
+}  // extern "C"
