@@ -466,13 +466,30 @@ def get_features(imgs, model, device=None) -> torch.Tensor:
     return feats if device is None else feats.to(device)
 
 
-def _ref_features(ref_feats, device) -> torch.Tensor:
+def _ref_features(ref_feats, device, what: str = "prdc") -> torch.Tensor:
     """``ref_feats``: an fp32-convertible [n, 2048] array / tensor or the path of a ``.npy`` holding one (the real images' pool3 features)"""
     if isinstance(ref_feats, (str, os.PathLike)):
         if not os.path.exists(ref_feats):
-            raise FileNotFoundError(f"prdc: blocked -- {ref_feats} (pool3 features of the real CIFAR10 images) is missing")
+            raise FileNotFoundError(f"{what}: blocked -- {ref_feats} (pool3 features of the real CIFAR10 images) is missing")
         ref_feats = np.load(ref_feats)
     return torch.as_tensor(ref_feats).to(device=device, dtype=torch.float32)
+
+
+def _gather_features(feats: torch.Tensor, device, group=None) -> torch.Tensor:
+    """The ranks' ragged shares of feature rows, all-gathered in rank order onto ``device`` (this rank's own rows when there is no group of two or more)"""
+    import torch.distributed as dist
+    if not (dist.is_available() and dist.is_initialized() and dist.get_world_size(group) > 1):
+        return feats
+    world, host = dist.get_world_size(group), dist.get_backend(group) != "nccl"
+    n = torch.tensor([feats.shape[0]], dtype=torch.int64, device="cpu" if host else feats.device)
+    ns = [torch.zeros_like(n) for _ in range(world)]
+    dist.all_gather(ns, n, group=group)
+    m = max(int(v) for v in ns)
+    pad = torch.zeros(m, feats.shape[1], dtype=torch.float32, device=n.device)
+    pad[:feats.shape[0]] = feats
+    parts = [torch.empty_like(pad) for _ in range(world)]
+    dist.all_gather(parts, pad, group=group)
+    return torch.cat([p[:int(c)] for p, c in zip(parts, ns)]).to(device)
 
 
 def calc_prdc(imgs, ref_feats, device, model=None, k: int = 3) -> dict:
@@ -493,19 +510,32 @@ def calc_prdc_sharded(imgs, ref_feats, device, group=None, model=None, k: int = 
     from . import prdc as P
     real = _ref_features(ref_feats, device)
     model = model or fid_inception(device, tuple(imgs.shape[1:3]))
-    feats = get_features(imgs, model, device)
-    if dist.is_available() and dist.is_initialized() and dist.get_world_size(group) > 1:
-        world, host = dist.get_world_size(group), dist.get_backend(group) != "nccl"
-        n = torch.tensor([feats.shape[0]], dtype=torch.int64, device="cpu" if host else feats.device)
-        ns = [torch.zeros_like(n) for _ in range(world)]
-        dist.all_gather(ns, n, group=group)
-        m = max(int(v) for v in ns)
-        pad = torch.zeros(m, feats.shape[1], dtype=torch.float32, device=n.device)
-        pad[:feats.shape[0]] = feats
-        parts = [torch.empty_like(pad) for _ in range(world)]
-        dist.all_gather(parts, pad, group=group)
-        feats = torch.cat([p[:int(c)] for p, c in zip(parts, ns)]).to(device)
+    feats = _gather_features(get_features(imgs, model, device), device, group)
     return P.prdc(P.FeatureSet(real, device=device), P.FeatureSet(feats, device=device), k=k, group=group)
+
+
+def calc_kid(imgs, ref_feats, device, model=None, estimator: str = "blocks", max_block_size: int = 1024) -> dict:
+    """dict(kid, std, n_blocks, estimator) of the images (uint8 [n, H, W, 3]) against the real images' pool3 features ``ref_feats`` (array or ``.npy`` path):
+    the Kernel Inception Distance with the cubic kernel on the features ``calc_fid`` is computed from (kid.py; include/natinf_kid.h) -- unbiased, so the
+    number for a few thousand images, where FID is not.  ``"blocks"`` is TF-GAN's estimate with its standard error and depends on the order of the images;
+    ``"full"`` is the MMD^2 of the whole sets.  A missing reference file raises ``kid: blocked``."""
+    from . import kid as K
+    from .prdc import FeatureSet
+    real = _ref_features(ref_feats, device, "kid")
+    model = model or fid_inception(device, tuple(imgs.shape[1:3]))
+    return K.kid(FeatureSet(real, device=device), FeatureSet(get_features(imgs, model, device), device=device), estimator=estimator,
+                 max_block_size=max_block_size, group=K.LOCAL)        # this process's images only, whatever process group exists
+
+
+def calc_kid_sharded(imgs, ref_feats, device, group=None, model=None, estimator: str = "blocks", max_block_size: int = 1024) -> dict:
+    """``calc_kid`` for a batch-sharded run: every rank scores ITS images, the features are all-gathered in rank order as ``calc_prdc_sharded`` does, and
+    ``kid(..., group=group)`` splits the sweeps over the ranks; every rank returns the same dict.  The block estimate is that of the gathered order."""
+    from . import kid as K
+    from .prdc import FeatureSet
+    real = _ref_features(ref_feats, device, "kid")
+    model = model or fid_inception(device, tuple(imgs.shape[1:3]))
+    feats = _gather_features(get_features(imgs, model, device), device, group)
+    return K.kid(FeatureSet(real, device=device), FeatureSet(feats, device=device), estimator=estimator, max_block_size=max_block_size, group=group)
 
 
 class FidBlocked:

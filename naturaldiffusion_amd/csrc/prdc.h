@@ -5,6 +5,8 @@
 //   k_prdc_merge   the lists of the column splits -> the k-th smallest per row
 //   k_prdc_balls   per row i the counts #{j: d2_ij <= r2_cols[j]} and #{j: d2_ij <= r2_rows[i]}
 //   k_prdc_dist2   the same tiles written out (test hook)
+//   k_kid_sums     per row i the fp64 sum of (gamma a_i.b_j + coef0)^3 over a range of column tiles (include/natinf_kid.h)
+//   k_kid_merge    the partial sums of the column splits, added in ascending split order
 //
 // d2_ij = max(0, (|a_i|^2 + |b_j|^2) - 2 a_i.b_j) in fp64.  a_i.b_j is six bf16 MFMA passes (lo.hi, hi.lo, mid.mid, mid.hi, hi.mid, hi.hi: the small
 // terms first; the three dropped products are below 2^-26 of |a_k b_k|) whose products are all exact in the fp32 accumulator; the accumulator is added
@@ -43,13 +45,14 @@ constexpr int OPERAND_BYTES = 3 * (BM + BN) * LDS_ROW * 2;
 constexpr int STAGE_BYTES = BM * STAGE_ROW * 8;
 constexpr int LDS_BYTES = OPERAND_BYTES > STAGE_BYTES ? OPERAND_BYTES : STAGE_BYTES;
 
-enum Mode { KNN = 0, BALLS = 1, DIST = 2 };
+enum Mode { KNN = 0, BALLS = 1, DIST = 2, KSUM = 3 };
 
 struct Operands {
-    const __bf16* a;        // [3][n_rows][d]
-    const double* na;       // [n_rows]
-    const __bf16* b;        // [3][n_cols][d]
-    const double* nb;       // [n_cols]
+    const __bf16* a;        // [3][n_rows][d], plane p at a + p * a_plane
+    const double* na;       // [n_rows] (KSUM: not read)
+    const __bf16* b;        // [3][n_cols][d], plane p at b + p * b_plane
+    const double* nb;       // [n_cols] (KSUM: not read)
+    int64_t a_plane, b_plane;   // elements between two planes: n * d for a whole set, the whole set's for a row range taken in place
     int n_rows, n_cols, d;
     int64_t self_offset;    // column self_offset + i is left out of row i; -1: none
 };
@@ -111,9 +114,13 @@ __device__ __forceinline__ void list_insert(double (&L)[K_MAX], double v) {
 // loads (across the column tile's end too) in flight during the MFMAs; rows and columns past n are zeros, never read.  After a column tile's last K tile the
 // fp64 d2 values go through LDS, one accumulator at a time, to the thread that owns (row t >> 2, every fourth column from t & 3): it keeps a sorted list
 // (KNN) or two counters (BALLS) over the whole sweep.  Columns past n_cols and the left-out column never reach a list or a counter.
+// KSUM stages nothing per tile: the lane that holds s_ij forms k = (gamma s + coef0)^3 in fp64 and adds it to the running sum of its row and column class
+// (one of 32 columns mod 32 of the wave's half tile), the tile's two accumulators and then the tiles in ascending order; after the sweep the 64 class sums of
+// a row go through LDS once and are added in a fixed order.  The order depends on the column range of the block alone, never on where the row sits in it.
 template <int MODE>
 __device__ __forceinline__ void sweep(const Operands& op, int splits, double* __restrict__ out_f64, const double* __restrict__ r2_rows,
-                                      const double* __restrict__ r2_cols, int* __restrict__ cnt_row_ball, int* __restrict__ cnt_col_ball)
+                                      const double* __restrict__ r2_cols, int* __restrict__ cnt_row_ball, int* __restrict__ cnt_col_ball,
+                                      double gamma = 0.0, double coef0 = 0.0)
 {
     __shared__ __attribute__((aligned(16))) unsigned char smem[LDS_BYTES];
     __shared__ double sNa[BM], sNb[BN], sR2c[BN];
@@ -133,7 +140,7 @@ __device__ __forceinline__ void sweep(const Operands& op, int splits, double* __
     const int crow = t >> 2, ccol = (t & 3) * 8;
     const bool oka = i0 + crow < op.n_rows;
     const __bf16* ga = op.a + (int64_t)(oka ? i0 + crow : 0) * d + ccol;
-    const int64_t a_plane = (int64_t)op.n_rows * d, b_plane = (int64_t)op.n_cols * d;
+    const int64_t a_plane = op.a_plane, b_plane = op.b_plane;
     bf16x8 ra[A_CHUNKS], rb[B_CHUNKS];
     const bf16x8 zero = {0, 0, 0, 0, 0, 0, 0, 0};
     int f_ct = ct0, f_kt = 0;                                // the tile the next fetch loads
@@ -154,7 +161,7 @@ __device__ __forceinline__ void sweep(const Operands& op, int splits, double* __
     const __bf16* pa = sA + ((w & 1) * 32 + fr) * LDS_ROW + fk;
     const __bf16* pb = sB + ((w >> 1) * 64 + fr) * LDS_ROW + fk;
 
-    if (t < BM) sNa[t] = i0 + t < op.n_rows ? op.na[i0 + t] : 0.0;      // published by the first barrier below
+    if (MODE != KSUM && t < BM) sNa[t] = i0 + t < op.n_rows ? op.na[i0 + t] : 0.0;      // published by the first barrier below
 
     f32x16 acc[2];
     double sum[2][16];
@@ -173,6 +180,9 @@ __device__ __forceinline__ void sweep(const Operands& op, int splits, double* __
     double my_r2 = 0.0;
     if (MODE == BALLS) my_r2 = (r2_rows && si < op.n_rows) ? r2_rows[si] : -INFINITY;
     const int64_t skip = op.self_offset >= 0 ? op.self_offset + si : -1;
+    double rsum[16];                                            // KSUM: register r's row, this lane's column class
+#pragma unroll
+    for (int r = 0; r < 16; ++r) rsum[r] = 0.0;
 
     if (ct0 < ct1) fetch();
     for (int ct = ct0; ct < ct1; ++ct) {
@@ -212,6 +222,23 @@ __device__ __forceinline__ void sweep(const Operands& op, int splits, double* __
 
         // ---- the column tile's epilogue ----
         const int64_t j0 = (int64_t)ct * BN;
+        if (MODE == KSUM) {
+#pragma unroll
+            for (int q = 0; q < 2; ++q) {
+                const int64_t j = j0 + (w >> 1) * 64 + q * 32 + (lane & 31);
+                // the left-out column of register r's row is self_offset + i0 + 32 (w & 1) + 4 (lane >> 5) + (r & 3) + 8 (r >> 2): compare what is left of j
+                const int64_t rel = op.self_offset >= 0 ? j - op.self_offset - i0 - (w & 1) * 32 - 4 * (lane >> 5) : -1;
+                const bool inside = j < op.n_cols;
+#pragma unroll
+                for (int r = 0; r < 16; ++r) {
+                    const double u = gamma * sum[q][r] + coef0;
+                    const double kv = u * u * u;
+                    sum[q][r] = 0.0;
+                    rsum[r] += (inside && rel != (r & 3) + 8 * (r >> 2)) ? kv : 0.0;
+                }
+            }
+            continue;
+        }
         if (t < BN) {
             const int64_t j = j0 + t;
             sNb[t] = j < op.n_cols ? op.nb[j] : INFINITY;
@@ -269,6 +296,18 @@ __device__ __forceinline__ void sweep(const Operands& op, int splits, double* __
             for (int s = 0; s < K_MAX; ++s) o[s] = L[s];
         }
     }
+    if (MODE == KSUM) {
+        __syncthreads();                                        // every wave is done with the operands in LDS
+#pragma unroll
+        for (int r = 0; r < 16; ++r) sD[((w & 1) * 32 + (r & 3) + 8 * (r >> 2) + 4 * (lane >> 5)) * STAGE_ROW + (w >> 1) * 32 + (lane & 31)] = rsum[r];
+        __syncthreads();
+        double v = 0.0;                                         // thread (row t >> 2, t & 3) adds every fourth class in ascending order, then a two-step tree
+#pragma unroll 4
+        for (int c = 0; c < STAGE_COLS / 4; ++c) v += sD[srow * STAGE_ROW + sc0 + 4 * c];
+        v += __shfl_xor(v, 1);
+        v += __shfl_xor(v, 2);
+        if (sc0 == 0 && si < op.n_rows) out_f64[(int64_t)blockIdx.x * op.n_rows + si] = v;
+    }
     if (MODE == BALLS) {
 #pragma unroll
         for (int step = 1; step <= 2; step <<= 1) {
@@ -299,6 +338,22 @@ __global__ __launch_bounds__(THREADS, 2) void k_prdc_balls(Operands op, int spli
 __global__ __launch_bounds__(THREADS, 2) void k_prdc_dist2(Operands op, double* __restrict__ d2_out)
 {
     sweep<DIST>(op, 1, d2_out, nullptr, nullptr, nullptr, nullptr);
+}
+
+// partial: [splits][n_rows], one sum per row and column split
+__global__ __launch_bounds__(THREADS, 2) void k_kid_sums(Operands op, int splits, double gamma, double coef0, double* __restrict__ partial)
+{
+    sweep<KSUM>(op, splits, partial, nullptr, nullptr, nullptr, nullptr, gamma, coef0);
+}
+
+// one thread per row: the splits' partial sums in ascending split order
+__global__ __launch_bounds__(THREADS) void k_kid_merge(const double* __restrict__ partial, int64_t n_rows, int splits, double* __restrict__ sums_out)
+{
+    const int64_t i = (int64_t)blockIdx.x * THREADS + threadIdx.x;
+    if (i >= n_rows) return;
+    double v = partial[i];
+    for (int sp = 1; sp < splits; ++sp) v += partial[(int64_t)sp * n_rows + i];
+    sums_out[i] = v;
 }
 
 // one thread per row: the k-th smallest of the splits' lists (a multiset: equal values count once each)

@@ -1,8 +1,10 @@
-// prdc.hip -- the k-nearest-neighbour manifold metrics' kernels (prdc.h) and their C ABI (include/natinf_prdc.h).
+// prdc.hip -- the k-nearest-neighbour manifold metrics' kernels (prdc.h) and their C ABI (include/natinf_prdc.h); the kernel-distance row sums on the same
+// sweep (include/natinf_kid.h).
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include "natinf.h"
 #include "natinf_prdc.h"
+#include "natinf_kid.h"
 
 namespace {
 #include "prdc.h"
@@ -44,9 +46,19 @@ inline prdc::Operands operands(const void* row_planes, const double* row_norms, 
                                int d, int64_t self_offset) {
     prdc::Operands op;
     op.a = (const __bf16*)row_planes; op.na = row_norms; op.b = (const __bf16*)col_planes; op.nb = col_norms;
+    op.a_plane = n_rows * d; op.b_plane = n_cols * d;
     op.n_rows = (int)n_rows; op.n_cols = (int)n_cols; op.d = d; op.self_offset = self_offset;
     return op;
 }
+
+// Column splits of the kernel sums: a function of n_cols alone.  An fp64 sum depends on where the column range is cut, so the cut must not move with the
+// number of rows of the call (splits_for's does).  Eight at the most: one column range per XCD, as the radius pass runs at 10,000 rows and more.
+constexpr int KID_MAX_SPLITS = MIN_SPLITS;
+inline int kid_splits(int64_t n_cols) {
+    const int64_t ctiles = (n_cols + prdc::BN - 1) / prdc::BN;
+    return (int)(ctiles < KID_MAX_SPLITS ? ctiles : KID_MAX_SPLITS);
+}
+inline bool stride_ok(int64_t stride, int64_t n, int d) { return stride % 8 == 0 && stride >= n * d; }
 }  // namespace
 
 extern "C" {
@@ -110,6 +122,33 @@ int natinf_prdc_debug_dist2(const void* row_planes, const double* row_norms, int
     const prdc::Operands op = operands(row_planes, row_norms, n_rows, col_planes, col_norms, n_cols, d, self_offset);
     const dim3 grid((unsigned)((n_cols + prdc::BN - 1) / prdc::BN), (unsigned)row_blocks(n_rows));
     hipLaunchKernelGGL(prdc::k_prdc_dist2, grid, dim3(prdc::THREADS), 0, (hipStream_t)stream, op, d2_out);
+    return launched();
+}
+
+int64_t natinf_kid_workspace_bytes(int64_t n_rows, int64_t n_cols, int d)
+{
+    if (!dims_ok(d, 1) || !count_ok(n_rows) || !count_ok(n_cols)) return NATINF_EINVAL;
+    return kid_splits(n_cols) * n_rows * (int64_t)sizeof(double);
+}
+
+int natinf_kid_row_sums(const void* row_planes, int64_t row_plane_stride, int64_t n_rows,
+                        const void* col_planes, int64_t col_plane_stride, int64_t n_cols,
+                        int d, int64_t self_offset, double gamma, double coef0,
+                        double* sums_out, void* workspace, int64_t workspace_bytes, natinf_stream_t stream)
+{
+    if (!aligned(row_planes, 16) || !aligned(col_planes, 16) || !dims_ok(d, 1) || !count_ok(n_rows) || !count_ok(n_cols) ||
+        !self_ok(self_offset, n_rows, n_cols) || (self_offset >= 0 && n_cols < 2))
+        return NATINF_EINVAL;
+    if (!stride_ok(row_plane_stride, n_rows, d) || !stride_ok(col_plane_stride, n_cols, d) || !isfinite(gamma) || !isfinite(coef0)) return NATINF_EINVAL;
+    if (!aligned(sums_out, 8) || !aligned(workspace, 256) || workspace_bytes < natinf_kid_workspace_bytes(n_rows, n_cols, d)) return NATINF_EINVAL;
+    prdc::Operands op = operands(row_planes, nullptr, n_rows, col_planes, nullptr, n_cols, d, self_offset);
+    op.a_plane = row_plane_stride; op.b_plane = col_plane_stride;
+    const int splits = kid_splits(n_cols);
+    hipStream_t s = (hipStream_t)stream;
+    hipLaunchKernelGGL(prdc::k_kid_sums, dim3(splits, (unsigned)row_blocks(n_rows)), dim3(prdc::THREADS), 0, s, op, splits, gamma, coef0, (double*)workspace);
+    if (launched() != NATINF_OK) return NATINF_ELAUNCH;
+    hipLaunchKernelGGL(prdc::k_kid_merge, dim3((unsigned)((n_rows + prdc::THREADS - 1) / prdc::THREADS)), dim3(prdc::THREADS), 0, s,
+                       (const double*)workspace, n_rows, splits, sums_out);
     return launched();
 }
 
