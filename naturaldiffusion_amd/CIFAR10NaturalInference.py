@@ -538,6 +538,46 @@ def calc_kid_sharded(imgs, ref_feats, device, group=None, model=None, estimator:
     return K.kid(FeatureSet(real, device=device), FeatureSet(feats, device=device), estimator=estimator, max_block_size=max_block_size, group=group)
 
 
+def fid_inception_head(device):
+    """The classifier head (``fc.weight``, ``fc.bias``: 1,008 classes on pool3) of the checkpoint ``fid_inception`` loads, as an ``iscore.ClassifierHead``
+    on ``device``.  The same file lookup, and without the file the same ``fid: blocked``."""
+    from .inception import load_fid_inception_head
+    from .iscore import ClassifierHead
+    path = inception_weights_path()
+    if not path.exists():
+        raise FileNotFoundError(f"fid: blocked -- Inception weights {path} missing (pytorch_fid's {INCEPTION_WEIGHTS}; set NATINF_INCEPTION_WEIGHTS)")
+    return ClassifierHead(*load_fid_inception_head(path), device=device)
+
+
+def _score_head(head, device, bias: bool):
+    head = head or fid_inception_head(device)
+    return head if bias else head.without_bias()
+
+
+def calc_is(imgs, device, model=None, head=None, splits: int = 1, bias: bool = True) -> dict:
+    """dict(is, std, log_is, splits, n) of the images (uint8 [n, H, W, 3]): the Inception Score of the reference's evaluation (its ``inception_score``
+    beside FID and KID), from the pool3 features ``calc_fid`` is computed from and the checkpoint's classifier head (iscore.py; include/natinf_is.h).
+    It needs no reference set.  ``head``: an ``iscore.ClassifierHead`` (default: ``fid_inception_head``, which raises ``fid: blocked`` without the file).
+
+    ``bias=True`` scores the graph's logits W a + b: TF-GAN's ``classifier_score_from_logits`` on the network's logits output, which the reference's
+    evaluation calls.  ``bias=False`` scores the bias-free logits W a: the original implementation of Salimans et al. multiplies pool3 by the weights of
+    ``softmax/logits/MatMul`` and never adds the bias, and torch-fidelity follows it (its ``logits_unbiased``).  ``splits=10`` is the protocol of
+    Salimans et al.: the mean and the population standard deviation of the scores of ten contiguous parts."""
+    from . import iscore as I
+    head = _score_head(head, device, bias)
+    model = model or fid_inception(device, tuple(imgs.shape[1:3]))
+    return I.inception_score(I.FeatureSet(get_features(imgs, model, device), device=device), head, splits=splits, group=I.LOCAL)
+
+
+def calc_is_sharded(imgs, device, group=None, model=None, head=None, splits: int = 1, bias: bool = True) -> dict:
+    """``calc_is`` for a batch-sharded run: every rank scores ITS images and keeps its features; only the integer class sums and one fp64 per image cross
+    ranks (``iscore.inception_score(..., group=group)``).  Every rank returns the same dict: that of one process on rank 0's images, then rank 1's, ..."""
+    from . import iscore as I
+    head = _score_head(head, device, bias)
+    model = model or fid_inception(device, tuple(imgs.shape[1:3]))
+    return I.inception_score(I.FeatureSet(get_features(imgs, model, device), device=device), head, splits=splits, group=group)
+
+
 class FidBlocked:
     """What ``natural_inference_tx(compute_fid=True)`` returns when the FID assets (Inception weights, ``cifar10_mu_sigma.npz``) are absent:
     the images it generated and the reason -- distinguishable from both a FID value (float) and the ``compute_fid=False`` result (a tensor)."""

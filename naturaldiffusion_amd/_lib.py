@@ -197,6 +197,9 @@ SIGNATURES = {
     # include/natinf_kid.h
     "natinf_kid_workspace_bytes": (C.c_int64, [_i64, _i64, _i32]),
     "natinf_kid_row_sums": (C.c_int, [_p, _i64, _i64, _p, _i64, _i64, _i32, _i64, _f64, _f64, _p, _p, _i64, _p]),
+    # include/natinf_is.h
+    "natinf_is_workspace_bytes": (C.c_int64, [_i64, _i32, _i32]),
+    "natinf_is_row_stats": (C.c_int, [_p, _i64, _i64, _p, _i64, _i32, _i32, _p, _p, _p, _p, _p, _p, _i64, _p]),
 }
 
 for _name, (_res, _args) in SIGNATURES.items():

@@ -7,6 +7,8 @@
 //   k_prdc_dist2   the same tiles written out (test hook)
 //   k_kid_sums     per row i the fp64 sum of (gamma a_i.b_j + coef0)^3 over a range of column tiles (include/natinf_kid.h)
 //   k_kid_merge    the partial sums of the column splits, added in ascending split order
+//   k_is_logits    the same tiles as z_ij = a_i.w_j + bias_j, written to a staging buffer (include/natinf_is.h)
+//   k_is_rows      per staged row its log-sum-exp, negative entropy and first largest class, and the rows' fixed-point class probabilities added per class
 //
 // d2_ij = max(0, (|a_i|^2 + |b_j|^2) - 2 a_i.b_j) in fp64.  a_i.b_j is six bf16 MFMA passes (lo.hi, hi.lo, mid.mid, mid.hi, hi.mid, hi.hi: the small
 // terms first; the three dropped products are below 2^-26 of |a_k b_k|) whose products are all exact in the fp32 accumulator; the accumulator is added
@@ -45,13 +47,13 @@ constexpr int OPERAND_BYTES = 3 * (BM + BN) * LDS_ROW * 2;
 constexpr int STAGE_BYTES = BM * STAGE_ROW * 8;
 constexpr int LDS_BYTES = OPERAND_BYTES > STAGE_BYTES ? OPERAND_BYTES : STAGE_BYTES;
 
-enum Mode { KNN = 0, BALLS = 1, DIST = 2, KSUM = 3 };
+enum Mode { KNN = 0, BALLS = 1, DIST = 2, KSUM = 3, LOGIT = 4 };
 
 struct Operands {
     const __bf16* a;        // [3][n_rows][d], plane p at a + p * a_plane
-    const double* na;       // [n_rows] (KSUM: not read)
+    const double* na;       // [n_rows] (KSUM, LOGIT: not read)
     const __bf16* b;        // [3][n_cols][d], plane p at b + p * b_plane
-    const double* nb;       // [n_cols] (KSUM: not read)
+    const double* nb;       // [n_cols] (KSUM, LOGIT: not read)
     int64_t a_plane, b_plane;   // elements between two planes: n * d for a whole set, the whole set's for a row range taken in place
     int n_rows, n_cols, d;
     int64_t self_offset;    // column self_offset + i is left out of row i; -1: none
@@ -117,10 +119,12 @@ __device__ __forceinline__ void list_insert(double (&L)[K_MAX], double v) {
 // KSUM stages nothing per tile: the lane that holds s_ij forms k = (gamma s + coef0)^3 in fp64 and adds it to the running sum of its row and column class
 // (one of 32 columns mod 32 of the wave's half tile), the tile's two accumulators and then the tiles in ascending order; after the sweep the 64 class sums of
 // a row go through LDS once and are added in a fixed order.  The order depends on the column range of the block alone, never on where the row sits in it.
+// LOGIT is DIST without the norms: the lane that holds s_ij writes z_ij = s_ij + bias[j] to row i of a staging buffer whose rows are whole tiles long
+// (ceil(n_cols / 128) * 128 doubles); columns past n_cols are not written.
 template <int MODE>
 __device__ __forceinline__ void sweep(const Operands& op, int splits, double* __restrict__ out_f64, const double* __restrict__ r2_rows,
                                       const double* __restrict__ r2_cols, int* __restrict__ cnt_row_ball, int* __restrict__ cnt_col_ball,
-                                      double gamma = 0.0, double coef0 = 0.0)
+                                      double gamma = 0.0, double coef0 = 0.0, const float* __restrict__ bias = nullptr)
 {
     __shared__ __attribute__((aligned(16))) unsigned char smem[LDS_BYTES];
     __shared__ double sNa[BM], sNb[BN], sR2c[BN];
@@ -132,8 +136,8 @@ __device__ __forceinline__ void sweep(const Operands& op, int splits, double* __
     const int i0 = blockIdx.y * BM;
     const int ktiles = op.d / BK;
     const int ctiles = (op.n_cols + BN - 1) / BN;
-    const int ct0 = MODE == DIST ? (int)blockIdx.x : (int)((int64_t)blockIdx.x * ctiles / splits);
-    const int ct1 = MODE == DIST ? ct0 + 1 : (int)((int64_t)(blockIdx.x + 1) * ctiles / splits);
+    const int ct0 = (MODE == DIST || MODE == LOGIT) ? (int)blockIdx.x : (int)((int64_t)blockIdx.x * ctiles / splits);
+    const int ct1 = (MODE == DIST || MODE == LOGIT) ? ct0 + 1 : (int)((int64_t)(blockIdx.x + 1) * ctiles / splits);
     const int64_t d = op.d;
 
     // this thread's chunks of a K tile: chunk c = t + 256 u is (row c >> 2, 16-byte column c & 3) of the stacked [3 * 64] (A) or [3 * 128] (B) rows
@@ -161,7 +165,7 @@ __device__ __forceinline__ void sweep(const Operands& op, int splits, double* __
     const __bf16* pa = sA + ((w & 1) * 32 + fr) * LDS_ROW + fk;
     const __bf16* pb = sB + ((w >> 1) * 64 + fr) * LDS_ROW + fk;
 
-    if (MODE != KSUM && t < BM) sNa[t] = i0 + t < op.n_rows ? op.na[i0 + t] : 0.0;      // published by the first barrier below
+    if (MODE != KSUM && MODE != LOGIT && t < BM) sNa[t] = i0 + t < op.n_rows ? op.na[i0 + t] : 0.0;      // published by the first barrier below
 
     f32x16 acc[2];
     double sum[2][16];
@@ -235,6 +239,23 @@ __device__ __forceinline__ void sweep(const Operands& op, int splits, double* __
                     const double kv = u * u * u;
                     sum[q][r] = 0.0;
                     rsum[r] += (inside && rel != (r & 3) + 8 * (r >> 2)) ? kv : 0.0;
+                }
+            }
+            continue;
+        }
+        if (MODE == LOGIT) {
+            const int64_t ldz = (int64_t)ctiles * BN;
+#pragma unroll
+            for (int q = 0; q < 2; ++q) {
+                const int64_t j = j0 + (w >> 1) * 64 + q * 32 + (lane & 31);
+                const bool inside = j < op.n_cols;
+                const double bj = (bias && inside) ? (double)bias[j] : 0.0;
+#pragma unroll
+                for (int r = 0; r < 16; ++r) {
+                    const int64_t i = (int64_t)i0 + (w & 1) * 32 + (r & 3) + 8 * (r >> 2) + 4 * (lane >> 5);
+                    const double z = sum[q][r] + bj;
+                    sum[q][r] = 0.0;
+                    if (inside && i < op.n_rows) out_f64[i * ldz + j] = z;
                 }
             }
             continue;
@@ -373,6 +394,76 @@ __global__ __launch_bounds__(THREADS) void k_prdc_merge(const double* __restrict
 #pragma unroll
     for (int s = 1; s < K_MAX; ++s) r = s == k - 1 ? L[s] : r;
     r2_out[i] = r;
+}
+
+// grid (column tiles, row blocks): z_out [n_rows][ceil(n_cols / 128) * 128], columns past n_cols not written
+__global__ __launch_bounds__(THREADS, 2) void k_is_logits(Operands op, const float* __restrict__ bias, double* __restrict__ z_out)
+{
+    sweep<LOGIT>(op, 1, z_out, nullptr, nullptr, nullptr, nullptr, 0.0, 0.0, bias);
+}
+
+constexpr int IS_ROWS = 32;             // rows per block of k_is_rows: eight per wave, one after the other
+constexpr int IS_MAX_CLASSES = 4096;
+constexpr double IS_ONE = 4398046511104.0;      // 2^42 (NATINF_IS_FRAC_BITS)
+
+// sum over the 64 lanes in a fixed tree; every lane returns the same bits
+__device__ __forceinline__ double wave_sum(double v) {
+#pragma unroll
+    for (int s = 1; s < 64; s <<= 1) v += __shfl_xor(v, s);
+    return v;
+}
+
+// Block b: rows [32 b, 32 b + 32) of the staged logits z [n_rows][ldz]; wave w takes rows 32 b + w, + 4, ...  One wave per row, lane l the classes
+// j = l, l + 64, ... in ascending order, three passes over the row (8 KB at 1,008 classes: the second and third are cache hits): the largest logit; the sum
+// of exp(z - m) and the lowest class at m; p = exp(z - lse), the sum of p (z - lse) and q = llrint(2^42 p).  Every sum is the lanes' strided partial sums
+// added in wave_sum's tree: a function of the row alone.  The q of the block's rows are added per class in LDS as integers (any order gives the same
+// total), then one integer atomicAdd per class with a non-zero total goes into class_sums.
+__global__ __launch_bounds__(THREADS) void k_is_rows(const double* __restrict__ z, int64_t ldz, int n_rows, int n_classes, double* __restrict__ neg_entropy,
+                                                     double* __restrict__ lse_out, int* __restrict__ top_out, unsigned long long* __restrict__ class_sums)
+{
+    __shared__ unsigned long long sQ[IS_MAX_CLASSES];
+    const int t = threadIdx.x, lane = t & 63, w = t >> 6;
+    for (int j = t; j < n_classes; j += THREADS) sQ[j] = 0ull;
+    __syncthreads();
+    for (int rr = w; rr < IS_ROWS; rr += THREADS / 64) {
+        const int64_t i = (int64_t)blockIdx.x * IS_ROWS + rr;
+        if (i >= n_rows) break;                                 // the wave's later rows lie further on
+        const double* zr = z + i * ldz;
+        double m = -INFINITY;
+        for (int j = lane; j < n_classes; j += 64) m = fmax(m, zr[j]);
+#pragma unroll
+        for (int s = 1; s < 64; s <<= 1) m = fmax(m, __shfl_xor(m, s));
+        double se = 0.0;
+        int top = n_classes;
+        for (int j = lane; j < n_classes; j += 64) {
+            const double v = zr[j];
+            se += exp(v - m);
+            top = (v == m && j < top) ? j : top;
+        }
+        se = wave_sum(se);
+#pragma unroll
+        for (int s = 1; s < 64; s <<= 1) top = min(top, __shfl_xor(top, s));
+        const double lse = m + log(se);
+        double h = 0.0;
+        for (int j = lane; j < n_classes; j += 64) {
+            const double lp = zr[j] - lse;
+            const double p = exp(lp);
+            h += p * lp;
+            const long long q = __double2ll_rn(p * IS_ONE);
+            if (q) atomicAdd(&sQ[j], (unsigned long long)q);
+        }
+        h = wave_sum(h);
+        if (lane == 0) {
+            neg_entropy[i] = h;
+            if (lse_out) lse_out[i] = lse;
+            if (top_out) top_out[i] = top;
+        }
+    }
+    __syncthreads();
+    for (int j = t; j < n_classes; j += THREADS) {
+        const unsigned long long v = sQ[j];
+        if (v) atomicAdd(class_sums + j, v);
+    }
 }
 
 }  // namespace prdc

@@ -1,10 +1,11 @@
 // prdc.hip -- the k-nearest-neighbour manifold metrics' kernels (prdc.h) and their C ABI (include/natinf_prdc.h); the kernel-distance row sums on the same
-// sweep (include/natinf_kid.h).
+// sweep (include/natinf_kid.h), and the Inception Score's row statistics on its logits (include/natinf_is.h).
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include "natinf.h"
 #include "natinf_prdc.h"
 #include "natinf_kid.h"
+#include "natinf_is.h"
 
 namespace {
 #include "prdc.h"
@@ -59,6 +60,8 @@ inline int kid_splits(int64_t n_cols) {
     return (int)(ctiles < KID_MAX_SPLITS ? ctiles : KID_MAX_SPLITS);
 }
 inline bool stride_ok(int64_t stride, int64_t n, int d) { return stride % 8 == 0 && stride >= n * d; }
+inline bool classes_ok(int n_classes) { return n_classes >= 1 && n_classes <= NATINF_IS_MAX_CLASSES; }
+inline int64_t staged_row(int n_classes) { return (int64_t)((n_classes + prdc::BN - 1) / prdc::BN) * prdc::BN; }     // doubles per row of staged logits
 }  // namespace
 
 extern "C" {
@@ -150,6 +153,40 @@ int natinf_kid_row_sums(const void* row_planes, int64_t row_plane_stride, int64_
     hipLaunchKernelGGL(prdc::k_kid_merge, dim3((unsigned)((n_rows + prdc::THREADS - 1) / prdc::THREADS)), dim3(prdc::THREADS), 0, s,
                        (const double*)workspace, n_rows, splits, sums_out);
     return launched();
+}
+
+int64_t natinf_is_workspace_bytes(int64_t n_rows, int n_classes, int d)
+{
+    if (!dims_ok(d, 1) || !count_ok(n_rows) || !classes_ok(n_classes)) return NATINF_EINVAL;
+    return (n_rows < NATINF_IS_CHUNK_ROWS ? n_rows : NATINF_IS_CHUNK_ROWS) * staged_row(n_classes) * (int64_t)sizeof(double);
+}
+
+int natinf_is_row_stats(const void* row_planes, int64_t row_plane_stride, int64_t n_rows,
+                        const void* head_planes, int64_t head_plane_stride, int n_classes, int d,
+                        const float* bias, double* neg_entropy_out, double* lse_out, int32_t* top_out, int64_t* class_sums,
+                        void* workspace, int64_t workspace_bytes, natinf_stream_t stream)
+{
+    if (!aligned(row_planes, 16) || !aligned(head_planes, 16) || !dims_ok(d, 1) || !count_ok(n_rows) || !classes_ok(n_classes)) return NATINF_EINVAL;
+    if (!stride_ok(row_plane_stride, n_rows, d) || !stride_ok(head_plane_stride, n_classes, d)) return NATINF_EINVAL;
+    if (!aligned(neg_entropy_out, 8) || !aligned(class_sums, 8) || ((uintptr_t)lse_out & 7) || ((uintptr_t)top_out & 3) || ((uintptr_t)bias & 3)) return NATINF_EINVAL;
+    if (!aligned(workspace, 256) || workspace_bytes < natinf_is_workspace_bytes(n_rows, n_classes, d)) return NATINF_EINVAL;
+    static_assert(prdc::IS_MAX_CLASSES == NATINF_IS_MAX_CLASSES && prdc::IS_ONE == (double)((int64_t)1 << NATINF_IS_FRAC_BITS), "natinf_is.h and prdc.h disagree");
+    const int64_t ldz = staged_row(n_classes);
+    hipStream_t s = (hipStream_t)stream;
+    // the rows in chunks through one staging buffer: a chunk's row statistics are enqueued behind its logits, the next chunk's logits behind those
+    for (int64_t r0 = 0; r0 < n_rows; r0 += NATINF_IS_CHUNK_ROWS) {
+        const int64_t nr = n_rows - r0 < NATINF_IS_CHUNK_ROWS ? n_rows - r0 : NATINF_IS_CHUNK_ROWS;
+        prdc::Operands op = operands((const __bf16*)row_planes + r0 * d, nullptr, nr, head_planes, nullptr, n_classes, d, -1);
+        op.a_plane = row_plane_stride; op.b_plane = head_plane_stride;
+        hipLaunchKernelGGL(prdc::k_is_logits, dim3((unsigned)(ldz / prdc::BN), (unsigned)row_blocks(nr)), dim3(prdc::THREADS), 0, s, op, bias,
+                           (double*)workspace);
+        if (launched() != NATINF_OK) return NATINF_ELAUNCH;
+        hipLaunchKernelGGL(prdc::k_is_rows, dim3((unsigned)((nr + prdc::IS_ROWS - 1) / prdc::IS_ROWS)), dim3(prdc::THREADS), 0, s, (const double*)workspace, ldz,
+                           (int)nr, n_classes, neg_entropy_out + r0, lse_out ? lse_out + r0 : nullptr, top_out ? (int*)top_out + r0 : nullptr,
+                           (unsigned long long*)class_sums);
+        if (launched() != NATINF_OK) return NATINF_ELAUNCH;
+    }
+    return NATINF_OK;
 }
 
 }  // extern "C"

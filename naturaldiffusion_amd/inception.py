@@ -88,6 +88,24 @@ def load_fid_inception_weights(path) -> torch.Tensor:
     return flatten_state_dict(torch.load(str(path), map_location="cpu", weights_only=True))
 
 
+def head_from_state_dict(sd: Dict[str, torch.Tensor]) -> Tuple[torch.Tensor, torch.Tensor]:
+    """(``fc.weight`` fp32 [1008, 2048], ``fc.bias`` fp32 [1008]) of a checkpoint's state dict: the classifier head behind pool3, which the pool3 engine
+    does not use.  A pytorch_fid ``InceptionV3(...).state_dict()`` has no head: a ``KeyError`` says so."""
+    missing = [k for k in ("fc.weight", "fc.bias") if k not in sd]
+    if missing:
+        raise KeyError(f"Inception weights: no classifier head ({', '.join(missing)} missing) -- the pt_inception checkpoint file holds it, "
+                       "a pytorch_fid InceptionV3(...).state_dict() does not")
+    w, b = sd["fc.weight"].detach().to(torch.float32), sd["fc.bias"].detach().to(torch.float32)
+    if w.dim() != 2 or tuple(b.shape) != (w.shape[0],):
+        raise ValueError(f"fc.weight / fc.bias: expected [classes, d] and [classes], got {tuple(w.shape)} and {tuple(b.shape)}")
+    return w.contiguous(), b.contiguous()
+
+
+def load_fid_inception_head(path) -> Tuple[torch.Tensor, torch.Tensor]:
+    """``pt_inception-2015-12-05-6726825d.pth`` -> (weight [1008, 2048], bias [1008]) of its classifier head (``iscore.ClassifierHead``)."""
+    return head_from_state_dict(torch.load(str(path), map_location="cpu", weights_only=True))
+
+
 class InceptionEngine:
     def __init__(self, flat_params: torch.Tensor, max_batch: int = 50, in_hw: Tuple[int, int] = (32, 32), device="cuda:0"):
         _lib.require_gpu()

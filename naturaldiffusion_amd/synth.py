@@ -111,6 +111,13 @@ def synthetic_inception_flat(seed: int = 0) -> torch.Tensor:
     return torch.cat(parts)
 
 
+def synthetic_inception_head(seed: int = 0, classes: int = 1008, d: int = 2048):
+    """Stand-in for the classifier head of the FID Inception checkpoint (``fc.weight``, ``fc.bias``): weights ~ N(0, 4 / d), bias ~ N(0, 0.25), so that
+    the logits of O(1) features are a few units apart.  The number it produces is not an Inception Score."""
+    g = torch.Generator().manual_seed(3000 + seed)
+    return torch.randn(classes, d, generator=g) * (2.0 / math.sqrt(d)), 0.5 * torch.randn(classes, generator=g)
+
+
 def synthetic_vae_flat(latent_ch: int = 4, seed: int = 0) -> torch.Tensor:
     """Stand-in AutoencoderKL decoder weights in ``vae.param_layout`` order behind an identity ``post_quant_conv``: norm scales 1,
     biases small, filters / matrices ~ N(0, 1 / fan_in)."""
