@@ -103,6 +103,26 @@ int natinf_dit_forward(natinf_dit_t h, const float* z, const float* t, const int
 int natinf_dit_attention_bf16(const void* q, const void* k, const void* v, int ld, void* o, int ld_o, int B, int T, int H,
                               int hd, int flags, natinf_stream_t stream);
 
+/* The row kernels of the transformer and VAE engines alone (tests): the engines' own launchers on caller-supplied operands.
+ *
+ * natinf_debug_ln_modulate: h[r][d] = LayerNorm(x[r])[d] * (1 + scale[b][d]) + shift[b][d], b = r / rows_per_sample (no affine,
+ * eps 1e-6, biased variance, fp32 statistics).  x: [rows][D] fp32, or IEEE half when x_f16 (read through the same pointer);
+ * shift / scale: row b at + b * mod_ld floats.  Exactly one output: h_bf16 [rows][D] bf16 (launch_ln_modulate), or h_fp8
+ * [rows][D] e4m3 bytes with row_scale [rows] (launch_ln_modulate_fp8: row_scale = max|h[r]| / 448, 1.0 for an all-zero
+ * row; bytes = e4m3(h / row_scale), round to nearest even, clamped to +-448).  *form_out: the kernel form the launcher chose,
+ * 0 scalar (any D, any alignment), 1 four columns per lane (D 256 / 1152 / 1536; D 256 / 1152 on the half stream), 2 eight
+ * columns per lane (D 1536 on the half stream); the vector forms need mod_ld % 4 == 0 and 16-byte aligned shift / scale.
+ * NATINF_EINVAL, nothing launched: a NULL x / shift / scale / form_out; both outputs or neither (h_fp8 and row_scale go
+ * together); D <= 0, D > 1536, D % 64 (fp8: D % 128); rows <= 0; rows_per_sample <= 0; mod_ld < D; x or the output not
+ * 16-byte aligned. */
+int natinf_debug_ln_modulate(const void* x, int x_f16, const float* shift, const float* scale, int mod_ld, void* h_bf16, void* h_fp8,
+                             float* row_scale, int D, int64_t rows, int rows_per_sample, int* form_out, natinf_stream_t stream);
+/* P[r] = softmax(S[r]): S fp32 [rows][T] -> P bf16 [rows][T], one wave per row, with the engines' grid and block.
+ * kind 0 k_softmax_rows (T <= 256, T % 4 == 0 or T == 16), 1 k_softmax_rows_1k (T % 64 == 0, T <= 1024), 2
+ * k_softmax_rows_wide (T % 64 == 0).  NATINF_EINVAL, nothing launched: a NULL S / P, kind outside 0..2, rows <= 0, T <= 0 or
+ * outside the kind's contract. */
+int natinf_debug_softmax_rows(int kind, const float* S, void* P, int T, int64_t rows, natinf_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -136,6 +136,8 @@ SIGNATURES = {
     "natinf_dit_stream_sites": (C.c_int, [_p]),
     "natinf_dit_stream_status_reset": (C.c_int, [_p, _p, _p]),
     "natinf_dit_stream_status": (C.c_int, [_p, _p, _p, _p]),
+    "natinf_debug_ln_modulate": (C.c_int, [_p, _i32, _p, _p, _i32, _p, _p, _p, _i32, _i64, _i32, C.POINTER(_i32), _p]),
+    "natinf_debug_softmax_rows": (C.c_int, [_i32, _p, _p, _i32, _i64, _p]),
     # include/natinf_mmdit.h
     "natinf_mmdit_create": (C.c_int, [C.POINTER(_p), _i32, _i32, _i32, _i32, _i32, _i32, _i32, _i32]),
     "natinf_mmdit_destroy": (C.c_int, [_p]),

@@ -222,22 +222,24 @@ __global__ __launch_bounds__(256) void k_ln_modulate_h8(const float* __restrict_
         out[64 * i] = __builtin_bit_cast(uint4, o);
     }
 }
-inline void launch_ln_modulate(const float* x, const float* shift, const float* scale, int mod_ld, bf16* h, int D, int64_t rows, int rows_per_sample,
-                               hipStream_t s, bool x_f16 = false)
+// Returns the form it launched -- 0 scalar, 1 four-column, 2 eight-column -- for natinf_debug_ln_modulate (tests/test_gpu_row_kernels.py); the engines ignore it.
+inline int launch_ln_modulate(const float* x, const float* shift, const float* scale, int mod_ld, bf16* h, int D, int64_t rows, int rows_per_sample,
+                              hipStream_t s, bool x_f16 = false)
 {
     const dim3 grid((unsigned)((rows + 3) / 4));
     const bool al = mod_ld % 4 == 0 && (reinterpret_cast<uintptr_t>(shift) | reinterpret_cast<uintptr_t>(scale)) % 16 == 0;
     if (x_f16) {                                                        // the MMDiT engine's 16-bit image stream
-        if (D == 1536 && al) hipLaunchKernelGGL(k_ln_modulate_h8<3>, grid, dim3(256), 0, s, x, shift, scale, mod_ld, h, rows, rows_per_sample);
-        else if (D == 256 && al) hipLaunchKernelGGL((k_ln_modulate_v4<1, 0, true>), grid, dim3(256), 0, s, x, shift, scale, mod_ld, h, rows, rows_per_sample);
-        else if (D == 1152 && al) hipLaunchKernelGGL((k_ln_modulate_v4<4, 128, true>), grid, dim3(256), 0, s, x, shift, scale, mod_ld, h, rows, rows_per_sample);      // DiT-XL/2
-        else hipLaunchKernelGGL(k_ln_modulate, grid, dim3(256), 0, s, x, shift, scale, mod_ld, h, D, rows, rows_per_sample, 1);
-        return;
+        if (D == 1536 && al) { hipLaunchKernelGGL(k_ln_modulate_h8<3>, grid, dim3(256), 0, s, x, shift, scale, mod_ld, h, rows, rows_per_sample); return 2; }
+        if (D == 256 && al) { hipLaunchKernelGGL((k_ln_modulate_v4<1, 0, true>), grid, dim3(256), 0, s, x, shift, scale, mod_ld, h, rows, rows_per_sample); return 1; }
+        if (D == 1152 && al) { hipLaunchKernelGGL((k_ln_modulate_v4<4, 128, true>), grid, dim3(256), 0, s, x, shift, scale, mod_ld, h, rows, rows_per_sample); return 1; }      // DiT-XL/2
+        hipLaunchKernelGGL(k_ln_modulate, grid, dim3(256), 0, s, x, shift, scale, mod_ld, h, D, rows, rows_per_sample, 1);
+        return 0;
     }
-    if (D == 1536 && al) hipLaunchKernelGGL(k_ln_modulate_v4<6>, grid, dim3(256), 0, s, x, shift, scale, mod_ld, h, rows, rows_per_sample);
-    else if (D == 256 && al) hipLaunchKernelGGL(k_ln_modulate_v4<1>, grid, dim3(256), 0, s, x, shift, scale, mod_ld, h, rows, rows_per_sample);
-    else if (D == 1152 && al) hipLaunchKernelGGL((k_ln_modulate_v4<4, 128>), grid, dim3(256), 0, s, x, shift, scale, mod_ld, h, rows, rows_per_sample);      // DiT-XL/2
-    else hipLaunchKernelGGL(k_ln_modulate, grid, dim3(256), 0, s, x, shift, scale, mod_ld, h, D, rows, rows_per_sample, 0);
+    if (D == 1536 && al) { hipLaunchKernelGGL(k_ln_modulate_v4<6>, grid, dim3(256), 0, s, x, shift, scale, mod_ld, h, rows, rows_per_sample); return 1; }
+    if (D == 256 && al) { hipLaunchKernelGGL(k_ln_modulate_v4<1>, grid, dim3(256), 0, s, x, shift, scale, mod_ld, h, rows, rows_per_sample); return 1; }
+    if (D == 1152 && al) { hipLaunchKernelGGL((k_ln_modulate_v4<4, 128>), grid, dim3(256), 0, s, x, shift, scale, mod_ld, h, rows, rows_per_sample); return 1; }      // DiT-XL/2
+    hipLaunchKernelGGL(k_ln_modulate, grid, dim3(256), 0, s, x, shift, scale, mod_ld, h, D, rows, rows_per_sample, 0);
+    return 0;
 }
 
 // out[n][c][gh*2+pi][gw*2+qi] = tok[n*g*g + gh*g+gw][(pi*2+qi)*OC + c]   (models.py:222-235)

@@ -293,22 +293,24 @@ __global__ __launch_bounds__(256) void k_ln_modulate_fp8_h8(const float* __restr
     for (int i = 0; i < NC8; ++i)
         out[64 * i] = make_uint2(pack_fp8x4(v[i][0] * inv, v[i][1] * inv, v[i][2] * inv, v[i][3] * inv), pack_fp8x4(v[i][4] * inv, v[i][5] * inv, v[i][6] * inv, v[i][7] * inv));
 }
-inline void launch_ln_modulate_fp8(const float* x, const float* shift, const float* scale, int mod_ld, uint8_t* h, float* row_scale, int D, int64_t rows,
-                                   int rows_per_sample, hipStream_t s, bool x_f16 = false)
+// Returns the form it launched -- 0 scalar, 1 four-column, 2 eight-column -- as launch_ln_modulate (dit_engine.inc); the engines ignore it.
+inline int launch_ln_modulate_fp8(const float* x, const float* shift, const float* scale, int mod_ld, uint8_t* h, float* row_scale, int D, int64_t rows,
+                                  int rows_per_sample, hipStream_t s, bool x_f16 = false)
 {
     const dim3 grid((unsigned)((rows + 3) / 4));
     const bool al = mod_ld % 4 == 0 && (reinterpret_cast<uintptr_t>(shift) | reinterpret_cast<uintptr_t>(scale)) % 16 == 0;
     if (x_f16) {
-        if (D == 1536 && al) hipLaunchKernelGGL(k_ln_modulate_fp8_h8<3>, grid, dim3(256), 0, s, x, shift, scale, mod_ld, h, row_scale, rows, rows_per_sample);
-        else if (D == 256 && al) hipLaunchKernelGGL((k_ln_modulate_fp8_v4<1, true>), grid, dim3(256), 0, s, x, shift, scale, mod_ld, h, row_scale, rows, rows_per_sample);
-        else if (D == 1152 && al) hipLaunchKernelGGL((k_ln_modulate_fp8_v4<4, true, 128>), grid, dim3(256), 0, s, x, shift, scale, mod_ld, h, row_scale, rows, rows_per_sample);      // DiT-XL/2
-        else hipLaunchKernelGGL(k_ln_modulate_fp8, grid, dim3(256), 0, s, x, shift, scale, mod_ld, h, row_scale, D, rows, rows_per_sample, 1);
-        return;
+        if (D == 1536 && al) { hipLaunchKernelGGL(k_ln_modulate_fp8_h8<3>, grid, dim3(256), 0, s, x, shift, scale, mod_ld, h, row_scale, rows, rows_per_sample); return 2; }
+        if (D == 256 && al) { hipLaunchKernelGGL((k_ln_modulate_fp8_v4<1, true>), grid, dim3(256), 0, s, x, shift, scale, mod_ld, h, row_scale, rows, rows_per_sample); return 1; }
+        if (D == 1152 && al) { hipLaunchKernelGGL((k_ln_modulate_fp8_v4<4, true, 128>), grid, dim3(256), 0, s, x, shift, scale, mod_ld, h, row_scale, rows, rows_per_sample); return 1; }      // DiT-XL/2
+        hipLaunchKernelGGL(k_ln_modulate_fp8, grid, dim3(256), 0, s, x, shift, scale, mod_ld, h, row_scale, D, rows, rows_per_sample, 1);
+        return 0;
     }
-    if (D == 1536 && al) hipLaunchKernelGGL(k_ln_modulate_fp8_v4<6>, grid, dim3(256), 0, s, x, shift, scale, mod_ld, h, row_scale, rows, rows_per_sample);
-    else if (D == 256 && al) hipLaunchKernelGGL(k_ln_modulate_fp8_v4<1>, grid, dim3(256), 0, s, x, shift, scale, mod_ld, h, row_scale, rows, rows_per_sample);
-    else if (D == 1152 && al) hipLaunchKernelGGL((k_ln_modulate_fp8_v4<4, false, 128>), grid, dim3(256), 0, s, x, shift, scale, mod_ld, h, row_scale, rows, rows_per_sample);      // DiT-XL/2
-    else hipLaunchKernelGGL(k_ln_modulate_fp8, grid, dim3(256), 0, s, x, shift, scale, mod_ld, h, row_scale, D, rows, rows_per_sample, 0);
+    if (D == 1536 && al) { hipLaunchKernelGGL(k_ln_modulate_fp8_v4<6>, grid, dim3(256), 0, s, x, shift, scale, mod_ld, h, row_scale, rows, rows_per_sample); return 1; }
+    if (D == 256 && al) { hipLaunchKernelGGL(k_ln_modulate_fp8_v4<1>, grid, dim3(256), 0, s, x, shift, scale, mod_ld, h, row_scale, rows, rows_per_sample); return 1; }
+    if (D == 1152 && al) { hipLaunchKernelGGL((k_ln_modulate_fp8_v4<4, false, 128>), grid, dim3(256), 0, s, x, shift, scale, mod_ld, h, row_scale, rows, rows_per_sample); return 1; }      // DiT-XL/2
+    hipLaunchKernelGGL(k_ln_modulate_fp8, grid, dim3(256), 0, s, x, shift, scale, mod_ld, h, row_scale, D, rows, rows_per_sample, 0);
+    return 0;
 }
 
 // weights: W fp32 [N][K] -> fp8 bytes [N][K] + one scale per output channel

@@ -516,4 +516,29 @@ int natinf_vae_encode(natinf_vae_enc_t h, const float* images, float* moments, f
     return natinf_vae_posterior_f32(mom, latents, B, h->Cl, hw, sample, scale, shift, seed, image_index, first_index, index_stride, stream);
 }
 
+// The row kernels of the transformer and VAE engines alone (include/natinf_dit.h; tests/test_gpu_row_kernels.py).  They sit here, after the last engine, because the three
+// softmax kernels live in three files.  Nothing but the engines' own launchers / launch shapes: no kernel is instantiated for these entries.
+int natinf_debug_ln_modulate(const void* x, int x_f16, const float* shift, const float* scale, int mod_ld, void* h_bf16, void* h_fp8, float* row_scale,
+                             int D, int64_t rows, int rows_per_sample, int* form_out, natinf_stream_t stream) {
+    const bool to_bf16 = h_bf16 != nullptr, to_fp8 = h_fp8 != nullptr || row_scale != nullptr;
+    if (!x || !shift || !scale || !form_out || to_bf16 == to_fp8 || (to_fp8 && (!h_fp8 || !row_scale))) return NATINF_EINVAL;
+    if (D <= 0 || D > 1536 || D % (to_fp8 ? 128 : 64) || rows <= 0 || rows_per_sample <= 0 || mod_ld < D) return NATINF_EINVAL;
+    if ((reinterpret_cast<uintptr_t>(x) | reinterpret_cast<uintptr_t>(to_bf16 ? h_bf16 : h_fp8)) % 16) return NATINF_EINVAL;
+    if (to_bf16) *form_out = launch_ln_modulate((const float*)x, shift, scale, mod_ld, (bf16*)h_bf16, D, rows, rows_per_sample, (hipStream_t)stream, x_f16 != 0);
+    else *form_out = launch_ln_modulate_fp8((const float*)x, shift, scale, mod_ld, (uint8_t*)h_fp8, row_scale, D, rows, rows_per_sample, (hipStream_t)stream, x_f16 != 0);
+    return hipGetLastError() == hipSuccess ? NATINF_OK : NATINF_ELAUNCH;
+}
+
+int natinf_debug_softmax_rows(int kind, const float* S, void* P, int T, int64_t rows, natinf_stream_t stream) {
+    if (!S || !P || T <= 0 || rows <= 0 || kind < 0 || kind > 2) return NATINF_EINVAL;
+    if (kind == 0 && (T > 256 || (T % 4 && T != 16))) return NATINF_EINVAL;      // the kernels' stated contracts
+    if (kind == 1 && (T % 64 || T > 1024)) return NATINF_EINVAL;
+    if (kind == 2 && T % 64) return NATINF_EINVAL;
+    const dim3 grid((unsigned)((rows + 3) / 4));                                 // one wave per row, as every engine launches them
+    if (kind == 0) hipLaunchKernelGGL(k_softmax_rows, grid, dim3(256), 0, (hipStream_t)stream, S, (bf16*)P, T, rows);
+    else if (kind == 1) hipLaunchKernelGGL(k_softmax_rows_1k, grid, dim3(256), 0, (hipStream_t)stream, S, (bf16*)P, T, rows);
+    else hipLaunchKernelGGL(k_softmax_rows_wide, grid, dim3(256), 0, (hipStream_t)stream, S, (bf16*)P, T, rows);
+    return hipGetLastError() == hipSuccess ? NATINF_OK : NATINF_ELAUNCH;
+}
+
 }  // extern "C"

@@ -234,6 +234,50 @@ def test_attention_block_hook_rejects_bad_arguments():
     assert call(plan=0, scratch=None) == -1 and call(plan=1, scratch=None) == -1      # (plan 2 needs no scratch)
 
 
+def test_ln_modulate_hook_rejects_bad_arguments():
+    """natinf_debug_ln_modulate (include/natinf_dit.h): every argument error is NATINF_EINVAL before anything is launched (there is no GPU here)."""
+    from naturaldiffusion_amd._lib import lib
+    d = 4096                                                # a non-NULL, 16-byte aligned dummy: never dereferenced by the argument check
+    form = C.c_int(-7)
+    names = ("x", "x_f16", "shift", "scale", "mod_ld", "h_bf16", "h_fp8", "row_scale", "D", "rows", "rows_per_sample", "form_out", "stream")
+    base = dict(x=d, x_f16=0, shift=d, scale=d, mod_ld=6 * 256, h_bf16=None, h_fp8=None, row_scale=None, D=256, rows=15, rows_per_sample=5, form_out=C.byref(form),
+                stream=None)
+    for out in (dict(h_bf16=d), dict(h_fp8=d, row_scale=d)):
+        call = lambda **kw: lib.natinf_debug_ln_modulate(*[{**base, **out, **kw}[n] for n in names])
+        for name in ("x", "shift", "scale", "form_out", *out):
+            assert call(**{name: None}) == -1, name
+        for D in (0, -64, 1536 + 128, 1600, 96, 257):
+            assert call(D=D, mod_ld=6 * 1600) == -1, D
+        for x_f16 in (0, 1):
+            assert call(rows=0, x_f16=x_f16) == -1 and call(rows=-3) == -1 and call(rows_per_sample=0) == -1 and call(rows_per_sample=-5) == -1
+        assert call(mod_ld=255) == -1 and call(mod_ld=0) == -1
+        assert call(x=d + 4) == -1 and call(x=d + 8) == -1 and call(**{next(iter(out)): d + 8}) == -1      # x, the output: 16-byte aligned
+    call = lambda **kw: lib.natinf_debug_ln_modulate(*[{**base, **kw}[n] for n in names])
+    assert call() == -1                                                                                     # neither output
+    assert call(h_bf16=d, h_fp8=d, row_scale=d) == -1 and call(h_bf16=d, h_fp8=d) == -1 and call(h_bf16=d, row_scale=d) == -1      # both
+    assert call(h_fp8=d) == -1 and call(row_scale=d) == -1                                                 # half of the fp8 pair
+    assert call(h_fp8=d, row_scale=d, D=64, mod_ld=384) == -1 and call(h_fp8=d, row_scale=d, D=192, mod_ld=6 * 192) == -1      # fp8: whole 128-column groups
+    assert form.value == -7                                                                                # a refusal leaves *form_out alone
+
+
+def test_softmax_rows_hook_rejects_bad_arguments():
+    """natinf_debug_softmax_rows (include/natinf_dit.h): NATINF_EINVAL outside each kernel's stated contract, before anything is launched."""
+    from naturaldiffusion_amd._lib import lib
+    d = 4096
+    call = lambda **kw: lib.natinf_debug_softmax_rows(*[{**dict(kind=0, S=d, P=d, T=64, rows=7, stream=None), **kw}[n] for n in ("kind", "S", "P", "T", "rows", "stream")])
+    for kind in (-1, 3):
+        assert call(kind=kind) == -1
+    for kind in (0, 1, 2):
+        assert call(kind=kind, S=None) == -1 and call(kind=kind, P=None) == -1 and call(kind=kind, rows=0) == -1 and call(kind=kind, rows=-1) == -1
+        assert call(kind=kind, T=0) == -1 and call(kind=kind, T=-64) == -1
+    for T in (260, 320, 1024, 18, 30, 255, 8 + 1):          # kind 0: T <= 256 and (T % 4 == 0 or T == 16)
+        assert call(kind=0, T=T) == -1, T
+    for T in (16, 100, 32, 1024 + 64, 4096):                # kind 1: T % 64 == 0 and T <= 1024
+        assert call(kind=1, T=T) == -1, T
+    for T in (16, 100, 1088 + 32, 4097):                    # kind 2: T % 64 == 0
+        assert call(kind=2, T=T) == -1, T
+
+
 def test_validation_grid_is_one_row_of_eight(tmp_path):
     """reference ValidateNaturalInference.py:236: save_image(samples, path, nrow=8, ...): 8 images -> 1 x 8."""
     import torch
