@@ -115,6 +115,10 @@ int natinf_debug_gemm_fp8(int M, int N, int K, const void* a8, const float* a_sc
  * natinf_debug_conv_gn calls take x at HALF the resolution ([B][res/2][res/2][cin]) and up-sample it (nearest, 2x) inside the patch fetch,
  * bit 1 = the same for the 1x1 shortcut operand a1.  0 restores the plain fetch. */
 int natinf_debug_conv_gn_up(int flags);
+/* Test hook for the GroupNorm table a producing tile writes for its consumer: the following natinf_debug_conv_gn calls (N = 256, res 16 / 8 / 4, gn_part given: the tiles that
+ * hold whole samples x every channel) also write fin_scale[b][n] = rstd * gamma[n] * mul and fin_shift[b][n] = (beta[n] - mean * rstd * gamma[n]) * mul, the statistics
+ * of sample b's output over groups of channels_per_group channels (eps 1e-6) -- what k_gn_finalize computes from the same partial sums.  fin_scale = NULL: off. */
+int natinf_debug_conv_gn_fin(float* fin_scale, float* fin_shift, const float* gamma, const float* beta, int channels_per_group, float mul);
 /* The fused GroupNorm-apply + SiLU + 3x3 convolution kernel (csrc/conv_gn2.h) on caller-supplied operands:
  *   out[m, n] = (sum_{tap, c} silu(x[pixel(m) + tap, c] * scale[b, c] + shift[b, c]) * w[n, c, tap] + sum_c a1[m, c] * w1[n, c]
  *                + bias_n[n] + resid[m, n]) * out_scale,  zero padding applied after the activation (layerspp.py:242-274).

@@ -117,6 +117,7 @@ SIGNATURES = {
     "natinf_debug_set_conv_operand": (C.c_int, [_i32, _p, _i32]),
     "natinf_debug_conv_gn": (C.c_int, [_i32, _i32, _i32, _i32, _i32, _p, _p, _p, _p, _p, _p, _p, _p, _f32, _p, _p, _i32, _p]),
     "natinf_debug_conv_gn_up": (C.c_int, [_i32]),
+    "natinf_debug_conv_gn_fin": (C.c_int, [_p, _p, _p, _p, _i32, _f32]),
     "natinf_debug_attn_block": (C.c_int, [_i32, _i32, _p, _i32, _p, _p, _p, _p, _p, _p, _p, _i32, _f32, _p, _p]),
     "natinf_ncsnpp_profile": (C.c_int, [_p, _i32]),
     "natinf_ncsnpp_profile_read": (C.c_int, [_p, C.POINTER(C.c_double), C.POINTER(C.c_int64)]),

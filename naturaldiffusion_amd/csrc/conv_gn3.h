@@ -356,7 +356,13 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
 #pragma unroll
     for (int i = 0; i < 8; ++i)
 #pragma unroll
-        for (int j = 0; j < 8; ++j) acc[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
+        for (int j = 0; j < 8; ++j) {
+            acc[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
+            // The empty statement makes the zeroed tile ONE definition.  As a bare constant hipcc re-materialises it on both sides of the guard of the
+            // two-half-chunk loop below: 256 v_accvgpr_write in front of the guard AND 256 in the loop's pre-header, which every launch with a0_C > 64
+            // runs through (round 8: ~1k clocks per tile with no MFMA under them).  Here, behind the prologue's requests, the writes run under their latency.
+            asm volatile("" : "+a"(acc[i][j]));
+        }
     NATINF_CG3_STAMP(1);
     // this wave's pieces of half-chunk 0, normalised in place as they land (requests retire in order: round r waits for everything up to its piece; no MFMAs
     // to hide behind yet, the arithmetic is left to hipcc to interleave)

@@ -1144,6 +1144,15 @@ int g_dbg_cg_up = 0;
 // bit 0: the next natinf_debug_conv_gn calls read x as [B][res/2][res/2][cin] through the kernel's nearest-2x up-sampling fetch (GemmArgs::a0_up);
 // bit 1: the same for a1 ([B*(res/2)^2][c1], GemmArgs::a1_up) -- the fetch paths of the up-sampling res-blocks (natinf_set_fuse_up)
 int natinf_debug_conv_gn_up(int flags) { if (flags & ~3) return NATINF_EINVAL; g_dbg_cg_up = flags; return NATINF_OK; }
+// the consumer's GroupNorm table from the producing tile (GemmArgs::fin_*; tests/test_gpu_gn_partials.py): the following natinf_debug_conv_gn calls pass these on -- the tiles
+// that hold whole samples x every channel (N = 256: k_conv_gn3 at 16x16, k_conv_gn2 at 8x8 / 4x4) then write fin_scale / fin_shift [B][N].  fin_scale = NULL: off again.
+float* g_dbg_fin_scale = nullptr; float* g_dbg_fin_shift = nullptr; const float* g_dbg_fin_gamma = nullptr; const float* g_dbg_fin_beta = nullptr;
+int g_dbg_fin_cg = 0; float g_dbg_fin_mul = 1.0f;
+int natinf_debug_conv_gn_fin(float* fin_scale, float* fin_shift, const float* gamma, const float* beta, int channels_per_group, float mul) {
+    if (fin_scale && (!fin_shift || !gamma || !beta || channels_per_group < 4 || channels_per_group % 4)) return NATINF_EINVAL;
+    g_dbg_fin_scale = fin_scale; g_dbg_fin_shift = fin_shift; g_dbg_fin_gamma = gamma; g_dbg_fin_beta = beta; g_dbg_fin_cg = channels_per_group; g_dbg_fin_mul = mul;
+    return NATINF_OK;
+}
 int natinf_debug_conv_gn(int res, int B, int N, int cin, int c1, const void* x, const float* scale, const float* shift, const void* w_packed,
                          void* w_frag, const void* a1, const float* bias_n, const void* resid, float out_scale, void* out, float* gn_part, int iters,
                          natinf_stream_t stream) {
@@ -1158,6 +1167,11 @@ int natinf_debug_conv_gn(int res, int B, int N, int cin, int c1, const void* x, 
     g.M = B * res * res; g.N = N; g.b = (const bf16*)w_packed; g.b_ld = 9 * cin + c1; g.bias_n = bias_n;
     g.resid = (const bf16*)resid; g.resid_ld = N; g.scale = out_scale; g.c = out; g.c_ld = N;
     g.gn_part = gn_part; g.gn_quads = N / 4;
+    if (g_dbg_fin_scale) {                                           // natinf_debug_conv_gn_fin
+        if (!gn_part || N != 256 || res > 16 || N % g_dbg_fin_cg) return NATINF_EINVAL;
+        g.fin_scale = g_dbg_fin_scale; g.fin_shift = g_dbg_fin_shift; g.fin_gamma = g_dbg_fin_gamma; g.fin_beta = g_dbg_fin_beta;
+        g.fin_ld = N; g.fin_cg = g_dbg_fin_cg; g.fin_mul = g_dbg_fin_mul; g.fin_eps = GN_EPS;
+    }
     g.dbg_ts = g_dbg_ts;
     g.a0_up = g_dbg_cg_up & 1; g.a1_up = (a1 && (g_dbg_cg_up & 2)) ? 1 : 0;      // natinf_debug_conv_gn_up: x / a1 are given at HALF the resolution
     if (w_frag && N % 16 == 0) g.b_frag = (const bf16*)w_frag;      // k_conv_gn2 (used when N is a whole number of its column tiles): w_frag receives the fragment-major copy
