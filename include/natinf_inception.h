@@ -44,6 +44,36 @@ int natinf_set_inception_conv(int mode);
 int natinf_debug_conv_ring(int tile, int f16, int B, int H, int W, int cin_p, int x_ld, int cout, int kh, int kw, int stride, int ph, int pw, int passes,
                            const void* x, const void* w_packed, const float* bias, const float* col_scale, const void* zeros, void* out, int out_ld,
                            natinf_stream_t stream);
+/* The engine's other kernels on caller-supplied DEVICE buffers (tests): each entry launches the production kernel through the function the plan itself calls,
+ * returns NATINF_EINVAL before anything is launched for an argument outside the contract stated here, and NATINF_ELAUNCH for a launch error.  16-bit means bf16
+ * (f16 = 0) or IEEE half (f16 = 1); every pointer is required unless stated and, where it is read or written 16 bytes at a time, 16-byte aligned (said per entry); every other pointer is aligned to its element (refused otherwise).
+ *
+ * k_inc_stem, on the plan's grid.  images: uint8 [B][H][W][3] (input_kind NATINF_INCEPTION_U8_HWC) or fp32 [B][3][H][W] (NATINF_INCEPTION_F32_CHW);
+ * out: 16-bit [B*149*149][row_width], 8-byte aligned: row (b*149 + oy)*149 + ox holds, at k = (ky*3 + kx)*3 + c, 2 r - 1 of pixel (2 oy + ky, 2 ox + kx) of the
+ * image resized to 299 x 299 (bilinear, align_corners = False; uint8 inputs / 255 first), and zeros at k = 27 .. row_width - 1.  1 <= H, W <= 4096 (the limit of
+ * natinf_inception_create), B >= 1 and B*149*149 < 2^31 (the limit of natinf_inception_forward), row_width 32 or 64, f16 0 or 1. */
+int natinf_debug_inc_stem(const void* images, int input_kind, int B, int H, int W, int f16, int row_width, void* out, natinf_stream_t stream);
+/* k_inc_pool<f16, mode, stride>: the 3 x 3 pool, mode 0 = max (padding never wins), 1 = average over the valid elements (count_include_pad = False).
+ * x: 16-bit [B][H][W][x_ld], channels 0 .. C-1 read; out: 16-bit [B*Ho*Wo][out_ld], channels 0 .. C-1 written, Ho = (H + 2 pad - 3) / stride + 1 (Wo alike).
+ * stride 1 or 2, pad 0 or 1, B >= 1, 1 <= H, W <= 65536, H + 2 pad >= 3 and W + 2 pad >= 3 (Ho, Wo >= 1), C >= 8, C % 8 == 0, x_ld and out_ld % 8 == 0 and >= C, x and out
+ * 16-byte aligned, B * Ho * (C / 8) (one thread each) < 2^32. */
+int natinf_debug_inc_pool(int f16, int mode, int stride, int pad, int B, int H, int W, int C, const void* x, int x_ld, void* out, int out_ld,
+                          natinf_stream_t stream);
+/* k_inc_global_avg: out[b][c] = mean over p of x[b][p][c]; x: 16-bit [B][HW][C] (no row padding), out: fp32 [B][C].  B, HW, C >= 1, B * C < 2^31. */
+int natinf_debug_inc_global_avg(int f16, int B, int HW, int C, const void* x, float* out, natinf_stream_t stream);
+/* The BatchNorm fold (eval, eps 1e-3) of one BasicConv2d: s[n] = gamma[n] / sqrt(var[n] + 1e-3), W'[n][(ky*kw + kx)*Cp + c] = w[n][c][ky][kx] * s[n],
+ * bias[n] = beta[n] - mean[n] * s[n]; zero for c >= C, for k >= kh*kw*Cp and in rows N .. Np-1 (bias too).  w: fp32 [N][C][kh][kw]; gamma, beta, mean, var: fp32 [N];
+ * bias: fp32 [Np].  f16 = 0: k_inc_pack, wp: bf16 [Np][2 Kp], columns [0, Kp) = bf16(W'), [Kp, 2 Kp) = bf16(W' - that); deq is not used (may be NULL).
+ * f16 = 1: k_inc_pack_f16 on a grid of Np rows, wp: half [Np][Kp] = half(W' / deq[n]), deq: fp32 [Np], the power of two that puts the row's largest magnitude in
+ * [0.5, 1) (1 for an all-zero row).  1 <= N <= Np, 1 <= C <= Cp, kh, kw >= 1, Kp >= kh*kw*Cp, Kp % 32 == 0, Np * 2 Kp < 2^31. */
+int natinf_debug_inc_pack(int f16, const float* w, const float* gamma, const float* beta, const float* mean, const float* var, int N, int Np, int C, int Cp,
+                          int kh, int kw, int Kp, void* wp, float* bias, float* deq, natinf_stream_t stream);
+/* k_inc_im2col (plan 0, the VAE encoder's and the `ddpm` plan's stride-2 convolutions): out[(b*Ho + oy)*Wo + ox][(ky*kw + kx)*C + c] =
+ * x[b][oy*stride - ph + ky][ox*stride - pw + kx][c], zero for padding taps and for k = kh*kw*C .. Kp-1; a copy of 16-bit words (either format).
+ * x: [B][H][W][ld], out: [B*Ho*Wo][Kp], both 16-byte aligned; B, kh, kw, stride >= 1, 1 <= H, W <= 65536, 0 <= ph, pw <= 4096, H + 2 ph >= kh and W + 2 pw >= kw (Ho, Wo >= 1),
+ * C >= 8, C % 8 == 0, ld % 8 == 0, ld >= C, Kp % 8 == 0, Kp >= kh*kw*C, B * Ho * Wo * (Kp / 8) (one thread each) < 2^31. */
+int natinf_debug_inc_im2col(int B, int H, int W, int ld, int C, int kh, int kw, int stride, int ph, int pw, int Kp, const void* x, void* out,
+                            natinf_stream_t stream);
 int64_t natinf_inception_param_count(natinf_inception_t h);
 int64_t natinf_inception_packed_bytes(natinf_inception_t h);
 int64_t natinf_inception_workspace_bytes(natinf_inception_t h, int max_batch);

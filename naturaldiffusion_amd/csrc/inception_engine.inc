@@ -241,6 +241,27 @@ __global__ __launch_bounds__(256) void k_inc_pack_f16(const float* __restrict__ 
     if (tid == 0) { bias[n] = n < N ? beta[n] - mean[n] * s : 0.f; deq[n] = scale; }
 }
 
+// The stem's and the pools' launches, as the plan (IncBuilder) and the debug entry points (natinf_debug_inc_stem / natinf_debug_inc_pool) both make them.
+// stem: blockIdx.y = (sample, output row), threads over (output column, 4-column slot of a patch row of row_width = 64 | 32 columns)
+inline void launch_inc_stem(const void* img, int is_u8, int H, int W, unsigned short* out, int B, int f16, int row_width, hipStream_t s) {
+    hipLaunchKernelGGL(k_inc_stem, dim3((unsigned)((149 * (row_width / 4) + 255) / 256), (unsigned)(B * 149)), dim3(256), 0, s, img, is_u8, H, W, out, B, f16,
+                       row_width == 64 ? 4 : 3);
+}
+// pool: one thread per (sample, output row, 8-channel chunk); the caller has checked that their number fits `unsigned`
+inline void launch_inc_pool(bool f16, int mode, int stride, int pad, int B, int H, int W, int C, const unsigned short* x, int x_ld, unsigned short* out, int out_ld,
+                            hipStream_t s) {
+    const int Ho = (H + 2 * pad - 3) / stride + 1, Wo = (W + 2 * pad - 3) / stride + 1;
+    const unsigned total = (unsigned)((int64_t)B * Ho * (C / 8));
+    auto go = [&](auto kern) {
+        hipLaunchKernelGGL(kern, dim3((unsigned)(((uint64_t)total + 255) / 256)), dim3(256), 0, s, x, H, W, x_ld, C, pad, Ho, Wo, out, out_ld, total);
+    };
+    const int sel = (f16 ? 4 : 0) + (mode ? 2 : 0) + (stride == 2 ? 1 : 0);
+    switch (sel) {
+        case 0: go(&k_inc_pool<0, 0, 1>); break;  case 1: go(&k_inc_pool<0, 0, 2>); break;  case 2: go(&k_inc_pool<0, 1, 1>); break;  case 3: go(&k_inc_pool<0, 1, 2>); break;
+        case 4: go(&k_inc_pool<1, 0, 1>); break;  case 5: go(&k_inc_pool<1, 0, 2>); break;  case 6: go(&k_inc_pool<1, 1, 1>); break;  default: go(&k_inc_pool<1, 1, 2>); break;
+    }
+}
+
 }  // namespace ncsn
 
 struct natinf_inception : EngineCore {
@@ -373,17 +394,8 @@ struct IncBuilder : PlanBuilder {
         const Ten xin = x;
         const bool h = f16;
         op([=](const Ctx& c) {
-            const unsigned total = (unsigned)((int64_t)c.B * Ho * (xin.C / 8));          // (one thread per sample, output row and 8-channel chunk)
-            const unsigned short* px = reinterpret_cast<const unsigned short*>(ptr_of(c, xin));
-            unsigned short* py = reinterpret_cast<unsigned short*>(ptr_of(c, y));
-            auto go = [&](auto kern) {
-                hipLaunchKernelGGL(kern, dim3((total + 255) / 256), dim3(256), 0, c.stream, px, xin.H, xin.W, xin.ld, xin.C, pad, Ho, Wo, py, y.ld, total);
-            };
-            const int sel = (h ? 4 : 0) + (mode ? 2 : 0) + (stride == 2 ? 1 : 0);
-            switch (sel) {
-                case 0: go(&k_inc_pool<0, 0, 1>); break;  case 1: go(&k_inc_pool<0, 0, 2>); break;  case 2: go(&k_inc_pool<0, 1, 1>); break;  case 3: go(&k_inc_pool<0, 1, 2>); break;
-                case 4: go(&k_inc_pool<1, 0, 1>); break;  case 5: go(&k_inc_pool<1, 0, 2>); break;  case 6: go(&k_inc_pool<1, 1, 1>); break;  default: go(&k_inc_pool<1, 1, 2>); break;
-            }
+            launch_inc_pool(h, mode, stride, pad, c.B, xin.H, xin.W, xin.C, reinterpret_cast<const unsigned short*>(ptr_of(c, xin)), xin.ld,
+                            reinterpret_cast<unsigned short*>(ptr_of(c, y)), y.ld, c.stream);
         });
         return y;
     }
@@ -469,8 +481,7 @@ struct IncBuilder : PlanBuilder {
             const int64_t zp = zero_page;
             op([=](const Ctx& c) {
                 const int64_t M = (int64_t)c.B * 149 * 149;
-                hipLaunchKernelGGL(k_inc_stem, dim3((unsigned)((149 * (kr / 4) + 255) / 256), (unsigned)(c.B * 149)), dim3(256), 0, c.stream, reinterpret_cast<const void*>(c.x), eng->input_u8, H, W,
-                                   c.at<unsigned short>(col), c.B, (int)h, kr == 64 ? 4 : 3);
+                launch_inc_stem(reinterpret_cast<const void*>(c.x), eng->input_u8, H, W, c.at<unsigned short>(col), c.B, (int)h, kr, c.stream);
                 // half-precision plan: the GEMM over the patch rows as a 1x1 "convolution" of k_conv_ring (32 channels per row: one K-tile, 256 x 64 tiles)
                 if (h) launch_conv(c, c.at<bf16>(col), kr, 149, 149, 149, 149, 1, 1, 1, 0, 0, kr, 32, p1a, ptr_of(c, y), y.ld, zp, true);
                 else gemm_relu(c, c.at<bf16>(col), 64, 64, M, p1a, 32, ptr_of(c, y), y.ld);
@@ -540,6 +551,55 @@ int natinf_debug_conv_ring(int tile, int f16, int B, int H, int W, int cin_p, in
         else if (tile == 1) launch_conv_ring<CfgC256x128>(&ncsn::k_conv_ring<2, 2, 8, 4, 3>, g, cv, s);
         else launch_conv_ring<CfgC128x128>(&ncsn::k_conv_ring<2, 2, 4, 4, 4>, g, cv, s);
     }
+    return hipGetLastError() == hipSuccess ? NATINF_OK : NATINF_ELAUNCH;
+}
+// the engine's other kernels on caller-supplied operands (tests): contracts in include/natinf_inception.h
+static inline bool inc_al16(const void* p) { return ((uintptr_t)p & 15) == 0; }
+int natinf_debug_inc_stem(const void* images, int input_kind, int B, int H, int W, int f16, int row_width, void* out, natinf_stream_t stream) {
+    if (!images || !out || ((uintptr_t)out & 7) || (input_kind != NATINF_INCEPTION_U8_HWC && input_kind != NATINF_INCEPTION_F32_CHW) || B <= 0 || H <= 0 || W <= 0 ||
+        H > 4096 || W > 4096 || (f16 != 0 && f16 != 1) || (row_width != 32 && row_width != 64) || (int64_t)B * 149 * 149 >= (1LL << 31)) return NATINF_EINVAL;
+    if (input_kind == NATINF_INCEPTION_F32_CHW && ((uintptr_t)images & 3)) return NATINF_EINVAL;
+    ncsn::launch_inc_stem(images, input_kind == NATINF_INCEPTION_U8_HWC, H, W, (unsigned short*)out, B, f16, row_width, (hipStream_t)stream);
+    return hipGetLastError() == hipSuccess ? NATINF_OK : NATINF_ELAUNCH;
+}
+int natinf_debug_inc_pool(int f16, int mode, int stride, int pad, int B, int H, int W, int C, const void* x, int x_ld, void* out, int out_ld,
+                          natinf_stream_t stream) {
+    if (!x || !out || !inc_al16(x) || !inc_al16(out) || (f16 != 0 && f16 != 1) || (mode != 0 && mode != 1) || (stride != 1 && stride != 2) || (pad != 0 && pad != 1) ||
+        B <= 0 || H <= 0 || W <= 0 || H > 65536 || W > 65536 || H + 2 * pad < 3 || W + 2 * pad < 3 || C < 8 || C % 8 || x_ld < C || x_ld % 8 || out_ld < C || out_ld % 8) return NATINF_EINVAL;
+    const int Ho = (H + 2 * pad - 3) / stride + 1;
+    if ((int64_t)B * Ho * (C / 8) >= (1LL << 32)) return NATINF_EINVAL;
+    ncsn::launch_inc_pool(f16 != 0, mode, stride, pad, B, H, W, C, (const unsigned short*)x, x_ld, (unsigned short*)out, out_ld, (hipStream_t)stream);
+    return hipGetLastError() == hipSuccess ? NATINF_OK : NATINF_ELAUNCH;
+}
+int natinf_debug_inc_global_avg(int f16, int B, int HW, int C, const void* x, float* out, natinf_stream_t stream) {
+    if (!x || !out || ((uintptr_t)x & 1) || ((uintptr_t)out & 3) || (f16 != 0 && f16 != 1) || B <= 0 || HW <= 0 || C <= 0 || (int64_t)B * C >= (1LL << 31))
+        return NATINF_EINVAL;
+    const int64_t total = (int64_t)B * C;
+    hipLaunchKernelGGL(ncsn::k_inc_global_avg, dim3(grid1d(total, 256, 1 << 30)), dim3(256), 0, (hipStream_t)stream, (const unsigned short*)x, HW, C, out, total, f16);
+    return hipGetLastError() == hipSuccess ? NATINF_OK : NATINF_ELAUNCH;
+}
+int natinf_debug_inc_pack(int f16, const float* w, const float* gamma, const float* beta, const float* mean, const float* var, int N, int Np, int C, int Cp,
+                          int kh, int kw, int Kp, void* wp, float* bias, float* deq, natinf_stream_t stream) {
+    if (!w || !gamma || !beta || !mean || !var || !wp || !bias || (f16 != 0 && f16 != 1) || (f16 && !deq) || N <= 0 || Np < N || C <= 0 || Cp < C || kh <= 0 || kw <= 0 ||
+        Kp <= 0 || Kp % 32 || (int64_t)kh * kw * Cp > Kp || (int64_t)Np * 2 * Kp >= (1LL << 31)) return NATINF_EINVAL;
+    if (((uintptr_t)w | (uintptr_t)gamma | (uintptr_t)beta | (uintptr_t)mean | (uintptr_t)var | (uintptr_t)bias | (uintptr_t)deq) & 3 || ((uintptr_t)wp & 1))
+        return NATINF_EINVAL;
+    hipStream_t s = (hipStream_t)stream;
+    if (f16) hipLaunchKernelGGL(ncsn::k_inc_pack_f16, dim3(Np), dim3(256), 0, s, w, gamma, beta, mean, var, N, C, Cp, kh, kw, Kp, (_Float16*)wp, bias, deq);
+    else hipLaunchKernelGGL(ncsn::k_inc_pack, dim3(grid1d((int64_t)Np * Kp, 256, 1 << 30)), dim3(256), 0, s, w, gamma, beta, mean, var, N, Np, C, Cp, kh, kw, Kp, (bf16*)wp,
+                            bias);
+    return hipGetLastError() == hipSuccess ? NATINF_OK : NATINF_ELAUNCH;
+}
+int natinf_debug_inc_im2col(int B, int H, int W, int ld, int C, int kh, int kw, int stride, int ph, int pw, int Kp, const void* x, void* out,
+                            natinf_stream_t stream) {
+    if (!x || !out || !inc_al16(x) || !inc_al16(out) || B <= 0 || H <= 0 || W <= 0 || H > 65536 || W > 65536 || kh <= 0 || kw <= 0 || stride <= 0 || ph < 0 || pw < 0 || C < 8 || C % 8 ||
+        ld < C || ld % 8 || Kp <= 0 || Kp % 8 || (int64_t)kh * kw * C > Kp || (int64_t)H + 2 * (int64_t)ph < kh || (int64_t)W + 2 * (int64_t)pw < kw ||
+        ph > 4096 || pw > 4096) return NATINF_EINVAL;
+    const int Ho = (H + 2 * ph - kh) / stride + 1, Wo = (W + 2 * pw - kw) / stride + 1;
+    if ((double)B * Ho * Wo * (Kp / 8) >= 2147483648.0) return NATINF_EINVAL;
+    const int64_t total = (int64_t)B * Ho * Wo * (Kp / 8);
+    hipLaunchKernelGGL(ncsn::k_inc_im2col, dim3(grid1d(total, 256, 1 << 30)), dim3(256), 0, (hipStream_t)stream, (const bf16*)x, H, W, ld, C, kh, kw, stride, ph, pw,
+                       Ho, Wo, Kp, (bf16*)out, total);
     return hipGetLastError() == hipSuccess ? NATINF_OK : NATINF_ELAUNCH;
 }
 int natinf_set_inception_conv(int mode) { if (mode < 0 || mode > 2) return NATINF_EINVAL; g_inc_conv = mode; return NATINF_OK; }

@@ -278,6 +278,55 @@ def test_softmax_rows_hook_rejects_bad_arguments():
         assert call(kind=2, T=T) == -1, T
 
 
+def test_inception_kernel_hooks_reject_bad_arguments():
+    """natinf_debug_inc_stem / _pool / _global_avg / _pack / _im2col (include/natinf_inception.h): NATINF_EINVAL outside each stated contract, before anything is
+    launched (there is no GPU here)."""
+    from naturaldiffusion_amd._lib import lib
+    d = 4096                                                # a non-NULL, 16-byte aligned dummy: never dereferenced by the argument check
+
+    def caller(fn, names, base):
+        return lambda **kw: fn(*[{**base, **kw}[n] for n in names])
+
+    call = caller(lib.natinf_debug_inc_stem, ("images", "input_kind", "B", "H", "W", "f16", "row_width", "out", "stream"),
+                  dict(images=d, input_kind=0, B=2, H=32, W=32, f16=1, row_width=32, out=d, stream=None))
+    assert call(images=None) == -1 and call(out=None) == -1 and call(out=d + 4) == -1 and call(input_kind=1, images=d + 2) == -1
+    for bad in (dict(input_kind=-1), dict(input_kind=2), dict(B=0), dict(B=-1), dict(H=0), dict(W=0), dict(H=-5), dict(H=4097), dict(W=4097), dict(f16=2), dict(f16=-1),
+                dict(row_width=0), dict(row_width=16), dict(row_width=48), dict(row_width=128), dict(B=(1 << 31) // (149 * 149) + 1)):
+        assert call(**bad) == -1, bad
+
+    call = caller(lib.natinf_debug_inc_pool, ("f16", "mode", "stride", "pad", "B", "H", "W", "C", "x", "x_ld", "out", "out_ld", "stream"),
+                  dict(f16=0, mode=1, stride=1, pad=1, B=2, H=8, W=8, C=72, x=d, x_ld=80, out=d, out_ld=80, stream=None))
+    assert call(x=None) == -1 and call(out=None) == -1 and call(x=d + 8) == -1 and call(out=d + 8) == -1
+    for bad in (dict(f16=2), dict(mode=2), dict(mode=-1), dict(stride=0), dict(stride=3), dict(pad=-1), dict(pad=2), dict(B=0), dict(H=0), dict(W=0), dict(H=65537),
+                dict(C=0), dict(C=4), dict(C=76), dict(x_ld=64), dict(x_ld=76), dict(out_ld=64), dict(out_ld=84),
+                dict(pad=0, H=2), dict(pad=0, W=2), dict(pad=0, H=1, stride=2), dict(pad=0, W=1, stride=2),          # Ho / Wo < 1 (1 - 3 rounds toward zero in C)
+                dict(B=1 << 20, H=65536, C=8 * 64, x_ld=512, out_ld=512)):                                           # 2^42 threads
+        assert call(**bad) == -1, bad
+
+    call = caller(lib.natinf_debug_inc_global_avg, ("f16", "B", "HW", "C", "x", "out", "stream"), dict(f16=0, B=2, HW=64, C=2048, x=d, out=d, stream=None))
+    for bad in (dict(x=None), dict(out=None), dict(x=d + 1), dict(out=d + 2), dict(f16=2), dict(B=0), dict(HW=0), dict(C=0), dict(B=-1), dict(HW=-64), dict(C=-8),
+                dict(B=1 << 16, C=1 << 15)):
+        assert call(**bad) == -1, bad
+
+    names = ("f16", "w", "gamma", "beta", "mean", "var", "N", "Np", "C", "Cp", "kh", "kw", "Kp", "wp", "bias", "deq", "stream")
+    base = dict(f16=0, w=d, gamma=d, beta=d, mean=d, var=d, N=48, Np=64, C=40, Cp=64, kh=1, kw=7, Kp=448, wp=d, bias=d, deq=None, stream=None)
+    for f16 in (0, 1):
+        call = caller(lib.natinf_debug_inc_pack, names, {**base, "f16": f16, "deq": d if f16 else None})
+        for name in ("w", "gamma", "beta", "mean", "var", "wp", "bias"):
+            assert call(**{name: None}) == -1, name
+        for bad in (dict(f16=2), dict(N=0), dict(Np=47), dict(C=0), dict(Cp=39), dict(kh=0), dict(kw=0), dict(Kp=0), dict(Kp=447), dict(Kp=416), dict(Kp=440),
+                    dict(w=d + 2), dict(bias=d + 2), dict(wp=d + 1), dict(Np=1 << 20, Kp=1 << 11)):
+            assert call(**bad) == -1, bad
+    assert call(deq=None) == -1 and call(deq=d + 2) == -1                                                 # the half pack needs its scales
+
+    call = caller(lib.natinf_debug_inc_im2col, ("B", "H", "W", "ld", "C", "kh", "kw", "stride", "ph", "pw", "Kp", "x", "out", "stream"),
+                  dict(B=2, H=17, W=17, ld=128, C=128, kh=3, kw=3, stride=2, ph=0, pw=0, Kp=1152, x=d, out=d, stream=None))
+    for bad in (dict(x=None), dict(out=None), dict(x=d + 8), dict(out=d + 8), dict(B=0), dict(H=0), dict(W=0), dict(H=65537), dict(kh=0), dict(kw=0), dict(stride=0),
+                dict(ph=-1), dict(pw=-1), dict(ph=4097), dict(C=0), dict(C=4), dict(C=124), dict(ld=120), dict(ld=132), dict(Kp=1144), dict(Kp=1156), dict(Kp=0),
+                dict(H=2), dict(W=2), dict(H=1, stride=4), dict(B=1 << 14, H=1025, W=1025, stride=1)):
+        assert call(**bad) == -1, bad
+
+
 def test_validation_grid_is_one_row_of_eight(tmp_path):
     """reference ValidateNaturalInference.py:236: save_image(samples, path, nrow=8, ...): 8 images -> 1 x 8."""
     import torch
