@@ -290,6 +290,41 @@ int natinf_gemm_profile_read(char* buf, int cap);
 int natinf_ncsnpp_debug_tap(natinf_ncsnpp_t h, int module_idx, float* out, int64_t capacity_elems,
                             natinf_stream_t stream);
 
+/* The GroupNorm, output-head and glue kernels ALONE, on caller-supplied device buffers, with the grid and block expressions of the plans' own launches
+ * (tests/test_gpu_gn_kernels.py).  Tables are fp32 [B][C]; activations bf16 NHWC with pixel stride ld (>= C, % 8 == 0).  Each entry answers NATINF_EINVAL, nothing
+ * launched, outside the preconditions stated with it -- the ones its kernel leaves to the caller; no plan of the library launches outside them (k_time_embed's grid, which
+ * the plan capped at 4096 blocks -- samples 8192.. of a larger batch kept unwritten embeddings --, now covers every B the forward accepts).
+ *
+ * natinf_debug_gn_stats (k_gn_stats): scale[b][c] = rstd gamma[c] out_mul, shift[b][c] = (beta[c] - mean rstd gamma[c]) out_mul over 32 groups of C / 32 channels x HW
+ *   pixels of x [B][HW][ld], biased variance.  C % 32 == 0, 32 <= C <= 512 (s_sum[512]; (256 / (C / 8)) C <= 2112 floats of s_part), x 16-byte aligned.
+ * natinf_debug_gn_finalize (k_gn_finalize): the same table from (sum, sum of squares) per tile and 4-channel quad, P0 float2 [B][tps0][quads0] followed channel-wise by P1
+ *   [B][tps1][quads1] (NULL with tps1 = quads1 = 0: one source).  C % 128 == 0 (a group is a whole number of quads), C <= 512, 4 (quads0 + quads1) == C (<= 128 quads).
+ * natinf_debug_gn_fold (k_gn_fold): P float2 [B][tps][quads] -> out [B][tps / fold][quads], sums of `fold` consecutive tiles.  256 % quads == 0, tps % fold == 0.
+ * natinf_debug_gn_apply (k_gn_apply): y = act(x scale + shift) (act 0 none, 1 SiLU), mode 0 plain / 1 nearest 2x up / 2 mean 2x2 down, x [B][H][W][ld] with W = 1 << logW,
+ *   H = 1 << (logHW - logW); y [B][Hd + 2 pad][Wd + 2 pad][C] with a zero border (pad 0 / 1); xr NULL or [B][Hd][Wd][C], the raw input resampled the same way.
+ *   C % 8 == 0, C / 8 <= 256, B <= 65535, x / y / xr / scale / shift 16-byte aligned, mode 2 needs H, W >= 2.
+ * natinf_debug_head_conv (k_head_conv): out fp32 [B][3][32][32] = conv3x3(g(x scale + shift)) + bias, g(t) = t / (1 + 2^t), x [B][32][32][ld] (ld >= 128), tables [B][128]
+ *   FOLDED (times -log2 e), w16 bf16 [16][1152] in K order ((c / 64) 9 + tap) 64 + c % 64 (times -ln 2; rows 3..15 feed columns that are never stored), bias [3].
+ * natinf_debug_time_embed (k_time_embed): emb bf16 [B][128] = sin | cos (labels[b] exp(-h ln 10000 / 63)), h = 0..63.  B < 2^21, natinf_ncsnpp_forward's own limit.
+ * natinf_debug_stem_im2col (k_stem_im2col): x fp32 [B][3][32][32] -> A bf16 [B 1024][64], column tap 3 + c (27 used, the rest zero).
+ * natinf_debug_pack_conv (k_pack_conv): src fp32 [N][Cin][taps] -> dst[n dst_ld + koff + k] = bf16(src wmul), k = tap tap_stride_c + c (chunked 0, tap_stride_c >= Cin)
+ *   or ((c / 64) taps + tap) 64 + c % 64 (chunked 1); the last column addressed must lie inside dst_ld.
+ * natinf_debug_pack_transpose (k_pack_transpose): src fp32 [K][N] -> dst[n dst_ld + k], dst_ld >= K.
+ * natinf_debug_nhwc_to_nchw (k_nhwc_to_nchw_f32): x bf16 [B][HW][ld] -> out fp32 [B][C][HW]. */
+int natinf_debug_gn_stats(const void* x, int ld, int C, int HW, int B, const float* gamma, const float* beta, float* scale, float* shift, float eps, float out_mul,
+                          natinf_stream_t stream);
+int natinf_debug_gn_finalize(const float* P0, int tps0, int quads0, const float* P1, int tps1, int quads1, int C, int HW, int B, const float* gamma, const float* beta,
+                             float* scale, float* shift, float eps, float out_mul, natinf_stream_t stream);
+int natinf_debug_gn_fold(const float* P, int tps, int quads, int fold, int B, float* out, natinf_stream_t stream);
+int natinf_debug_gn_apply(const void* x, int ld, int C, int logW, int logHW, int B, const float* scale, const float* shift, void* y, void* xr, int act, int mode, int pad,
+                          natinf_stream_t stream);
+int natinf_debug_head_conv(const void* x, int ld, int B, const float* scale, const float* shift, const void* w16, const float* bias, float* out, natinf_stream_t stream);
+int natinf_debug_time_embed(const float* labels, void* emb, int B, natinf_stream_t stream);
+int natinf_debug_stem_im2col(const float* x, void* A, int B, natinf_stream_t stream);
+int natinf_debug_pack_conv(const float* src, void* dst, int N, int Cin, int taps, int dst_ld, int koff, int tap_stride_c, int chunked, float wmul, natinf_stream_t stream);
+int natinf_debug_pack_transpose(const float* src, void* dst, int K, int N, int dst_ld, natinf_stream_t stream);
+int natinf_debug_nhwc_to_nchw(const void* x, int ld, int C, int HW, int B, float* out, natinf_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

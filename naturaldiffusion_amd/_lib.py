@@ -119,6 +119,16 @@ SIGNATURES = {
     "natinf_debug_conv_gn_up": (C.c_int, [_i32]),
     "natinf_debug_conv_gn_fin": (C.c_int, [_p, _p, _p, _p, _i32, _f32]),
     "natinf_debug_attn_block": (C.c_int, [_i32, _i32, _p, _i32, _p, _p, _p, _p, _p, _p, _p, _i32, _f32, _p, _p]),
+    "natinf_debug_gn_stats": (C.c_int, [_p, _i32, _i32, _i32, _i32, _p, _p, _p, _p, _f32, _f32, _p]),
+    "natinf_debug_gn_finalize": (C.c_int, [_p, _i32, _i32, _p, _i32, _i32, _i32, _i32, _i32, _p, _p, _p, _p, _f32, _f32, _p]),
+    "natinf_debug_gn_fold": (C.c_int, [_p, _i32, _i32, _i32, _i32, _p, _p]),
+    "natinf_debug_gn_apply": (C.c_int, [_p, _i32, _i32, _i32, _i32, _i32, _p, _p, _p, _p, _i32, _i32, _i32, _p]),
+    "natinf_debug_head_conv": (C.c_int, [_p, _i32, _i32, _p, _p, _p, _p, _p, _p]),
+    "natinf_debug_time_embed": (C.c_int, [_p, _p, _i32, _p]),
+    "natinf_debug_stem_im2col": (C.c_int, [_p, _p, _i32, _p]),
+    "natinf_debug_pack_conv": (C.c_int, [_p, _p, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _f32, _p]),
+    "natinf_debug_pack_transpose": (C.c_int, [_p, _p, _i32, _i32, _i32, _p]),
+    "natinf_debug_nhwc_to_nchw": (C.c_int, [_p, _i32, _i32, _i32, _i32, _p, _p]),
     "natinf_ncsnpp_profile": (C.c_int, [_p, _i32]),
     "natinf_ncsnpp_profile_read": (C.c_int, [_p, C.POINTER(C.c_double), C.POINTER(C.c_int64)]),
     "natinf_debug_quant_fp8_rows": (C.c_int, [_p, _p, _p, _i32, _i32, _p]),

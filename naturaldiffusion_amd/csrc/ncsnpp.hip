@@ -737,7 +737,8 @@ struct Builder : PlanBuilder {        // (wtop: the packed-weight bump pointer i
             const int64_t b0 = pack_f32(pb0, TEMB), b1 = pack_f32(pb1, TEMB);
             const int64_t dw = dense_w, db = dense_b, dout = dense_out; const int dtot = dense_total;
             op(CLS_OTHER, [=](const Ctx& c) {
-                hipLaunchKernelGGL(k_time_embed, dim3(grid1d((int64_t)c.B * 128)), dim3(256), 0, c.stream, c.labels, c.at<bf16>(emb), c.B);
+                // one thread per element and no grid stride: the grid must cover B * 128 (grid1d's default cap of 4096 blocks left samples 8192.. unwritten)
+                hipLaunchKernelGGL(k_time_embed, dim3(grid1d((int64_t)c.B * 128, 256, 1 << 30)), dim3(256), 0, c.stream, c.labels, c.at<bf16>(emb), c.B);
             });
             op(CLS_GEMM, [=](const Ctx& c) {
                 GemmArgs g = gemm_defaults();                        // act(Linear_0(emb))
@@ -1381,6 +1382,93 @@ int natinf_ncsnpp_debug_tap(natinf_ncsnpp_t h, int module_idx, float* out, int64
     if (capacity_elems < total) return NATINF_EINVAL;
     const bf16* src = reinterpret_cast<const bf16*>(h->last_ws + t.off * h->last_B) + t.coff;
     hipLaunchKernelGGL(k_nhwc_to_nchw_f32, dim3(grid1d(total, 256, 1 << 30)), dim3(256), 0, (hipStream_t)stream, src, t.ld, t.C, HW, out, total);
+    return hipGetLastError() == hipSuccess ? NATINF_OK : NATINF_ELAUNCH;
+}
+
+// The GroupNorm, output-head and glue kernels alone (include/natinf_ncsnpp.h; tests/test_gpu_gn_kernels.py): the grid and block expressions of emit_gn_stats,
+// emit_gn_from_parts, emit_gn_apply, the head op and the embedding / stem / pack / tap launches above.  Every precondition a kernel leaves to its caller is
+// NATINF_EINVAL here, before anything is launched; no plan of the library launches outside them (kernel table: k_time_embed's capped grid was the exception).
+static bool dbg_misaligned(const void* p, uintptr_t a) { return reinterpret_cast<uintptr_t>(p) % a != 0; }
+
+int natinf_debug_gn_stats(const void* x, int ld, int C, int HW, int B, const float* gamma, const float* beta, float* scale, float* shift, float eps, float out_mul,
+                          natinf_stream_t stream) {
+    if (!x || !gamma || !beta || !scale || !shift || B < 1 || HW < 1 || C < 32 || C > 512 || C % 32 || ld < C || ld % 8 || dbg_misaligned(x, 16)) return NATINF_EINVAL;
+    if ((256 / (C >> 3)) * C > 16 * 128 + 64) return NATINF_EINVAL;      // s_part (never true for C % 8 == 0: lanes * C <= 2048; kept next to the array it guards)
+    hipLaunchKernelGGL(k_gn_stats, dim3((unsigned)B), dim3(256), 0, (hipStream_t)stream, (const bf16*)x, ld, C, HW, gamma, beta, scale, shift, eps, out_mul);
+    return hipGetLastError() == hipSuccess ? NATINF_OK : NATINF_ELAUNCH;
+}
+
+int natinf_debug_gn_finalize(const float* P0, int tps0, int quads0, const float* P1, int tps1, int quads1, int C, int HW, int B, const float* gamma, const float* beta,
+                             float* scale, float* shift, float eps, float out_mul, natinf_stream_t stream) {
+    if (!P0 || !gamma || !beta || !scale || !shift || B < 1 || HW < 1 || tps0 < 1 || quads0 < 1) return NATINF_EINVAL;
+    if (P1 ? (tps1 < 1 || quads1 < 1) : (tps1 != 0 || quads1 != 0)) return NATINF_EINVAL;
+    // C % 128: qpg = (C / 32) >> 2 quads per group (0 below 128: the table would be gamma / sqrt(eps)); s_p[128]; every quad of the C channels is summed
+    if (C < 128 || C > 512 || C % 128 || quads0 + quads1 > 128 || (quads0 + quads1) * 4 != C || dbg_misaligned(P0, 8) || dbg_misaligned(P1, 8)) return NATINF_EINVAL;
+    hipLaunchKernelGGL(k_gn_finalize, dim3((unsigned)B), dim3(256), 0, (hipStream_t)stream, reinterpret_cast<const float2*>(P0), tps0, quads0,
+                       reinterpret_cast<const float2*>(P1), tps1, quads1, C, HW, gamma, beta, scale, shift, eps, out_mul);
+    return hipGetLastError() == hipSuccess ? NATINF_OK : NATINF_ELAUNCH;
+}
+
+int natinf_debug_gn_apply(const void* x, int ld, int C, int logW, int logHW, int B, const float* scale, const float* shift, void* y, void* xr, int act, int mode, int pad,
+                          natinf_stream_t stream) {
+    if (!x || !scale || !shift || !y || B < 1 || B > 65535 || C < 8 || C % 8 || (C >> 3) > 256 || ld < C || ld % 8) return NATINF_EINVAL;
+    if (logW < 0 || logHW < logW || logHW > 24 || mode < RS_NONE || mode > RS_DOWN || (pad != 0 && pad != 1) || (act != ACT_NONE && act != ACT_SILU)) return NATINF_EINVAL;
+    if (mode == RS_DOWN && (logW < 1 || logHW - logW < 1)) return NATINF_EINVAL;
+    if (dbg_misaligned(x, 16) || dbg_misaligned(y, 16) || dbg_misaligned(xr, 16) || dbg_misaligned(scale, 16) || dbg_misaligned(shift, 16)) return NATINF_EINVAL;
+    const int Hs = 1 << (logHW - logW), Hd = mode == RS_UP ? 2 * Hs : (mode == RS_DOWN ? Hs / 2 : Hs);
+    const int rows_per_img = Hd + 2 * pad;
+    hipLaunchKernelGGL(k_gn_apply, dim3((unsigned)((rows_per_img + GN_ROWS - 1) / GN_ROWS), (unsigned)B), dim3(256), 0, (hipStream_t)stream, (const bf16*)x, ld, C,
+                       logW, logHW, scale, shift, (bf16*)y, (bf16*)xr, act, mode, pad);
+    return hipGetLastError() == hipSuccess ? NATINF_OK : NATINF_ELAUNCH;
+}
+
+int natinf_debug_head_conv(const void* x, int ld, int B, const float* scale, const float* shift, const void* w16, const float* bias, float* out, natinf_stream_t stream) {
+    if (!x || !scale || !shift || !w16 || !bias || !out || B < 1 || ld < HeadConvCfg::C || ld % 8) return NATINF_EINVAL;
+    if (dbg_misaligned(x, 16) || dbg_misaligned(w16, 16) || dbg_misaligned(out, 16)) return NATINF_EINVAL;
+    // the engine's init (configure_ncsnpp_kernels): 49,472 bytes of dynamic LDS need the attribute
+    if (hipFuncSetAttribute(reinterpret_cast<const void*>(&k_head_conv), hipFuncAttributeMaxDynamicSharedMemorySize, HeadConvCfg::LDS_BYTES) != hipSuccess) {
+        (void)hipGetLastError();
+        return NATINF_ENODEV;
+    }
+    hipLaunchKernelGGL(k_head_conv, dim3((unsigned)(B * (HeadConvCfg::RES / HeadConvCfg::ROWS))), dim3(256), HeadConvCfg::LDS_BYTES, (hipStream_t)stream,
+                       (const bf16*)x, ld, scale, shift, (const bf16*)w16, bias, out);
+    return hipGetLastError() == hipSuccess ? NATINF_OK : NATINF_ELAUNCH;
+}
+
+int natinf_debug_time_embed(const float* labels, void* emb, int B, natinf_stream_t stream) {
+    if (!labels || !emb || B < 1 || B >= (1 << 21)) return NATINF_EINVAL;      // natinf_ncsnpp_forward's own limit (B * 1024 < 2^31); the index is an int
+    hipLaunchKernelGGL(k_time_embed, dim3(grid1d((int64_t)B * 128, 256, 1 << 30)), dim3(256), 0, (hipStream_t)stream, labels, (bf16*)emb, B);
+    return hipGetLastError() == hipSuccess ? NATINF_OK : NATINF_ELAUNCH;
+}
+
+int natinf_debug_stem_im2col(const float* x, void* A, int B, natinf_stream_t stream) {
+    if (!x || !A || B < 1 || B > (1 << 17) || dbg_misaligned(A, 16)) return NATINF_EINVAL;
+    const int64_t rows = (int64_t)B * 1024;
+    hipLaunchKernelGGL(k_stem_im2col, dim3((unsigned)((rows * 8 + 255) / 256)), dim3(256), 0, (hipStream_t)stream, x, (bf16*)A, rows);
+    return hipGetLastError() == hipSuccess ? NATINF_OK : NATINF_ELAUNCH;
+}
+
+int natinf_debug_pack_conv(const float* src, void* dst, int N, int Cin, int taps, int dst_ld, int koff, int tap_stride_c, int chunked, float wmul, natinf_stream_t stream) {
+    if (!src || !dst || N < 1 || Cin < 1 || taps < 1 || koff < 0 || (chunked != 0 && chunked != 1)) return NATINF_EINVAL;
+    const int64_t n = (int64_t)N * Cin * taps;
+    // the last column a row of the source reaches must lie inside the destination row
+    const int64_t span = chunked ? (int64_t)((Cin + 63) / 64) * taps * 64 : (int64_t)(taps - 1) * tap_stride_c + Cin;
+    if ((!chunked && tap_stride_c < Cin) || koff + span > dst_ld || n > ((int64_t)1 << 30) * 256) return NATINF_EINVAL;
+    hipLaunchKernelGGL(k_pack_conv, dim3(grid1d(n, 256, 1 << 30)), dim3(256), 0, (hipStream_t)stream, src, (bf16*)dst, N, Cin, taps, dst_ld, koff, tap_stride_c, chunked, wmul);
+    return hipGetLastError() == hipSuccess ? NATINF_OK : NATINF_ELAUNCH;
+}
+
+int natinf_debug_pack_transpose(const float* src, void* dst, int K, int N, int dst_ld, natinf_stream_t stream) {
+    if (!src || !dst || K < 1 || N < 1 || dst_ld < K) return NATINF_EINVAL;
+    hipLaunchKernelGGL(k_pack_transpose, dim3(grid1d((int64_t)K * N, 256, 1 << 30)), dim3(256), 0, (hipStream_t)stream, src, (bf16*)dst, K, N, dst_ld);
+    return hipGetLastError() == hipSuccess ? NATINF_OK : NATINF_ELAUNCH;
+}
+
+int natinf_debug_nhwc_to_nchw(const void* x, int ld, int C, int HW, int B, float* out, natinf_stream_t stream) {
+    if (!x || !out || B < 1 || C < 1 || HW < 1 || ld < C) return NATINF_EINVAL;
+    const int64_t total = (int64_t)B * C * HW;
+    if (total > ((int64_t)1 << 30) * 256) return NATINF_EINVAL;
+    hipLaunchKernelGGL(k_nhwc_to_nchw_f32, dim3(grid1d(total, 256, 1 << 30)), dim3(256), 0, (hipStream_t)stream, (const bf16*)x, ld, C, HW, out, total);
     return hipGetLastError() == hipSuccess ? NATINF_OK : NATINF_ELAUNCH;
 }
 

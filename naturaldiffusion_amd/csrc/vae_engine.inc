@@ -541,4 +541,14 @@ int natinf_debug_softmax_rows(int kind, const float* S, void* P, int T, int64_t 
     return hipGetLastError() == hipSuccess ? NATINF_OK : NATINF_ELAUNCH;
 }
 
+// k_gn_fold alone (include/natinf_ncsnpp.h; tests/test_gpu_gn_kernels.py), with VaeBase::gn_stats' launch shape: grid (tps / fold, B).  quads must divide 256: with
+// quads = 96 the threads 192..255 would form a third, partial lane beside lanes = 2 and their tiles would be added twice.  VaeBase launches quads = C / 4 in {32, 64, 128}.
+int natinf_debug_gn_fold(const float* P, int tps, int quads, int fold, int B, float* out, natinf_stream_t stream) {
+    if (!P || !out || B < 1 || B > 65535 || quads < 1 || quads > 256 || 256 % quads || fold < 1 || tps < fold || tps % fold) return NATINF_EINVAL;
+    if ((reinterpret_cast<uintptr_t>(P) | reinterpret_cast<uintptr_t>(out)) % 8) return NATINF_EINVAL;
+    hipLaunchKernelGGL(k_gn_fold, dim3((unsigned)(tps / fold), (unsigned)B), dim3(256), 0, (hipStream_t)stream, reinterpret_cast<const float2*>(P), tps, quads, fold,
+                       reinterpret_cast<float2*>(out));
+    return hipGetLastError() == hipSuccess ? NATINF_OK : NATINF_ELAUNCH;
+}
+
 }  // extern "C"

@@ -327,6 +327,73 @@ def test_inception_kernel_hooks_reject_bad_arguments():
         assert call(**bad) == -1, bad
 
 
+def test_gn_kernel_hooks_reject_bad_arguments():
+    """natinf_debug_gn_stats / _gn_finalize / _gn_fold / _gn_apply / _head_conv / _time_embed / _stem_im2col / _pack_conv / _pack_transpose / _nhwc_to_nchw
+    (include/natinf_ncsnpp.h): NATINF_EINVAL outside the preconditions each kernel leaves to its caller, before anything is launched (there is no GPU here)."""
+    from naturaldiffusion_amd._lib import lib
+    d = 4096
+
+    def caller(fn, names, base):
+        return lambda **kw: fn(*[{**base, **kw}[n] for n in names])
+
+    call = caller(lib.natinf_debug_gn_stats, ("x", "ld", "C", "HW", "B", "gamma", "beta", "scale", "shift", "eps", "out_mul", "stream"),
+                  dict(x=d, ld=128, C=128, HW=64, B=2, gamma=d, beta=d, scale=d, shift=d, eps=1e-6, out_mul=1.0, stream=None))
+    for name in ("x", "gamma", "beta", "scale", "shift"):
+        assert call(**{name: None}) == -1, name
+    for bad in (dict(C=0), dict(C=16), dict(C=120), dict(C=136, ld=136), dict(C=544, ld=544), dict(C=1024, ld=1024), dict(ld=120), dict(ld=132), dict(HW=0), dict(B=0),
+                dict(x=d + 8)):
+        assert call(**bad) == -1, bad
+
+    names = ("P0", "tps0", "quads0", "P1", "tps1", "quads1", "C", "HW", "B", "gamma", "beta", "scale", "shift", "eps", "out_mul", "stream")
+    base = dict(P0=d, tps0=4, quads0=64, P1=None, tps1=0, quads1=0, C=256, HW=256, B=2, gamma=d, beta=d, scale=d, shift=d, eps=1e-6, out_mul=1.0, stream=None)
+    call = caller(lib.natinf_debug_gn_finalize, names, base)
+    for name in ("P0", "gamma", "beta", "scale", "shift"):
+        assert call(**{name: None}) == -1, name
+    for bad in (dict(C=64, quads0=16), dict(C=96, quads0=24), dict(C=192, quads0=48), dict(C=320, quads0=80),      # C % 128: qpg would be 0 or drop a quad
+                dict(C=640, quads0=160), dict(C=1024, quads0=256), dict(quads0=32), dict(quads0=128), dict(tps0=0), dict(HW=0), dict(B=0),
+                dict(tps1=2), dict(quads1=32, C=384), dict(P1=d, tps1=2, quads1=0), dict(P1=d, tps1=0, quads1=32, C=384), dict(P1=d, tps1=2, quads1=32),
+                dict(P1=d, tps1=2, quads1=96, C=640), dict(P0=d + 4), dict(P1=d + 4, tps1=2, quads1=32, C=384)):
+        assert call(**bad) == -1, bad
+
+    call = caller(lib.natinf_debug_gn_fold, ("P", "tps", "quads", "fold", "B", "out", "stream"), dict(P=d, tps=320, quads=64, fold=5, B=2, out=d, stream=None))
+    for bad in (dict(P=None), dict(out=None), dict(quads=96), dict(quads=48), dict(quads=0), dict(quads=512), dict(fold=0), dict(fold=3), dict(tps=4), dict(B=0),
+                dict(B=65536), dict(P=d + 4), dict(out=d + 4)):      # quads = 96 (C = 384): a third, partial lane would add tiles twice
+        assert call(**bad) == -1, bad
+
+    names = ("x", "ld", "C", "logW", "logHW", "B", "scale", "shift", "y", "xr", "act", "mode", "pad", "stream")
+    call = caller(lib.natinf_debug_gn_apply, names, dict(x=d, ld=128, C=128, logW=3, logHW=6, B=2, scale=d, shift=d, y=d, xr=None, act=1, mode=0, pad=1, stream=None))
+    for name in ("x", "scale", "shift", "y"):
+        assert call(**{name: None}) == -1, name
+    for bad in (dict(C=0), dict(C=4), dict(C=100), dict(C=2056, ld=2056), dict(ld=120), dict(ld=132), dict(B=0), dict(B=65536), dict(logW=-1), dict(logHW=2),
+                dict(logHW=25), dict(mode=3), dict(mode=-1), dict(pad=2), dict(pad=-1), dict(act=2), dict(act=-1), dict(mode=2, logW=0, logHW=0),
+                dict(scale=d + 4), dict(shift=d + 8), dict(x=d + 8), dict(y=d + 8), dict(xr=d + 8)):
+        assert call(**bad) == -1, bad
+
+    call = caller(lib.natinf_debug_head_conv, ("x", "ld", "B", "scale", "shift", "w16", "bias", "out", "stream"),
+                  dict(x=d, ld=128, B=2, scale=d, shift=d, w16=d, bias=d, out=d, stream=None))
+    for name in ("x", "scale", "shift", "w16", "bias", "out"):
+        assert call(**{name: None}) == -1, name
+    for bad in (dict(ld=120), dict(ld=132), dict(B=0), dict(x=d + 8), dict(w16=d + 8), dict(out=d + 4)):
+        assert call(**bad) == -1, bad
+
+    assert lib.natinf_debug_time_embed(None, d, 2, None) == -1 and lib.natinf_debug_time_embed(d, None, 2, None) == -1
+    assert lib.natinf_debug_time_embed(d, d, 0, None) == -1 and lib.natinf_debug_time_embed(d, d, 1 << 21, None) == -1
+    assert lib.natinf_debug_stem_im2col(None, d, 2, None) == -1 and lib.natinf_debug_stem_im2col(d, None, 2, None) == -1
+    assert lib.natinf_debug_stem_im2col(d, d, 0, None) == -1 and lib.natinf_debug_stem_im2col(d, d + 8, 2, None) == -1
+
+    names = ("src", "dst", "N", "Cin", "taps", "dst_ld", "koff", "tap_stride_c", "chunked", "wmul", "stream")
+    call = caller(lib.natinf_debug_pack_conv, names, dict(src=d, dst=d, N=3, Cin=128, taps=9, dst_ld=1152, koff=0, tap_stride_c=128, chunked=1, wmul=1.0, stream=None))
+    for bad in (dict(src=None), dict(dst=None), dict(N=0), dict(Cin=0), dict(taps=0), dict(koff=-1), dict(chunked=2), dict(dst_ld=1151), dict(koff=1),
+                dict(Cin=129), dict(chunked=0, tap_stride_c=127), dict(chunked=0, dst_ld=1151), dict(chunked=0, Cin=3, tap_stride_c=3, dst_ld=26)):
+        assert call(**bad) == -1, bad
+    call = caller(lib.natinf_debug_pack_transpose, ("src", "dst", "K", "N", "dst_ld", "stream"), dict(src=d, dst=d, K=40, N=24, dst_ld=48, stream=None))
+    for bad in (dict(src=None), dict(dst=None), dict(K=0), dict(N=0), dict(dst_ld=39)):
+        assert call(**bad) == -1, bad
+    call = caller(lib.natinf_debug_nhwc_to_nchw, ("x", "ld", "C", "HW", "B", "out", "stream"), dict(x=d, ld=48, C=40, HW=12, B=2, out=d, stream=None))
+    for bad in (dict(x=None), dict(out=None), dict(C=0), dict(HW=0), dict(B=0), dict(ld=39)):
+        assert call(**bad) == -1, bad
+
+
 def test_validation_grid_is_one_row_of_eight(tmp_path):
     """reference ValidateNaturalInference.py:236: save_image(samples, path, nrow=8, ...): 8 images -> 1 x 8."""
     import torch
