@@ -108,7 +108,7 @@ int natinf_dit_attention_bf16(const void* q, const void* k, const void* v, int l
  * natinf_debug_ln_modulate: h[r][d] = LayerNorm(x[r])[d] * (1 + scale[b][d]) + shift[b][d], b = r / rows_per_sample (no affine,
  * eps 1e-6, biased variance, fp32 statistics).  x: [rows][D] fp32, or IEEE half when x_f16 (read through the same pointer);
  * shift / scale: row b at + b * mod_ld floats.  Exactly one output: h_bf16 [rows][D] bf16 (launch_ln_modulate), or h_fp8
- * [rows][D] e4m3 bytes with row_scale [rows] (launch_ln_modulate_fp8: row_scale = max|h[r]| / 448, 1.0 for an all-zero
+ * [rows][D] e4m3 bytes with row_scale [rows] (launch_ln_modulate<RowsFp8>: row_scale = max|h[r]| / 448, 1.0 for an all-zero
  * row; bytes = e4m3(h / row_scale), round to nearest even, clamped to +-448).  *form_out: the kernel form the launcher chose,
  * 0 scalar (any D, any alignment), 1 four columns per lane (D 256 / 1152 / 1536; D 256 / 1152 on the half stream), 2 eight
  * columns per lane (D 1536 on the half stream); the vector forms need mod_ld % 4 == 0 and 16-byte aligned shift / scale.

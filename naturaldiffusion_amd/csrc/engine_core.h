@@ -1,6 +1,7 @@
 // engine_core.h -- what every engine (NCSN++, DiT, MMDiT, VAE decoder, Inception) is built on: the per-forward launch context, the
 // workspace arena, the engine base (a launch plan over a packed-weight image) and the plan builder's shared recipes.  Part of the one
-// translation unit ncsnpp.hip; the GEMM launch layer the ops call is gemm_launch.h.
+// translation unit ncsnpp.hip; the GEMM launch layer the ops call is gemm_launch.h.  What only the transformer plans share (Lin / Lin8, the builder
+// base that takes and packs a Linear, the GEMM recipes) is transformer_plan.h.
 #pragma once
 #include <functional>
 #include <map>

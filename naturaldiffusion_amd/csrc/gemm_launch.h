@@ -458,12 +458,8 @@ int launch_gemm_run(const GemmArgs& g0, hipStream_t s) {
             const int nM = (p.M + 255) / 256, nN = (p.N + 255) / 256;
             p.raster_g = 0;
             hipLaunchKernelGGL((k_gemm_w128<9>), dim3(nM * nN, S8, p.batch), dim3(256), W128Cfg::LDS_BYTES, s, p);
-            const int64_t per = (int64_t)g0.M * (g0.N / 4);
             if (g0.stream_guard) ncsn_sg::launch_splitk_reduce(&g0, S8, (void*)s);
-            else
-            hipLaunchKernelGGL(k_splitk_reduce_f32, dim3((unsigned)((per + 255) / 256), (unsigned)g0.batch), dim3(256), 0, s, g0.splitk_ws, S8, (int64_t)g0.batch * g0.M * g0.N, g0.M, g0.N,
-                               g0.bias_n, g0.gate, g0.gate_ld, g0.log_rows_per_sample, g0.z_samples, g0.resid_f32, g0.resid_f32_ld, g0.c_bs, g0.scale,
-                               reinterpret_cast<float*>(g0.c), g0.c_ld, g0.stream_f16);
+            else launch_splitk_reduce_f32<false>(g0, S8, s);
             return 256;
         }
     }

@@ -325,33 +325,56 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
 // Split-K of an under-filled long-K GEMM whose epilogue is the gated fp32 residual stream (DiT-XL/2's fc2 at Validate's size: (4096, 1152, 4608) is 80 tiles of
 // 256 x 256 -- or 288 of 128 x 128 on 512 slots -- for 72 K-tiles each): S slices of K as S x 80 blocks of k_gemm_w128<9>, then this pass sums the slices IN ORDER
 // (deterministic) and applies out = (resid + gate[sample] * (sum + bias)) * scale, four columns per thread.  resid may be out (same element, same thread).
+// GUARD: the guarded form (GemmArgs::stream_guard; ncsnpp_kernels.h; instantiated in stream_guard.hip): the same sums in the same order, every value through
+// stream_guard_value before it is stored, one commit per wave.  No lane leaves before the commit (the wave reduction reads all 64): a lane past the end computes
+// nothing and contributes zeros.  guard: read by GUARD only.
+template <bool GUARD>
 __global__ __launch_bounds__(256) void k_splitk_reduce_f32(const float* __restrict__ part, int S, int64_t slice_stride, int M, int N, const float* __restrict__ bias_n,
                                                             const float* __restrict__ gate, int gate_ld, int log_rows_per_sample, int z_samples,
-                                                            const float* resid, int resid_ld, int64_t c_bs, float scale, float* c, int c_ld, int stream_f16 = 0)
+                                                            const float* resid, int resid_ld, int64_t c_bs, float scale, float* c, int c_ld, int stream_f16, uint32_t* guard)
 {
     const int64_t idx = (int64_t)blockIdx.x * 256 + threadIdx.x, per = (int64_t)M * (N >> 2);
     const int z = blockIdx.y;
-    if (idx >= per) return;
-    const int m = (int)(idx / (N >> 2)), n = (int)(idx - (int64_t)m * (N >> 2)) * 4;
-    const float* p = part + ((int64_t)z * M + m) * N + n;
-    f32x4 v = *reinterpret_cast<const f32x4*>(p);
-    for (int sl = 1; sl < S; ++sl) { const f32x4 u = *reinterpret_cast<const f32x4*>(p + sl * slice_stride); v += u; }
-    if (bias_n) { const f32x4 b = *reinterpret_cast<const f32x4*>(bias_n + n); v += b; }
-    if (gate) { const f32x4 gt = *reinterpret_cast<const f32x4*>(gate + (int64_t)((m >> log_rows_per_sample) + z * z_samples) * gate_ld + n); v *= gt; }
-    typedef _Float16 f16x4_sk __attribute__((ext_vector_type(4)));
-    if (stream_f16) {                                                 // (GemmArgs::stream_f16: resid and c are IEEE-half rows -- the transformer engines' 16-bit residual stream)
-        if (resid) {
-            const f16x4_sk rs = *reinterpret_cast<const f16x4_sk*>(reinterpret_cast<const _Float16*>(resid) + (int64_t)z * c_bs + (int64_t)m * resid_ld + n);
-            v += f32x4{(float)rs[0], (float)rs[1], (float)rs[2], (float)rs[3]};
+    [[maybe_unused]] StreamGuardAcc ga;
+    if (idx < per) {
+        const int m = (int)(idx / (N >> 2)), n = (int)(idx - (int64_t)m * (N >> 2)) * 4;
+        const float* p = part + ((int64_t)z * M + m) * N + n;
+        f32x4 v = *reinterpret_cast<const f32x4*>(p);
+        for (int sl = 1; sl < S; ++sl) { const f32x4 u = *reinterpret_cast<const f32x4*>(p + sl * slice_stride); v += u; }
+        if (bias_n) { const f32x4 b = *reinterpret_cast<const f32x4*>(bias_n + n); v += b; }
+        if (gate) { const f32x4 gt = *reinterpret_cast<const f32x4*>(gate + (int64_t)((m >> log_rows_per_sample) + z * z_samples) * gate_ld + n); v *= gt; }
+        typedef _Float16 f16x4_sk __attribute__((ext_vector_type(4)));
+        if (stream_f16) {                                             // (GemmArgs::stream_f16: resid and c are IEEE-half rows -- the transformer engines' 16-bit residual stream)
+            if (resid) {
+                const f16x4_sk rs = *reinterpret_cast<const f16x4_sk*>(reinterpret_cast<const _Float16*>(resid) + (int64_t)z * c_bs + (int64_t)m * resid_ld + n);
+                v += f32x4{(float)rs[0], (float)rs[1], (float)rs[2], (float)rs[3]};
+            }
+            v *= scale;
+            if constexpr (GUARD) {
+#pragma unroll
+                for (int e = 0; e < 4; ++e) v[e] = stream_guard_value<true>(ga, v[e]);
+            }
+            const f16x4_sk o = {(_Float16)v[0], (_Float16)v[1], (_Float16)v[2], (_Float16)v[3]};
+            *reinterpret_cast<f16x4_sk*>(reinterpret_cast<_Float16*>(c) + (int64_t)z * c_bs + (int64_t)m * c_ld + n) = o;
+        } else {
+            if (resid) { const f32x4 rs = *reinterpret_cast<const f32x4*>(resid + (int64_t)z * c_bs + (int64_t)m * resid_ld + n); v += rs; }
+            v *= scale;
+            if constexpr (GUARD) {
+#pragma unroll
+                for (int e = 0; e < 4; ++e) v[e] = stream_guard_value<false>(ga, v[e]);
+            }
+            *reinterpret_cast<f32x4*>(c + (int64_t)z * c_bs + (int64_t)m * c_ld + n) = v;
         }
-        v *= scale;
-        const f16x4_sk o = {(_Float16)v[0], (_Float16)v[1], (_Float16)v[2], (_Float16)v[3]};
-        *reinterpret_cast<f16x4_sk*>(reinterpret_cast<_Float16*>(c) + (int64_t)z * c_bs + (int64_t)m * c_ld + n) = o;
-        return;
     }
-    if (resid) { const f32x4 rs = *reinterpret_cast<const f32x4*>(resid + (int64_t)z * c_bs + (int64_t)m * resid_ld + n); v += rs; }
-    v *= scale;
-    *reinterpret_cast<f32x4*>(c + (int64_t)z * c_bs + (int64_t)m * c_ld + n) = v;
+    if constexpr (GUARD) stream_guard_commit(ga, guard);
+}
+template <bool GUARD>
+inline void launch_splitk_reduce_f32(const GemmArgs& g, int slices, hipStream_t s)      // behind k_gemm_w128<9> (gemm_launch.h: w128_splitk_slices)
+{
+    const int64_t per = (int64_t)g.M * (g.N / 4);
+    hipLaunchKernelGGL(k_splitk_reduce_f32<GUARD>, dim3((unsigned)((per + 255) / 256), (unsigned)g.batch), dim3(256), 0, s, g.splitk_ws, slices, (int64_t)g.batch * g.M * g.N, g.M, g.N,
+                       g.bias_n, g.gate, g.gate_ld, g.log_rows_per_sample, g.z_samples, g.resid_f32, g.resid_f32_ld, g.c_bs, g.scale, reinterpret_cast<float*>(g.c), g.c_ld,
+                       g.stream_f16, g.stream_guard);
 }
 
 // ---------------------------------------------------------------------------------------------------------------------------------------------------------

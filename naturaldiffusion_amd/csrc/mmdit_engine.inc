@@ -1,4 +1,5 @@
-// mmdit_engine.inc -- SD3 MMDiT denoiser engine (C ABI of include/natinf_mmdit.h); included after dit_engine.inc.
+// mmdit_engine.inc -- SD3 MMDiT denoiser engine (C ABI of include/natinf_mmdit.h); included after dit_engine.inc, on which it does not depend: the row and glue
+// kernels it shares with the DiT engine are transformer_rows.h's, the plan base and the GEMM recipes transformer_plan.h's.
 //
 // Two residual streams (image tokens x [Tx][D]: fp32, or IEEE half with natinf_set_mmdit_stream16; text tokens e [Tc][D]: fp32) and one joint bf16 attention buffer per
 // sequence, padded to Tp = roundup(Tx + Tc, 128) rows: Q|K [Tp][2D], V^T [D][Tp], O [Tp][D].  Per block:
@@ -8,7 +9,7 @@
 // All adaLN linears of the network run as one GEMM per forward.  include/natinf_mmdit.h states what this replaces
 // and the parity status of that third-party arithmetic.
 #include "natinf_mmdit.h"
-#include "engine_core.h"
+#include "transformer_plan.h"
 #include "flash_attn.h"
 
 struct natinf_mmdit : EngineCore {
@@ -70,27 +71,9 @@ void launch_flash(const bf16* q, const bf16* k, int ld_qk, int64_t qk_bs, const 
     if (e.first) { (void)hipEventRecord(e.second, s); g_flash_prof.ev.push_back(e); }
 }
 
-struct MMDitBuilder : PlanBuilder {
+struct MMDitBuilder : TransformerBuilder {
     natinf_mmdit& E;
-    explicit MMDitBuilder(natinf_mmdit& e) : PlanBuilder(e), E(e) {}
-
-    struct Lin { int64_t w, b; };
-    struct Lin8 { int64_t w, s, b; };                              // fp8 bytes [out][in], per-output-channel scale, fp32 bias
-    Lin8 linear8(int out, int in) {
-        const int64_t pw = take((int64_t)out * in), pb = take(out);
-        const Lin8 r{wres((int64_t)out * in), wres((int64_t)out * 4), pack_f32(pb, out)};
-        pack_fp8_at(pw, out, in, r.w, r.s);
-        return r;
-    }
-    Lin linear(int out, int in) {                                  // takes weight then bias from the parameter stream
-        const int64_t pw = take((int64_t)out * in), pb = take(out);
-        return Lin{pack_bf16(pw, out, in), pack_f32(pb, out)};
-    }
-    void linear_at(int out, int in, int64_t wdst, int64_t bdst) {
-        const int64_t pw = take((int64_t)out * in), pb = take(out);
-        pack_bf16_at(pw, out, in, wdst);
-        pack_f32_at(pb, out, bdst);
-    }
+    explicit MMDitBuilder(natinf_mmdit& e) : TransformerBuilder(e), E(e) {}
 
     void build() {
         const int L = E.L, H = E.H, D = E.D, Jd = E.Jd, Pd = E.Pd, C = E.C, gr = E.g, Tx = E.Tx, Tc = E.Tc, Tp = E.Tp;
@@ -119,13 +102,6 @@ struct MMDitBuilder : PlanBuilder {
         const int64_t mx_slack = fp8 ? arena.alloc(2048) : 0;         // a 256-row scale piece may reach past the last plane (small grids, text rows)
         (void)mx_slack;
 
-        auto dense = [](const Ctx& c, const bf16* a, int K, int M, const Lin& w, int N, int act, void* out, int mode) {
-            GemmArgs g = gemm_defaults();
-            g.a0 = a; g.a0_ld = K; g.a0_C = K; g.M = M; g.N = N; g.b = c.w<bf16>(w.w); g.b_ld = K; g.bias_n = c.w<float>(w.b);
-            g.act = act; g.c = out; g.c_ld = N; g.c_mode = mode;
-            return g;
-        };
-
         op([=](const Ctx& c) {                                      // embeddings and conditioning
             // V^T columns past the joint sequence must be finite: P is exactly 0 there, 0 * garbage must be 0
             // ... and the q | k rows past it must be the same whatever the workspace held: the padded KEYS are masked, but the padded QUERIES share waves with real ones
@@ -149,10 +125,7 @@ struct MMDitBuilder : PlanBuilder {
             g.resid_f32 = c.at<float>(cf); g.resid_f32_ld = D;
             launch_gemm(g, c.stream);
             hipLaunchKernelGGL(k_silu_bf16, dim3(grid1d((int64_t)c.B * D, 256, 1 << 30)), dim3(256), 0, c.stream, c.at<float>(cf), c.at<bf16>(cs), (int64_t)c.B * D);
-            g = gemm_defaults();                                    // every adaLN linear at once
-            g.a0 = c.at<bf16>(cs); g.a0_ld = D; g.a0_C = D; g.M = c.B; g.N = nmod; g.b = c.w<bf16>(w_mod); g.b_ld = D;
-            g.bias_n = c.w<float>(b_mod); g.c = c.at<float>(mod); g.c_ld = nmod; g.c_mode = OUT_F32;
-            launch_gemm(g, c.stream);
+            launch_gemm(dense(c, c.at<bf16>(cs), D, c.B, Lin{w_mod, b_mod}, nmod, ACT_NONE, c.at<float>(mod), OUT_F32), c.stream);      // every adaLN linear at once
             launch_gemm(dense(c, c.at<bf16>(tx), Jd, c.B * Tc, ce, D, ACT_NONE, c.at<float>(e), OUT_F32), c.stream);   // context_embedder
         });
 
@@ -160,29 +133,20 @@ struct MMDitBuilder : PlanBuilder {
             const bool src16 = s16 && src == x;                       // (the image stream in half; the text stream e is fp32)
             return [=](const Ctx& c) {
                 const int64_t rows = (int64_t)c.B * rows_per_seq;
-                launch_ln_modulate(c.at<float>(src), c.at<float>(mod) + shift_off, c.at<float>(mod) + scale_off, nmod, c.at<bf16>(dst), D, rows, rows_per_seq, c.stream, src16);
+                launch_ln_modulate<RowsBf16>(c.at<float>(src), c.at<float>(mod) + shift_off, c.at<float>(mod) + scale_off, nmod, c.at<bf16>(dst), nullptr, D, rows, rows_per_seq, c.stream, src16);
             };
         };
         auto ln_mod8 = [=](int shift_off, int scale_off) {         // image stream -> fp8 rows + per-token scales
             return [=](const Ctx& c) {
                 const int64_t rows = (int64_t)c.B * Tx;
-                launch_ln_modulate_fp8(c.at<float>(x), c.at<float>(mod) + shift_off, c.at<float>(mod) + scale_off, nmod, c.at<uint8_t>(hx8), c.at<float>(sx), D, rows, Tx,
-                                       c.stream, s16);
+                launch_ln_modulate<RowsFp8>(c.at<float>(x), c.at<float>(mod) + shift_off, c.at<float>(mod) + scale_off, nmod, c.at<uint8_t>(hx8), c.at<float>(sx), D, rows, Tx,
+                                   c.stream, s16);
             };
         };
-        // per-sequence batched GEMM: rows of stream `a` (T rows per sequence) -> rows of the per-sequence output
-        auto seq_gemm = [](const Ctx& c, const bf16* a, int K, int64_t a_bs, int T, const Lin& w, int N, void* out, int ld, int64_t c_bs, int mode) {
-            GemmArgs g = gemm_defaults();
-            g.a0 = a; g.a0_ld = K; g.a0_C = K; g.a_bs = a_bs; g.M = T; g.N = N; g.b = c.w<bf16>(w.w); g.b_ld = K; g.bias_n = c.w<float>(w.b);
-            g.c = out; g.c_ld = ld; g.c_bs = c_bs; g.c_mode = mode; g.batch = c.B;
-            return g;
-        };
-        auto gated = [=](GemmArgs g, const Ctx& c, int gate_off, int64_t stream_off, int site = -1) {      // stream += gate * (. + bias); site: the launch's slot of the stream guard (image stream only)
-            g.stream_guard = site >= 0 ? c.site(site) : nullptr;
-            g.gate = c.at<float>(mod) + gate_off; g.gate_ld = nmod; g.log_rows_per_sample = 30; g.z_samples = 1;
-            g.resid_f32 = c.at<float>(stream_off); g.resid_f32_ld = D;
-            g.stream_f16 = s16 && stream_off == x;                     // (g.c is the same stream: both sides of the update are half rows then)
-            return g;
+        // stream += gate * (. + bias), one sequence per batch index; site: the launch's slot of the stream guard (image stream only).  The image stream may be half
+        // (g.c is the same stream: both sides of the update are half rows then)
+        auto update = [=](GemmArgs g, const Ctx& c, int gate_off, int64_t stream_off, int site = -1) {
+            return gated(g, c.at<float>(mod) + gate_off, nmod, 30, 1, c.at<float>(stream_off), D, s16 && stream_off == x, site >= 0 ? c.site(site) : nullptr);
         };
 
         // the text stream's launches: on Ctx::stream2 when the forward has one (natinf_set_mmdit_text_stream), joined with the image stream by events where the
@@ -235,35 +199,22 @@ struct MMDitBuilder : PlanBuilder {
             op(fp8 ? OpFn(ln_mod8(mx, mx + D)) : OpFn(ln_mod(x, Tx, mx, mx + D, hx)));
             // text stream: adaLN-Zero (shift, scale, ...) or, in the last block, AdaLayerNormContinuous (scale, shift)
             op(on_text(last ? ln_mod(e, Tc, me + D, me, he) : ln_mod(e, Tc, me, me + D, he)));
-            auto vt = [=](const Ctx& c, const Lin& w, const bf16* hsrc, int T, int col) {          // V^T[:, col : col+T] = Wv h^T + bv
-                GemmArgs g = gemm_defaults();
-                g.a0 = c.w<bf16>(w.w); g.a0_ld = D; g.a0_C = D; g.a_bs = 0; g.M = D; g.N = T;
-                g.b = hsrc; g.b_ld = D; g.b_bs = (int64_t)T * D; g.bias_m = c.w<float>(w.b);
-                g.c = c.at<bf16>(vT) + col; g.c_ld = Tp; g.c_bs = (int64_t)D * Tp; g.batch = c.B;
-                launch_gemm(g, c.stream);
-            };
+            const Lin8 qkx8{w_qk8, s_qk8, b_qkx};
             const int64_t qk_bs = (int64_t)Tp * 2 * D;
             op([=](const Ctx& c) {                          // image stream: q | k into rows [0, Tx) of the joint buffer, V^T columns [0, Tx)
                 if (fp8) {                                  // on e4m3 operands
-                    GemmArgs g = gemm_defaults();
-                    g.a0 = reinterpret_cast<const bf16*>(c.at<uint8_t>(hx8)); g.a0_ld = D; g.a0_C = D; g.a_bs = (int64_t)Tx * D; g.M = Tx; g.N = 2 * D;
-                    g.b = reinterpret_cast<const bf16*>(c.w<uint8_t>(w_qk8)); g.b_ld = D; g.deq_m = c.at<float>(sx); g.deq_m_bs = Tx; g.deq_n = c.w<float>(s_qk8);
-                    g.bias_n = c.w<float>(b_qkx); g.c = c.at<bf16>(qk); g.c_ld = 2 * D; g.c_bs = qk_bs; g.batch = c.B;
+                    GemmArgs g = seq_gemm(c, nullptr, D, (int64_t)Tx * D, Tx, qkx8, 2 * D, c.at<bf16>(qk), 2 * D, qk_bs, OUT_BF16);
+                    a_fp8_rows(g, c.at<uint8_t>(hx8), c.at<float>(sx), Tx);
                     launch_gemm_fp8(g, c.stream);
-                    g = gemm_defaults();                    // V^T: weights as the row operand
-                    g.a0 = reinterpret_cast<const bf16*>(c.w<uint8_t>(vx8.w)); g.a0_ld = D; g.a0_C = D; g.a_bs = 0; g.M = D; g.N = Tx;
-                    g.b = reinterpret_cast<const bf16*>(c.at<uint8_t>(hx8)); g.b_ld = D; g.b_bs = (int64_t)Tx * D;
-                    g.deq_m = c.w<float>(vx8.s); g.deq_m_bs = 0; g.deq_n = c.at<float>(sx); g.deq_n_bs = Tx; g.bias_m = c.w<float>(vx8.b);
-                    g.c = c.at<bf16>(vT); g.c_ld = Tp; g.c_bs = (int64_t)D * Tp; g.batch = c.B;
-                    launch_gemm_fp8(g, c.stream);
+                    launch_gemm_fp8(vt8(c, vx8, D, c.at<uint8_t>(hx8), c.at<float>(sx), Tx, c.at<bf16>(vT), Tp), c.stream);
                 } else {
                     launch_gemm(seq_gemm(c, c.at<bf16>(hx), D, (int64_t)Tx * D, Tx, qkx, 2 * D, c.at<bf16>(qk), 2 * D, qk_bs, OUT_BF16), c.stream);
-                    vt(c, vx, c.at<bf16>(hx), Tx, 0);
+                    launch_gemm(vt(c, vx, D, c.at<bf16>(hx), Tx, c.at<bf16>(vT), Tp), c.stream);
                 }
             });
             op(on_text([=](const Ctx& c) {                  // text stream: rows / columns [Tx, Tx + Tc)
                 launch_gemm(seq_gemm(c, c.at<bf16>(he), D, (int64_t)Tc * D, Tc, qke, 2 * D, c.at<bf16>(qk) + (int64_t)Tx * 2 * D, 2 * D, qk_bs, OUT_BF16), c.stream);
-                vt(c, ve, c.at<bf16>(he), Tc, Tx);
+                launch_gemm(vt(c, ve, D, c.at<bf16>(he), Tc, c.at<bf16>(vT), Tp, Tx), c.stream);
             }));
             op(ev_record(1 + 2 * i, true)); op(ev_wait(1 + 2 * i, false));          // the joint attention needs both
             op([=](const Ctx& c) {
@@ -276,48 +227,39 @@ struct MMDitBuilder : PlanBuilder {
                 }
             });
             op(ev_record(2 + 2 * i, false));
-            auto proj8 = [=](const Ctx& c, const Lin8& w, int row0, int T, float* stream_ptr_, int64_t stream_off, int gate_off, int site = -1) {     // stream += gate * (O8 W^T + b)
-                GemmArgs g = gemm_defaults();
-                g.a0 = reinterpret_cast<const bf16*>(c.at<uint8_t>(o8) + (int64_t)row0 * D); g.a0_ld = D; g.a0_C = D; g.a_bs = (int64_t)Tp * D; g.M = T; g.N = D;
-                g.a_mx = c.at<uint8_t>(omx) + (int64_t)row0 * 4; g.a_mx_ld = Tp; g.a_mx_bs = (int64_t)Tp * (D / 32);      // K-tile-major planes of Tp rows
-                g.b = reinterpret_cast<const bf16*>(c.w<uint8_t>(w.w)); g.b_ld = D; g.deq_n = c.w<float>(w.s); g.bias_n = c.w<float>(w.b);
-                g.c = stream_ptr_; g.c_ld = D; g.c_bs = (int64_t)T * D; g.c_mode = OUT_F32; g.batch = c.B;
-                launch_gemm_fp8(gated(g, c, gate_off, stream_off, site), c.stream);
+            // stream += gate * (O W^T + b) for rows [row0, row0 + T) of the joint attention output: bf16 rows, or (fp8) e4m3 rows + MX scales in K-tile-major planes of Tp rows
+            auto proj = [=](const Ctx& c, const Lin& w, const Lin8& w8, int row0, int T, int64_t stream_off, int gate_off, int site = -1) {
+                if (fp8) {
+                    GemmArgs g = seq_gemm(c, nullptr, D, (int64_t)Tp * D, T, w8, D, c.at<float>(stream_off), D, (int64_t)T * D, OUT_F32);
+                    a_fp8_mx(g, c.at<uint8_t>(o8) + (int64_t)row0 * D, c.at<uint8_t>(omx) + (int64_t)row0 * 4, Tp, (int64_t)Tp * (D / 32));
+                    launch_gemm_fp8(update(g, c, gate_off, stream_off, site), c.stream);
+                } else {
+                    launch_gemm(update(seq_gemm(c, c.at<bf16>(o) + (int64_t)row0 * D, D, (int64_t)Tp * D, T, w, D, c.at<float>(stream_off), D, (int64_t)T * D, OUT_F32), c, gate_off, stream_off, site),
+                                c.stream);
+                }
             };
-            op([=](const Ctx& c) {                          // image stream's output projection
-                if (fp8) proj8(c, ox8, 0, Tx, c.at<float>(x), x, mx + 2 * D, 1 + 2 * i);
-                else launch_gemm(gated(seq_gemm(c, c.at<bf16>(o), D, (int64_t)Tp * D, Tx, ox, D, c.at<float>(x), D, (int64_t)Tx * D, OUT_F32), c, mx + 2 * D, x, 1 + 2 * i), c.stream);
-            });
+            op([=](const Ctx& c) { proj(c, ox, ox8, 0, Tx, x, mx + 2 * D, 1 + 2 * i); });                  // image stream's output projection
             if (!last) {
                 op(ev_wait(2 + 2 * i, true));
-                op(on_text([=](const Ctx& c) {              // text stream's output projection
-                    if (fp8) proj8(c, oe8, Tx, Tc, c.at<float>(e), e, me + 2 * D);
-                    else launch_gemm(gated(seq_gemm(c, c.at<bf16>(o) + (int64_t)Tx * D, D, (int64_t)Tp * D, Tc, oe, D, c.at<float>(e), D, (int64_t)Tc * D, OUT_F32), c, me + 2 * D, e), c.stream);
-                }));
+                op(on_text([=](const Ctx& c) { proj(c, oe, oe8, Tx, Tc, e, me + 2 * D); }));             // text stream's output projection
             }
             op(fp8 ? OpFn(ln_mod8(mx + 3 * D, mx + 4 * D)) : OpFn(ln_mod(x, Tx, mx + 3 * D, mx + 4 * D, hx)));
             op([=](const Ctx& c) {
                 if (fp8) {
-                    GemmArgs g = gemm_defaults();
-                    g.a0 = reinterpret_cast<const bf16*>(c.at<uint8_t>(hx8)); g.a0_ld = D; g.a0_C = D; g.a_bs = (int64_t)Tx * D; g.M = Tx; g.N = 4 * D;
-                    g.b = reinterpret_cast<const bf16*>(c.w<uint8_t>(f18.w)); g.b_ld = D; g.deq_m = c.at<float>(sx); g.deq_m_bs = Tx; g.deq_n = c.w<float>(f18.s);
-                    g.bias_n = c.w<float>(f18.b); g.act = ACT_GELU_TANH; g.batch = c.B;
-                    g.c = c.at<uint8_t>(f8); g.c_ld = 4 * D; g.c_bs = (int64_t)Tx * 4 * D; g.c_mode = OUT_FP8_MX;          // e4m3 + a scale per 32 columns: fc2's operand
-                    g.c_mx = c.at<uint8_t>(fmx); g.c_mx_ld = Tx; g.c_mx_bs = (int64_t)Tx * (4 * D / 32);
+                    const int64_t mx_bs = (int64_t)Tx * (4 * D / 32);
+                    GemmArgs g = seq_gemm(c, nullptr, D, (int64_t)Tx * D, Tx, f18, 4 * D, c.at<uint8_t>(f8), 4 * D, (int64_t)Tx * 4 * D, OUT_FP8_MX);      // e4m3 + a scale per 32 columns: fc2's operand
+                    a_fp8_rows(g, c.at<uint8_t>(hx8), c.at<float>(sx), Tx);
+                    g.act = ACT_GELU_TANH; g.c_mx = c.at<uint8_t>(fmx); g.c_mx_ld = Tx; g.c_mx_bs = mx_bs;
                     launch_gemm_fp8(g, c.stream);
-                    g = gemm_defaults();                                                                                     // x += gate_mlp * (f8 W2^T + b)
-                    g.a0 = reinterpret_cast<const bf16*>(c.at<uint8_t>(f8)); g.a0_ld = 4 * D; g.a0_C = 4 * D; g.a_bs = (int64_t)Tx * 4 * D; g.M = Tx; g.N = D;
-                    g.a_mx = c.at<uint8_t>(fmx); g.a_mx_ld = Tx; g.a_mx_bs = (int64_t)Tx * (4 * D / 32);
-                    g.b = reinterpret_cast<const bf16*>(c.w<uint8_t>(f28.w)); g.b_ld = 4 * D; g.deq_n = c.w<float>(f28.s); g.bias_n = c.w<float>(f28.b);
-                    g.c = c.at<float>(x); g.c_ld = D; g.c_bs = (int64_t)Tx * D; g.c_mode = OUT_F32; g.batch = c.B;
-                    launch_gemm_fp8(gated(g, c, mx + 5 * D, x, 2 + 2 * i), c.stream);
+                    g = seq_gemm(c, nullptr, 4 * D, (int64_t)Tx * 4 * D, Tx, f28, D, c.at<float>(x), D, (int64_t)Tx * D, OUT_F32);                          // x += gate_mlp * (f8 W2^T + b)
+                    a_fp8_mx(g, c.at<uint8_t>(f8), c.at<uint8_t>(fmx), Tx, mx_bs);
+                    launch_gemm_fp8(update(g, c, mx + 5 * D, x, 2 + 2 * i), c.stream);
                     return;
-                } else {
+                }
                 GemmArgs g = seq_gemm(c, c.at<bf16>(hx), D, (int64_t)Tx * D, Tx, f1, 4 * D, c.at<bf16>(fx), 4 * D, (int64_t)Tx * 4 * D, OUT_BF16);
                 g.act = ACT_GELU_TANH;
                 launch_gemm(g, c.stream);
-                }
-                launch_gemm(gated(seq_gemm(c, c.at<bf16>(fx), 4 * D, (int64_t)Tx * 4 * D, Tx, f2, D, c.at<float>(x), D, (int64_t)Tx * D, OUT_F32), c, mx + 5 * D, x, 2 + 2 * i), c.stream);
+                launch_gemm(update(seq_gemm(c, c.at<bf16>(fx), 4 * D, (int64_t)Tx * 4 * D, Tx, f2, D, c.at<float>(x), D, (int64_t)Tx * D, OUT_F32), c, mx + 5 * D, x, 2 + 2 * i), c.stream);
             });
             if (!last) {
                 op(on_text(ln_mod(e, Tc, me + 3 * D, me + 4 * D, he)));
@@ -328,7 +270,7 @@ struct MMDitBuilder : PlanBuilder {
                                                    : seq_gemm(c, c.at<bf16>(he), D, (int64_t)Tc * D, Tc, g1, 4 * D, c.at<bf16>(fe), 4 * D, (int64_t)Tc * 4 * D, OUT_BF16);
                     g.act = ACT_GELU_TANH;
                     launch_gemm(g, c.stream);
-                    launch_gemm(gated(seq_gemm(c, c.at<bf16>(fe), 4 * D, (int64_t)Tc * 4 * D, Tc, g2, D, c.at<float>(e), D, (int64_t)Tc * D, OUT_F32), c, me + 5 * D, e), c.stream);
+                    launch_gemm(update(seq_gemm(c, c.at<bf16>(fe), 4 * D, (int64_t)Tc * 4 * D, Tc, g2, D, c.at<float>(e), D, (int64_t)Tc * D, OUT_F32), c, me + 5 * D, e), c.stream);
                 }));
             }
         }

@@ -1,7 +1,8 @@
 // ncsnpp.hip -- the one translation unit of the engines.  Its own code is the host side of the NCSN++ denoiser engine: the static execution
 // plan (Builder), weight packing, forward; the C ABI of include/natinf_ncsnpp.h with the natinf_debug_* / natinf_set_* entries.  The GEMM
 // launch layer every engine calls is gemm_launch.h, the engine base and the plan builder's shared recipes engine_core.h, the kernels
-// ncsnpp_kernels.h and the headers below; the other four engines are included at the end of this file.
+// ncsnpp_kernels.h and the headers below; the other four engines are included at the end of this file (the two transformer engines bring their
+// own shared pieces: the row and glue kernels of transformer_rows.h, the plan base and GEMM recipes of transformer_plan.h).
 //
 // Design (MI355X-first, not a translation of the reference's nn.Module tree):
 //   * the network is compiled once into a flat op list (~330 launches) over ONE caller-supplied

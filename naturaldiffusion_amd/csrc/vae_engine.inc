@@ -11,7 +11,7 @@
 // convolutions run as k_inc_im2col + one GEMM (the `ddpm` plan's emit_downconv), conv_out leaves fp32 NCHW moments, k_vae_quant (vae_quant.hip) applies quant_conv,
 // and natinf_vae_encode ends with the posterior kernel of ni_step.hip.
 #include "natinf_vae.h"
-#include "engine_core.h"
+#include "transformer_plan.h"      // the mid-block attention's q | k, V^T and output-projection launches are its recipes
 
 // the encoder's quant_conv pass k_vae_quant: vae_quant.hip
 namespace ncsn_vq { void launch(const float* m, const float* W, const float* bias, float* out, int N, int hw, int64_t total, void* stream); }
@@ -95,6 +95,20 @@ __global__ __launch_bounds__(256) void k_softmax_rows_wide(const float* __restri
 }
 
 }  // namespace ncsn
+
+// The three row-softmax kernels alone (include/natinf_dit.h; tests/test_gpu_row_kernels.py): k_softmax_rows (ncsnpp_kernels.h), k_softmax_rows_1k (transformer_rows.h)
+// and k_softmax_rows_wide above, the last of them to be defined.  Nothing but the engines' own launch shape: no kernel is instantiated for this entry.
+extern "C" int natinf_debug_softmax_rows(int kind, const float* S, void* P, int T, int64_t rows, natinf_stream_t stream) {
+    if (!S || !P || T <= 0 || rows <= 0 || kind < 0 || kind > 2) return NATINF_EINVAL;
+    if (kind == 0 && (T > 256 || (T % 4 && T != 16))) return NATINF_EINVAL;      // the kernels' stated contracts
+    if (kind == 1 && (T % 64 || T > 1024)) return NATINF_EINVAL;
+    if (kind == 2 && T % 64) return NATINF_EINVAL;
+    const dim3 grid((unsigned)((rows + 3) / 4));                                 // one wave per row, as every engine launches them
+    if (kind == 0) hipLaunchKernelGGL(k_softmax_rows, grid, dim3(256), 0, (hipStream_t)stream, S, (bf16*)P, T, rows);
+    else if (kind == 1) hipLaunchKernelGGL(k_softmax_rows_1k, grid, dim3(256), 0, (hipStream_t)stream, S, (bf16*)P, T, rows);
+    else hipLaunchKernelGGL(k_softmax_rows_wide, grid, dim3(256), 0, (hipStream_t)stream, S, (bf16*)P, T, rows);
+    return hipGetLastError() == hipSuccess ? NATINF_OK : NATINF_ELAUNCH;
+}
 
 struct natinf_vae : EngineCore {
     int Cl = 0, r = 0;
@@ -251,15 +265,9 @@ struct VaeBase : PlanBuilder {
         const int64_t S = arena.alloc((int64_t)T * T * 4), P = arena.alloc((int64_t)T * T * 2);
         TRef O = new_act(res, C), y = new_act(res, C);
         op([=](const Ctx& c) {
-            GemmArgs g = gemm_defaults();                       // q | k
-            g.a0 = c.act(h); g.a0_ld = C; g.a0_C = C; g.M = c.B * T; g.N = 2 * C; g.b = c.w<bf16>(wqk); g.b_ld = C; g.bias_n = c.w<float>(bqk);
-            g.c = c.at<bf16>(qk); g.c_ld = 2 * C;
-            launch_gemm(g, c.stream);
-            g = gemm_defaults();                                // V^T[b] = Wv h[b]^T + bv
-            g.a0 = c.w<bf16>(wv); g.a0_ld = C; g.a0_C = C; g.a_bs = 0; g.M = C; g.N = T; g.b = c.act(h); g.b_ld = C; g.b_bs = (int64_t)T * C;
-            g.bias_m = c.w<float>(bv); g.c = c.at<bf16>(vT); g.c_ld = T; g.c_bs = (int64_t)C * T; g.batch = c.B;
-            launch_gemm(g, c.stream);
-            g = gemm_defaults();                                // S[b] = q k^T / sqrt(C)
+            launch_gemm(dense(c, c.act(h), C, c.B * T, Lin{wqk, bqk}, 2 * C, ACT_NONE, c.at<bf16>(qk), OUT_BF16), c.stream);      // q | k
+            launch_gemm(vt(c, Lin{wv, bv}, C, c.act(h), T, c.at<bf16>(vT), T), c.stream);                                       // V^T[b] = Wv h[b]^T + bv
+            GemmArgs g = gemm_defaults();                       // S[b] = q k^T / sqrt(C)
             g.a0 = c.at<bf16>(qk); g.a0_ld = 2 * C; g.a0_C = C; g.a_bs = (int64_t)T * 2 * C; g.M = T; g.N = T;
             g.b = c.at<bf16>(qk) + C; g.b_ld = 2 * C; g.b_bs = (int64_t)T * 2 * C; g.scale = 1.0f / sqrtf((float)C);
             g.c = c.at<float>(S); g.c_ld = T; g.c_bs = (int64_t)T * T; g.c_mode = OUT_F32; g.batch = c.B;
@@ -270,9 +278,8 @@ struct VaeBase : PlanBuilder {
             g.a0 = c.at<bf16>(P); g.a0_ld = T; g.a0_C = T; g.a_bs = (int64_t)T * T; g.M = T; g.N = C;
             g.b = c.at<bf16>(vT); g.b_ld = T; g.b_bs = (int64_t)C * T; g.c = c.act(O); g.c_ld = C; g.c_bs = (int64_t)T * C; g.batch = c.B;
             launch_gemm(g, c.stream);
-            g = gemm_defaults();                                // y = x + O Wo^T + bo
-            g.a0 = c.act(O); g.a0_ld = C; g.a0_C = C; g.M = c.B * T; g.N = C; g.b = c.w<bf16>(wo); g.b_ld = C; g.bias_n = c.w<float>(bo);
-            g.resid = c.act(x); g.resid_ld = x.ld; g.c = c.act(y); g.c_ld = C;
+            g = dense(c, c.act(O), C, c.B * T, Lin{wo, bo}, C, ACT_NONE, c.act(y), OUT_BF16);      // y = x + O Wo^T + bo
+            g.resid = c.act(x); g.resid_ld = x.ld;
             if (pt.valid()) { g.gn_part = c.at<float>(pt.off); g.gn_quads = pt.quads; }
             const int bm = launch_gemm(g, c.stream);
             if (pt.valid()) c.part_bm[pt.id] = bm;
@@ -514,31 +521,6 @@ int natinf_vae_encode(natinf_vae_enc_t h, const float* images, float* moments, f
     const int rc = h->run(images, images, mom, B, workspace, workspace_bytes, (hipStream_t)stream);
     if (rc != NATINF_OK || !latents) return rc;
     return natinf_vae_posterior_f32(mom, latents, B, h->Cl, hw, sample, scale, shift, seed, image_index, first_index, index_stride, stream);
-}
-
-// The row kernels of the transformer and VAE engines alone (include/natinf_dit.h; tests/test_gpu_row_kernels.py).  They sit here, after the last engine, because the three
-// softmax kernels live in three files.  Nothing but the engines' own launchers / launch shapes: no kernel is instantiated for these entries.
-int natinf_debug_ln_modulate(const void* x, int x_f16, const float* shift, const float* scale, int mod_ld, void* h_bf16, void* h_fp8, float* row_scale,
-                             int D, int64_t rows, int rows_per_sample, int* form_out, natinf_stream_t stream) {
-    const bool to_bf16 = h_bf16 != nullptr, to_fp8 = h_fp8 != nullptr || row_scale != nullptr;
-    if (!x || !shift || !scale || !form_out || to_bf16 == to_fp8 || (to_fp8 && (!h_fp8 || !row_scale))) return NATINF_EINVAL;
-    if (D <= 0 || D > 1536 || D % (to_fp8 ? 128 : 64) || rows <= 0 || rows_per_sample <= 0 || mod_ld < D) return NATINF_EINVAL;
-    if ((reinterpret_cast<uintptr_t>(x) | reinterpret_cast<uintptr_t>(to_bf16 ? h_bf16 : h_fp8)) % 16) return NATINF_EINVAL;
-    if (to_bf16) *form_out = launch_ln_modulate((const float*)x, shift, scale, mod_ld, (bf16*)h_bf16, D, rows, rows_per_sample, (hipStream_t)stream, x_f16 != 0);
-    else *form_out = launch_ln_modulate_fp8((const float*)x, shift, scale, mod_ld, (uint8_t*)h_fp8, row_scale, D, rows, rows_per_sample, (hipStream_t)stream, x_f16 != 0);
-    return hipGetLastError() == hipSuccess ? NATINF_OK : NATINF_ELAUNCH;
-}
-
-int natinf_debug_softmax_rows(int kind, const float* S, void* P, int T, int64_t rows, natinf_stream_t stream) {
-    if (!S || !P || T <= 0 || rows <= 0 || kind < 0 || kind > 2) return NATINF_EINVAL;
-    if (kind == 0 && (T > 256 || (T % 4 && T != 16))) return NATINF_EINVAL;      // the kernels' stated contracts
-    if (kind == 1 && (T % 64 || T > 1024)) return NATINF_EINVAL;
-    if (kind == 2 && T % 64) return NATINF_EINVAL;
-    const dim3 grid((unsigned)((rows + 3) / 4));                                 // one wave per row, as every engine launches them
-    if (kind == 0) hipLaunchKernelGGL(k_softmax_rows, grid, dim3(256), 0, (hipStream_t)stream, S, (bf16*)P, T, rows);
-    else if (kind == 1) hipLaunchKernelGGL(k_softmax_rows_1k, grid, dim3(256), 0, (hipStream_t)stream, S, (bf16*)P, T, rows);
-    else hipLaunchKernelGGL(k_softmax_rows_wide, grid, dim3(256), 0, (hipStream_t)stream, S, (bf16*)P, T, rows);
-    return hipGetLastError() == hipSuccess ? NATINF_OK : NATINF_ELAUNCH;
 }
 
 // k_gn_fold alone (include/natinf_ncsnpp.h; tests/test_gpu_gn_kernels.py), with VaeBase::gn_stats' launch shape: grid (tps / fold, B).  quads must divide 256: with

@@ -1,6 +1,6 @@
 """Inputs, fp64 references and comparators for the row kernels tested alone (tests/test_row_kernels_host.py on the CPU, tests/test_gpu_row_kernels.py on the GPU):
-LayerNorm-modulate to bf16 (k_ln_modulate, k_ln_modulate_v4, k_ln_modulate_h8: csrc/dit_engine.inc) and to fp8 e4m3 with a scale per row (k_ln_modulate_fp8*:
-csrc/gemm_fp8.h), the row quantiser k_pack_fp8_rows, and the three row softmaxes (k_softmax_rows, k_softmax_rows_1k, k_softmax_rows_wide).  numpy only.
+LayerNorm-modulate (k_ln_modulate, k_ln_modulate_v4, k_ln_modulate_h8: csrc/transformer_rows.h) to bf16 (their RowsBf16 instances) and to fp8 e4m3 with a scale per
+row (their RowsFp8 instances), the row quantiser k_pack_fp8_rows, and the three row softmaxes (k_softmax_rows, k_softmax_rows_1k, k_softmax_rows_wide).  numpy only.
 
 u = 2^-24 is the unit roundoff of fp32 (every kernel keeps its statistics and its arithmetic in fp32).
 
@@ -108,7 +108,7 @@ def f32_to_e4m3(v, truncate=False, saturate_first=True):
 # ---- LayerNorm-modulate: cases ----------------------------------------------------------------------------------------------------------------------------------
 
 def expected_form(D, half, layout):
-    """what launch_ln_modulate / launch_ln_modulate_fp8 must choose: 0 scalar, 1 four-column, 2 eight-column"""
+    """what launch_ln_modulate must choose (either output policy): 0 scalar, 1 four-column, 2 eight-column"""
     if layout != "aligned" or D not in LN_D_VECTOR:
         return 0
     return 2 if (half and D == 1536) else 1
@@ -198,7 +198,7 @@ def _lane_sums(v, form, fp8, what):
     if form == 0 and not fp8:                                   # k_ln_modulate: lane l owns columns l + 64 i, added one by one
         for i in range(D // 64):
             s = s + v[:, 64 * i:64 * i + 64]
-    elif form == 0:                                             # k_ln_modulate_fp8: columns 2 l, 2 l + 1 of every 128; the sum adds the pair first, the squares one by one
+    elif form == 0:                                             # k_ln_modulate<RowsFp8>: columns 2 l, 2 l + 1 of every 128; the sum adds the pair first, the squares one by one
         for i in range(D // 128):
             p = v[:, 128 * i:128 * i + 128].reshape(rows, 64, 2)
             if what == "sum": s = s + (p[:, :, 0] + p[:, :, 1])
@@ -246,7 +246,7 @@ def ln_restated(c, form, fp8, mutant=None):
 
 
 def quant_restated(v, mutant=None, amax_from=None):
-    """k_pack_fp8_rows / the tail of k_ln_modulate_fp8* on fp32 rows: scale = amax / 448 (1.0 for an all-zero row), bytes = e4m3(clamp(v * (1 / scale)))"""
+    """k_pack_fp8_rows / the tail of the k_ln_modulate*<..., RowsFp8> kernels on fp32 rows: scale = amax / 448 (1.0 for an all-zero row), bytes = e4m3(clamp(v * (1 / scale)))"""
     v = np.asarray(v, F)
     amax = np.abs(v if amax_from is None else amax_from).max(axis=1, keepdims=True).astype(F)
     qs = np.where(amax > 0, amax / F(448.0), F(1.0)).astype(F)

@@ -18,7 +18,7 @@ DMA = ["k_gemm_dmaILi2ELi2ELi4ELi4ELi2ELi%dEE", "k_gemm_ringILi2ELi2ELi8ELi4ELi3
        "k_gemm_w128ILi%dEN"]
 FP8 = ["k_gemm_fp8ILb0ELi%dEE", "k_gemm_fp8ILb1ELi%dEE", "k_gemm_w128_fp8ILb0ELi%dEE", "k_gemm_w128_fp8ILb1ELi%dEE"]
 PAIRS = [(t % 7, t % 10) for t in DMA] + [(t % 3, t % 4) for t in FP8] + \
-        [("k_splitk_reduce_f32EPKf", "k_splitk_reduce_f32_guardEPKf"), ("k_patch_embedILb1EE", "k_patch_embed_guardILb1EE"), ("k_patch_embedILb0EE", "k_patch_embed_guardILb0EE")]
+        [("k_splitk_reduce_f32ILb0EE", "k_splitk_reduce_f32ILb1EE"), ("k_patch_embedILb1ELb0EE", "k_patch_embedILb1ELb1EE"), ("k_patch_embedILb0ELb0EE", "k_patch_embedILb0ELb1EE")]
 
 
 @pytest.fixture(scope="module")
@@ -57,7 +57,7 @@ def test_guarded_instance(listing, plain, guarded):
     # the report: vector atomics on global memory, at least one unsigned max and one add
     assert ops_g["global_atomic_umax"] >= 1, {k: v for k, v in ops_g.items() if "atomic" in k}
     assert all(k.startswith("global_atomic_") for k in ops_g if "atomic" in k), [k for k in ops_g if "atomic" in k]
-    if guarded != "k_patch_embed_guardILb0EE":                  # (that instance writes an fp32 stream only: tracked, never clamped or counted)
+    if guarded != "k_patch_embedILb0ELb1EE":                  # (that instance writes an fp32 stream only: tracked, never clamped or counted)
         assert ops_g["global_atomic_add"] >= 1, {k: v for k, v in ops_g.items() if "atomic" in k}
         assert ops_g["v_med3_f32"] >= 1, "the clamp"
     # the same stores, nothing more: the guard changes what is stored, not how

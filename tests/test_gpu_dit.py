@@ -58,7 +58,7 @@ def test_xl2_matches_oracle_and_batch_independent():
 
 def test_xl2_half_stream_against_the_fp32_stream():
     """natinf_set_dit_stream16 (round 6; the library's default): the residual stream in IEEE half against the fp32 stream at DiT-XL/2 size -- the direct residual
-    epilogue on 128 x 128 tiles (its 16-byte form: v_permlane16_swap) and behind the split-K reduce pass, k_ln_modulate_v4<4, 128, true>, k_patch_embed<true> --:
+    epilogue on 128 x 128 tiles (its 16-byte form: v_permlane16_swap) and behind the split-K reduce pass, k_ln_modulate_v4<4, 128, true, RowsBf16>, k_patch_embed<true, false> (csrc/transformer_rows.h) --:
     both inside the oracle bound, close to each other, and the stream is the only buffer that shrinks."""
     from oracle import dit_oracle as D
     from naturaldiffusion_amd.dit import DiTEngine

@@ -55,7 +55,7 @@ def _run_ln(c, fp8):
 
 @pytest.mark.parametrize("D,half,layout", R.ln_case_ids(False), ids=lambda v: str(v))
 def test_ln_modulate_bf16(D, half, layout):
-    """k_ln_modulate / k_ln_modulate_v4<1 | 4,128 | 6>(, true) / k_ln_modulate_h8<3>: every element within [rne_bf16(y - delta), rne_bf16(y + delta)], the constant
+    """k_ln_modulate / k_ln_modulate_v4<1,0 | 4,128 | 6,0, false | true> / k_ln_modulate_h8<3> with RowsBf16 (csrc/transformer_rows.h): every element within [rne_bf16(y - delta), rne_bf16(y + delta)], the constant
     rows equal to bf16(shift), the form the launcher chose as tests/row_kernel_cases.py::expected_form states it"""
     c = R.ln_case(D, half, layout)
     form, bits = _run_ln(c, False)
@@ -67,7 +67,7 @@ def test_ln_modulate_bf16(D, half, layout):
 
 @pytest.mark.parametrize("D,half,layout", R.ln_case_ids(True), ids=lambda v: str(v))
 def test_ln_modulate_fp8(D, half, layout):
-    """k_ln_modulate_fp8 / k_ln_modulate_fp8_v4<...> / k_ln_modulate_fp8_h8<3>: R.check_fp8 -- the row scale, half an e4m3 ulp per byte, no NaN byte, the row maximum
+    """The same kernels with RowsFp8: R.check_fp8 -- the row scale, half an e4m3 ulp per byte, no NaN byte, the row maximum
     at +-448, the all-zero rows (scale 1.0, bytes 0), the constant rows the quantised shift with no radius at all"""
     c = R.ln_case(D, half, layout)
     form, (q, s) = _run_ln(c, True)
