@@ -514,6 +514,89 @@ def calc_prdc_sharded(imgs, ref_feats, device, group=None, model=None, k: int = 
     return P.prdc(P.FeatureSet(real, device=device), P.FeatureSet(feats, device=device), k=k, group=group)
 
 
+def _nearest_table(imgs, ref, device, space: str, k: int, model):
+    """(d2 fp64 [n, k], idx int64 [n, k]) on the device: this process's images against the whole reference"""
+    from . import neighbours as N
+    from .prdc import FeatureSet
+    if space == "pixel":
+        ref = torch.as_tensor(ref)
+        if tuple(ref.shape[1:]) != tuple(imgs.shape[1:]):
+            raise ValueError(f"nearest: the reference images {tuple(ref.shape[1:])} and the generated ones {tuple(imgs.shape[1:])} differ in shape")
+        cols, rows = N.pixel_features(ref, device), N.pixel_features(imgs, device)
+    elif space == "pool3":
+        cols = _ref_features(ref, device, "nearest")
+        model = model or fid_inception(device, tuple(imgs.shape[1:3]))
+        rows = get_features(imgs, model, device)
+    else:
+        raise ValueError(f"nearest: space must be 'pixel' or 'pool3', got {space!r}")
+    return N.nearest(FeatureSet(rows, device=device), FeatureSet(cols, device=device), k=k)
+
+
+def _gather_rows_of(t: torch.Tensor, group) -> torch.Tensor:
+    """The ranks' ragged shares of rows of a 2-d tensor, all-gathered in rank order (``_gather_features``'s scheme for any dtype; the result stays on ``t``'s device)"""
+    import torch.distributed as dist
+    world, host = dist.get_world_size(group), dist.get_backend(group) != "nccl"
+    n = torch.tensor([t.shape[0]], dtype=torch.int64, device="cpu" if host else t.device)
+    ns = [torch.zeros_like(n) for _ in range(world)]
+    dist.all_gather(ns, n, group=group)
+    pad = torch.zeros(max(int(v) for v in ns), t.shape[1], dtype=t.dtype, device=n.device)
+    pad[:t.shape[0]] = t
+    parts = [torch.empty_like(pad) for _ in range(world)]
+    dist.all_gather(parts, pad, group=group)
+    return torch.cat([p[:int(c)] for p, c in zip(parts, ns)]).to(t.device)
+
+
+def _nearest_result(d2: torch.Tensor, idx: torch.Tensor, space: str, k: int) -> dict:
+    from . import neighbours as N
+    d2, idx = d2.cpu().numpy(), idx.cpu().numpy()
+    return dict(d2=d2, idx=idx, summary=N.summary(d2), space=space, k=k)
+
+
+def calc_nearest(imgs, ref, device, space: str = "pixel", k: int = 1, model=None) -> dict:
+    """The memorisation audit beside the FID table: for every image (uint8 [n, H, W, 3]) its ``k`` nearest reference images.  dict(d2 fp64 [n, k],
+    idx int64 [n, k] -- host arrays, nearest first, among equal distances the lower reference index first --, summary: ``neighbours.summary``'s min /
+    median / mean of the nearest distance and the count of exact copies, space, k).  ``space="pixel"``: ``ref`` is the training images as uint8
+    [M, H, W, 3] and d2 is the exact integer sum of squared pixel differences (values 0..255).  ``space="pool3"``: ``ref`` is what ``calc_prdc``
+    takes as ``ref_feats`` and d2 is the squared distance of the Inception features ``calc_fid`` is computed from.  The M x n distances are never
+    stored (neighbours.py; include/natinf_nn.h)."""
+    d2, idx = _nearest_table(imgs, ref, device, space, k, model)
+    return _nearest_result(d2, idx, space, k)                            # this process's images only, whatever process group exists
+
+
+def calc_nearest_sharded(imgs, ref, device, space: str = "pixel", k: int = 1, model=None, group=None) -> dict:
+    """``calc_nearest`` for a batch-sharded run: every rank measures ITS images against the whole reference (a row's neighbours depend on no other row), the
+    ranks' tables are all-gathered in rank order as ``calc_prdc_sharded`` gathers features, and every rank returns the same dict: that of one process on
+    rank 0's images, then rank 1's, ...  With ``group=None`` and no process group it is ``calc_nearest``."""
+    import torch.distributed as dist
+    d2, idx = _nearest_table(imgs, ref, device, space, k, model)
+    if dist.is_available() and dist.is_initialized() and dist.get_world_size(group) > 1:
+        d2, idx = _gather_rows_of(d2, group), _gather_rows_of(idx, group)
+    return _nearest_result(d2, idx, space, k)
+
+
+def save_neighbour_sheet(imgs, ref_imgs, idx, path, count: int = 16) -> None:
+    """One PNG of the first ``count`` images (uint8 [n, H, W, 3]), one per line, each followed by its k neighbours ``ref_imgs[idx[i, t]]`` (nearest first;
+    a slot without a neighbour, idx -1, stays black): ``count`` lines of 1 + k tiles with 2 pixels of black padding, (2 + count (H + 2)) x (2 + (1 + k) (W + 2))
+    pixels."""
+    from .ValidateNaturalInference import write_png_rgb
+    to_np = lambda v: np.asarray(v.detach().cpu() if isinstance(v, torch.Tensor) else v)
+    imgs, ref_imgs, idx = to_np(imgs), to_np(ref_imgs), to_np(idx)
+    if idx.ndim != 2 or idx.shape[0] != imgs.shape[0] or imgs.ndim != 4 or imgs.shape[1:] != ref_imgs.shape[1:] or imgs.shape[3] != 3:
+        raise ValueError("nearest: the sheet takes uint8 [n, H, W, 3] images, reference images of the same size and idx [n, k]")
+    if idx.size and (idx.min() < -1 or idx.max() >= ref_imgs.shape[0]):
+        raise ValueError("nearest: idx points outside the reference images")
+    rows, k = max(0, min(int(count), imgs.shape[0])), idx.shape[1]
+    h, w, pad = imgs.shape[1], imgs.shape[2], 2
+    sheet = np.zeros((pad + rows * (h + pad), pad + (1 + k) * (w + pad), 3), np.uint8)
+    for i in range(rows):
+        tiles = [imgs[i]] + [ref_imgs[j] if j >= 0 else None for j in idx[i]]
+        for t, tile in enumerate(tiles):
+            if tile is not None:
+                y, x = pad + i * (h + pad), pad + t * (w + pad)
+                sheet[y:y + h, x:x + w] = tile
+    write_png_rgb(sheet, path)
+
+
 def calc_kid(imgs, ref_feats, device, model=None, estimator: str = "blocks", max_block_size: int = 1024) -> dict:
     """dict(kid, std, n_blocks, estimator) of the images (uint8 [n, H, W, 3]) against the real images' pool3 features ``ref_feats`` (array or ``.npy`` path):
     the Kernel Inception Distance with the cubic kernel on the features ``calc_fid`` is computed from (kid.py; include/natinf_kid.h) -- unbiased, so the

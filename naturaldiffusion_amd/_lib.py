@@ -212,6 +212,9 @@ SIGNATURES = {
     "natinf_prdc_knn_radius": (C.c_int, [_p, _p, _i64, _p, _p, _i64, _i32, _i32, _i64, _p, _p, _i64, _p]),
     "natinf_prdc_ball_counts": (C.c_int, [_p, _p, _i64, _p, _p, _i64, _i32, _i64, _p, _p, _p, _p, _p]),
     "natinf_prdc_debug_dist2": (C.c_int, [_p, _p, _i64, _p, _p, _i64, _i32, _i64, _p, _p]),
+    # include/natinf_nn.h
+    "natinf_nn_workspace_bytes": (C.c_int64, [_i64, _i64, _i32, _i32]),
+    "natinf_nn_nearest": (C.c_int, [_p, _p, _i64, _p, _p, _i64, _i32, _i32, _i64, _p, _p, _p, _i64, _p]),
     # include/natinf_kid.h
     "natinf_kid_workspace_bytes": (C.c_int64, [_i64, _i64, _i32]),
     "natinf_kid_row_sums": (C.c_int, [_p, _i64, _i64, _p, _i64, _i64, _i32, _i64, _f64, _f64, _p, _p, _i64, _p]),

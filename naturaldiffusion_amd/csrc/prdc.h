@@ -3,6 +3,8 @@
 //   k_prdc_planes  fp32 features -> three bf16 planes hi + mid + lo == x (every residual exact in fp32) and |x_i|^2 in fp64
 //   k_prdc_knn     per row i the K_MAX smallest d2_ij over a range of column tiles, as a sorted list that stays in registers
 //   k_prdc_merge   the lists of the column splits -> the k-th smallest per row
+//   k_nn_nearest   k_prdc_knn with the column index carried through the list: per row the K_MAX smallest pairs (d2_ij, j) (include/natinf_nn.h)
+//   k_nn_merge     the pair lists of the column splits -> the k smallest pairs per row
 //   k_prdc_balls   per row i the counts #{j: d2_ij <= r2_cols[j]} and #{j: d2_ij <= r2_rows[i]}
 //   k_prdc_dist2   the same tiles written out (test hook)
 //   k_kid_sums     per row i the fp64 sum of (gamma a_i.b_j + coef0)^3 over a range of column tiles (include/natinf_kid.h)
@@ -47,7 +49,7 @@ constexpr int OPERAND_BYTES = 3 * (BM + BN) * LDS_ROW * 2;
 constexpr int STAGE_BYTES = BM * STAGE_ROW * 8;
 constexpr int LDS_BYTES = OPERAND_BYTES > STAGE_BYTES ? OPERAND_BYTES : STAGE_BYTES;
 
-enum Mode { KNN = 0, BALLS = 1, DIST = 2, KSUM = 3, LOGIT = 4 };
+enum Mode { KNN = 0, BALLS = 1, DIST = 2, KSUM = 3, LOGIT = 4, NN = 5 };
 
 struct Operands {
     const __bf16* a;        // [3][n_rows][d], plane p at a + p * a_plane
@@ -110,6 +112,25 @@ __device__ __forceinline__ void list_insert(double (&L)[K_MAX], double v) {
     }
 }
 
+// (d2, column) pairs in lexicographic order: among equal distances the lower column comes first.  An empty slot is (+inf, -1): nothing is below it but a finite
+// distance, so a column at +inf never enters a list (a NaN never gets here: the max(0, .) of d2 turns it into 0).
+__device__ __forceinline__ bool pair_less(double v, int j, double w, int i) { return v < w || (v == w && j < i); }
+
+// list_insert for pairs: the lists the callers merge hold disjoint columns, so no pair is ever met twice
+__device__ __forceinline__ void pair_insert(double (&L)[K_MAX], int (&I)[K_MAX], double v, int j) {
+    if (pair_less(v, j, L[K_MAX - 1], I[K_MAX - 1])) {
+#pragma unroll
+        for (int s = K_MAX - 1; s > 0; --s) {
+            const bool up = pair_less(v, j, L[s - 1], I[s - 1]), here = pair_less(v, j, L[s], I[s]);
+            L[s] = up ? L[s - 1] : (here ? v : L[s]);
+            I[s] = up ? I[s - 1] : (here ? j : I[s]);
+        }
+        const bool here = pair_less(v, j, L[0], I[0]);
+        L[0] = here ? v : L[0];
+        I[0] = here ? j : I[0];
+    }
+}
+
 // Block (bx, by): rows i0 = 64 by .. of A against the column tiles [bx T / S, (bx + 1) T / S) of B, T = ceil(n_cols / 128) (DIST: the one tile bx).  The column
 // split is the fast grid index: blocks that follow each other share their rows of A, and with S a multiple of 8 one XCD sweeps one column range.  Four waves,
 // wave w owns the 32 x 64 piece at (32 (w & 1), 64 (w >> 1)) of a tile: two 32x32 accumulators.  Operands go global -> registers -> LDS, the next K tile's
@@ -121,10 +142,12 @@ __device__ __forceinline__ void list_insert(double (&L)[K_MAX], double v) {
 // a row go through LDS once and are added in a fixed order.  The order depends on the column range of the block alone, never on where the row sits in it.
 // LOGIT is DIST without the norms: the lane that holds s_ij writes z_ij = s_ij + bias[j] to row i of a staging buffer whose rows are whole tiles long
 // (ceil(n_cols / 128) * 128 doubles); columns past n_cols are not written.
+// NN is KNN with the column beside every distance: the same staged values reach the same threads, which keep (d2, j) pairs in pair_less's order.  A thread
+// does not meet its columns in ascending order (a tile's two accumulators interleave), so the tie rule is in the comparison, not in the order of arrival.
 template <int MODE>
 __device__ __forceinline__ void sweep(const Operands& op, int splits, double* __restrict__ out_f64, const double* __restrict__ r2_rows,
                                       const double* __restrict__ r2_cols, int* __restrict__ cnt_row_ball, int* __restrict__ cnt_col_ball,
-                                      double gamma = 0.0, double coef0 = 0.0, const float* __restrict__ bias = nullptr)
+                                      double gamma = 0.0, double coef0 = 0.0, const float* __restrict__ bias = nullptr, int* __restrict__ out_idx = nullptr)
 {
     __shared__ __attribute__((aligned(16))) unsigned char smem[LDS_BYTES];
     __shared__ double sNa[BM], sNb[BN], sR2c[BN];
@@ -180,6 +203,9 @@ __device__ __forceinline__ void sweep(const Operands& op, int splits, double* __
     double L[K_MAX];
 #pragma unroll
     for (int s = 0; s < K_MAX; ++s) L[s] = INFINITY;
+    int LI[K_MAX];                                              // NN: the column of L[s]
+#pragma unroll
+    for (int s = 0; s < K_MAX; ++s) LI[s] = -1;
     int n_rowball = 0, n_colball = 0;
     double my_r2 = 0.0;
     if (MODE == BALLS) my_r2 = (r2_rows && si < op.n_rows) ? r2_rows[si] : -INFINITY;
@@ -293,6 +319,7 @@ __device__ __forceinline__ void sweep(const Operands& op, int splits, double* __
                     const double v = sD[srow * STAGE_ROW + cs];
                     if (j < op.n_cols && j != skip) {
                         if (MODE == KNN) list_insert(L, v);
+                        if (MODE == NN) pair_insert(L, LI, v, (int)j);
                         if (MODE == BALLS) { n_rowball += v <= my_r2; n_colball += v <= sR2c[jl2]; }
                     }
                 }
@@ -315,6 +342,23 @@ __device__ __forceinline__ void sweep(const Operands& op, int splits, double* __
             double* o = out_f64 + ((int64_t)blockIdx.x * op.n_rows + si) * K_MAX;
 #pragma unroll
             for (int s = 0; s < K_MAX; ++s) o[s] = L[s];
+        }
+    }
+    if (MODE == NN) {
+        // as KNN: the four threads of a row hold the row's four column classes (j mod 4), disjoint at both exchanges
+#pragma unroll
+        for (int step = 1; step <= 2; step <<= 1) {
+            double P[K_MAX];
+            int PI[K_MAX];
+#pragma unroll
+            for (int s = 0; s < K_MAX; ++s) { P[s] = __shfl_xor(L[s], step); PI[s] = __shfl_xor(LI[s], step); }
+#pragma unroll
+            for (int s = 0; s < K_MAX; ++s) pair_insert(L, LI, P[s], PI[s]);
+        }
+        if (sc0 == 0 && si < op.n_rows) {
+            const int64_t o = ((int64_t)blockIdx.x * op.n_rows + si) * K_MAX;
+#pragma unroll
+            for (int s = 0; s < K_MAX; ++s) { out_f64[o + s] = L[s]; out_idx[o + s] = LI[s]; }
         }
     }
     if (MODE == KSUM) {
@@ -394,6 +438,32 @@ __global__ __launch_bounds__(THREADS) void k_prdc_merge(const double* __restrict
 #pragma unroll
     for (int s = 1; s < K_MAX; ++s) r = s == k - 1 ? L[s] : r;
     r2_out[i] = r;
+}
+
+// lists, cols: [splits][n_rows][K_MAX]
+__global__ __launch_bounds__(THREADS, 2) void k_nn_nearest(Operands op, int splits, double* __restrict__ lists, int* __restrict__ cols)
+{
+    sweep<NN>(op, splits, lists, nullptr, nullptr, nullptr, nullptr, 0.0, 0.0, nullptr, cols);
+}
+
+// one thread per row: the k smallest pairs of the splits' lists (the splits hold disjoint columns) -> d2_out, idx_out [n_rows][k]
+__global__ __launch_bounds__(THREADS) void k_nn_merge(const double* __restrict__ lists, const int* __restrict__ cols, int64_t n_rows, int splits, int k,
+                                                      double* __restrict__ d2_out, int* __restrict__ idx_out)
+{
+    const int64_t i = (int64_t)blockIdx.x * THREADS + threadIdx.x;
+    if (i >= n_rows) return;
+    double L[K_MAX];
+    int LI[K_MAX];
+#pragma unroll
+    for (int s = 0; s < K_MAX; ++s) { L[s] = INFINITY; LI[s] = -1; }
+    for (int sp = 0; sp < splits; ++sp) {
+        const int64_t o = ((int64_t)sp * n_rows + i) * K_MAX;
+#pragma unroll
+        for (int s = 0; s < K_MAX; ++s) pair_insert(L, LI, lists[o + s], cols[o + s]);
+    }
+#pragma unroll
+    for (int s = 0; s < K_MAX; ++s)
+        if (s < k) { d2_out[i * k + s] = L[s]; idx_out[i * k + s] = LI[s]; }
 }
 
 // grid (column tiles, row blocks): z_out [n_rows][ceil(n_cols / 128) * 128], columns past n_cols not written

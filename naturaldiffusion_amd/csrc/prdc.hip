@@ -1,9 +1,10 @@
-// prdc.hip -- the k-nearest-neighbour manifold metrics' kernels (prdc.h) and their C ABI (include/natinf_prdc.h); the kernel-distance row sums on the same
-// sweep (include/natinf_kid.h), and the Inception Score's row statistics on its logits (include/natinf_is.h).
+// prdc.hip -- the k-nearest-neighbour manifold metrics' kernels (prdc.h) and their C ABI (include/natinf_prdc.h); the nearest neighbours' indices
+// (include/natinf_nn.h) and the kernel-distance row sums on the same sweep (include/natinf_kid.h), and the Inception Score's row statistics on its logits (include/natinf_is.h).
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include "natinf.h"
 #include "natinf_prdc.h"
+#include "natinf_nn.h"
 #include "natinf_kid.h"
 #include "natinf_is.h"
 
@@ -125,6 +126,35 @@ int natinf_prdc_debug_dist2(const void* row_planes, const double* row_norms, int
     const prdc::Operands op = operands(row_planes, row_norms, n_rows, col_planes, col_norms, n_cols, d, self_offset);
     const dim3 grid((unsigned)((n_cols + prdc::BN - 1) / prdc::BN), (unsigned)row_blocks(n_rows));
     hipLaunchKernelGGL(prdc::k_prdc_dist2, grid, dim3(prdc::THREADS), 0, (hipStream_t)stream, op, d2_out);
+    return launched();
+}
+
+// the column ranges' lists: [list_rows][K_MAX] distances, then as many columns
+int64_t natinf_nn_workspace_bytes(int64_t n_rows, int64_t n_cols, int d, int k)
+{
+    if (!dims_ok(d, k) || !count_ok(n_rows) || !count_ok(n_cols) || k > n_cols) return NATINF_EINVAL;
+    return list_rows(n_rows) * prdc::K_MAX * (int64_t)(sizeof(double) + sizeof(int32_t));
+}
+
+int natinf_nn_nearest(const void* row_planes, const double* row_norms, int64_t n_rows,
+                      const void* col_planes, const double* col_norms, int64_t n_cols,
+                      int d, int k, int64_t self_offset, double* d2_out, int32_t* idx_out,
+                      void* workspace, int64_t workspace_bytes, natinf_stream_t stream)
+{
+    if (!operands_ok(row_planes, row_norms, n_rows, col_planes, col_norms, n_cols, d, k, self_offset) || !aligned(d2_out, 8) || !aligned(idx_out, 4) ||
+        !aligned(workspace, 256))
+        return NATINF_EINVAL;
+    if (workspace_bytes < natinf_nn_workspace_bytes(n_rows, n_cols, d, k)) return NATINF_EINVAL;
+    static_assert(NATINF_PRDC_MAX_N <= INT32_MAX && prdc::K_MAX == NATINF_PRDC_MAX_K, "natinf_nn.h and prdc.h disagree");
+    const prdc::Operands op = operands(row_planes, row_norms, n_rows, col_planes, col_norms, n_cols, d, self_offset);
+    const int splits = splits_for(n_rows, n_cols);
+    double* lists = (double*)workspace;
+    int* cols = (int*)(lists + list_rows(n_rows) * prdc::K_MAX);
+    hipStream_t s = (hipStream_t)stream;
+    hipLaunchKernelGGL(prdc::k_nn_nearest, dim3(splits, (unsigned)row_blocks(n_rows)), dim3(prdc::THREADS), 0, s, op, splits, lists, cols);
+    if (launched() != NATINF_OK) return NATINF_ELAUNCH;
+    hipLaunchKernelGGL(prdc::k_nn_merge, dim3((unsigned)((n_rows + prdc::THREADS - 1) / prdc::THREADS)), dim3(prdc::THREADS), 0, s,
+                       (const double*)lists, (const int*)cols, n_rows, splits, k, d2_out, (int*)idx_out);
     return launched();
 }
 
