@@ -574,6 +574,57 @@ def calc_nearest_sharded(imgs, ref, device, space: str = "pixel", k: int = 1, mo
     return _nearest_result(d2, idx, space, k)
 
 
+def ideal_denoiser(train_images, device="cuda:0"):
+    """The ideal (empirical-Bayes) denoiser of ``train_images`` (uint8 [N, 32, 32, 3] or centred fp32 [N, 3, 32, 32]) as a ``model_fn`` for
+    ``natural_inference`` / ``generate_sharded``: every step's x0 is the posterior mean over the training set, so every generated image collapses
+    onto a training image -- the positive control of ``calc_nearest`` (ideal.py; include/natinf_ideal.h)."""
+    from .ideal import IdealDenoiser
+    return IdealDenoiser(train_images, device=device)
+
+
+@torch.no_grad()
+def calc_denoiser_gap(model_fn, train, ts, rows, seed: int = 888, device="cuda:0", group=None, batch_size: int = 256) -> dict:
+    """How far a network's x0 prediction is from the optimal one, per noise level.  ``train``: the training images (``ideal_denoiser``'s argument), an
+    ``ideal.TrainingSet`` or an ``IdealDenoiser``; ``ts``: the levels' times; ``rows``: indices of the training images that are noised, image r with
+    ``philox_noise`` keyed by r (the same noise at every level), x_t = alpha f_r + sigma eps at the level the label fp32(t) * 999 names.  Both
+    denoisers see (x_t, labels); both outputs become x0 = (x_t - sigma out) / alpha in fp64, so a ``model_fn`` that IS the ideal denoiser has a gap
+    of exactly 0.  dict of fp64 arrays, one entry per level: ``t``; ``gap`` mean |x0_net - x0_ideal|^2 / d; ``ideal_mse`` mean |E[x0 | x_t] - f_r|^2 / d;
+    ``pmax`` the mean largest posterior weight; ``own`` the share of rows whose nearest training image is their own.  In a process group every rank
+    measures ``prdc.row_slice`` of ``rows`` and one all-reduce gives every rank the same dict."""
+    import torch.distributed as dist
+    from .ideal import IdealDenoiser, TrainingSet, levels_of_labels
+    from .prdc import row_slice
+    den = train if isinstance(train, IdealDenoiser) else IdealDenoiser(train, device=device)
+    dev, d = den.device, den.train.d
+    rows = [int(r) for r in rows]
+    if not rows or min(rows) < 0 or max(rows) >= den.train.n:
+        raise ValueError("denoiser gap: rows must be indices of training images")
+    on = dist.is_available() and dist.is_initialized() and dist.get_world_size(group) > 1
+    mine = [rows[i] for i in (row_slice(len(rows), dist.get_rank(group), dist.get_world_size(group)) if on else range(len(rows)))]
+    ts = np.asarray(ts, np.float64).reshape(-1)
+    sums = torch.zeros(len(ts), 4, dtype=torch.float64, device=dev)
+    for b0 in range(0, len(mine), batch_size):
+        batch = mine[b0:b0 + batch_size]
+        f = den.train.feats[torch.as_tensor(batch, device=dev)].view(-1, 3, 32, 32)
+        eps = philox_noise(batch, (3, 32, 32), seed, dev)
+        for li, t in enumerate(ts):
+            labels = torch.full((len(batch),), float(np.float32(t) * np.float32(999)), dtype=torch.float32, device=dev)
+            alpha, sigma = (float(v[0]) for v in levels_of_labels(labels[:1]))
+            x = (alpha * f.double() + sigma * eps.double()).float()
+            recover = lambda out: (x.double() - sigma * out.double()) / alpha
+            x0_mean, out_ideal, st = den._run(x, labels, return_stats=True)
+            gap = (recover(model_fn(x, labels)) - recover(out_ideal.view(x.shape))).reshape(len(batch), -1).pow(2).sum(1) / d
+            mse = (x0_mean.double() - f.reshape(len(batch), -1).double()).pow(2).sum(1) / d
+            own = (st["nearest"] == torch.as_tensor(batch, device=dev)).double()
+            sums[li] += torch.stack([gap.sum(), mse.sum(), st["pmax"].sum(), own.sum()])
+    if on:
+        host = dist.get_backend(group) != "nccl"
+        sums = sums.cpu() if host else sums
+        dist.all_reduce(sums, group=group)
+    s = sums.cpu().numpy() / len(rows)
+    return dict(t=ts, gap=s[:, 0], ideal_mse=s[:, 1], pmax=s[:, 2], own=s[:, 3])
+
+
 def save_neighbour_sheet(imgs, ref_imgs, idx, path, count: int = 16) -> None:
     """One PNG of the first ``count`` images (uint8 [n, H, W, 3]), one per line, each followed by its k neighbours ``ref_imgs[idx[i, t]]`` (nearest first;
     a slot without a neighbour, idx -1, stays black): ``count`` lines of 1 + k tiles with 2 pixels of black padding, (2 + count (H + 2)) x (2 + (1 + k) (W + 2))

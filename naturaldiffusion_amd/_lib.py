@@ -221,6 +221,11 @@ SIGNATURES = {
     # include/natinf_is.h
     "natinf_is_workspace_bytes": (C.c_int64, [_i64, _i32, _i32]),
     "natinf_is_row_stats": (C.c_int, [_p, _i64, _i64, _p, _i64, _i32, _i32, _p, _p, _p, _p, _p, _p, _i64, _p]),
+    # include/natinf_ideal.h
+    "natinf_ideal_tplanes": (C.c_int, [_p, _i64, _i32, _p, _p]),
+    "natinf_ideal_workspace_bytes": (C.c_int64, [_i64, _i64, _i32]),
+    "natinf_ideal_posterior_mean": (C.c_int, [_p, _p, _i64, _p, _p, _p, _i64, _i32, _i64, _p, _p, _p, _p, _p, _p, _p, _p, _p, _i64, _p]),
+    "natinf_ideal_debug_weights": (C.c_int, [_p, _p, _i64, _p, _p, _i64, _i32, _i64, _p, _p, _p, _i64, _p]),
 }
 
 for _name, (_res, _args) in SIGNATURES.items():

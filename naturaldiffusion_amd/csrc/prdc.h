@@ -11,6 +11,7 @@
 //   k_kid_merge    the partial sums of the column splits, added in ascending split order
 //   k_is_logits    the same tiles as z_ij = a_i.w_j + bias_j, written to a staging buffer (include/natinf_is.h)
 //   k_is_rows      per staged row its log-sum-exp, negative entropy and first largest class, and the rows' fixed-point class probabilities added per class
+//   (ideal.h, included behind this file, builds the ideal denoiser on the sweep: its weighted sum is sweep<PART>; include/natinf_ideal.h)
 //
 // d2_ij = max(0, (|a_i|^2 + |b_j|^2) - 2 a_i.b_j) in fp64.  a_i.b_j is six bf16 MFMA passes (lo.hi, hi.lo, mid.mid, mid.hi, hi.mid, hi.hi: the small
 // terms first; the three dropped products are below 2^-26 of |a_k b_k|) whose products are all exact in the fp32 accumulator; the accumulator is added
@@ -49,13 +50,15 @@ constexpr int OPERAND_BYTES = 3 * (BM + BN) * LDS_ROW * 2;
 constexpr int STAGE_BYTES = BM * STAGE_ROW * 8;
 constexpr int LDS_BYTES = OPERAND_BYTES > STAGE_BYTES ? OPERAND_BYTES : STAGE_BYTES;
 
-enum Mode { KNN = 0, BALLS = 1, DIST = 2, KSUM = 3, LOGIT = 4, NN = 5 };
+enum Mode { KNN = 0, BALLS = 1, DIST = 2, KSUM = 3, LOGIT = 4, NN = 5, PART = 6 };
+constexpr int PART_K = NATINF_IDEAL_K_RANGE;        // PART: values of k per block (include/natinf_ideal.h)
+static_assert(PART_K >= 64 && PART_K % (BK * FLUSH_TILES) == 0 && PART_K % 64 == 0, "a K range is whole flush intervals of 64 values");
 
 struct Operands {
     const __bf16* a;        // [3][n_rows][d], plane p at a + p * a_plane
-    const double* na;       // [n_rows] (KSUM, LOGIT: not read)
+    const double* na;       // [n_rows] (KSUM, LOGIT, PART: not read)
     const __bf16* b;        // [3][n_cols][d], plane p at b + p * b_plane
-    const double* nb;       // [n_cols] (KSUM, LOGIT: not read)
+    const double* nb;       // [n_cols] (KSUM, LOGIT, PART: not read)
     int64_t a_plane, b_plane;   // elements between two planes: n * d for a whole set, the whole set's for a row range taken in place
     int n_rows, n_cols, d;
     int64_t self_offset;    // column self_offset + i is left out of row i; -1: none
@@ -142,6 +145,9 @@ __device__ __forceinline__ void pair_insert(double (&L)[K_MAX], int (&I)[K_MAX],
 // a row go through LDS once and are added in a fixed order.  The order depends on the column range of the block alone, never on where the row sits in it.
 // LOGIT is DIST without the norms: the lane that holds s_ij writes z_ij = s_ij + bias[j] to row i of a staging buffer whose rows are whole tiles long
 // (ceil(n_cols / 128) * 128 doubles); columns past n_cols are not written.
+// PART is LOGIT over one range of k: block (bx, by, bz) forms the dot products of the one tile bx over k in [PART_K bz, min(PART_K (bz + 1), d)) and writes them,
+// without a bias, to slab bz of a buffer [ranges][n_rows][n_cols] (csrc/ideal.h).  PART_K is whole flush intervals, so the fp32 accumulator is flushed at the
+// same k as in an unsplit sweep, and a range's value is a function of the two rows and the range only.
 // NN is KNN with the column beside every distance: the same staged values reach the same threads, which keep (d2, j) pairs in pair_less's order.  A thread
 // does not meet its columns in ascending order (a tile's two accumulators interleave), so the tie rule is in the comparison, not in the order of arrival.
 template <int MODE>
@@ -157,10 +163,11 @@ __device__ __forceinline__ void sweep(const Operands& op, int splits, double* __
 
     const int t = threadIdx.x, lane = t & 63, w = t >> 6;
     const int i0 = blockIdx.y * BM;
-    const int ktiles = op.d / BK;
+    const int kbase = MODE == PART ? (int)blockIdx.z * PART_K : 0;
+    const int ktiles = MODE == PART ? (op.d - kbase < PART_K ? op.d - kbase : PART_K) / BK : op.d / BK;
     const int ctiles = (op.n_cols + BN - 1) / BN;
-    const int ct0 = (MODE == DIST || MODE == LOGIT) ? (int)blockIdx.x : (int)((int64_t)blockIdx.x * ctiles / splits);
-    const int ct1 = (MODE == DIST || MODE == LOGIT) ? ct0 + 1 : (int)((int64_t)(blockIdx.x + 1) * ctiles / splits);
+    const int ct0 = (MODE == DIST || MODE == LOGIT || MODE == PART) ? (int)blockIdx.x : (int)((int64_t)blockIdx.x * ctiles / splits);
+    const int ct1 = (MODE == DIST || MODE == LOGIT || MODE == PART) ? ct0 + 1 : (int)((int64_t)(blockIdx.x + 1) * ctiles / splits);
     const int64_t d = op.d;
 
     // this thread's chunks of a K tile: chunk c = t + 256 u is (row c >> 2, 16-byte column c & 3) of the stacked [3 * 64] (A) or [3 * 128] (B) rows
@@ -172,7 +179,7 @@ __device__ __forceinline__ void sweep(const Operands& op, int splits, double* __
     const bf16x8 zero = {0, 0, 0, 0, 0, 0, 0, 0};
     int f_ct = ct0, f_kt = 0;                                // the tile the next fetch loads
     auto fetch = [&]() __attribute__((always_inline)) {
-        const int k = f_kt * BK;
+        const int k = kbase + f_kt * BK;
 #pragma unroll
         for (int u = 0; u < A_CHUNKS; ++u) ra[u] = oka ? *reinterpret_cast<const bf16x8*>(ga + u * a_plane + k) : zero;
 #pragma unroll
@@ -188,7 +195,7 @@ __device__ __forceinline__ void sweep(const Operands& op, int splits, double* __
     const __bf16* pa = sA + ((w & 1) * 32 + fr) * LDS_ROW + fk;
     const __bf16* pb = sB + ((w >> 1) * 64 + fr) * LDS_ROW + fk;
 
-    if (MODE != KSUM && MODE != LOGIT && t < BM) sNa[t] = i0 + t < op.n_rows ? op.na[i0 + t] : 0.0;      // published by the first barrier below
+    if (MODE != KSUM && MODE != LOGIT && MODE != PART && t < BM) sNa[t] = i0 + t < op.n_rows ? op.na[i0 + t] : 0.0;      // published by the first barrier below
 
     f32x16 acc[2];
     double sum[2][16];
@@ -282,6 +289,19 @@ __device__ __forceinline__ void sweep(const Operands& op, int splits, double* __
                     const double z = sum[q][r] + bj;
                     sum[q][r] = 0.0;
                     if (inside && i < op.n_rows) out_f64[i * ldz + j] = z;
+                }
+            }
+            continue;
+        }
+        if (MODE == PART) {
+            double* slab = out_f64 + (int64_t)blockIdx.z * op.n_rows * op.n_cols;
+#pragma unroll
+            for (int q = 0; q < 2; ++q) {
+                const int64_t j = j0 + (w >> 1) * 64 + q * 32 + (lane & 31);
+#pragma unroll
+                for (int r = 0; r < 16; ++r) {
+                    const int64_t i = (int64_t)i0 + (w & 1) * 32 + (r & 3) + 8 * (r >> 2) + 4 * (lane >> 5);
+                    if (j < op.n_cols && i < op.n_rows) slab[i * op.n_cols + j] = sum[q][r];
                 }
             }
             continue;

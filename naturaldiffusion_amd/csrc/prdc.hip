@@ -1,5 +1,6 @@
 // prdc.hip -- the k-nearest-neighbour manifold metrics' kernels (prdc.h) and their C ABI (include/natinf_prdc.h); the nearest neighbours' indices
-// (include/natinf_nn.h) and the kernel-distance row sums on the same sweep (include/natinf_kid.h), and the Inception Score's row statistics on its logits (include/natinf_is.h).
+// (include/natinf_nn.h) and the kernel-distance row sums on the same sweep (include/natinf_kid.h), the Inception Score's row statistics on its logits (include/natinf_is.h) and the ideal denoiser, two sweeps around a row softmax
+// (ideal.h; include/natinf_ideal.h).
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include "natinf.h"
@@ -7,9 +8,11 @@
 #include "natinf_nn.h"
 #include "natinf_kid.h"
 #include "natinf_is.h"
+#include "natinf_ideal.h"
 
 namespace {
 #include "prdc.h"
+#include "ideal.h"
 
 inline int launched() { return hipGetLastError() == hipSuccess ? NATINF_OK : NATINF_ELAUNCH; }
 
@@ -63,6 +66,48 @@ inline int kid_splits(int64_t n_cols) {
 inline bool stride_ok(int64_t stride, int64_t n, int d) { return stride % 8 == 0 && stride >= n * d; }
 inline bool classes_ok(int n_classes) { return n_classes >= 1 && n_classes <= NATINF_IS_MAX_CLASSES; }
 inline int64_t staged_row(int n_classes) { return (int64_t)((n_classes + prdc::BN - 1) / prdc::BN) * prdc::BN; }     // doubles per row of staged logits
+
+// ---- the ideal denoiser's staging buffers, one chunk of rows at a time ----
+static_assert(NATINF_IDEAL_CHUNK_ROWS >= 64 && NATINF_IDEAL_CHUNK_ROWS % prdc::BM == 0, "a chunk is whole row blocks");
+inline int64_t up256(int64_t v) { return (v + 255) & ~(int64_t)255; }
+inline int64_t ideal_np(int64_t n_cols) { return (n_cols + 63) / 64 * 64; }
+inline int64_t ideal_ranges(int64_t n_cols) { return (ideal_np(n_cols) + prdc::PART_K - 1) / prdc::PART_K; }
+struct IdealLayout {
+    int64_t R, np, ranges;                                      // rows of the staging buffers (whole row blocks), padded columns, K ranges
+    int64_t uplanes, unorms, d2, wplanes, partial, bytes;       // byte offsets into the workspace
+};
+inline IdealLayout ideal_layout(int64_t n_rows, int64_t n_cols, int d) {
+    IdealLayout l;
+    const int64_t r64 = row_blocks(n_rows) * prdc::BM;
+    l.R = r64 < NATINF_IDEAL_CHUNK_ROWS ? r64 : NATINF_IDEAL_CHUNK_ROWS;
+    l.np = ideal_np(n_cols);
+    l.ranges = ideal_ranges(n_cols);
+    l.uplanes = 0;
+    l.unorms = l.uplanes + up256(3 * l.R * d * 2);
+    l.d2 = l.unorms + up256(l.R * 8);
+    l.wplanes = l.d2 + up256(l.R * n_cols * 8);
+    l.partial = l.wplanes + up256(3 * l.R * l.np * 2);
+    l.bytes = l.partial + up256(l.ranges * l.R * d * 8);
+    return l;
+}
+inline bool ideal_shape_ok(int64_t n_rows, int64_t n_cols, int d) { return dims_ok(d, 1) && count_ok(n_rows) && count_ok(n_cols); }
+
+// rows [r0, r0 + nr) of the call: planes and norms of the query rows, the d2 chunk, the row stage.  The weight planes are [3][R][np] at ws + wplanes.
+inline int ideal_stage(const IdealLayout& l, char* ws, const float* rows, const double* c, int64_t r0, int64_t nr, const void* col_planes,
+                       const double* col_norms, int64_t n_cols, int d, int64_t self_offset, double* lse_out, double* pmax_out, int32_t* nearest_out, hipStream_t s)
+{
+    hipLaunchKernelGGL(prdc::k_prdc_planes, dim3((unsigned)nr), dim3(prdc::THREADS), 0, s, (const float4*)(rows + r0 * d), (prdc::bf16x8*)(ws + l.uplanes),
+                       (double*)(ws + l.unorms), d / 8, nr * (d / 8));
+    if (launched() != NATINF_OK) return NATINF_ELAUNCH;
+    const prdc::Operands op = operands(ws + l.uplanes, (const double*)(ws + l.unorms), nr, col_planes, col_norms, n_cols, d, self_offset >= 0 ? self_offset + r0 : -1);
+    const dim3 grid((unsigned)((n_cols + prdc::BN - 1) / prdc::BN), (unsigned)row_blocks(nr));
+    hipLaunchKernelGGL(prdc::k_prdc_dist2, grid, dim3(prdc::THREADS), 0, s, op, (double*)(ws + l.d2));
+    if (launched() != NATINF_OK) return NATINF_ELAUNCH;
+    hipLaunchKernelGGL(ideal::k_ideal_rows, dim3((unsigned)(row_blocks(nr) * prdc::BM)), dim3(64), 0, s, (const double*)(ws + l.d2), (int)nr, (int)n_cols, l.np,
+                       c + r0, (__bf16*)(ws + l.wplanes), l.R * l.np, lse_out ? lse_out + r0 : nullptr, pmax_out ? pmax_out + r0 : nullptr,
+                       nearest_out ? (int*)nearest_out + r0 : nullptr);
+    return launched();
+}
 }  // namespace
 
 extern "C" {
@@ -215,6 +260,86 @@ int natinf_is_row_stats(const void* row_planes, int64_t row_plane_stride, int64_
                            (int)nr, n_classes, neg_entropy_out + r0, lse_out ? lse_out + r0 : nullptr, top_out ? (int*)top_out + r0 : nullptr,
                            (unsigned long long*)class_sums);
         if (launched() != NATINF_OK) return NATINF_ELAUNCH;
+    }
+    return NATINF_OK;
+}
+
+int natinf_ideal_tplanes(const void* planes_bf16, int64_t n, int d, void* tplanes_bf16, natinf_stream_t stream)
+{
+    if (!aligned(planes_bf16, 16) || !aligned(tplanes_bf16, 16) || !count_ok(n) || !dims_ok(d, 1)) return NATINF_EINVAL;
+    const int64_t np = ideal_np(n);
+    hipLaunchKernelGGL(ideal::k_ideal_tplanes, dim3((unsigned)(np / ideal::TP), (unsigned)(d / ideal::TP), 3), dim3(prdc::THREADS), 0, (hipStream_t)stream,
+                       (const __bf16*)planes_bf16, n, d, np, (__bf16*)tplanes_bf16);
+    return launched();
+}
+
+int64_t natinf_ideal_workspace_bytes(int64_t n_rows, int64_t n_cols, int d)
+{
+    if (!ideal_shape_ok(n_rows, n_cols, d)) return NATINF_EINVAL;
+    return ideal_layout(n_rows, n_cols, d).bytes;
+}
+
+int natinf_ideal_posterior_mean(const float* rows, const double* c, int64_t n_rows,
+                                const void* col_planes, const double* col_norms, const void* col_tplanes, int64_t n_cols,
+                                int d, int64_t self_offset,
+                                const float* x, const double* alpha, const double* sigma,
+                                float* x0_out, double* lse_out, double* pmax_out, int32_t* nearest_out, float* out,
+                                void* workspace, int64_t workspace_bytes, natinf_stream_t stream)
+{
+    if (!aligned(rows, 16) || !aligned(c, 8) || !aligned(col_tplanes, 16) || !aligned(x0_out, 4) ||
+        !operands_ok(rows, c, n_rows, col_planes, col_norms, n_cols, d, 1, self_offset))
+        return NATINF_EINVAL;
+    if (((uintptr_t)lse_out & 7) || ((uintptr_t)pmax_out & 7) || ((uintptr_t)nearest_out & 3)) return NATINF_EINVAL;
+    if (!x != !alpha || !x != !sigma || !x != !out || ((uintptr_t)x & 3) || ((uintptr_t)out & 3) || ((uintptr_t)alpha & 7) || ((uintptr_t)sigma & 7))
+        return NATINF_EINVAL;
+    if (!aligned(workspace, 256) || workspace_bytes < natinf_ideal_workspace_bytes(n_rows, n_cols, d)) return NATINF_EINVAL;
+    const IdealLayout l = ideal_layout(n_rows, n_cols, d);
+    char* ws = (char*)workspace;
+    hipStream_t s = (hipStream_t)stream;
+    // a chunk's launches are enqueued behind each other, the next chunk's behind those: one set of staging buffers
+    for (int64_t r0 = 0; r0 < n_rows; r0 += NATINF_IDEAL_CHUNK_ROWS) {
+        const int64_t nr = n_rows - r0 < NATINF_IDEAL_CHUNK_ROWS ? n_rows - r0 : NATINF_IDEAL_CHUNK_ROWS;
+        const int rc = ideal_stage(l, ws, rows, c, r0, nr, col_planes, col_norms, n_cols, d, self_offset, lse_out, pmax_out, nearest_out, s);
+        if (rc != NATINF_OK) return rc;
+        // mean = W . F on the sweep's tiles: rows = the weight planes, columns = the d rows of the transposed training set, K = np
+        prdc::Operands op = operands(ws + l.wplanes, nullptr, nr, col_tplanes, nullptr, d, (int)l.np, -1);
+        op.a_plane = l.R * l.np; op.b_plane = (int64_t)d * l.np;
+        const dim3 grid((unsigned)((d + prdc::BN - 1) / prdc::BN), (unsigned)row_blocks(nr), (unsigned)l.ranges);
+        hipLaunchKernelGGL(ideal::k_ideal_part, grid, dim3(prdc::THREADS), 0, s, op, (double*)(ws + l.partial));
+        if (launched() != NATINF_OK) return NATINF_ELAUNCH;
+        hipLaunchKernelGGL(ideal::k_ideal_merge, dim3((unsigned)((nr * d + prdc::THREADS - 1) / prdc::THREADS)), dim3(prdc::THREADS), 0, s,
+                           (const double*)(ws + l.partial), nr, d, (int)l.ranges, x ? x + r0 * d : nullptr, x ? alpha + r0 : nullptr, x ? sigma + r0 : nullptr,
+                           x0_out + r0 * d, out ? out + r0 * d : nullptr);
+        if (launched() != NATINF_OK) return NATINF_ELAUNCH;
+    }
+    return NATINF_OK;
+}
+
+int natinf_ideal_debug_weights(const float* rows, const double* c, int64_t n_rows,
+                               const void* col_planes, const double* col_norms, int64_t n_cols,
+                               int d, int64_t self_offset, float* w_out, void* planes_out,
+                               void* workspace, int64_t workspace_bytes, natinf_stream_t stream)
+{
+    if (!aligned(rows, 16) || !aligned(c, 8) || !aligned(w_out, 4) || ((uintptr_t)planes_out & 15) ||
+        !operands_ok(rows, c, n_rows, col_planes, col_norms, n_cols, d, 1, self_offset))
+        return NATINF_EINVAL;
+    if (n_rows * n_cols > ((int64_t)1 << 20)) return NATINF_EINVAL;
+    if (!aligned(workspace, 256) || workspace_bytes < natinf_ideal_workspace_bytes(n_rows, n_cols, d)) return NATINF_EINVAL;
+    const IdealLayout l = ideal_layout(n_rows, n_cols, d);
+    char* ws = (char*)workspace;
+    hipStream_t s = (hipStream_t)stream;
+    for (int64_t r0 = 0; r0 < n_rows; r0 += NATINF_IDEAL_CHUNK_ROWS) {
+        const int64_t nr = n_rows - r0 < NATINF_IDEAL_CHUNK_ROWS ? n_rows - r0 : NATINF_IDEAL_CHUNK_ROWS;
+        const int rc = ideal_stage(l, ws, rows, c, r0, nr, col_planes, col_norms, n_cols, d, self_offset, nullptr, nullptr, nullptr, s);
+        if (rc != NATINF_OK) return rc;
+        hipLaunchKernelGGL(ideal::k_ideal_wdebug, dim3((unsigned)((nr * n_cols + prdc::THREADS - 1) / prdc::THREADS)), dim3(prdc::THREADS), 0, s,
+                           (const __bf16*)(ws + l.wplanes), l.R * l.np, nr, (int)n_cols, l.np, w_out + r0 * n_cols);
+        if (launched() != NATINF_OK) return NATINF_ELAUNCH;
+        if (planes_out) {                                       // plane p's rows [r0, r0 + nr) of [3][n_rows][np]
+            for (int p = 0; p < 3; ++p)
+                if (hipMemcpyAsync((__bf16*)planes_out + (p * n_rows + r0) * l.np, (const __bf16*)(ws + l.wplanes) + p * l.R * l.np, nr * l.np * 2,
+                                   hipMemcpyDeviceToDevice, s) != hipSuccess) { (void)hipGetLastError(); return NATINF_ELAUNCH; }
+        }
     }
     return NATINF_OK;
 }
