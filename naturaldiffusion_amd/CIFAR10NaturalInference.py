@@ -625,6 +625,39 @@ def calc_denoiser_gap(model_fn, train, ts, rows, seed: int = 888, device="cuda:0
     return dict(t=ts, gap=s[:, 0], ideal_mse=s[:, 1], pmax=s[:, 2], own=s[:, 3])
 
 
+@torch.no_grad()
+def fit_coeff_matrix(model_fn, init_path, teacher, sample_count: int, out_path=None, seed: int = 888, *, holdout: Optional[int] = None,
+                     device="cuda:0", **fit_kw) -> dict:
+    """Fit the coefficient matrix in ``init_path`` to a teacher run (``teacher``: the path of a matrix file or a (C, B, node) triple, deterministic, with
+    a node at the end of every fitted row) on ``sample_count`` images and write it to ``out_path`` (``coeffgen.save_coeff_matrix``: it loads through
+    ``coeff.load_coeff_npz`` like a shipped file).  The noise of image i is ``philox_noise`` keyed by its global index i, as ``generate_sharded`` draws
+    it.  ``fit_kw``: ``fit.fit_matrix``'s rows, order, ridge, constraint, batch_size, t_tol.  -> ``fit_matrix``'s report, with ``C``, ``B``, ``node``
+    and, for ``holdout`` > 0 (default: ``sample_count``), ``holdout``: dict(n, indices (first, last), init_mse, fit_mse, ratio) -- the final mean
+    squared difference to the teacher of the init matrix and of the fitted one on ``holdout`` images of fresh indices ``sample_count ...``: what the fit
+    is worth on images it has not seen (a fitted row is optimal on the fitting images only)."""
+    from . import fit as F
+    from .coeffgen import save_coeff_matrix
+    init = load_coeff_npz(init_path)
+    teacher = load_coeff_npz(teacher) if isinstance(teacher, (str, os.PathLike)) else teacher
+    n, n_hold = int(sample_count), int(sample_count if holdout is None else holdout)
+    if n < 1 or n_hold < 0:
+        raise ValueError("fit_coeff_matrix: sample_count >= 1 and holdout >= 0")
+    checked = {k: fit_kw[k] for k in ("rows", "order", "ridge", "constraint", "batch_size", "t_tol") if k in fit_kw}
+    F._check_fit_args(init, teacher, checked.get("rows"), checked.get("order"), checked.get("ridge", 0.0), checked.get("constraint", "marginal"),
+                      checked.get("batch_size", 256), checked.get("t_tol", 1e-6))           # refusals before the first draw
+    noise = philox_noise(range(n), (3, 32, 32), seed, device)
+    C, B, node, report = F.fit_matrix(model_fn, init, teacher, noise, seed=seed, **fit_kw)
+    report.update(C=C, B=B, node=node)
+    if n_hold:
+        held = philox_noise(range(n, n + n_hold), (3, 32, 32), seed, device)
+        kw = {k: fit_kw[k] for k in ("batch_size", "t_tol") if k in fit_kw}
+        m_fit, m_init = F.final_mse(model_fn, [(C, B, node), init], teacher, held, seed=seed, **kw)
+        report["holdout"] = dict(n=n_hold, indices=(n, n + n_hold - 1), init_mse=m_init, fit_mse=m_fit, ratio=m_fit / m_init if m_init > 0 else float("nan"))
+    if out_path is not None:
+        save_coeff_matrix(out_path, C, B, node)
+    return report
+
+
 def save_neighbour_sheet(imgs, ref_imgs, idx, path, count: int = 16) -> None:
     """One PNG of the first ``count`` images (uint8 [n, H, W, 3]), one per line, each followed by its k neighbours ``ref_imgs[idx[i, t]]`` (nearest first;
     a slot without a neighbour, idx -1, stays black): ``count`` lines of 1 + k tiles with 2 pixels of black padding, (2 + count (H + 2)) x (2 + (1 + k) (W + 2))

@@ -226,6 +226,8 @@ SIGNATURES = {
     "natinf_ideal_workspace_bytes": (C.c_int64, [_i64, _i64, _i32]),
     "natinf_ideal_posterior_mean": (C.c_int, [_p, _p, _i64, _p, _p, _p, _i64, _i32, _i64, _p, _p, _p, _p, _p, _p, _p, _p, _p, _i64, _p]),
     "natinf_ideal_debug_weights": (C.c_int, [_p, _p, _i64, _p, _p, _i64, _i32, _i64, _p, _p, _p, _i64, _p]),
+    # include/natinf_fit.h
+    "natinf_fit_gram_f64": (C.c_int, [_p, _i64, C.POINTER(C.c_int32), _i32, _p, _p, _i64, _i64, _p, _p]),
 }
 
 for _name, (_res, _args) in SIGNATURES.items():
