@@ -191,6 +191,54 @@ int natinf_step_f64hist_x0fix(const float* x_k, const float* model_out, const fl
                               float known_alpha_f32, float known_std_f32, uint32_t known_column,
                               int mode, double ratio, double max_val, double* s_out, natinf_stream_t stream);
 
+/* Super-resolution on the CIFAR10 form: the predicted x0 of every image projected onto the pictures whose s x s block averages are a given
+ * low-resolution picture, x0 <- x0 + A+(low - A x0) with A the block average and A+ pixel replication (the range-null-space correction of DDNM,
+ * Wang et al. 2022).  The projection on its own, in place on x0 [n_images][elems_per_image] fp64.  An image is `channels` planes of
+ * height x width values in NCHW order, elems_per_image = channels*height*width; scale = s in {2, 4, 8}.  For block (c, I, J), x[c][r][w] the
+ * image's values and low[c][I][J] the given low-resolution value (fp64, [channels][height/s][width/s]):
+ *
+ *   r_j  = x[c][sI+j][sJ] + x[c][sI+j][sJ+1] + ... + x[c][sI+j][sJ+s-1]     left to right, plain fp64 adds, started from the first element
+ *   S    = r_0 + r_1 + ... + r_{s-1}                                          top to bottom, likewise (no zero seed in either sum)
+ *   m    = S * 2^(-2 log2 s)                                                  one fp64 multiply (exact unless it underflows)
+ *   d    = low[c][I][J] - m
+ *   y[e] = x[e] + d          for every element e of the block; a NaN result is stored as 0x7FF8000000000000
+ *   r    = max over the image's blocks of |d|, compared as the 64-bit patterns of |d| (a NaN pattern sorts above +inf); a NaN maximum is that
+ *          same quiet NaN
+ *
+ * No operation is fused.  The row-then-column order is part of the definition (a thread may own a block row without changing a bit), and r is
+ * an integer maximum, so nothing depends on the order in which threads arrive: no float atomics, no global atomics, no workspace.
+ * r_out: NULL or [n_images] fp64, how far the image's block means were from the data.  low_image_stride: elems_per_image / s^2 (one picture per
+ * image of the call) or 0 (one picture for every image).  One workgroup per image; the image lives in LDS, so elems_per_image <= 8192.  `width`
+ * need not be a multiple of 4: an element quad may straddle rows and blocks.
+ * NATINF_EINVAL, nothing launched: x0 or low NULL, n_images <= 0, scale not 2, 4 or 8, channels, height or width <= 0, height or width not a
+ * multiple of scale, channels*height*width not a multiple of 4 or > 8192, low_image_stride neither 0 nor channels*height*width / s^2. */
+int natinf_x0_project_f64(double* x0, const double* low, double* r_out, int64_t n_images, int channels, int height, int width, int scale,
+                          int64_t low_image_stride, natinf_stream_t stream);
+
+/* natinf_step_f64hist_noise with that projection between the denoiser and the history, in one launch and without a workspace: one workgroup
+ * per image computes the image's raw x0 into LDS (it is never written to memory), finds the block residuals d, and then, per element,
+ *
+ *   hist[k] <- y                 byte for byte natinf_x0_project_f64 applied to the hist[k] natinf_step_f64hist_noise writes
+ *   acc     = sum over terms t of hist[idx[t]] * val[t], then + y * c_diag      (the diagonal term uses the projected value)
+ *   x_next  = (float)acc + (float)nacc
+ *
+ * everything else operation for operation natinf_step_f64hist_noise's.  Every sampler the matrices express is linear in the x0_j, so "matrix X
+ * plus this projection" is the classical solver X run as DDNM, and every history row satisfies A x0_j = low up to rounding.  A deterministic
+ * matrix goes through as a one-term noise row (column 0, val_b[0] = fp32(B[k,0])).  There are no known pixels here: the projection is not
+ * composed with the inpainting, colorization or correction entries.  r_out as above.
+ * NATINF_EINVAL, nothing launched: every refusal of natinf_step_f64hist_noise for its own arguments, and every refusal of
+ * natinf_x0_project_f64 for low / channels / height / width / scale / low_image_stride, with channels*height*width != elems_per_image
+ * refused too.  All of them are pure argument checks: a refusal touches no device. */
+int natinf_step_f64hist_project(const float* x_k, const float* model_out, const float* noise,
+                                double* hist, float* x_next,
+                                const int32_t* idx, const double* val, int n_terms, double c_diag,
+                                const int32_t* idx_b, const float* val_b, int n_b,
+                                int k, double alpha, double sigma, float std_f32,
+                                uint64_t seed, const int64_t* image_index, int64_t first_index, int64_t index_stride,
+                                int64_t elems_per_image, int64_t E,
+                                const double* low, int64_t low_image_stride, int channels, int height, int width, int scale,
+                                double* r_out, natinf_stream_t stream);
+
 /* Colorization on the CIFAR10 form: the gray channel of a rotated colour space overwritten with the gray data diffused to the
  * current noise level (deps/score_sde_pytorch/controllable_generation.py:85-181, get_pc_colorizer; :142 with mask = (1, 0, 0)).
  * An image is three planes of P = elems_per_image / 3 elements (NCHW).  The blend on its own, pixel p of image i, with

@@ -19,7 +19,7 @@ from . import _lib
 from ._lib import lib, check, ptr, stream_ptr
 from .coeff import load_coeff_npz, SparseRows
 from .jobs import KnownRows, check_row_count, gather_known, host_mask, mask_table  # noqa: F401  (gather_known: importable from here as before)
-from .sampler import CifarNI, check_x0_fix, decouple0_host, vp_std_f32
+from .sampler import CifarNI, check_project, check_x0_fix, decouple0_host, downsample_host, vp_std_f32
 
 root_path = Path(__file__).resolve().parent.parent
 
@@ -148,6 +148,53 @@ def prepare_gray(gray, sample_count: int, known_final: str = "mean") -> torch.Te
     return torch.from_numpy(np.ascontiguousarray(decouple0_host(gf.contiguous().numpy()))).reshape(gf.shape[0], -1)
 
 
+IMAGE_SHAPE = (3, 32, 32)
+
+
+def _check_sr_job(lowres, sr_scale, sr_final: str, *, seed, x0_fix=None, conditioned: bool = False) -> int:
+    """The super-resolution arguments of a job, checked on the host -> the scale (0: off).  ``lowres`` and ``sr_scale`` come together."""
+    if sr_final not in ("step", "x0"):
+        raise ValueError('sr_final must be "step" or "x0"')
+    if (lowres is None) != (sr_scale is None):
+        raise ValueError("super-resolution needs both lowres= and sr_scale=")
+    if sr_scale is None and sr_final != "step":
+        raise ValueError('sr_final="x0" belongs to super-resolution (lowres= and sr_scale=)')
+    return check_project(sr_scale, IMAGE_SHAPE, seed=seed, elems_per_image=3 * 32 * 32, x0_fix=x0_fix, conditioned=conditioned)
+
+
+def downsample_images(images, sr_scale: int) -> torch.Tensor:
+    """The low-resolution rows of pictures -> fp64 [K, 3*(32/s)^2] on the CPU, the s x s block averages in ``sampler.downsample_host``'s order: how a
+    caller (or a test) makes ``lowres`` from a picture.  ``images``: uint8 [K, 32, 32, 3] (mapped by ``u8_to_centered``) or centred fp32 [K, 3, 32, 32]."""
+    images = torch.as_tensor(images).cpu()
+    if images.dtype == torch.uint8 and images.dim() == 4 and tuple(images.shape[1:]) == (32, 32, 3):
+        f = u8_to_centered(images.permute(0, 3, 1, 2))
+    elif images.dtype == torch.float32 and images.dim() == 4 and tuple(images.shape[1:]) == (3, 32, 32):
+        f = images
+    else:
+        raise ValueError("images must be uint8 [K, 32, 32, 3] or fp32 [K, 3, 32, 32] (centred)")
+    low = downsample_host(f.contiguous().numpy().reshape(f.shape[0], -1), IMAGE_SHAPE, sr_scale)
+    return torch.from_numpy(np.ascontiguousarray(low))
+
+
+def prepare_lowres(lowres, sr_scale: int, sample_count: int) -> torch.Tensor:
+    """The super-resolution argument of ``generate_sharded`` -> fp64 [K, 3*(32/s)^2] on the CPU, K ``sample_count`` (row i belongs to global image index
+    i) or 1 (shared by every image).  ``lowres``: uint8 [K, 32/s, 32/s, 3] (mapped by ``u8_to_centered``) or fp32 / fp64 [K, 3, 32/s, 32/s] centred
+    (``downsample_images`` of a picture, reshaped, is one).  Pure host code: every refusal comes before any GPU call."""
+    s = check_project(sr_scale, IMAGE_SHAPE, elems_per_image=3 * 32 * 32)
+    if lowres is None or not s:
+        raise ValueError("super-resolution needs both lowres= and sr_scale=")
+    n = 32 // s
+    lowres = torch.as_tensor(lowres).cpu()
+    if lowres.dtype == torch.uint8 and lowres.dim() == 4 and tuple(lowres.shape[1:]) == (n, n, 3):
+        lf = u8_to_centered(lowres.permute(0, 3, 1, 2)).to(torch.float64)
+    elif lowres.dtype in (torch.float32, torch.float64) and lowres.dim() == 4 and tuple(lowres.shape[1:]) == (3, n, n):
+        lf = lowres.to(torch.float64)
+    else:
+        raise ValueError(f"lowres must be uint8 [K, {n}, {n}, 3] or fp32 / fp64 [K, 3, {n}, {n}] (centred)")
+    check_row_count("lowres", lf, sample_count)
+    return lf.reshape(lf.shape[0], -1).contiguous()
+
+
 class BatchLanes:
     """The batch pipeline of ``natural_inference_tx`` / ``generate_sharded``: the batches of a generation job are independent
     trajectories (reference loop :287-309), so consecutive batches go to ``len(models)`` lanes -- one HIP stream, one denoiser handle and
@@ -156,12 +203,15 @@ class BatchLanes:
     images stay on the device until ``finish``; at most ``depth`` batches per lane are enqueued ahead of the GPU.  ``seed`` keys the noise a
     stochastic matrix injects after each step (``CifarNI``), per image by the global indices ``submit`` gets.  ``x0_fix`` / ``x0_ratio`` /
     ``x0_max``: the x0 correction every lane's sampler applies (``CifarNI``: "clip" or "dynamic" thresholding of each step's predicted x0);
-    a bad value is a ValueError before any GPU call."""
+    a bad value is a ValueError before any GPU call.  ``sr_scale``: super-resolution (``CifarNI``: every step's predicted x0 projected onto the
+    low-resolution picture ``submit`` gets as ``low``); refused together with ``x0_fix``, likewise on the host."""
 
     def __init__(self, models, C, B, node, device, depth: int = 2, seed: Optional[int] = None,
-                 x0_fix: Optional[str] = None, x0_ratio: float = 0.995, x0_max: float = 1.0):
+                 x0_fix: Optional[str] = None, x0_ratio: float = 0.995, x0_max: float = 1.0, sr_scale: Optional[int] = None):
         check_x0_fix(x0_fix, x0_ratio, x0_max, seed=seed, elems_per_image=3 * 32 * 32)
+        check_project(sr_scale, IMAGE_SHAPE, seed=seed, elems_per_image=3 * 32 * 32, x0_fix=x0_fix)
         self.x0 = dict(x0_fix=x0_fix, x0_ratio=x0_ratio, x0_max=x0_max) if x0_fix is not None else {}
+        self.sr = dict(sr_scale=sr_scale, image_shape=IMAGE_SHAPE) if sr_scale is not None else {}
         _lib.require_gpu()
         self.device = torch.device(device)
         self.coeff = (C, B, node)
@@ -178,18 +228,29 @@ class BatchLanes:
 
     def _sampler(self, k: int, n: int) -> CifarNI:
         if n not in self.samplers[k]:
-            self.samplers[k][n] = CifarNI(*self.coeff, n * 3 * 32 * 32, device=self.device, seed=self.seed, elems_per_image=3 * 32 * 32, **self.x0)
+            self.samplers[k][n] = CifarNI(*self.coeff, n * 3 * 32 * 32, device=self.device, seed=self.seed, elems_per_image=3 * 32 * 32, **self.x0, **self.sr)
         return self.samplers[k][n]
 
-    def submit(self, n: int, noise=None, noise_fn=None, index=None, known=None, mask=None, known_final: str = "mean", gray_u=None) -> torch.Tensor:
+    def submit(self, n: int, noise=None, noise_fn=None, index=None, known=None, mask=None, known_final: str = "mean", gray_u=None,
+               low=None, sr_final: str = "step") -> torch.Tensor:
         """One batch of ``n`` images: ``noise`` (drawn on the CALLER's current stream) or ``noise_fn()`` (called on the lane's stream).
         ``index``: the images' global indices, which key the noise a stochastic matrix injects -- an int64 device tensor made on the
         caller's stream, the int index of the first image, or ``(first, stride)`` (``CifarNI.step``).  ``known`` / ``mask`` (inpainting): device
-        tensors made on the caller's stream, forwarded to ``CifarNI.run``; ``gray_u`` (colorization) likewise.  Returns the uint8 [n, 32, 32, 3] DEVICE tensor the lane will fill."""
+        tensors made on the caller's stream, forwarded to ``CifarNI.run``; ``gray_u`` (colorization) likewise; ``low`` / ``sr_final`` (super-resolution, lanes made with
+        ``sr_scale``) likewise.  Returns the uint8 [n, 32, 32, 3] DEVICE tensor the lane will fill."""
         idx_t = isinstance(index, torch.Tensor)
         if gray_u is not None and self.x0:
             raise ValueError("x0_fix does not go with gray_u (colorization)")
-        inpaint = [t for t in (known, mask, gray_u) if t is not None]       # the lane is ordered behind their upload
+        if sr_final not in ("step", "x0"):
+            raise ValueError('sr_final must be "step" or "x0"')
+        if self.sr:
+            check_project(self.sr["sr_scale"], IMAGE_SHAPE, seed=self.seed, elems_per_image=3 * 32 * 32,
+                          conditioned=known is not None or mask is not None or gray_u is not None)
+            if low is None:
+                raise ValueError("lanes made with sr_scale need low= for every batch")
+        elif low is not None or sr_final != "step":
+            raise ValueError('low= and sr_final="x0" belong to lanes made with sr_scale')
+        inpaint = [t for t in (known, mask, gray_u, low) if t is not None]  # the lane is ordered behind their upload
         k = self.count % len(self.models)
         self.count += 1
         st = self.streams[k]
@@ -215,6 +276,8 @@ class BatchLanes:
                 kw = dict(known=known, mask=mask, known_final=known_final) if known is not None or mask is not None else {}
                 if gray_u is not None:
                     kw.update(gray_u=gray_u, known_final=known_final)
+                if self.sr:
+                    kw.update(low=low, sr_final=sr_final)
                 pix = _to_pixel(ni.run(self.models[k], z, index=index, **kw), 1, to_cpu=False)
                 ev = torch.cuda.Event()
                 ev.record()
@@ -254,7 +317,8 @@ def _lane_models(model_fn, streams: int, n_batches: int):
 def generate_sharded(model_fn, weight_path, sample_count: int, batch_size: int, rank: int = 0, world: int = 1,
                      seed: int = 888, device="cuda:0", streams: int = 3, to_cpu: bool = True, coeff=None,
                      known=None, mask=None, known_final: str = "mean", gray=None,
-                     x0_fix: Optional[str] = None, x0_ratio: float = 0.995, x0_max: float = 1.0):
+                     x0_fix: Optional[str] = None, x0_ratio: float = 0.995, x0_max: float = 1.0,
+                     lowres=None, sr_scale: Optional[int] = None, sr_final: str = "step"):
     """Batch-sharded generation (BASELINE config 3): this rank generates the images whose
     global index is rank, rank+world, ... in batches of ``batch_size`` -- no collective on the data path -- on the two-lane pipeline
     of ``natural_inference_tx`` (``BatchLanes``): Philox noise keyed by the GLOBAL image index drawn on the lane's own stream, uint8 images
@@ -272,10 +336,16 @@ def generate_sharded(model_fn, weight_path, sample_count: int, batch_size: int, 
     ``"dynamic"`` clamps it to, and divides it by, s = max(the ``x0_ratio`` quantile of the image's |x0|, ``x0_max``) (Imagen's dynamic thresholding, the
     reference's ``correcting_x0_fn="dynamic_thresholding"``), inside the step's launch, before the history and the sum see it.  A per-image function: image
     i stays the same bytes for any split.  It goes with ``known`` / ``mask``, not with ``gray``; ``None`` (default) is the job without the option.
+    ``lowres`` / ``sr_scale`` (super-resolution, ``prepare_lowres``): the low-resolution picture of image i -- row i, or the only row --
+    at 1 / ``sr_scale`` (2, 4 or 8) of the size; every step projects its predicted x0 onto the pictures whose block averages are that picture, inside the
+    step's launch (DDNM).  ``sr_final="step"`` returns x_N as every other job does, ``"x0"`` the last projected prediction, whose block means are the data.
+    A function of the image's own x0 and its own row: image i stays the same bytes for any split.  Not together with ``known`` / ``mask``, ``gray`` or ``x0_fix``.
     Returns (uint8 images [n_local, 32, 32, 3], their global indices [n_local] int64 on the CPU)."""
     from .shard import rank_batches
     check_x0_fix(x0_fix, x0_ratio, x0_max, seed=seed, elems_per_image=3 * 32 * 32, gray=gray is not None)
     inpaint = known is not None or mask is not None
+    if _check_sr_job(lowres, sr_scale, sr_final, seed=seed, x0_fix=x0_fix, conditioned=inpaint or gray is not None):
+        lowres = prepare_lowres(lowres, sr_scale, sample_count)
     if gray is not None:
         if inpaint:
             raise ValueError("gray (colorization) does not go with known / mask (inpainting)")
@@ -287,10 +357,12 @@ def generate_sharded(model_fn, weight_path, sample_count: int, batch_size: int, 
     dev = torch.device(device)
     if not batches:
         return torch.empty((0, 32, 32, 3), dtype=torch.uint8, device="cpu" if to_cpu else dev), torch.empty(0, dtype=torch.int64)
-    lanes = BatchLanes(_lane_models(model_fn, streams, len(batches)), C, B, node, dev, seed=seed, x0_fix=x0_fix, x0_ratio=x0_ratio, x0_max=x0_max)
-    rows = KnownRows(dev, known=known, mask=mask) if inpaint else KnownRows(dev, gray_u=gray) if gray is not None else None
+    lanes = BatchLanes(_lane_models(model_fn, streams, len(batches)), C, B, node, dev, seed=seed, x0_fix=x0_fix, x0_ratio=x0_ratio, x0_max=x0_max,
+                       sr_scale=sr_scale)
+    rows = (KnownRows(dev, known=known, mask=mask) if inpaint else KnownRows(dev, gray_u=gray) if gray is not None else
+            KnownRows(dev, low=lowres) if sr_scale is not None else None)
     for batch in batches:                                                # the batch's rows are uploaded here, on the caller's stream, in front of submit
-        kw = dict(rows.batch(batch), known_final=known_final) if rows is not None else {}
+        kw = dict(rows.batch(batch), sr_final=sr_final) if sr_scale is not None else dict(rows.batch(batch), known_final=known_final) if rows is not None else {}
         lanes.submit(len(batch), noise_fn=lambda b=batch: philox_noise(b, (3, 32, 32), seed, dev), index=(batch[0], world), **kw)   # = batch
     imgs = torch.cat(lanes.finish())
     idxs = torch.cat([torch.tensor(b, dtype=torch.int64) for b in batches])
@@ -762,7 +834,8 @@ def natural_inference_tx(batch_size: int = 500,
                          weight_path: Optional[str] = None,
                          sample_count: int = 50 * 1000, seed: int = 888, device: str = "cuda:0",
                          compute_fid: bool = True, flat_params: Optional[torch.Tensor] = None, streams: int = 3,
-                         x0_fix: Optional[str] = None, x0_ratio: float = 0.995, x0_max: float = 1.0):
+                         x0_fix: Optional[str] = None, x0_ratio: float = 0.995, x0_max: float = 1.0,
+                         lowres=None, sr_scale: Optional[int] = None, sr_final: str = "step"):
     """Reference :242-317: generate ``sample_count`` CIFAR10 images with the NI matrix at ``weight_path``
     and score them.  ``flat_params`` lets a caller supply weights directly (engine order) instead of the
     score_sde checkpoint.
@@ -774,8 +847,13 @@ def natural_inference_tx(batch_size: int = 500,
     the reference's one-after-the-other order (tests/test_gpu_ncsnpp.py; DESIGN.md section 5 for what that took).
 
     ``x0_fix`` / ``x0_ratio`` / ``x0_max``: the x0 correction of ``generate_sharded`` ("clip" or "dynamic" thresholding of every step's predicted x0;
-    DESIGN.md section 3i), refused on the host when a value is bad; ``None`` (default) is the reference's sampler."""
+    DESIGN.md section 3i), refused on the host when a value is bad; ``None`` (default) is the reference's sampler.
+
+    ``lowres`` / ``sr_scale`` / ``sr_final``: the super-resolution of ``generate_sharded``; a per-image ``lowres`` holds one row for each of the
+    ``ceil(sample_count / batch_size) * batch_size`` images the loop generates.  Refused on the host when a value is bad; ``None`` (default) is the reference's sampler."""
     check_x0_fix(x0_fix, x0_ratio, x0_max, seed=seed, elems_per_image=3 * 32 * 32)
+    if _check_sr_job(lowres, sr_scale, sr_final, seed=seed, x0_fix=x0_fix):
+        lowres = prepare_lowres(lowres, sr_scale, int(np.ceil(sample_count / batch_size)) * batch_size)
     from .ncsnpp import NCSNppEngine, load_score_sde_checkpoint
     ckpt_filename = ckpt_filename or str(root_path / "deps/score_sde_pytorch/checkpoint_8.pth")
     weight_path = weight_path or str(root_path / "weights/step_5_weight_00.npz")
@@ -788,13 +866,16 @@ def natural_inference_tx(batch_size: int = 500,
     bz = batch_size
     num = int(np.ceil(sample_count / bz))
     engine = NCSNppEngine(flat_params, max_batch=batch_size, device=device)
-    lanes = BatchLanes(_lane_models(engine, streams, num), C, B, node, device, seed=seed, x0_fix=x0_fix, x0_ratio=x0_ratio, x0_max=x0_max)   # the second lane shares the first's packed weights
+    lanes = BatchLanes(_lane_models(engine, streams, num), C, B, node, device, seed=seed, x0_fix=x0_fix, x0_ratio=x0_ratio, x0_max=x0_max,
+                       sr_scale=sr_scale)                                             # the second lane shares the first's packed weights
+    rows = KnownRows(torch.device(device), low=lowres) if sr_scale is not None else None
     torch.cuda.synchronize(torch.device(device))
     torch.manual_seed(seed)
     for ii in range(num):
         print("processing", ii)
         noise = torch.randn(bz, 3, 32, 32, dtype=torch.float32, device=device)      # the reference's stream of normals, in its order (:290)
-        lanes.submit(bz, noise=noise, index=ii * bz)                                  # (stochastic matrices: image b of batch ii is ii*bz + b)
+        kw = dict(rows.batch(range(ii * bz, ii * bz + bz)), sr_final=sr_final) if rows is not None else {}
+        lanes.submit(bz, noise=noise, index=ii * bz, **kw)                            # (stochastic matrices: image b of batch ii is ii*bz + b)
     all_batch = torch.concatenate(lanes.finish()).cpu()                                # ONE copy to the host, after the last batch
     if not compute_fid:
         return all_batch

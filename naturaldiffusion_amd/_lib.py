@@ -45,6 +45,9 @@ SIGNATURES = {
     "natinf_step_f64hist_x0fix": (C.c_int, [_p, _p, _p, _p, _p, _p, _p, _i32, _f64, _p, _p, _i32, _i32, _f64, _f64, _f32,
                                             C.c_uint64, _p, _i64, _i64, _i64, _i64, _p, _p, _i64, _i64, _f32, _f32, C.c_uint32,
                                             _i32, _f64, _f64, _p, _p]),
+    "natinf_x0_project_f64": (C.c_int, [_p, _p, _p, _i64, _i32, _i32, _i32, _i32, _i64, _p]),
+    "natinf_step_f64hist_project": (C.c_int, [_p, _p, _p, _p, _p, _p, _p, _i32, _f64, _p, _p, _i32, _i32, _f64, _f64, _f32,
+                                              C.c_uint64, _p, _i64, _i64, _i64, _i64, _p, _i64, _i32, _i32, _i32, _i32, _p, _p]),
     "natinf_color_blend_f32": (C.c_int, [_p, _p, _p, _i64, _p, _p, _f32, _f32, C.c_uint32, C.c_uint64, _p, _i64, _i64, _i64, _i64, _p]),
     "natinf_step_f64hist_colorize": (C.c_int, [_p, _p, _p, _p, _p, _p, _p, _i32, _f64, _p, _p, _i32, _i32, _f64, _f64, _f32,
                                                C.c_uint64, _p, _i64, _i64, _i64, _i64, _p, _i64, _p, _p, _f32, _f32, C.c_uint32, _p]),

@@ -799,6 +799,163 @@ __global__ __launch_bounds__(kBlock) void k_stepfix_f64(
     }
 }
 
+// ---- pieces of the x0 projection (super-resolution from a low-resolution picture, DDNM): x0 <- x0 + A+(low - A x0), A the s x s block average of
+// an NCHW image, A+ pixel replication.  One workgroup per image, the image's raw x0 in LDS as for the correction above ----
+// The LDS of a workgroup: the four planes x[i][q], each padded by kProjPad doubles, and one value per block ROW (the s consecutive elements of one
+// image row inside one block; block row br is elements br*s .. br*s + s - 1, since W is a multiple of s): first its sum, then, in the entry of a
+// block's top row, the block's residual d.  The pad puts planes two apart (2*(kCapQuads + 8) doubles) half a bank row (128 B) from each other: at
+// s = 2 neighbouring lanes read the same quad of planes 0 and 2 (then 1 and 3), which an unpadded plane stride (a multiple of 256 B) would put on
+// the same banks.
+constexpr int kProjPad = 8;
+template <int kCapQuads>
+struct ProjLds {
+    double x[4][kCapQuads + kProjPad];
+    double rs[2 * kCapQuads];                                       // elems / s block rows, s >= 2
+    unsigned long long rmax;                                        // max |d| of the image as its 64-bit pattern
+};
+// the geometry of a call: quads per image, log2 s, blocks per image row (W / s) and the exact fp64 value 2^(-2 log2 s)
+struct ProjGeom { int qpi, l2s, wb; double inv; };
+
+// r_j of block row br: its s elements added left to right, started from the first one.  A thread owns a block row: at s = 4 that is quad br
+// (consecutive lanes read consecutive 8-byte words of one plane: conflict-free), at s = 8 quads 2br and 2br + 1 (a stride of two words: the 32 lanes
+// of a ds_read_b64 group span two bank rows, 2-way), at s = 2 half of quad br / 2 (planes 0, 1 or 2, 3: conflict-free with the pad above).
+template <int kCapQuads>
+__device__ __forceinline__ double proj_row_sum(const ProjLds<kCapQuads>& L, int br, int l2s) {
+    if (l2s == 1) {
+        const int q = br >> 1, p = (br & 1) * 2;
+        return L.x[p][q] + L.x[p + 1][q];
+    }
+    int q = br << (l2s - 2);
+    double r = L.x[0][q] + L.x[1][q];
+    r = r + L.x[2][q];
+    r = r + L.x[3][q];
+    for (int i = 1; i < (1 << (l2s - 2)); ++i) {
+        ++q;
+        r = r + L.x[0][q]; r = r + L.x[1][q]; r = r + L.x[2][q]; r = r + L.x[3][q];
+    }
+    return r;
+}
+
+// The residuals of the image in L.x: block row sums (a thread per block row), then a thread per block b = (c, I, J) -- the index of its value in
+// `low` -- adds its s row sums top to bottom (rows Wb entries apart), m = S * 2^(-2 log2 s), d = low[b] - m, kept in the entry of the block's top
+// row; max |d| by an integer LDS maximum on the 64-bit patterns (a NaN pattern sorts above +inf), so arrival order cannot matter.  Begins with
+// the barrier that completes the planes and ends with the one that completes the residuals.
+template <int kCapQuads>
+__device__ __forceinline__ void x0_project_residuals(ProjLds<kCapQuads>& L, const double* __restrict__ low, ProjGeom g)
+{
+    const int tid = threadIdx.x;
+    const int nbr = (4 * g.qpi) >> g.l2s, nblk = nbr >> g.l2s, s = 1 << g.l2s;
+    if (tid == 0) L.rmax = 0ull;
+    __syncthreads();
+    for (int br = tid; br < nbr; br += kBlock) L.rs[br] = proj_row_sum(L, br, g.l2s);
+    __syncthreads();
+    uint64_t mx = 0;
+    for (int b = tid; b < nblk; b += kBlock) {
+        const unsigned grp = (unsigned)b / (unsigned)g.wb, J = (unsigned)b - grp * (unsigned)g.wb;       // grp = c * (H / s) + I
+        const int br0 = (int)((grp << g.l2s) * (unsigned)g.wb + J);
+        double S = L.rs[br0];
+        for (int j = 1; j < s; ++j) S = S + L.rs[br0 + j * g.wb];
+        const double m = S * g.inv;
+        const double d = low[b] - m;
+        L.rs[br0] = d;                                              // (no other thread reads or writes this block's entries)
+        const uint64_t key = abs_key(d);
+        mx = key > mx ? key : mx;
+    }
+    if (mx) atomicMax(&L.rmax, (unsigned long long)mx);
+    __syncthreads();
+}
+
+// r of the workgroup's image: max |d|, a NaN maximum as the one quiet NaN
+template <int kCapQuads>
+__device__ __forceinline__ double proj_r(const ProjLds<kCapQuads>& L) {
+    const uint64_t key = L.rmax;
+    return key > kInfKey ? __builtin_nan("") : __longlong_as_double((long long)key);
+}
+
+// the residual of the block that holds elements e and e + 1, e even (a block row starts at a multiple of s >= 2): row rr = c * H + r of block row
+// e / s, its block's top row rr - rr % s (H is a multiple of s)
+template <int kCapQuads>
+__device__ __forceinline__ double proj_d(const ProjLds<kCapQuads>& L, int e, ProjGeom g) {
+    const unsigned br = (unsigned)e >> g.l2s, rr = br / (unsigned)g.wb, J = br - rr * (unsigned)g.wb;
+    return L.rs[(rr & ~((1u << g.l2s) - 1u)) * (unsigned)g.wb + J];
+}
+
+// the projected quad q: y = x + d, one fp64 addition; a NaN result leaves as the one quiet NaN pattern.  A quad may straddle two block rows (s = 2)
+// and, when W is no multiple of 4, two image rows or planes: its two halves are looked up separately.
+template <int kCapQuads>
+__device__ __forceinline__ void x0_project(double (&y)[4], const ProjLds<kCapQuads>& L, int q, ProjGeom g) {
+    const double x[4] = {L.x[0][q], L.x[1][q], L.x[2][q], L.x[3][q]};
+    const double d[2] = {proj_d(L, 4 * q, g), proj_d(L, 4 * q + 2, g)};
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+        const double r = x[i] + d[i >> 1];
+        y[i] = r != r ? __builtin_nan("") : r;
+    }
+}
+
+// the projection on its own, in place: the definition the fused step is tested against.  blockIdx.x = image; lstride = 0 or blocks per image.
+template <int kCapQuads>
+__global__ __launch_bounds__(kBlock) void k_x0project_f64(double* x0, const double* __restrict__ low, double* __restrict__ r_out, int64_t lstride,
+                                                         ProjGeom g)
+{
+    __shared__ ProjLds<kCapQuads> L;
+    const int tid = threadIdx.x;
+    d2* img = reinterpret_cast<d2*>(x0) + 2 * (int64_t)blockIdx.x * g.qpi;
+    for (int q = tid; q < g.qpi; q += kBlock) {
+        const d2 a = img[2 * q], b = img[2 * q + 1];
+        L.x[0][q] = a.x; L.x[1][q] = a.y; L.x[2][q] = b.x; L.x[3][q] = b.y;
+    }
+    x0_project_residuals(L, low + (int64_t)blockIdx.x * lstride, g);
+    for (int q = tid; q < g.qpi; q += kBlock) {
+        double y[4];
+        x0_project(y, L, q, g);
+        img[2 * q] = d2{y[0], y[1]};
+        img[2 * q + 1] = d2{y[2], y[3]};
+    }
+    if (r_out && tid == 0) r_out[blockIdx.x] = proj_r(L);
+}
+
+// ------------------------------------------------------------------------------------------
+// CIFAR10 form with the x0 projection: k_stepfix_f64's shape (blockIdx.x = image; a thread owns the quads tid, tid + kBlock, ...).  The raw x0 of
+// the image goes to LDS and nowhere else; after the residuals are known each quad is projected, stored once as hist[k], and used for the diagonal
+// term; the rest is k_step_noise_f64 operation for operation.  hist[k] equals k_step_noise_f64 followed by k_x0project_f64, byte for byte.
+// ------------------------------------------------------------------------------------------
+template <int kCapQuads>
+__global__ __launch_bounds__(kBlock) void k_stepproject_f64(
+    const float4* __restrict__ x_k, const float4* __restrict__ mout, const float4* __restrict__ noise,
+    double* __restrict__ hist, float4* __restrict__ x_next,
+    const int32_t* __restrict__ idx, const double* __restrict__ val, int n_terms, double c_diag,
+    const int32_t* __restrict__ idx_b, const float* __restrict__ val_b, int n_b,
+    const int64_t* __restrict__ index, int64_t first_index, int64_t index_stride,
+    uint32_t k0, uint32_t k1, int k, double alpha, double sigma2, float stdv,
+    const double* __restrict__ low, int64_t lstride, ProjGeom g, double* __restrict__ r_out, int64_t E)
+{
+    __shared__ ProjLds<kCapQuads> L;
+    const int tid = threadIdx.x;
+    const int64_t img = blockIdx.x, v0 = img * g.qpi;
+    for (int q = tid; q < g.qpi; q += kBlock) {
+        double x0[4];
+        x0_score_f64(x0, x_k[v0 + q], mout[v0 + q], stdv, sigma2, alpha);
+        L.x[0][q] = x0[0]; L.x[1][q] = x0[1]; L.x[2][q] = x0[2]; L.x[3][q] = x0[3];
+    }
+    x0_project_residuals(L, low + img * lstride, g);
+    if (r_out && tid == 0) r_out[img] = proj_r(L);
+
+    const uint64_t gi = global_index(index, first_index, index_stride, img);
+    // the Philox key pinned in vector registers, as in k_stepfix_f64 and for its reason: left scalar, the 20 round keys hoisted out of this loop spill
+    asm("" : "+v"(k0), "+v"(k1));
+    for (int q = tid; q < g.qpi; q += kBlock) {
+        const int64_t v = v0 + q;
+        double y[4], acc[4] = {0.0, 0.0, 0.0, 0.0}, nacc[4] = {0.0, 0.0, 0.0, 0.0};
+        x0_project(y, L, q, g);
+        st_quad_f64(hist + (int64_t)k * E, v, y);
+        wsum_f64(acc, hist, idx, val, n_terms, v, E);
+        acc_f64(acc, y[0], y[1], y[2], y[3], c_diag);
+        noise_row_sum(nacc, noise, idx_b, val_b, n_b, v, gi, q, k0, k1);
+        x_next[v] = combine(acc, nacc);
+    }
+}
+
 // ---- pieces of the colorization forms: the gray channel of a rotated colour space re-noised to the level of the step's output ----
 // a 3x3 fp32 matrix carried to the kernel by value, row-major m[3*i + j] = M[i][j]: the caller's basis or its inverse, neither is hard-coded here
 struct mat3 { float m[9]; };
@@ -1242,6 +1399,25 @@ inline QuantilePos quantile_pos(double ratio, int64_t elems_per_image) {
     return QuantilePos{(unsigned)lo, std::ceil(rank) != lo, rank - lo};
 }
 
+// channels * height * width of a projection call, 0 when a factor is not positive or the product cannot be an image the kernels hold
+inline int64_t project_elems(int channels, int height, int width) {
+    constexpr int64_t cap = 4 * (int64_t)kFixQuadsMax;
+    if (channels <= 0 || height <= 0 || width <= 0 || channels > cap || height > cap || width > cap) return 0;
+    const int64_t n = (int64_t)channels * height * width;
+    return n <= cap ? n : 0;
+}
+// the x0 projection of a call: `low` given, a scale of 2, 4 or 8 dividing height and width, an image of channels * height * width elements that
+// is whole quads and fits the largest kernel instantiation, and a per-image stride of `low` that is 0 or the image's block count; fills g
+inline bool project_ok(ProjGeom& g, const double* low, int channels, int height, int width, int scale, int64_t lstride, int64_t elems_per_image) {
+    if (!low || (scale != 2 && scale != 4 && scale != 8)) return false;
+    const int64_t n = project_elems(channels, height, width);
+    if (!n || n != elems_per_image || (n & 3) || height % scale || width % scale) return false;
+    if (lstride != 0 && lstride != n / (scale * scale)) return false;
+    const int l2s = scale == 2 ? 1 : scale == 4 ? 2 : 3;
+    g = ProjGeom{(int)(n / 4), l2s, width / scale, 1.0 / (double)(scale * scale)};
+    return true;
+}
+
 // Host-side check of a small device int32 array before a launch (the noise row of natinf_step_f32prod_noise, the slots of
 // natinf_step_f32prod_noise_guided and natinf_step_f16chain_guided): every one of the n values lies in lo..hi.  They are read back, kRowChunk at a time into
 // one pinned buffer, on a private non-blocking stream of the current device: the host waits for those small copies only,
@@ -1465,6 +1641,45 @@ int natinf_step_f64hist_x0fix(const float* x_k, const float* model_out, const fl
                        (int)qpi, (uint32_t)seed, (uint32_t)(seed >> 32), k, alpha, sigma * sigma, std_f32,
                        known, mask, known_image_stride, mask_image_stride, known_alpha_f32, known_std_f32, known_column,
                        mode, p.lo, p.next, p.w, max_val, s_out, E);
+    return launched();
+}
+
+int natinf_x0_project_f64(double* x0, const double* low, double* r_out, int64_t n_images, int channels, int height, int width, int scale,
+                          int64_t low_image_stride, natinf_stream_t stream)
+{
+    const int64_t elems_per_image = project_elems(channels, height, width);
+    ProjGeom g;
+    if (!x0 || n_images <= 0 || n_images > INT32_MAX ||
+        !project_ok(g, low, channels, height, width, scale, low_image_stride, elems_per_image))
+        return NATINF_EINVAL;
+    auto kernel = g.qpi <= kFixQuadsSmall ? k_x0project_f64<kFixQuadsSmall> : k_x0project_f64<kFixQuadsMax>;
+    hipLaunchKernelGGL(kernel, dim3((unsigned)n_images), dim3(kBlock), 0, (hipStream_t)stream, x0, low, r_out, low_image_stride, g);
+    return launched();
+}
+
+int natinf_step_f64hist_project(const float* x_k, const float* model_out, const float* noise,
+                                double* hist, float* x_next,
+                                const int32_t* idx, const double* val, int n_terms, double c_diag,
+                                const int32_t* idx_b, const float* val_b, int n_b,
+                                int k, double alpha, double sigma, float std_f32,
+                                uint64_t seed, const int64_t* image_index, int64_t first_index, int64_t index_stride,
+                                int64_t elems_per_image, int64_t E,
+                                const double* low, int64_t low_image_stride, int channels, int height, int width, int scale,
+                                double* r_out, natinf_stream_t stream)
+{
+    const int64_t nvec = vec_count(E, 4);
+    ProjGeom g;
+    if (!x_k || !model_out || !noise || !hist || !x_next || !terms_ok(idx, val, n_terms) || !terms_ok(idx_b, val_b, n_b) ||
+        k < 0 || !nvec || !image_ok(elems_per_image, E) || !quad_blocks(nvec) || E / elems_per_image > INT32_MAX ||
+        !project_ok(g, low, channels, height, width, scale, low_image_stride, elems_per_image))
+        return NATINF_EINVAL;
+    // no read-back of the noise row (natinf_step_f64hist_noise): every check above is a pure argument check, no device is touched
+    auto kernel = g.qpi <= kFixQuadsSmall ? k_stepproject_f64<kFixQuadsSmall> : k_stepproject_f64<kFixQuadsMax>;
+    hipLaunchKernelGGL(kernel, dim3((unsigned)(E / elems_per_image)), dim3(kBlock), 0, (hipStream_t)stream,
+                       (const float4*)x_k, (const float4*)model_out, (const float4*)noise, hist, (float4*)x_next,
+                       idx, val, n_terms, c_diag, idx_b, val_b, n_b, image_index, first_index, index_stride,
+                       (uint32_t)seed, (uint32_t)(seed >> 32), k, alpha, sigma * sigma, std_f32,
+                       low, low_image_stride, g, r_out, E);
     return launched();
 }
 

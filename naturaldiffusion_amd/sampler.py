@@ -333,6 +333,112 @@ def x0_threshold_host(x0, mode, ratio: float = 0.995, max_val: float = 1.0):
     return y.reshape(x.shape), s
 
 
+# Super-resolution: the predicted x0 projected onto the pictures whose s x s block averages are the given low-resolution picture
+SR_SCALES = (2, 4, 8)
+SR_MAX_ELEMS = X0_FIX_MAX_ELEMS      # the same kernel shape: one workgroup holds an image's fp64 x0 in LDS
+_QNAN = np.uint64(0x7FF8000000000000)
+_INF_KEY = np.uint64(0x7FF0000000000000)
+
+
+def _sr_geometry(shape, scale):
+    """(C, H, W) and s of a projection, checked -> (C, H, W, s) as ints"""
+    if isinstance(scale, bool) or not isinstance(scale, (int, np.integer)) or int(scale) not in SR_SCALES:
+        raise ValueError("sr_scale must be 2, 4 or 8")
+    try:
+        ok = len(shape) == 3 and all(not isinstance(v, bool) and isinstance(v, (int, np.integer)) for v in shape)
+    except TypeError:
+        ok = False
+    if not ok:
+        raise ValueError("image_shape must be (channels, height, width)")
+    c, h, w, s = int(shape[0]), int(shape[1]), int(shape[2]), int(scale)
+    if c <= 0 or h <= 0 or w <= 0:
+        raise ValueError("image_shape must be positive")
+    if h % s or w % s:
+        raise ValueError(f"image_shape: height and width must be multiples of sr_scale ({s})")
+    if (c * h * w) % 4 or c * h * w > SR_MAX_ELEMS:
+        raise ValueError(f"image_shape: channels*height*width must be a multiple of 4 and <= {SR_MAX_ELEMS}")
+    return c, h, w, s
+
+
+def downsample_host(x, shape, scale) -> np.ndarray:
+    """The s x s block average A of NCHW images in numpy fp64, in the library's order (include/natinf.h, natinf_x0_project_f64): each block row added left
+    to right, the row sums top to bottom, neither sum seeded with a zero, one multiplication by 2^(-2 log2 s).  ``x``: [..., C*H*W] (or [..., C, H, W]),
+    ``shape`` = (C, H, W) -> fp64 [n, C*(H/s)*(W/s)], or 1-d for one flat image."""
+    c, h, w, s = _sr_geometry(shape, scale)
+    a = np.ascontiguousarray(x, dtype=np.float64)
+    if a.size == 0 or a.size % (c * h * w):
+        raise ValueError("downsample_host: x must hold whole images of image_shape")
+    v = a.reshape(-1, c, h // s, s, w // s, s)
+    with np.errstate(invalid="ignore", over="ignore"):
+        rows = v[..., 0]
+        for i in range(1, s):
+            rows = rows + v[..., i]                                      # [n, C, H/s, s, W/s]
+        total = rows[:, :, :, 0, :]
+        for j in range(1, s):
+            total = total + rows[:, :, :, j, :]
+        m = total * (1.0 / (s * s))
+    m = m.reshape(v.shape[0], -1)
+    return m[0] if a.ndim == 1 else m
+
+
+def x0_project_host(x0, low, shape, scale):
+    """The x0 projection in numpy fp64, operation for operation the library's (include/natinf.h, natinf_x0_project_f64): ``x0`` fp64 [n_images, C*H*W] (or
+    one flat image), ``low`` fp64 [n_images, C*(H/s)*(W/s)] or one row shared by every image -> (y like ``x0``, r fp64 [n_images], the largest |low - A x0|
+    of each image).  The CPU replay of a GPU step, and what the GPU is compared against byte for byte."""
+    c, h, w, s = _sr_geometry(shape, scale)
+    x = np.ascontiguousarray(x0, dtype=np.float64)
+    rows = x.reshape(-1, c * h * w)
+    nblk = c * (h // s) * (w // s)
+    lo = np.ascontiguousarray(low, dtype=np.float64).reshape(-1, nblk)
+    if lo.shape[0] not in (1, rows.shape[0]):
+        raise ValueError("x0_project_host: low must hold one row per image or one shared row")
+    with np.errstate(invalid="ignore", over="ignore"):
+        d = lo - downsample_host(rows, shape, scale)                     # [n, nblk]
+        up = np.broadcast_to(d.reshape(-1, c, h // s, 1, w // s, 1), (rows.shape[0], c, h // s, s, w // s, s))
+        y = rows.reshape(up.shape) + up
+    y = np.ascontiguousarray(y).reshape(rows.shape)
+    y[np.isnan(y)] = np.nan                                              # every NaN the projection produces: the one quiet pattern 0x7FF8000000000000
+    keys = np.ascontiguousarray(np.abs(d)).view(np.uint64).max(axis=1)  # non-negative doubles order as their patterns, a NaN above +inf
+    r = np.where(keys > _INF_KEY, _QNAN, keys).astype(np.uint64).view(np.float64)
+    return y.reshape(x.shape), r
+
+
+def check_project(sr_scale, image_shape, *, seed=0, elems_per_image: Optional[int] = None, fast_f32: bool = False, x0_fix=None,
+                  conditioned: bool = False, epi_later: bool = False) -> int:
+    """The argument checks of a super-resolution call, made before anything is launched -> the scale (0 for ``sr_scale=None``, which checks nothing
+    else).  ``seed`` / ``elems_per_image``: pass the sampler's own (None is refused; ``epi_later``: a missing ``elems_per_image`` may still come with the
+    step); ``conditioned``: known / mask / gray_u were given, which the projection does not go with; ``x0_fix``: the sampler's correction, likewise."""
+    if sr_scale is None:
+        return 0
+    c, h, w, s = _sr_geometry(image_shape, sr_scale)
+    if fast_f32:
+        raise ValueError("sr_scale: the fast_f32 mode has no projection")
+    if x0_fix is not None:
+        raise ValueError("sr_scale does not go with x0_fix: the two act on the same predicted x0 and are not composed")
+    if conditioned:
+        raise ValueError("sr_scale does not go with known / mask (inpainting) or gray_u (colorization)")
+    if seed is None:
+        raise ValueError("sr_scale: the step takes the noise-drawing form, which needs a seed (deterministic matrices too)")
+    if elems_per_image is None and not epi_later:
+        raise ValueError("sr_scale: elems_per_image is needed, the projection is a per-image operation")
+    if elems_per_image is not None and int(elems_per_image) != c * h * w:
+        raise ValueError(f"sr_scale: elems_per_image ({int(elems_per_image)}) must be channels*height*width of image_shape ({c * h * w})")
+    return s
+
+
+def check_low(low, n_elem: int, elems_per_image: int, scale: int, device=None) -> int:
+    """The low-resolution picture of a super-resolution step -> its image stride: flat contiguous fp64 of ``n_elem / s^2`` elements (one picture per image:
+    stride ``elems_per_image / s^2``) or ``elems_per_image / s^2`` (one picture shared by every image: stride 0)."""
+    per = int(elems_per_image) // (scale * scale)
+    if not isinstance(low, torch.Tensor) or low.dtype != torch.float64 or low.dim() != 1 or not low.is_contiguous():
+        raise ValueError("low must be a flat contiguous float64 tensor")
+    if low.numel() not in (n_elem // (scale * scale), per):
+        raise ValueError(f"low must have n_elem / s^2 ({n_elem // (scale * scale)}) or elems_per_image / s^2 ({per}) elements, not {low.numel()}")
+    if device is not None and low.device != device:
+        raise ValueError("low must be on the sampler's device")
+    return per if low.numel() == n_elem // (scale * scale) and n_elem != elems_per_image else 0
+
+
 class CifarNI:
     """x_{k+1} = fp32(sum_j C[k,j]*x0_j) + fp32(B[k,0])*noise with x0_k = ((-out/std)*sigma^2 + x_k)/alpha.
 
@@ -354,13 +460,23 @@ class CifarNI:
     quantile of the image's |x0|, ``x0_max``) (Imagen's dynamic thresholding, the reference's ``correcting_x0_fn="dynamic_thresholding"``).  Matrix
     X with it is the classical solver X with that ``correcting_x0_fn``.  It needs a ``seed`` and ``elems_per_image`` (<= 8192) like inpainting,
     goes with ``known`` / ``mask``, and not with ``fast_f32`` or ``gray_u``.  ``x0_s`` [n_step, n_images] fp64 (device) holds the thresholds used
-    (``"clip"``: ``x0_max``), row k written by step k.  ``x0_fix=None`` (default) launches exactly what the class launched without the option."""
+    (``"clip"``: ``x0_max``), row k written by step k.  ``x0_fix=None`` (default) launches exactly what the class launched without the option.
+
+    Super-resolution (``sr_scale=2 | 4 | 8`` with ``image_shape=(C, H, W)``, and ``low=`` of ``step`` and ``run``; natinf_step_f64hist_project): every step
+    projects its predicted x0 onto the pictures whose s x s block averages are ``low``, x0 <- x0 + up(low - A x0), before it enters the history and the
+    sum.  Matrix X with it is the classical solver X run as DDNM (Wang et al. 2022), and every history row has the block means of the data.  It needs a
+    ``seed`` and ``elems_per_image`` (= C*H*W <= 8192), and goes with none of ``fast_f32``, ``x0_fix``, ``known`` / ``mask`` and ``gray_u``.  ``sr_r``
+    [n_step, n_images] fp64 (device) holds the largest |low - A x0| of each image, row k written by step k: how far each step's prediction was from the
+    data.  ``sr_scale=None`` (default) launches exactly what the class launched without the option."""
 
     def __init__(self, C: np.ndarray, B: np.ndarray, node: np.ndarray, n_elem: int, device="cuda:0",
                  dense: bool = False, fast_f32: bool = False, stds=None, *, seed: Optional[int] = None,
-                 elems_per_image: Optional[int] = None, x0_fix: Optional[str] = None, x0_ratio: float = 0.995, x0_max: float = 1.0):
-        # (the correction's refusals come first: they need no GPU; elems_per_image may still come with the step)
+                 elems_per_image: Optional[int] = None, x0_fix: Optional[str] = None, x0_ratio: float = 0.995, x0_max: float = 1.0,
+                 sr_scale: Optional[int] = None, image_shape=None):
+        # (the correction's and the projection's refusals come first: they need no GPU; elems_per_image may still come with the step)
         self.x0_mode = check_x0_fix(x0_fix, x0_ratio, x0_max, seed=seed, elems_per_image=elems_per_image, fast_f32=fast_f32, epi_later=True)
+        self.sr_scale = check_project(sr_scale, image_shape, seed=seed, elems_per_image=elems_per_image, fast_f32=fast_f32, x0_fix=x0_fix, epi_later=True)
+        self.image_shape, self.sr_r = (tuple(int(v) for v in image_shape) if self.sr_scale else None), None
         self.x0_fix, self.x0_ratio, self.x0_max, self.x0_s = x0_fix, float(x0_ratio), float(x0_max), None
         _lib.require_gpu()
         if n_elem % 4:
@@ -426,7 +542,7 @@ class CifarNI:
     def step(self, k: int, x_k: torch.Tensor, model_out: torch.Tensor, noise: torch.Tensor,
              x_next: Optional[torch.Tensor] = None, index=None, elems_per_image: Optional[int] = None, *,
              known: Optional[torch.Tensor] = None, mask: Optional[torch.Tensor] = None, known_final: str = "mean",
-             gray_u: Optional[torch.Tensor] = None) -> torch.Tensor:
+             gray_u: Optional[torch.Tensor] = None, low: Optional[torch.Tensor] = None) -> torch.Tensor:
         """``index`` (stochastic matrices): the batch's global image indices -- an int64 device tensor with one entry per
         image, an int ``first`` (image i is ``first + i``) or a pair ``(first, stride)`` (image i is ``first + i*stride``);
         None = 0.  ``elems_per_image`` overrides the constructor's value for this call.
@@ -438,9 +554,20 @@ class CifarNI:
 
         ``gray_u`` (colorization): a flat fp32 device tensor of ``n_elem / 3`` elements (one row per image) or ``elems_per_image / 3`` (one
         picture for every image): latent channel 0 of the known picture (``decouple0_host``), which leaves the step, in every pixel's latent
-        channel 0, diffused to the level of x_{k+1} (``color_schedule``).  Not together with ``known`` / ``mask``."""
+        channel 0, diffused to the level of x_{k+1} (``color_schedule``).  Not together with ``known`` / ``mask``.
+
+        ``low`` (super-resolution, a sampler made with ``sr_scale``): a flat fp64 device tensor of ``n_elem / s^2`` elements (one low-resolution picture
+        per image, [C][H/s][W/s]) or ``elems_per_image / s^2`` (one picture for every image).  Not together with ``known`` / ``mask`` / ``gray_u``."""
         epi = self.epi if elems_per_image is None else int(elems_per_image)
         inpaint = known is not None or mask is not None
+        if self.sr_scale:                                                 # refusals first: conditioning, a missing or wrong elems_per_image, a bad low
+            check_project(self.sr_scale, self.image_shape, seed=self.seed, elems_per_image=epi, conditioned=inpaint or gray_u is not None)
+            _check_elems_per_image(epi, self.E)
+            if low is None:
+                raise ValueError("a sampler made with sr_scale needs low= at every step")
+            ls = check_low(low, self.E, epi, self.sr_scale, device=x_k.device)
+        elif low is not None:
+            raise ValueError("low= belongs to a sampler made with sr_scale")
         if self.x0_mode:                                                  # refusals first: gray_u, a missing or oversized elems_per_image
             check_x0_fix(self.x0_fix, self.x0_ratio, self.x0_max, seed=self.seed, elems_per_image=epi, gray=gray_u is not None)
             _check_elems_per_image(epi, self.E)
@@ -460,11 +587,21 @@ class CifarNI:
         idx, val, n = self.rows.ptrs(k)
         r = self.rows.rows[k]
         a, s = float(self.node[k, 1]), float(self.node[k, 2])
-        if inpaint or gray_u is not None or self.stochastic or self.x0_mode:    # the entries that draw noise: B's rows and the images' global indices
+        if inpaint or gray_u is not None or self.stochastic or self.x0_mode or self.sr_scale:    # the entries that draw noise: B's rows and the images' global indices
             if epi is None:
                 raise ValueError("stochastic NI matrix: elems_per_image is needed to key the injected noise")
             ib, vb, nb = self._noise_rows().ptrs(k)
             index, first, stride = image_index_args(index, self.E // epi, x_k.device)
+        if self.sr_scale:
+            n_images = self.E // epi
+            if self.sr_r is None or self.sr_r.shape[1] != n_images:
+                self.sr_r = torch.zeros((self.n_step, n_images), dtype=torch.float64, device=self.device)
+            c, h, w = self.image_shape
+            check(lib.natinf_step_f64hist_project(ptr(x_k), ptr(model_out), ptr(noise), ptr(self.hist), ptr(x_next), idx, val, n,
+                                                  r.diag, ib, vb, nb, k, a, s, self.std[k], self.seed, ptr(index), first, stride,
+                                                  epi, self.E, ptr(low), ls, c, h, w, self.sr_scale, ptr(self.sr_r[k]), stream_ptr()),
+                  "natinf_step_f64hist_project")
+            return x_next
         if self.x0_mode:                                                  # with or without known pixels: one entry
             n_images = self.E // epi
             if self.x0_s is None or self.x0_s.shape[1] != n_images:
@@ -500,22 +637,35 @@ class CifarNI:
 
     def run(self, model_fn: Callable, noise: torch.Tensor, return_all: bool = False, index=None, *,
             known: Optional[torch.Tensor] = None, mask: Optional[torch.Tensor] = None, known_final: str = "mean",
-            gray_u: Optional[torch.Tensor] = None):
+            gray_u: Optional[torch.Tensor] = None, low: Optional[torch.Tensor] = None, sr_final: str = "step"):
         """``model_fn(x [B,...] fp32, labels [B] fp32) -> out`` (raw network output).  ``index``: see ``step``.
         ``known`` / ``mask`` (inpainting; any shape holding B or 1 images, ``mask`` uint8 or bool): the first model input is ``noise``
         with the known pixels at level 0, and every step blends (``step``); with ``return_all`` entry 0 is that first input.
-        ``gray_u`` (colorization; any shape holding B or 1 gray pictures of one value per pixel): the same with the gray-channel blend."""
+        ``gray_u`` (colorization; any shape holding B or 1 gray pictures of one value per pixel): the same with the gray-channel blend.
+        ``low`` (super-resolution; fp64, any shape holding B or 1 low-resolution pictures): every step projects its x0 (``step``).  ``sr_final="step"``
+        returns x_N as every other job does; ``"x0"`` returns fp32(hist[N-1]), the last projected prediction -- what DDNM returns, and the only result
+        whose block means are the data whatever the matrix's end level (with ``return_all`` it is appended behind x_N)."""
         shape, B = noise.shape, noise.shape[0]
         noise = noise.contiguous()
         epi = self.epi if self.epi is not None else noise.numel() // B
         inpaint = known is not None or mask is not None
+        if sr_final not in ("step", "x0"):
+            raise ValueError('sr_final must be "step" or "x0"')
+        if self.sr_scale:
+            check_project(self.sr_scale, self.image_shape, seed=self.seed, elems_per_image=epi, conditioned=inpaint or gray_u is not None)
+            if low is None:
+                raise ValueError("a sampler made with sr_scale needs low=")
+        elif low is not None or sr_final != "step":
+            raise ValueError('low= and sr_final="x0" belong to a sampler made with sr_scale')
         if gray_u is not None and inpaint:
             raise ValueError("gray_u (colorization) does not go with known / mask (inpainting)")
         if self.x0_mode:
             check_x0_fix(self.x0_fix, self.x0_ratio, self.x0_max, seed=self.seed, elems_per_image=epi, gray=gray_u is not None)
         # every step goes through self.step (callers wrap it per instance, e.g. bench.py's timed replica): a column-0 matrix gets exactly the four
         # positional arguments it always got, a stochastic one index= and elems_per_image=, a conditioned trajectory its blend arguments as well
-        kw = dict(index=index, elems_per_image=epi) if self.stochastic or inpaint or gray_u is not None or self.x0_mode else {}
+        kw = dict(index=index, elems_per_image=epi) if self.stochastic or inpaint or gray_u is not None or self.x0_mode or self.sr_scale else {}
+        if self.sr_scale:
+            kw.update(low=low.reshape(-1))
         if gray_u is not None:
             kw.update(gray_u=gray_u.reshape(-1), known_final=known_final)
         elif inpaint:
@@ -530,6 +680,9 @@ class CifarNI:
             if return_all:
                 x = x.clone()
                 xs.append(x.view(shape))
+        if sr_final == "x0":
+            x = self.hist[self.n_step - 1].to(torch.float32)
+            xs.append(x.view(shape))
         return xs if return_all else x.view(shape)
 
 
