@@ -14,7 +14,12 @@
 //
 // Every expression of that contract is written ONCE, as a __device__ __forceinline__ piece that keeps
 // the named fp32 / fp64 temporaries which fix its roundings; a kernel is a short composition of pieces,
-// so a kernel with in-kernel noise cannot drift from its slab twin (DESIGN.md section 3 lists them).
+// so a kernel with in-kernel noise cannot drift from its slab twin (DESIGN.md section 3 lists them).  Whole step bodies are pieces too: a new conditioning
+// is a new piece plus a thin __global__ function, never a copied body.  The kernels' listings rest on this: kernel names, template parameters and __global__
+// parameter lists stay; pointers stay individual __restrict__ parameters, never bundled into by-value structs (after the store of hist[k] that keeps the
+// coefficient rows on wave-uniform scalar loads; ProjGeom and mat3 hold scalars only); kernels are not merged into bool-templated ones; every empty-asm pin
+// (hmulf, the Philox key of k_stepfix_f64 / k_stepproject_f64, ld_whole, color_blend's planes) stays where it is relative to its loop; the Philox kernels
+// keep one quad per thread.  The loop of k_stepfix_f64 / k_stepproject_f64 that fills the LDS planes stays in them: as a piece it changed their addressing.
 //
 // Reference lines replaced: src/CIFAR10NaturalInference.py:219-238,299-304;
 // src/ValidateNaturalInference.py:193,198-204,355,362-366; src/SD3NaturalInference.py:61-69,
@@ -111,24 +116,11 @@ __device__ __forceinline__ h8 flow_input(h8 nz, h8 m, float sig, float oms) {
     return r;
 }
 
-// ---- piece of the SD3 form with per-image guidance (fp16 chain) ----
-// the fused x0 of one 8-vector: image img's null-prompt velocity is row uncond_slot[img] of the compacted v_null (quad q of it) and
-// its scale cfg_image[img]; a negative slot = an unguided image, f = x - sig*v_text for both flag values (neither v_null nor
-// cfg_image[img] is read then).  With a slot it is the arithmetic of k_step_f16chain for the flag, in its order of fp16 roundings.
-// Both per-image values are uniform over the svec consecutive threads of an image: plain vector loads, served by one cache line.
+// the fused x0 of one 8-vector from the text and null-prompt velocities tv, uv, six fp16 roundings per element whose order is the contract: CFG on
+// the velocities, then x - sig*v (kVelocityCfg), or CFG on the two x0 (k_step_f16chain with its launch-wide cfg, x0_cfg_image with the image's)
 template <bool kVelocityCfg>
-__device__ __forceinline__ h8 x0_cfg_image(h8 xv, h8 tv, const h8* v_null, const float* cfg_image, const int32_t* uncond_slot,
-                                           int64_t img, int64_t q, int64_t svec, float sig)
-{
-    const int32_t slot = uncond_slot[img];
+__device__ __forceinline__ h8 x0_cfg(h8 xv, h8 tv, h8 uv, float sig, float cfg) {
     h8 f;
-    if (slot < 0) {
-#pragma unroll
-        for (int i = 0; i < 8; ++i) f.v[i] = hsub(xv.v[i], hmulf(sig, tv.v[i]));
-        return f;
-    }
-    const float cfg = cfg_image[img];
-    const h8 uv = v_null[(int64_t)slot * svec + q];
 #pragma unroll
     for (int i = 0; i < 8; ++i) {
         if (kVelocityCfg) {
@@ -143,6 +135,39 @@ __device__ __forceinline__ h8 x0_cfg_image(h8 xv, h8 tv, const h8* v_null, const
         }
     }
     return f;
+}
+
+// ---- piece of the SD3 form with per-image guidance (fp16 chain) ----
+// the fused x0 of one 8-vector: image img's null-prompt velocity is row uncond_slot[img] of the compacted v_null (quad q of it) and
+// its scale cfg_image[img]; a negative slot = an unguided image, f = x - sig*v_text for both flag values (neither v_null nor
+// cfg_image[img] is read then).  With a slot it is x0_cfg, the arithmetic of k_step_f16chain for the flag.
+// Both per-image values are uniform over the svec consecutive threads of an image: plain vector loads, served by one cache line.
+// (k_step_f16chain_guided, k_step_inpaint_f16chain)
+template <bool kVelocityCfg>
+__device__ __forceinline__ h8 x0_cfg_image(h8 xv, h8 tv, const h8* v_null, const float* cfg_image, const int32_t* uncond_slot,
+                                           int64_t img, int64_t q, int64_t svec, float sig)
+{
+    const int32_t slot = uncond_slot[img];
+    if (slot < 0) {
+        h8 f;
+#pragma unroll
+        for (int i = 0; i < 8; ++i) f.v[i] = hsub(xv.v[i], hmulf(sig, tv.v[i]));
+        return f;
+    }
+    const float cfg = cfg_image[img];
+    return x0_cfg<kVelocityCfg>(xv, tv, v_null[(int64_t)slot * svec + q], sig, cfg);
+}
+
+// f stored as hist[k], then the chain's row mean: chain_terms over the history, the diagonal term c_diag*f, mean_of (the three fp16 step kernels)
+__device__ __forceinline__ h8 chain_mean(h8 f, h16* hist, const int32_t* idx, const float* val, int n_terms, float c_diag, float w_total,
+                                         int k, int64_t v, int64_t E)
+{
+    reinterpret_cast<h8*>(hist + (int64_t)k * E)[v] = f;
+    h8 acc = h8_zero();
+    chain_terms(acc, hist, idx, val, n_terms, v, E);
+#pragma unroll
+    for (int i = 0; i < 8; ++i) acc.v[i] = hadd(acc.v[i], hmulf(c_diag, f.v[i]));
+    return mean_of(acc, w_total);
 }
 
 // ---- pieces of the CIFAR10 form (fp64 history) ----
@@ -163,14 +188,6 @@ __device__ __forceinline__ void st_quad_f64(double* row, int64_t v, const double
     d2* r = reinterpret_cast<d2*>(row) + 2 * v;
     r[0] = d2{x[0], x[1]};
     r[1] = d2{x[2], x[3]};
-}
-
-// x0_score_f64, stored as quad v of the slab row
-__device__ __forceinline__ void x0_from_score_f64(double (&x0)[4], float4 xv, float4 ov, float stdv, double sigma2,
-                                                  double alpha, double* hist_k, int64_t v)
-{
-    x0_score_f64(x0, xv, ov, stdv, sigma2, alpha);
-    st_quad_f64(hist_k, v, x0);
 }
 
 // acc <- acc + h*c, four lanes: one fp64 product, one fp64 sum
@@ -254,6 +271,15 @@ __device__ __forceinline__ float4 combine(const double (&a)[4], const double (&b
                        (float)a[2] + (float)b[2], (float)a[3] + (float)b[3]);
 }
 
+// the finished x0 quad stored as hist_x0[k], then a <- the signal sum over the history plus the diagonal term (k_step_f32prod, noise_step_f32prod)
+__device__ __forceinline__ void signal_sum_f32prod(double (&a)[4], float4 x0, float* hist_x0, const int32_t* idx_c, const float* val_c,
+                                                   int n_c, float c_diag, int k, int64_t v, int64_t E)
+{
+    reinterpret_cast<float4*>(hist_x0 + (int64_t)k * E)[v] = x0;
+    wsum_f32prod(a, hist_x0, idx_c, val_c, n_c, v, E);
+    acc_prod(a, x0, c_diag);
+}
+
 // ------------------------------------------------------------------------------------------
 // CIFAR10 form, fp64 history
 // ------------------------------------------------------------------------------------------
@@ -266,7 +292,8 @@ __global__ __launch_bounds__(kBlock) void k_step_f64hist(
     for (int64_t v = first_vec(); v < nvec; v += vec_stride()) {
         const float4 nv = noise[v];
         double x0[4], acc[4] = {0.0, 0.0, 0.0, 0.0};
-        x0_from_score_f64(x0, x_k[v], mout[v], stdv, sigma2, alpha, hist + (int64_t)k * E, v);
+        x0_score_f64(x0, x_k[v], mout[v], stdv, sigma2, alpha);
+        st_quad_f64(hist + (int64_t)k * E, v, x0);
         wsum_f64(acc, hist, idx, val, n_terms, v, E);
         acc_f64(acc, x0[0], x0[1], x0[2], x0[3], c_diag);
         x_next[v] = make_float4((float)acc[0] + b0 * nv.x, (float)acc[1] + b0 * nv.y,
@@ -346,11 +373,8 @@ __global__ __launch_bounds__(kBlock) void k_step_f32prod(
     for (int64_t v = first_vec(); v < nvec; v += vec_stride()) {
         const int64_t img = v / svec, q = v - img * svec;
         const float4 x0 = x0_f32prod(c1, z[v], c2, cfg_eps(cond, uncond, cfg, img, q, sstride));
-        reinterpret_cast<float4*>(hist_x0 + (int64_t)k * E)[v] = x0;
-
         double a[4] = {0.0, 0.0, 0.0, 0.0}, b[4] = {0.0, 0.0, 0.0, 0.0};
-        wsum_f32prod(a, hist_x0, idx_c, val_c, n_c, v, E);
-        acc_prod(a, x0, c_diag);
+        signal_sum_f32prod(a, x0, hist_x0, idx_c, val_c, n_c, c_diag, k, v, E);
         wsum_f32prod(b, hist_eps, idx_b, val_b, n_b, v, E);
         z_next[v] = combine(a, b);
     }
@@ -378,28 +402,8 @@ __global__ __launch_bounds__(kBlock) void k_step_f16chain(
     int k, float sig, float sig_next, float oms_next, float cfg, int64_t nvec, int64_t E)
 {
     for (int64_t v = first_vec(); v < nvec; v += vec_stride()) {
-        const h8 xv = x[v], tv = v_text[v], uv = v_null[v];
-        h8 f;
-#pragma unroll
-        for (int i = 0; i < 8; ++i) {
-            if (kVelocityCfg) {
-                const h16 d = hsub(tv.v[i], uv.v[i]);
-                const h16 vv = hadd(uv.v[i], hmulf(cfg, d));
-                f.v[i] = hsub(xv.v[i], hmulf(sig, vv));
-            } else {
-                const h16 x0n = hsub(xv.v[i], hmulf(sig, uv.v[i]));
-                const h16 x0t = hsub(xv.v[i], hmulf(sig, tv.v[i]));
-                const h16 d = hsub(x0t, x0n);
-                f.v[i] = hadd(x0n, hmulf(cfg, d));
-            }
-        }
-        reinterpret_cast<h8*>(hist + (int64_t)k * E)[v] = f;
-
-        h8 acc = h8_zero();
-        chain_terms(acc, hist, idx, val, n_terms, v, E);
-#pragma unroll
-        for (int i = 0; i < 8; ++i) acc.v[i] = hadd(acc.v[i], hmulf(c_diag, f.v[i]));
-        const h8 mean = mean_of(acc, w_total);
+        const h8 f = x0_cfg<kVelocityCfg>(x[v], v_text[v], v_null[v], sig, cfg);
+        const h8 mean = chain_mean(f, hist, idx, val, n_terms, c_diag, w_total, k, v, E);
         if (mean_out) mean_out[v] = mean;
         if (x_next) x_next[v] = flow_input(noise[v], mean, sig_next, oms_next);
     }
@@ -422,13 +426,7 @@ __global__ __launch_bounds__(kBlock) void k_step_f16chain_guided(
     for (int64_t v = first_vec(); v < nvec; v += vec_stride()) {
         const int64_t img = v / svec, q = v - img * svec;            // an image is svec 8-vectors
         const h8 f = x0_cfg_image<kVelocityCfg>(x[v], v_text[v], v_null, cfg_image, uncond_slot, img, q, svec, sig);
-        reinterpret_cast<h8*>(hist + (int64_t)k * E)[v] = f;
-
-        h8 acc = h8_zero();
-        chain_terms(acc, hist, idx, val, n_terms, v, E);
-#pragma unroll
-        for (int i = 0; i < 8; ++i) acc.v[i] = hadd(acc.v[i], hmulf(c_diag, f.v[i]));
-        const h8 mean = mean_of(acc, w_total);
+        const h8 mean = chain_mean(f, hist, idx, val, n_terms, c_diag, w_total, k, v, E);
         if (mean_out) mean_out[v] = mean;
         if (x_next) x_next[v] = flow_input(noise[v], mean, sig_next, oms_next);
     }
@@ -513,6 +511,44 @@ __device__ __forceinline__ void noise_row_sum(double (&acc)[4], const float4* no
     }
 }
 
+// ---- the step bodies with in-kernel noise, each written here and nowhere else ----
+// CIFAR10 form, the tail of element quad v (quad q of its image) once its x0 is final: x0 stored as hist[k], signal sum, diagonal term, noise_row_sum,
+// x_next = (float)acc_x0 + (float)acc_eps.  (noise_step_quad; k_stepfix_f64 and k_stepproject_f64 with the corrected / projected quad)
+__device__ __forceinline__ float4 noise_step_tail_f64(
+    const double (&x0)[4], const float4* noise, double* hist, const int32_t* idx, const double* val, int n_terms, double c_diag,
+    const int32_t* idx_b, const float* val_b, int n_b, uint64_t gi, int64_t q, uint32_t k0, uint32_t k1, int k, int64_t v, int64_t E)
+{
+    double acc[4] = {0.0, 0.0, 0.0, 0.0}, nacc[4] = {0.0, 0.0, 0.0, 0.0};
+    st_quad_f64(hist + (int64_t)k * E, v, x0);
+    wsum_f64(acc, hist, idx, val, n_terms, v, E);
+    acc_f64(acc, x0[0], x0[1], x0[2], x0[3], c_diag);
+    noise_row_sum(nacc, noise, idx_b, val_b, n_b, v, gi, q, k0, k1);
+    return combine(acc, nacc);
+}
+
+// CIFAR10 form, one quad per thread: x0 from the score, then the tail above (k_step_noise_f64, k_step_inpaint_f64, k_step_colorize_f64).  Only the
+// unblended float4 leaves: in k_step_colorize_f64 the fp64 accumulators of a plane are dead before the next plane's begin.
+__device__ __forceinline__ float4 noise_step_quad(
+    const float4* x_k, const float4* mout, const float4* noise, double* hist, const int32_t* idx, const double* val, int n_terms, double c_diag,
+    const int32_t* idx_b, const float* val_b, int n_b, uint64_t gi, int64_t q, uint32_t k0, uint32_t k1, int k, double alpha, double sigma2,
+    float stdv, int64_t v, int64_t E)
+{
+    double x0[4];
+    x0_score_f64(x0, x_k[v], mout[v], stdv, sigma2, alpha);
+    return noise_step_tail_f64(x0, noise, hist, idx, val, n_terms, c_diag, idx_b, val_b, n_b, gi, q, k0, k1, k, v, E);
+}
+
+// Validate form, one quad per thread: signal_sum_f32prod, noise_row_sum in place of a hist_eps slab's row sum, combine (the three seeded step kernels)
+__device__ __forceinline__ float4 noise_step_f32prod(
+    float4 x0, float* hist_x0, const float4* noise, const int32_t* idx_c, const float* val_c, int n_c, float c_diag,
+    const int32_t* idx_b, const float* val_b, int n_b, uint64_t gi, int64_t q, uint32_t k0, uint32_t k1, int k, int64_t v, int64_t E)
+{
+    double a[4] = {0.0, 0.0, 0.0, 0.0}, b[4] = {0.0, 0.0, 0.0, 0.0};
+    signal_sum_f32prod(a, x0, hist_x0, idx_c, val_c, n_c, c_diag, k, v, E);
+    noise_row_sum(b, noise, idx_b, val_b, n_b, v, gi, q, k0, k1);
+    return combine(a, b);
+}
+
 __global__ __launch_bounds__(kBlock) void k_randn_philox(
     float4* __restrict__ out, const int64_t* __restrict__ index, int64_t first_index, int64_t index_stride,
     int64_t quads_per_image, int64_t total_quads, uint32_t column, uint32_t k0, uint32_t k1)
@@ -541,14 +577,9 @@ __global__ __launch_bounds__(kBlock) void k_step_noise_f64(
     // compiler hoists into SGPRs spill (10-35 SGPRs); without it the kernel needs 57 SGPRs and spills nothing
     const int64_t v = first_vec();
     if (v < nvec) {
-        double x0[4], acc[4] = {0.0, 0.0, 0.0, 0.0}, nacc[4] = {0.0, 0.0, 0.0, 0.0};
-        x0_from_score_f64(x0, x_k[v], mout[v], stdv, sigma2, alpha, hist + (int64_t)k * E, v);
-        wsum_f64(acc, hist, idx, val, n_terms, v, E);
-        acc_f64(acc, x0[0], x0[1], x0[2], x0[3], c_diag);
-
         const int64_t img = v / quads_per_image, q = v - img * quads_per_image;
-        noise_row_sum(nacc, noise, idx_b, val_b, n_b, v, global_index(index, first_index, index_stride, img), q, k0, k1);
-        x_next[v] = combine(acc, nacc);
+        x_next[v] = noise_step_quad(x_k, mout, noise, hist, idx, val, n_terms, c_diag, idx_b, val_b, n_b,
+                                    global_index(index, first_index, index_stride, img), q, k0, k1, k, alpha, sigma2, stdv, v, E);
     }
 }
 
@@ -607,20 +638,14 @@ __global__ __launch_bounds__(kBlock) void k_step_inpaint_f64(
     const float* __restrict__ known, const uint8_t* __restrict__ mask, int64_t kstride, int64_t mstride,
     float kalpha, float kstd, uint32_t kcolumn, int64_t nvec, int64_t E)
 {
-    // one element quad per thread, no grid-stride loop (k_step_noise_f64: the loop's carried scalars make the hoisted
-    // Philox round keys spill SGPRs)
+    // one element quad per thread, no grid-stride loop (k_step_noise_f64: with one, the hoisted Philox round keys spill SGPRs)
     const int64_t v = first_vec();
     if (v < nvec) {
-        double x0[4], acc[4] = {0.0, 0.0, 0.0, 0.0}, nacc[4] = {0.0, 0.0, 0.0, 0.0};
-        x0_from_score_f64(x0, x_k[v], mout[v], stdv, sigma2, alpha, hist + (int64_t)k * E, v);
-        wsum_f64(acc, hist, idx, val, n_terms, v, E);
-        acc_f64(acc, x0[0], x0[1], x0[2], x0[3], c_diag);
-
         const int64_t img = v / quads_per_image, q = v - img * quads_per_image;
         const uint64_t gi = global_index(index, first_index, index_stride, img);
-        noise_row_sum(nacc, noise, idx_b, val_b, n_b, v, gi, q, k0, k1);
-        x_next[v] = known_blend(combine(acc, nacc), known, mask, kstride, mstride, img, q, quads_per_image, kalpha, kstd, kcolumn,
-                                gi, k0, k1);
+        const float4 xn = noise_step_quad(x_k, mout, noise, hist, idx, val, n_terms, c_diag, idx_b, val_b, n_b, gi, q, k0, k1, k, alpha,
+                                          sigma2, stdv, v, E);
+        x_next[v] = known_blend(xn, known, mask, kstride, mstride, img, q, quads_per_image, kalpha, kstd, kcolumn, gi, k0, k1);
     }
 }
 
@@ -637,6 +662,32 @@ struct FixLds {
     unsigned int sel_bin, sel_rank, sel_count, any_nan;
     unsigned long long min_above;
 };
+
+// ---- quad <-> planes, for any LDS struct with x[4][...] (FixLds, and ProjLds below) ----
+template <class Lds>
+__device__ __forceinline__ void st_planes(Lds& L, int q, const double (&x)[4]) { L.x[0][q] = x[0]; L.x[1][q] = x[1]; L.x[2][q] = x[2]; L.x[3][q] = x[3]; }
+template <class Lds>
+__device__ __forceinline__ void ld_planes(double (&x)[4], const Lds& L, int q) { x[0] = L.x[0][q]; x[1] = L.x[1][q]; x[2] = L.x[2][q]; x[3] = L.x[3][q]; }
+
+// quad q of the planes <- the raw x0 of the image's quad (xv, ov) = (x_k, mout): x0_score_f64, to LDS and nowhere else (k_stepfix_f64, k_stepproject_f64).
+// The one-line loop over the thread's quads stays in the kernel: inside a piece the compiler walks x_k / mout with vector pointers, not scalar ones.
+template <class Lds>
+__device__ __forceinline__ void plane_quad_from_score(Lds& L, int q, float4 xv, float4 ov, float stdv, double sigma2, double alpha) {
+    double x0[4];
+    x0_score_f64(x0, xv, ov, stdv, sigma2, alpha);
+    st_planes(L, q, x0);
+}
+
+// the planes <- an image of qpi fp64 quads in memory; back to memory, one quad at a time, is st_quad_f64 (k_x0fix_f64, k_x0project_f64)
+template <class Lds>
+__device__ __forceinline__ void planes_from_image(Lds& L, const double* img, int qpi) {
+    const d2* p = reinterpret_cast<const d2*>(img);
+    for (int q = threadIdx.x; q < qpi; q += kBlock) {
+        const d2 a = p[2 * q], b = p[2 * q + 1];
+        const double x[4] = {a.x, a.y, b.x, b.y};
+        st_planes(L, q, x);
+    }
+}
 
 // |x| as its 64-bit pattern: non-negative doubles order as unsigned integers, NaN patterns sort above +inf
 __device__ __forceinline__ uint64_t abs_key(double x) { return (uint64_t)__double_as_longlong(x) & 0x7FFFFFFFFFFFFFFFull; }
@@ -734,19 +785,15 @@ __global__ __launch_bounds__(kBlock) void k_x0fix_f64(double* x0, double* __rest
 {
     __shared__ FixLds<kCapQuads> L;
     const int tid = threadIdx.x;
-    d2* img = reinterpret_cast<d2*>(x0) + 2 * (int64_t)blockIdx.x * qpi;
-    for (int q = tid; q < qpi; q += kBlock) {
-        const d2 a = img[2 * q], b = img[2 * q + 1];
-        L.x[0][q] = a.x; L.x[1][q] = a.y; L.x[2][q] = b.x; L.x[3][q] = b.y;
-    }
+    double* img = x0 + 4 * (int64_t)blockIdx.x * qpi;
+    planes_from_image(L, img, qpi);
     // (a thread reads back only what it wrote itself; the search's first barrier comes before any other thread's read)
     const double s = x0_threshold(L, qpi, mode, lo, next != 0, w, max_val);
     for (int q = tid; q < qpi; q += kBlock) {
-        const double x[4] = {L.x[0][q], L.x[1][q], L.x[2][q], L.x[3][q]};
-        double y[4];
+        double x[4], y[4];
+        ld_planes(x, L, q);
         x0_fix(y, x, mode, s);
-        img[2 * q] = d2{y[0], y[1]};
-        img[2 * q + 1] = d2{y[2], y[3]};
+        st_quad_f64(img, q, y);
     }
     if (s_out && tid == 0) s_out[blockIdx.x] = s;
 }
@@ -772,11 +819,7 @@ __global__ __launch_bounds__(kBlock) void k_stepfix_f64(
     __shared__ FixLds<kCapQuads> L;
     const int tid = threadIdx.x;
     const int64_t img = blockIdx.x, v0 = img * qpi;
-    for (int q = tid; q < qpi; q += kBlock) {
-        double x0[4];
-        x0_score_f64(x0, x_k[v0 + q], mout[v0 + q], stdv, sigma2, alpha);
-        L.x[0][q] = x0[0]; L.x[1][q] = x0[1]; L.x[2][q] = x0[2]; L.x[3][q] = x0[3];
-    }
+    for (int q = tid; q < qpi; q += kBlock) plane_quad_from_score(L, q, x_k[v0 + q], mout[v0 + q], stdv, sigma2, alpha);
     const double s = x0_threshold(L, qpi, mode, lo, next != 0, w, max_val);
     if (s_out && tid == 0) s_out[img] = s;
 
@@ -786,14 +829,10 @@ __global__ __launch_bounds__(kBlock) void k_stepfix_f64(
     asm("" : "+v"(k0), "+v"(k1));
     for (int q = tid; q < qpi; q += kBlock) {
         const int64_t v = v0 + q;
-        const double x[4] = {L.x[0][q], L.x[1][q], L.x[2][q], L.x[3][q]};
-        double y[4], acc[4] = {0.0, 0.0, 0.0, 0.0}, nacc[4] = {0.0, 0.0, 0.0, 0.0};
+        double x[4], y[4];
+        ld_planes(x, L, q);
         x0_fix(y, x, mode, s);
-        st_quad_f64(hist + (int64_t)k * E, v, y);
-        wsum_f64(acc, hist, idx, val, n_terms, v, E);
-        acc_f64(acc, y[0], y[1], y[2], y[3], c_diag);
-        noise_row_sum(nacc, noise, idx_b, val_b, n_b, v, gi, q, k0, k1);
-        float4 xn = combine(acc, nacc);
+        float4 xn = noise_step_tail_f64(y, noise, hist, idx, val, n_terms, c_diag, idx_b, val_b, n_b, gi, q, k0, k1, k, v, E);
         if (known) xn = known_blend(xn, known, mask, kstride, mstride, img, q, qpi, kalpha, kstd, kcolumn, gi, k0, k1);
         x_next[v] = xn;
     }
@@ -884,7 +923,8 @@ __device__ __forceinline__ double proj_d(const ProjLds<kCapQuads>& L, int e, Pro
 // and, when W is no multiple of 4, two image rows or planes: its two halves are looked up separately.
 template <int kCapQuads>
 __device__ __forceinline__ void x0_project(double (&y)[4], const ProjLds<kCapQuads>& L, int q, ProjGeom g) {
-    const double x[4] = {L.x[0][q], L.x[1][q], L.x[2][q], L.x[3][q]};
+    double x[4];
+    ld_planes(x, L, q);
     const double d[2] = {proj_d(L, 4 * q, g), proj_d(L, 4 * q + 2, g)};
 #pragma unroll
     for (int i = 0; i < 4; ++i) {
@@ -900,17 +940,13 @@ __global__ __launch_bounds__(kBlock) void k_x0project_f64(double* x0, const doub
 {
     __shared__ ProjLds<kCapQuads> L;
     const int tid = threadIdx.x;
-    d2* img = reinterpret_cast<d2*>(x0) + 2 * (int64_t)blockIdx.x * g.qpi;
-    for (int q = tid; q < g.qpi; q += kBlock) {
-        const d2 a = img[2 * q], b = img[2 * q + 1];
-        L.x[0][q] = a.x; L.x[1][q] = a.y; L.x[2][q] = b.x; L.x[3][q] = b.y;
-    }
+    double* img = x0 + 4 * (int64_t)blockIdx.x * g.qpi;
+    planes_from_image(L, img, g.qpi);
     x0_project_residuals(L, low + (int64_t)blockIdx.x * lstride, g);
     for (int q = tid; q < g.qpi; q += kBlock) {
         double y[4];
         x0_project(y, L, q, g);
-        img[2 * q] = d2{y[0], y[1]};
-        img[2 * q + 1] = d2{y[2], y[3]};
+        st_quad_f64(img, q, y);
     }
     if (r_out && tid == 0) r_out[blockIdx.x] = proj_r(L);
 }
@@ -933,11 +969,7 @@ __global__ __launch_bounds__(kBlock) void k_stepproject_f64(
     __shared__ ProjLds<kCapQuads> L;
     const int tid = threadIdx.x;
     const int64_t img = blockIdx.x, v0 = img * g.qpi;
-    for (int q = tid; q < g.qpi; q += kBlock) {
-        double x0[4];
-        x0_score_f64(x0, x_k[v0 + q], mout[v0 + q], stdv, sigma2, alpha);
-        L.x[0][q] = x0[0]; L.x[1][q] = x0[1]; L.x[2][q] = x0[2]; L.x[3][q] = x0[3];
-    }
+    for (int q = tid; q < g.qpi; q += kBlock) plane_quad_from_score(L, q, x_k[v0 + q], mout[v0 + q], stdv, sigma2, alpha);
     x0_project_residuals(L, low + img * lstride, g);
     if (r_out && tid == 0) r_out[img] = proj_r(L);
 
@@ -946,13 +978,9 @@ __global__ __launch_bounds__(kBlock) void k_stepproject_f64(
     asm("" : "+v"(k0), "+v"(k1));
     for (int q = tid; q < g.qpi; q += kBlock) {
         const int64_t v = v0 + q;
-        double y[4], acc[4] = {0.0, 0.0, 0.0, 0.0}, nacc[4] = {0.0, 0.0, 0.0, 0.0};
+        double y[4];
         x0_project(y, L, q, g);
-        st_quad_f64(hist + (int64_t)k * E, v, y);
-        wsum_f64(acc, hist, idx, val, n_terms, v, E);
-        acc_f64(acc, y[0], y[1], y[2], y[3], c_diag);
-        noise_row_sum(nacc, noise, idx_b, val_b, n_b, v, gi, q, k0, k1);
-        x_next[v] = combine(acc, nacc);
+        x_next[v] = noise_step_tail_f64(y, noise, hist, idx, val, n_terms, c_diag, idx_b, val_b, n_b, gi, q, k0, k1, k, v, E);
     }
 }
 
@@ -1021,21 +1049,6 @@ __global__ __launch_bounds__(kBlock) void k_color_blend(
     }
 }
 
-// the body of k_step_noise_f64 for element quad v (quad q of image img), operation for operation: hist[k] <- x0_k, the unblended x_next returned.
-// Only the float4 leaves: the fp64 accumulators of a plane are dead before the next plane's begin.
-__device__ __forceinline__ float4 noise_step_quad(
-    const float4* x_k, const float4* mout, const float4* noise, double* hist, const int32_t* idx, const double* val, int n_terms, double c_diag,
-    const int32_t* idx_b, const float* val_b, int n_b, uint64_t gi, int64_t q, uint32_t k0, uint32_t k1, int k, double alpha, double sigma2,
-    float stdv, int64_t v, int64_t E)
-{
-    double x0[4], acc[4] = {0.0, 0.0, 0.0, 0.0}, nacc[4] = {0.0, 0.0, 0.0, 0.0};
-    x0_from_score_f64(x0, x_k[v], mout[v], stdv, sigma2, alpha, hist + (int64_t)k * E, v);
-    wsum_f64(acc, hist, idx, val, n_terms, v, E);
-    acc_f64(acc, x0[0], x0[1], x0[2], x0[3], c_diag);
-    noise_row_sum(nacc, noise, idx_b, val_b, n_b, v, gi, q, k0, k1);
-    return combine(acc, nacc);
-}
-
 // ------------------------------------------------------------------------------------------
 // CIFAR10 form, colorization: one thread per PIXEL quad.  For each plane the thread runs k_step_noise_f64's body on that plane's element quad
 // (hist[k] and the unblended values are that kernel's bytes) and keeps the resulting float4 only, then color_blend on the three in registers and
@@ -1051,8 +1064,7 @@ __global__ __launch_bounds__(kBlock) void k_step_colorize_f64(
     const float* __restrict__ gray_u, int64_t gstride, mat3 M, mat3 W, float galpha, float gstd, uint32_t gcolumn,
     int64_t npq, int64_t E)
 {
-    // one pixel quad per thread, no grid-stride loop (k_step_noise_f64: the loop's carried scalars make the hoisted
-    // Philox round keys spill SGPRs)
+    // one pixel quad per thread, no grid-stride loop (k_step_noise_f64: with one, the hoisted Philox round keys spill SGPRs)
     const int64_t t = first_vec();
     if (t < npq) {
         const int64_t img = t / ppq, pq = t - img * ppq, v0 = img * 3 * ppq + pq;
@@ -1080,19 +1092,13 @@ __global__ __launch_bounds__(kBlock) void k_step_noise_f32prod(
     const int64_t* __restrict__ index, int64_t first_index, int64_t index_stride,
     uint32_t k0, uint32_t k1, int k, float c1, float c2, int64_t nvec, int64_t E)
 {
-    // one element quad per thread, no grid-stride loop (k_step_noise_f64: the loop's carried scalars make the hoisted
-    // Philox round keys spill SGPRs)
+    // one element quad per thread, no grid-stride loop (k_step_noise_f64: with one, the hoisted Philox round keys spill SGPRs)
     const int64_t v = first_vec();
     if (v < nvec) {
         const int64_t img = v / svec, q = v - img * svec;            // an image is one sample: svec quads
         const float4 x0 = x0_f32prod(c1, z[v], c2, cfg_eps(cond, uncond, cfg, img, q, sstride));
-        reinterpret_cast<float4*>(hist_x0 + (int64_t)k * E)[v] = x0;
-
-        double a[4] = {0.0, 0.0, 0.0, 0.0}, b[4] = {0.0, 0.0, 0.0, 0.0};
-        wsum_f32prod(a, hist_x0, idx_c, val_c, n_c, v, E);
-        acc_prod(a, x0, c_diag);
-        noise_row_sum(b, noise, idx_b, val_b, n_b, v, global_index(index, first_index, index_stride, img), q, k0, k1);
-        z_next[v] = combine(a, b);
+        z_next[v] = noise_step_f32prod(x0, hist_x0, noise, idx_c, val_c, n_c, c_diag, idx_b, val_b, n_b,
+                                       global_index(index, first_index, index_stride, img), q, k0, k1, k, v, E);
     }
 }
 
@@ -1110,19 +1116,13 @@ __global__ __launch_bounds__(kBlock) void k_step_guided_f32prod(
     const int64_t* __restrict__ index, int64_t first_index, int64_t index_stride,
     uint32_t k0, uint32_t k1, int k, float c1, float c2, int64_t nvec, int64_t E)
 {
-    // one element quad per thread, no grid-stride loop (k_step_noise_f64: the loop's carried scalars make the hoisted
-    // Philox round keys spill SGPRs)
+    // one element quad per thread, no grid-stride loop (k_step_noise_f64: with one, the hoisted Philox round keys spill SGPRs)
     const int64_t v = first_vec();
     if (v < nvec) {
         const int64_t img = v / svec, q = v - img * svec;            // an image is one sample: svec quads
         const float4 x0 = x0_f32prod(c1, z[v], c2, cfg_eps_image(cond, uncond, cfg_image, uncond_slot, img, q, sstride));
-        reinterpret_cast<float4*>(hist_x0 + (int64_t)k * E)[v] = x0;
-
-        double a[4] = {0.0, 0.0, 0.0, 0.0}, b[4] = {0.0, 0.0, 0.0, 0.0};
-        wsum_f32prod(a, hist_x0, idx_c, val_c, n_c, v, E);
-        acc_prod(a, x0, c_diag);
-        noise_row_sum(b, noise, idx_b, val_b, n_b, v, global_index(index, first_index, index_stride, img), q, k0, k1);
-        z_next[v] = combine(a, b);
+        z_next[v] = noise_step_f32prod(x0, hist_x0, noise, idx_c, val_c, n_c, c_diag, idx_b, val_b, n_b,
+                                       global_index(index, first_index, index_stride, img), q, k0, k1, k, v, E);
     }
 }
 
@@ -1142,20 +1142,14 @@ __global__ __launch_bounds__(kBlock) void k_step_inpaint_f32prod(
     const float* __restrict__ known, const uint8_t* __restrict__ mask, int64_t kstride, int64_t mstride,
     float kalpha, float kstd, uint32_t kcolumn, int64_t nvec, int64_t E)
 {
-    // one element quad per thread, no grid-stride loop (k_step_noise_f64: the loop's carried scalars make the hoisted
-    // Philox round keys spill SGPRs)
+    // one element quad per thread, no grid-stride loop (k_step_noise_f64: with one, the hoisted Philox round keys spill SGPRs)
     const int64_t v = first_vec();
     if (v < nvec) {
         const int64_t img = v / svec, q = v - img * svec;            // an image is one sample: svec quads
         const float4 x0 = x0_f32prod(c1, z[v], c2, cfg_eps_image(cond, uncond, cfg_image, uncond_slot, img, q, sstride));
-        reinterpret_cast<float4*>(hist_x0 + (int64_t)k * E)[v] = x0;
-
-        double a[4] = {0.0, 0.0, 0.0, 0.0}, b[4] = {0.0, 0.0, 0.0, 0.0};
-        wsum_f32prod(a, hist_x0, idx_c, val_c, n_c, v, E);
-        acc_prod(a, x0, c_diag);
         const uint64_t gi = global_index(index, first_index, index_stride, img);
-        noise_row_sum(b, noise, idx_b, val_b, n_b, v, gi, q, k0, k1);
-        z_next[v] = known_blend(combine(a, b), known, mask, kstride, mstride, img, q, svec, kalpha, kstd, kcolumn, gi, k0, k1);
+        const float4 zn = noise_step_f32prod(x0, hist_x0, noise, idx_c, val_c, n_c, c_diag, idx_b, val_b, n_b, gi, q, k0, k1, k, v, E);
+        z_next[v] = known_blend(zn, known, mask, kstride, mstride, img, q, svec, kalpha, kstd, kcolumn, gi, k0, k1);
     }
 }
 
@@ -1239,19 +1233,12 @@ __global__ __launch_bounds__(kBlock) void k_step_inpaint_f16chain(
     const int64_t* __restrict__ index, int64_t first_index, int64_t index_stride, uint32_t k0, uint32_t k1,
     int64_t nvec, int64_t E)
 {
-    // one 8-vector per thread, no grid-stride loop (k_step_noise_f64: the loop's carried scalars make the hoisted
-    // Philox round keys spill SGPRs)
+    // one 8-vector per thread, no grid-stride loop (k_step_noise_f64: with one, the hoisted Philox round keys spill SGPRs)
     const int64_t v = first_vec();
     if (v < nvec) {
         const int64_t img = v / svec, q = v - img * svec;            // an image is svec 8-vectors
         const h8 f = x0_cfg_image<kVelocityCfg>(x[v], v_text[v], v_null, cfg_image, uncond_slot, img, q, svec, sig);
-        reinterpret_cast<h8*>(hist + (int64_t)k * E)[v] = f;
-
-        h8 acc = h8_zero();
-        chain_terms(acc, hist, idx, val, n_terms, v, E);
-#pragma unroll
-        for (int i = 0; i < 8; ++i) acc.v[i] = hadd(acc.v[i], hmulf(c_diag, f.v[i]));
-        h8 mean = mean_of(acc, w_total);
+        h8 mean = chain_mean(f, hist, idx, val, n_terms, c_diag, w_total, k, v, E);
 
         const uint64_t m = reinterpret_cast<const uint64_t*>(mask)[(mstride ? img * svec : 0) + q];
         h8 kv = h8_zero(), xn = h8_zero();
@@ -1357,6 +1344,32 @@ inline unsigned quad_blocks(int64_t nvec) {
     return blocks > INT32_MAX ? 0u : (unsigned)blocks;
 }
 
+inline uint32_t seed_lo(uint64_t seed) { return (uint32_t)seed; }              // the two halves of a seed: the Philox key (k0, k1)
+inline uint32_t seed_hi(uint64_t seed) { return (uint32_t)(seed >> 32); }
+
+// what every noise-drawing f64 entry (natinf_step_f64hist_noise, _inpaint, _x0fix, _project, _colorize) refuses: a missing tensor, a bad signal or noise
+// row, k < 0, E no positive multiple of 4 (nvec == 0), an elems_per_image that is no image of E.  How large an image or a grid may be is each entry's own.
+inline bool step_f64_noise_ok(const float* x_k, const float* model_out, const float* noise, const double* hist, const float* x_next, const int32_t* idx,
+                              const double* val, int n_terms, const int32_t* idx_b, const float* val_b, int n_b, int k, int64_t nvec, int64_t epi, int64_t E)
+{
+    return x_k && model_out && noise && hist && x_next && terms_ok(idx, val, n_terms) && terms_ok(idx_b, val_b, n_b) && k >= 0 && nvec && image_ok(epi, E);
+}
+
+// what every seeded f32prod entry (natinf_step_f32prod_noise, _noise_guided, _inpaint) refuses before its read-backs: a missing tensor, a bad row, k < 0,
+// a noise row longer than its k + 2 columns, a bad E, sample or eps stride, a sample whose quads do not fit counter word 2, a grid too large (blocks == 0)
+inline bool step_f32prod_seeded_ok(const float* z, const float* cond, const float* hist_x0, const float* z_next, const int32_t* idx_c, const float* val_c,
+                                   int n_c, const int32_t* idx_b, const float* val_b, int n_b, int k, int64_t nvec, unsigned blocks, int64_t sample_elems,
+                                   int64_t eps_sample_stride, int64_t E) {
+    return z && cond && hist_x0 && z_next && terms_ok(idx_c, val_c, n_c) && terms_ok(idx_b, val_b, n_b) && k >= 0 && n_b <= (int64_t)k + 2 &&
+           nvec && image_ok(sample_elems, E) && eps_sample_stride >= sample_elems && !(eps_sample_stride & 3) &&
+           !((sample_elems / 4) >> 32) && blocks;
+}
+
+// per-image guidance: scales and slots given, and unconditional rows to read when there are any
+inline bool guidance_ok(const float* cfg_image, const int32_t* uncond_slot, int n_uncond, const void* uncond) {
+    return cfg_image && uncond_slot && n_uncond >= 0 && (n_uncond == 0 || uncond);
+}
+
 // the known pixels of an inpainting call: both arrays given, each per-image stride 0 (one row shared by every image) or elems_per_image,
 // the mask readable as 32-bit words, and a replacement column no noise column of a matrix (<= N + 1) can collide with
 inline bool known_ok(const float* known, const uint8_t* mask, int64_t kstride, int64_t mstride, uint32_t column, int64_t elems_per_image) {
@@ -1459,6 +1472,8 @@ inline int noise_row_ok(const int32_t* idx_b, int n_b, int k, bool have_noise) {
 inline int slots_ok(const int32_t* uncond_slot, int64_t n_images, int n_uncond) {
     return device_i32_in_range(uncond_slot, n_images, -1, (int64_t)n_uncond - 1);
 }
+// what an entry returns for a read-back's result: NATINF_OK (0) = go on, a value outside the range is the caller's fault, a failed HIP call the runtime's
+inline int readback_code(int r) { return r > 0 ? NATINF_OK : (r < 0 ? NATINF_ELAUNCH : NATINF_EINVAL); }
 
 }  // namespace
 
@@ -1527,7 +1542,7 @@ int natinf_randn_philox_col_f32(float* out, int64_t n_images, int64_t elems_per_
     if (column && (qpi >> 32)) return NATINF_EINVAL;               // counter word 3 carries the column: the quad must fit word 2
     const int64_t total = qpi * n_images;
     hipLaunchKernelGGL(k_randn_philox, dim3(grid_for(total)), dim3(kBlock), 0, (hipStream_t)stream, (float4*)out,
-                       image_index, first_index, index_stride, qpi, total, column, (uint32_t)seed, (uint32_t)(seed >> 32));
+                       image_index, first_index, index_stride, qpi, total, column, seed_lo(seed), seed_hi(seed));
     return launched();
 }
 
@@ -1547,15 +1562,14 @@ int natinf_step_f64hist_noise(const float* x_k, const float* model_out, const fl
 {
     const int64_t nvec = vec_count(E, 4);
     const unsigned blocks = quad_blocks(nvec);
-    if (!x_k || !model_out || !noise || !hist || !x_next || !terms_ok(idx, val, n_terms) || !terms_ok(idx_b, val_b, n_b) ||
-        k < 0 || !nvec || !image_ok(elems_per_image, E) || ((elems_per_image / 4) >> 32) || !blocks)
+    if (!step_f64_noise_ok(x_k, model_out, noise, hist, x_next, idx, val, n_terms, idx_b, val_b, n_b, k, nvec, elems_per_image, E) ||
+        ((elems_per_image / 4) >> 32) || !blocks)
         return NATINF_EINVAL;
     // no read-back of the noise row here (natinf_step_f32prod_noise makes one): the caller keeps its columns in 0..k+1
     hipLaunchKernelGGL(k_step_noise_f64, dim3(blocks), dim3(kBlock), 0, (hipStream_t)stream,
                        (const float4*)x_k, (const float4*)model_out, (const float4*)noise, hist, (float4*)x_next,
                        idx, val, n_terms, c_diag, idx_b, val_b, n_b, image_index, first_index, index_stride,
-                       elems_per_image / 4, (uint32_t)seed, (uint32_t)(seed >> 32), k, alpha, sigma * sigma, std_f32,
-                       nvec, E);
+                       elems_per_image / 4, seed_lo(seed), seed_hi(seed), k, alpha, sigma * sigma, std_f32, nvec, E);
     return launched();
 }
 
@@ -1573,7 +1587,7 @@ int natinf_known_blend_f32(const float* x_in, float* out, const float* known, co
     hipLaunchKernelGGL(k_known_blend, dim3(blocks), dim3(kBlock), 0, (hipStream_t)stream,
                        (const float4*)x_in, (float4*)out, known, mask, known_image_stride, mask_image_stride,
                        known_alpha_f32, known_std_f32, known_column, image_index, first_index, index_stride,
-                       elems_per_image / 4, (uint32_t)seed, (uint32_t)(seed >> 32), nvec);
+                       elems_per_image / 4, seed_lo(seed), seed_hi(seed), nvec);
     return launched();
 }
 
@@ -1589,16 +1603,15 @@ int natinf_step_f64hist_inpaint(const float* x_k, const float* model_out, const 
 {
     const int64_t nvec = vec_count(E, 4);
     const unsigned blocks = quad_blocks(nvec);
-    if (!x_k || !model_out || !noise || !hist || !x_next || !terms_ok(idx, val, n_terms) || !terms_ok(idx_b, val_b, n_b) ||
-        k < 0 || !nvec || !image_ok(elems_per_image, E) || ((elems_per_image / 4) >> 32) || !blocks ||
+    if (!step_f64_noise_ok(x_k, model_out, noise, hist, x_next, idx, val, n_terms, idx_b, val_b, n_b, k, nvec, elems_per_image, E) ||
+        ((elems_per_image / 4) >> 32) || !blocks ||
         !known_ok(known, mask, known_image_stride, mask_image_stride, known_column, elems_per_image))
         return NATINF_EINVAL;
     hipLaunchKernelGGL(k_step_inpaint_f64, dim3(blocks), dim3(kBlock), 0, (hipStream_t)stream,
                        (const float4*)x_k, (const float4*)model_out, (const float4*)noise, hist, (float4*)x_next,
                        idx, val, n_terms, c_diag, idx_b, val_b, n_b, image_index, first_index, index_stride,
-                       elems_per_image / 4, (uint32_t)seed, (uint32_t)(seed >> 32), k, alpha, sigma * sigma, std_f32,
-                       known, mask, known_image_stride, mask_image_stride, known_alpha_f32, known_std_f32, known_column,
-                       nvec, E);
+                       elems_per_image / 4, seed_lo(seed), seed_hi(seed), k, alpha, sigma * sigma, std_f32,
+                       known, mask, known_image_stride, mask_image_stride, known_alpha_f32, known_std_f32, known_column, nvec, E);
     return launched();
 }
 
@@ -1626,8 +1639,8 @@ int natinf_step_f64hist_x0fix(const float* x_k, const float* model_out, const fl
                               int mode, double ratio, double max_val, double* s_out, natinf_stream_t stream)
 {
     const int64_t nvec = vec_count(E, 4);
-    if (!x_k || !model_out || !noise || !hist || !x_next || !terms_ok(idx, val, n_terms) || !terms_ok(idx_b, val_b, n_b) ||
-        k < 0 || !nvec || !image_ok(elems_per_image, E) || !x0fix_ok(mode, ratio, max_val, elems_per_image) ||
+    if (!step_f64_noise_ok(x_k, model_out, noise, hist, x_next, idx, val, n_terms, idx_b, val_b, n_b, k, nvec, elems_per_image, E) ||
+        !x0fix_ok(mode, ratio, max_val, elems_per_image) ||
         E / elems_per_image > INT32_MAX || (!known != !mask) ||
         (known && !known_ok(known, mask, known_image_stride, mask_image_stride, known_column, elems_per_image)))
         return NATINF_EINVAL;
@@ -1638,7 +1651,7 @@ int natinf_step_f64hist_x0fix(const float* x_k, const float* model_out, const fl
     hipLaunchKernelGGL(kernel, dim3((unsigned)(E / elems_per_image)), dim3(kBlock), 0, (hipStream_t)stream,
                        (const float4*)x_k, (const float4*)model_out, (const float4*)noise, hist, (float4*)x_next,
                        idx, val, n_terms, c_diag, idx_b, val_b, n_b, image_index, first_index, index_stride,
-                       (int)qpi, (uint32_t)seed, (uint32_t)(seed >> 32), k, alpha, sigma * sigma, std_f32,
+                       (int)qpi, seed_lo(seed), seed_hi(seed), k, alpha, sigma * sigma, std_f32,
                        known, mask, known_image_stride, mask_image_stride, known_alpha_f32, known_std_f32, known_column,
                        mode, p.lo, p.next, p.w, max_val, s_out, E);
     return launched();
@@ -1669,8 +1682,8 @@ int natinf_step_f64hist_project(const float* x_k, const float* model_out, const 
 {
     const int64_t nvec = vec_count(E, 4);
     ProjGeom g;
-    if (!x_k || !model_out || !noise || !hist || !x_next || !terms_ok(idx, val, n_terms) || !terms_ok(idx_b, val_b, n_b) ||
-        k < 0 || !nvec || !image_ok(elems_per_image, E) || !quad_blocks(nvec) || E / elems_per_image > INT32_MAX ||
+    if (!step_f64_noise_ok(x_k, model_out, noise, hist, x_next, idx, val, n_terms, idx_b, val_b, n_b, k, nvec, elems_per_image, E) ||
+        !quad_blocks(nvec) || E / elems_per_image > INT32_MAX ||
         !project_ok(g, low, channels, height, width, scale, low_image_stride, elems_per_image))
         return NATINF_EINVAL;
     // no read-back of the noise row (natinf_step_f64hist_noise): every check above is a pure argument check, no device is touched
@@ -1678,7 +1691,7 @@ int natinf_step_f64hist_project(const float* x_k, const float* model_out, const 
     hipLaunchKernelGGL(kernel, dim3((unsigned)(E / elems_per_image)), dim3(kBlock), 0, (hipStream_t)stream,
                        (const float4*)x_k, (const float4*)model_out, (const float4*)noise, hist, (float4*)x_next,
                        idx, val, n_terms, c_diag, idx_b, val_b, n_b, image_index, first_index, index_stride,
-                       (uint32_t)seed, (uint32_t)(seed >> 32), k, alpha, sigma * sigma, std_f32,
+                       seed_lo(seed), seed_hi(seed), k, alpha, sigma * sigma, std_f32,
                        low, low_image_stride, g, r_out, E);
     return launched();
 }
@@ -1699,7 +1712,7 @@ int natinf_color_blend_f32(const float* x_in, float* out, const float* gray_u, i
     hipLaunchKernelGGL(k_color_blend, dim3(blocks), dim3(kBlock), 0, (hipStream_t)stream,
                        (const float4*)x_in, (float4*)out, gray_u, gray_image_stride, mat3_of(basis), mat3_of(inverse),
                        gray_alpha_f32, gray_std_f32, gray_column, image_index, first_index, index_stride,
-                       elems_per_image / 12, (uint32_t)seed, (uint32_t)(seed >> 32), npq);
+                       elems_per_image / 12, seed_lo(seed), seed_hi(seed), npq);
     return launched();
 }
 
@@ -1714,17 +1727,16 @@ int natinf_step_f64hist_colorize(const float* x_k, const float* model_out, const
                                  float gray_alpha_f32, float gray_std_f32, uint32_t gray_column, natinf_stream_t stream)
 {
     const int64_t nvec = vec_count(E, 4);
-    if (!x_k || !model_out || !noise || !hist || !x_next || !terms_ok(idx, val, n_terms) || !terms_ok(idx_b, val_b, n_b) ||
-        k < 0 || !nvec || !image_ok(elems_per_image, E) || ((elems_per_image / 4) >> 32) || !quad_blocks(nvec) ||
+    if (!step_f64_noise_ok(x_k, model_out, noise, hist, x_next, idx, val, n_terms, idx_b, val_b, n_b, k, nvec, elems_per_image, E) ||
+        ((elems_per_image / 4) >> 32) || !quad_blocks(nvec) ||
         !gray_ok(gray_u, basis, inverse, gray_image_stride, gray_column, elems_per_image))
         return NATINF_EINVAL;
     const int64_t npq = nvec / 3;                                   // pixel quads: one thread each
     hipLaunchKernelGGL(k_step_colorize_f64, dim3(quad_blocks(npq)), dim3(kBlock), 0, (hipStream_t)stream,
                        (const float4*)x_k, (const float4*)model_out, (const float4*)noise, hist, (float4*)x_next,
                        idx, val, n_terms, c_diag, idx_b, val_b, n_b, image_index, first_index, index_stride,
-                       elems_per_image / 12, (uint32_t)seed, (uint32_t)(seed >> 32), k, alpha, sigma * sigma, std_f32,
-                       gray_u, gray_image_stride, mat3_of(basis), mat3_of(inverse), gray_alpha_f32, gray_std_f32, gray_column,
-                       npq, E);
+                       elems_per_image / 12, seed_lo(seed), seed_hi(seed), k, alpha, sigma * sigma, std_f32,
+                       gray_u, gray_image_stride, mat3_of(basis), mat3_of(inverse), gray_alpha_f32, gray_std_f32, gray_column, npq, E);
     return launched();
 }
 
@@ -1778,16 +1790,13 @@ int natinf_step_f32prod_noise(const float* z, const float* cond, const float* un
 {
     const int64_t nvec = vec_count(E, 4);
     const unsigned blocks = quad_blocks(nvec);
-    if (!z || !cond || !hist_x0 || !z_next || !terms_ok(idx_c, val_c, n_c) || !terms_ok(idx_b, val_b, n_b) ||
-        k < 0 || n_b > (int64_t)k + 2 || !nvec || !image_ok(sample_elems, E) || eps_sample_stride < sample_elems ||
-        (eps_sample_stride & 3) || ((sample_elems / 4) >> 32) || !blocks)
+    if (!step_f32prod_seeded_ok(z, cond, hist_x0, z_next, idx_c, val_c, n_c, idx_b, val_b, n_b, k, nvec, blocks, sample_elems, eps_sample_stride, E))
         return NATINF_EINVAL;
-    const int row = noise_row_ok(idx_b, n_b, k, noise != nullptr);
-    if (row <= 0) return row < 0 ? NATINF_ELAUNCH : NATINF_EINVAL;
+    if (const int rc = readback_code(noise_row_ok(idx_b, n_b, k, noise != nullptr))) return rc;
     hipLaunchKernelGGL(k_step_noise_f32prod, dim3(blocks), dim3(kBlock), 0, (hipStream_t)stream,
                        (const float4*)z, cond, uncond, cfg, sample_elems / 4, eps_sample_stride,
                        hist_x0, (const float4*)noise, (float4*)z_next, idx_c, val_c, n_c, c_diag, idx_b, val_b, n_b,
-                       image_index, first_index, index_stride, (uint32_t)seed, (uint32_t)(seed >> 32),
+                       image_index, first_index, index_stride, seed_lo(seed), seed_hi(seed),
                        k, c1_f32, c2_f32, nvec, E);
     return launched();
 }
@@ -1804,19 +1813,15 @@ int natinf_step_f32prod_noise_guided(const float* z, const float* cond, const fl
 {
     const int64_t nvec = vec_count(E, 4);
     const unsigned blocks = quad_blocks(nvec);
-    if (!z || !cond || !hist_x0 || !z_next || !terms_ok(idx_c, val_c, n_c) || !terms_ok(idx_b, val_b, n_b) ||
-        k < 0 || n_b > (int64_t)k + 2 || !nvec || !image_ok(sample_elems, E) || eps_sample_stride < sample_elems ||
-        (eps_sample_stride & 3) || ((sample_elems / 4) >> 32) || !blocks ||
-        !cfg_image || !uncond_slot || n_uncond < 0 || (n_uncond > 0 && !uncond))
+    if (!step_f32prod_seeded_ok(z, cond, hist_x0, z_next, idx_c, val_c, n_c, idx_b, val_b, n_b, k, nvec, blocks, sample_elems, eps_sample_stride, E) ||
+        !guidance_ok(cfg_image, uncond_slot, n_uncond, uncond))
         return NATINF_EINVAL;
-    const int row = noise_row_ok(idx_b, n_b, k, noise != nullptr);
-    if (row <= 0) return row < 0 ? NATINF_ELAUNCH : NATINF_EINVAL;
-    const int slots = slots_ok(uncond_slot, E / sample_elems, n_uncond);
-    if (slots <= 0) return slots < 0 ? NATINF_ELAUNCH : NATINF_EINVAL;
+    if (const int rc = readback_code(noise_row_ok(idx_b, n_b, k, noise != nullptr))) return rc;
+    if (const int rc = readback_code(slots_ok(uncond_slot, E / sample_elems, n_uncond))) return rc;
     hipLaunchKernelGGL(k_step_guided_f32prod, dim3(blocks), dim3(kBlock), 0, (hipStream_t)stream,
                        (const float4*)z, cond, uncond, cfg_image, uncond_slot, sample_elems / 4, eps_sample_stride,
                        hist_x0, (const float4*)noise, (float4*)z_next, idx_c, val_c, n_c, c_diag, idx_b, val_b, n_b,
-                       image_index, first_index, index_stride, (uint32_t)seed, (uint32_t)(seed >> 32),
+                       image_index, first_index, index_stride, seed_lo(seed), seed_hi(seed),
                        k, c1_f32, c2_f32, nvec, E);
     return launched();
 }
@@ -1836,20 +1841,16 @@ int natinf_step_f32prod_inpaint(const float* z, const float* cond, const float* 
     const int64_t nvec = vec_count(E, 4);
     const unsigned blocks = quad_blocks(nvec);
     // every pure argument check, the blend's included, before the first read-back: a refusal of these touches no device
-    if (!z || !cond || !hist_x0 || !z_next || !terms_ok(idx_c, val_c, n_c) || !terms_ok(idx_b, val_b, n_b) ||
-        k < 0 || n_b > (int64_t)k + 2 || !nvec || !image_ok(sample_elems, E) || eps_sample_stride < sample_elems ||
-        (eps_sample_stride & 3) || ((sample_elems / 4) >> 32) || !blocks ||
-        !cfg_image || !uncond_slot || n_uncond < 0 || (n_uncond > 0 && !uncond) ||
+    if (!step_f32prod_seeded_ok(z, cond, hist_x0, z_next, idx_c, val_c, n_c, idx_b, val_b, n_b, k, nvec, blocks, sample_elems, eps_sample_stride, E) ||
+        !guidance_ok(cfg_image, uncond_slot, n_uncond, uncond) ||
         !known_ok(known, mask, known_image_stride, mask_image_stride, known_column, sample_elems))
         return NATINF_EINVAL;
-    const int row = noise_row_ok(idx_b, n_b, k, noise != nullptr);
-    if (row <= 0) return row < 0 ? NATINF_ELAUNCH : NATINF_EINVAL;
-    const int slots = slots_ok(uncond_slot, E / sample_elems, n_uncond);
-    if (slots <= 0) return slots < 0 ? NATINF_ELAUNCH : NATINF_EINVAL;
+    if (const int rc = readback_code(noise_row_ok(idx_b, n_b, k, noise != nullptr))) return rc;
+    if (const int rc = readback_code(slots_ok(uncond_slot, E / sample_elems, n_uncond))) return rc;
     hipLaunchKernelGGL(k_step_inpaint_f32prod, dim3(blocks), dim3(kBlock), 0, (hipStream_t)stream,
                        (const float4*)z, cond, uncond, cfg_image, uncond_slot, sample_elems / 4, eps_sample_stride,
                        hist_x0, (const float4*)noise, (float4*)z_next, idx_c, val_c, n_c, c_diag, idx_b, val_b, n_b,
-                       image_index, first_index, index_stride, (uint32_t)seed, (uint32_t)(seed >> 32),
+                       image_index, first_index, index_stride, seed_lo(seed), seed_hi(seed),
                        k, c1_f32, c2_f32, known, mask, known_image_stride, mask_image_stride,
                        known_alpha_f32, known_std_f32, known_column, nvec, E);
     return launched();
@@ -1893,10 +1894,9 @@ int natinf_step_f16chain_guided(const void* x, const void* v_text, const void* v
     const int64_t nvec = vec_count(E, 8);
     if (!x || !v_text || !hist || !terms_ok(idx, val, n_terms) || k < 0 || !nvec ||
         (x_next && !noise) || (flags & ~NATINF_SD3_CFG_ON_VELOCITY) || !image_ok(sample_elems, E, 8) ||
-        !cfg_image || !uncond_slot || n_uncond < 0 || (n_uncond > 0 && !v_null))
+        !guidance_ok(cfg_image, uncond_slot, n_uncond, v_null))
         return NATINF_EINVAL;
-    const int slots = slots_ok(uncond_slot, E / sample_elems, n_uncond);
-    if (slots <= 0) return slots < 0 ? NATINF_ELAUNCH : NATINF_EINVAL;
+    if (const int rc = readback_code(slots_ok(uncond_slot, E / sample_elems, n_uncond))) return rc;
     const auto kern = (flags & NATINF_SD3_CFG_ON_VELOCITY) ? k_step_f16chain_guided<true> : k_step_f16chain_guided<false>;
     hipLaunchKernelGGL(kern, dim3(grid_for(nvec)), dim3(kBlock), 0, (hipStream_t)stream,
                        (const h8*)x, (const h8*)v_text, (const h8*)v_null, cfg_image, uncond_slot, sample_elems / 8,
@@ -1919,7 +1919,7 @@ int natinf_known_blend_f16(const void* x_in, void* out, const void* noise, const
     hipLaunchKernelGGL(k_blend_known_f16, dim3(blocks), dim3(kBlock), 0, (hipStream_t)stream,
                        (const h8*)x_in, (h8*)out, (const h8*)noise, (const h8*)known, mask, known_image_stride, mask_image_stride,
                        sig, one_minus_sig, known_column, image_index, first_index, index_stride, elems_per_image / 8,
-                       (uint32_t)seed, (uint32_t)(seed >> 32), nvec);
+                       seed_lo(seed), seed_hi(seed), nvec);
     return launched();
 }
 
@@ -1938,18 +1938,17 @@ int natinf_step_f16chain_inpaint(const void* x, const void* v_text, const void* 
     // every pure argument check, the blend's included, before the slot read-back: a refusal of these touches no device
     if (!x || !v_text || !hist || !terms_ok(idx, val, n_terms) || k < 0 || !nvec || !blocks ||
         (x_next && !noise) || (flags & ~(NATINF_SD3_CFG_ON_VELOCITY | NATINF_SD3_BLEND_MEAN)) || !image_ok(sample_elems, E, 8) ||
-        !cfg_image || !uncond_slot || n_uncond < 0 || (n_uncond > 0 && !v_null) ||
+        !guidance_ok(cfg_image, uncond_slot, n_uncond, v_null) ||
         !known_ok_f16(known, mask, known_image_stride, mask_image_stride, known_column, sample_elems, noise != nullptr || !x_next))
         return NATINF_EINVAL;
-    const int slots = slots_ok(uncond_slot, E / sample_elems, n_uncond);
-    if (slots <= 0) return slots < 0 ? NATINF_ELAUNCH : NATINF_EINVAL;
+    if (const int rc = readback_code(slots_ok(uncond_slot, E / sample_elems, n_uncond))) return rc;
     const auto kern = (flags & NATINF_SD3_CFG_ON_VELOCITY) ? k_step_inpaint_f16chain<true> : k_step_inpaint_f16chain<false>;
     hipLaunchKernelGGL(kern, dim3(blocks), dim3(kBlock), 0, (hipStream_t)stream,
                        (const h8*)x, (const h8*)v_text, (const h8*)v_null, cfg_image, uncond_slot, sample_elems / 8,
                        (const h8*)noise, (h16*)hist, (h8*)mean_out, (h8*)x_next, idx, val, n_terms, c_diag, w_total,
                        k, sig, sig_next, one_minus_sig_next,
                        (const h8*)known, mask, known_image_stride, mask_image_stride, known_column, (flags & NATINF_SD3_BLEND_MEAN) != 0,
-                       image_index, first_index, index_stride, (uint32_t)seed, (uint32_t)(seed >> 32), nvec, E);
+                       image_index, first_index, index_stride, seed_lo(seed), seed_hi(seed), nvec, E);
     return launched();
 }
 
@@ -1985,7 +1984,7 @@ int natinf_vae_posterior_f32(const float* moments, float* latents, int64_t n_ima
     const unsigned blocks = quad_blocks(nvec);
     if (!blocks) return NATINF_EINVAL;
     hipLaunchKernelGGL(k_vae_posterior, dim3(blocks), dim3(kBlock), 0, (hipStream_t)stream, (const float4*)moments, (float4*)latents,
-                       sample != 0, scale, shift, image_index, first_index, index_stride, qpi, (uint32_t)seed, (uint32_t)(seed >> 32), nvec);
+                       sample != 0, scale, shift, image_index, first_index, index_stride, qpi, seed_lo(seed), seed_hi(seed), nvec);
     return launched();
 }
 
@@ -1999,7 +1998,7 @@ int natinf_posterior_samples(const void* feats_bf16, const float* noise_or_null,
     const int d8 = d / 8;
     hipLaunchKernelGGL(k_post_samples, dim3((d8 + kBlock - 1) / kBlock, n), dim3(kBlock), 0, (hipStream_t)stream,
                        (const bf16x8*)feats_bf16, (const float4*)noise_or_null, a, b, index, first_index, index_stride,
-                       (uint32_t)seed, (uint32_t)(seed >> 32), d8, (int64_t)n * d8,
+                       seed_lo(seed), seed_hi(seed), d8, (int64_t)n * d8,
                        reinterpret_cast<bf16x8*>(static_cast<unsigned char*>(workspace) + L.planes));
     return launched();
 }

@@ -592,14 +592,14 @@ class CifarNI:
                 raise ValueError("stochastic NI matrix: elems_per_image is needed to key the injected noise")
             ib, vb, nb = self._noise_rows().ptrs(k)
             index, first, stride = image_index_args(index, self.E // epi, x_k.device)
+            head = (ptr(x_k), ptr(model_out), ptr(noise), ptr(self.hist), ptr(x_next), idx, val, n, r.diag, ib, vb, nb, k, a, s, self.std[k],
+                    self.seed, ptr(index), first, stride, epi, self.E)             # what the five natinf_step_f64hist_* noise entries share
         if self.sr_scale:
             n_images = self.E // epi
             if self.sr_r is None or self.sr_r.shape[1] != n_images:
                 self.sr_r = torch.zeros((self.n_step, n_images), dtype=torch.float64, device=self.device)
             c, h, w = self.image_shape
-            check(lib.natinf_step_f64hist_project(ptr(x_k), ptr(model_out), ptr(noise), ptr(self.hist), ptr(x_next), idx, val, n,
-                                                  r.diag, ib, vb, nb, k, a, s, self.std[k], self.seed, ptr(index), first, stride,
-                                                  epi, self.E, ptr(low), ls, c, h, w, self.sr_scale, ptr(self.sr_r[k]), stream_ptr()),
+            check(lib.natinf_step_f64hist_project(*head, ptr(low), ls, c, h, w, self.sr_scale, ptr(self.sr_r[k]), stream_ptr()),
                   "natinf_step_f64hist_project")
             return x_next
         if self.x0_mode:                                                  # with or without known pixels: one entry
@@ -607,27 +607,19 @@ class CifarNI:
             if self.x0_s is None or self.x0_s.shape[1] != n_images:
                 self.x0_s = torch.zeros((self.n_step, n_images), dtype=torch.float64, device=self.device)
             kargs = (ptr(known), ptr(mask), ks, ms, ka, kstd, kcol) if inpaint else (0, 0, 0, 0, 0.0, 0.0, 0)
-            check(lib.natinf_step_f64hist_x0fix(ptr(x_k), ptr(model_out), ptr(noise), ptr(self.hist), ptr(x_next), idx, val, n,
-                                                r.diag, ib, vb, nb, k, a, s, self.std[k], self.seed, ptr(index), first, stride,
-                                                epi, self.E, *kargs, self.x0_mode, self.x0_ratio, self.x0_max, ptr(self.x0_s[k]),
-                                                stream_ptr()), "natinf_step_f64hist_x0fix")
+            check(lib.natinf_step_f64hist_x0fix(*head, *kargs, self.x0_mode, self.x0_ratio, self.x0_max, ptr(self.x0_s[k]), stream_ptr()),
+                  "natinf_step_f64hist_x0fix")
             return x_next
         if inpaint:
-            check(lib.natinf_step_f64hist_inpaint(ptr(x_k), ptr(model_out), ptr(noise), ptr(self.hist), ptr(x_next), idx, val, n,
-                                                  r.diag, ib, vb, nb, k, a, s, self.std[k], self.seed, ptr(index), first, stride,
-                                                  epi, self.E, ptr(known), ptr(mask), ks, ms, ka, kstd, kcol, stream_ptr()),
+            check(lib.natinf_step_f64hist_inpaint(*head, ptr(known), ptr(mask), ks, ms, ka, kstd, kcol, stream_ptr()),
                   "natinf_step_f64hist_inpaint")
             return x_next
         if gray_u is not None:
-            check(lib.natinf_step_f64hist_colorize(ptr(x_k), ptr(model_out), ptr(noise), ptr(self.hist), ptr(x_next), idx, val, n,
-                                                   r.diag, ib, vb, nb, k, a, s, self.std[k], self.seed, ptr(index), first, stride,
-                                                   epi, self.E, ptr(gray_u), gs, _f9(COLOR_M), _f9(COLOR_W), ga, gstd, gcol, stream_ptr()),
+            check(lib.natinf_step_f64hist_colorize(*head, ptr(gray_u), gs, _f9(COLOR_M), _f9(COLOR_W), ga, gstd, gcol, stream_ptr()),
                   "natinf_step_f64hist_colorize")
             return x_next
         if self.stochastic:
-            check(lib.natinf_step_f64hist_noise(ptr(x_k), ptr(model_out), ptr(noise), ptr(self.hist), ptr(x_next), idx, val, n,
-                                                r.diag, ib, vb, nb, k, a, s, self.std[k], self.seed, ptr(index), first, stride,
-                                                epi, self.E, stream_ptr()), "natinf_step_f64hist_noise")
+            check(lib.natinf_step_f64hist_noise(*head, stream_ptr()), "natinf_step_f64hist_noise")
             return x_next
         b0 = float(np.float32(self.B[k, 0]))
         fn = lib.natinf_step_f32hist if self.fast else lib.natinf_step_f64hist
@@ -794,6 +786,9 @@ class ValidateNI:
             raise ValueError("sample_elems must be the per-image element count: a multiple of 4 dividing the element count"
                              + ("" if self.epi is None else f" (elems_per_image = {self.epi})"))
         index, first, stride = image_index_args(index, self.E // se, z.device)
+        # what the three seeded natinf_step_f32prod_* entries share behind their guidance arguments
+        tail = (se, st, ptr(self.hist_x0), ptr(noise), ptr(z_next), ic, vc, nc, self.rows_c.rows[k].diag, ib, vb, nb, k, self.c1[k], self.c2[k],
+                self.seed, ptr(index), first, stride, self.E)
         if inpaint and not guided:
             cfg, uncond_slot = self._launch_wide_guidance(self.E // se, float(cfg), uncond is not None)
             n_uncond = self.E // se if uncond is not None else 0
@@ -802,21 +797,13 @@ class ValidateNI:
             if n_uncond is None:
                 n_uncond = 0 if uncond is None else uncond.numel() // st
             if inpaint:
-                check(lib.natinf_step_f32prod_inpaint(ptr(z), ptr(cond), ptr(uncond), ptr(cfg), ptr(uncond_slot), int(n_uncond), se, st,
-                                                      ptr(self.hist_x0), ptr(noise), ptr(z_next), ic, vc, nc, self.rows_c.rows[k].diag,
-                                                      ib, vb, nb, k, self.c1[k], self.c2[k], self.seed, ptr(index), first, stride,
-                                                      self.E, ptr(known), ptr(mask), ks, ms, ka, kstd, kcol, stream_ptr()),
-                      "natinf_step_f32prod_inpaint")
+                check(lib.natinf_step_f32prod_inpaint(ptr(z), ptr(cond), ptr(uncond), ptr(cfg), ptr(uncond_slot), int(n_uncond), *tail,
+                                                      ptr(known), ptr(mask), ks, ms, ka, kstd, kcol, stream_ptr()), "natinf_step_f32prod_inpaint")
                 return z_next
-            check(lib.natinf_step_f32prod_noise_guided(ptr(z), ptr(cond), ptr(uncond), ptr(cfg), ptr(uncond_slot), int(n_uncond), se, st,
-                                                       ptr(self.hist_x0), ptr(noise), ptr(z_next), ic, vc, nc, self.rows_c.rows[k].diag,
-                                                       ib, vb, nb, k, self.c1[k], self.c2[k], self.seed, ptr(index), first, stride,
-                                                       self.E, stream_ptr()), "natinf_step_f32prod_noise_guided")
+            check(lib.natinf_step_f32prod_noise_guided(ptr(z), ptr(cond), ptr(uncond), ptr(cfg), ptr(uncond_slot), int(n_uncond), *tail,
+                                                       stream_ptr()), "natinf_step_f32prod_noise_guided")
             return z_next
-        check(lib.natinf_step_f32prod_noise(ptr(z), ptr(cond), ptr(uncond), float(cfg), se, st, ptr(self.hist_x0), ptr(noise),
-                                            ptr(z_next), ic, vc, nc, self.rows_c.rows[k].diag, ib, vb, nb, k, self.c1[k],
-                                            self.c2[k], self.seed, ptr(index), first, stride, self.E, stream_ptr()),
-              "natinf_step_f32prod_noise")
+        check(lib.natinf_step_f32prod_noise(ptr(z), ptr(cond), ptr(uncond), float(cfg), *tail, stream_ptr()), "natinf_step_f32prod_noise")
         return z_next
 
 
@@ -949,18 +936,15 @@ class SD3NI:
             _check_guidance_tensors(cfg, uncond_slot, m, x.device)
             if n_uncond is None:
                 n_uncond = 0 if v_null is None else v_null.numel() // se
+            # what natinf_step_f16chain_guided and natinf_step_f16chain_inpaint share in front of their flags
+            head = (ptr(x), ptr(v_text), ptr(v_null), ptr(cfg), ptr(uncond_slot), int(n_uncond), se, ptr(noises), ptr(self.hist), ptr(self.mean),
+                    ptr(x_next) if want_next else None, idx, val, n, r.diag, self.totals[k], k, self.sig[k], self.sig[k + 1], self.oms[k + 1])
             if inpaint:
-                check(lib.natinf_step_f16chain_inpaint(ptr(x), ptr(v_text), ptr(v_null), ptr(cfg), ptr(uncond_slot), int(n_uncond), se,
-                                                       ptr(noises), ptr(self.hist), ptr(self.mean), ptr(x_next) if want_next else None,
-                                                       idx, val, n, r.diag, self.totals[k], k, self.sig[k], self.sig[k + 1],
-                                                       self.oms[k + 1], flags | (_lib.SD3_BLEND_MEAN if blend_mean else 0), self.E,
-                                                       ptr(known), ptr(mask), ks, ms, col, 0 if seed is None else int(seed) & (2 ** 64 - 1),
-                                                       ptr(index), first, stride, stream_ptr()), "natinf_step_f16chain_inpaint")
+                check(lib.natinf_step_f16chain_inpaint(*head, flags | (_lib.SD3_BLEND_MEAN if blend_mean else 0), self.E, ptr(known), ptr(mask),
+                                                       ks, ms, col, 0 if seed is None else int(seed) & (2 ** 64 - 1), ptr(index), first, stride,
+                                                       stream_ptr()), "natinf_step_f16chain_inpaint")
                 return self.mean, (x_next if want_next else None)
-            check(lib.natinf_step_f16chain_guided(ptr(x), ptr(v_text), ptr(v_null), ptr(cfg), ptr(uncond_slot), int(n_uncond), se,
-                                                  ptr(noises), ptr(self.hist), ptr(self.mean), ptr(x_next) if want_next else None,
-                                                  idx, val, n, r.diag, self.totals[k], k, self.sig[k], self.sig[k + 1],
-                                                  self.oms[k + 1], flags, self.E, stream_ptr()), "natinf_step_f16chain_guided")
+            check(lib.natinf_step_f16chain_guided(*head, flags, self.E, stream_ptr()), "natinf_step_f16chain_guided")
             return self.mean, (x_next if want_next else None)
         check(lib.natinf_step_f16chain(ptr(x), ptr(v_text), ptr(v_null), ptr(noises), ptr(self.hist), ptr(self.mean),
                                        ptr(x_next) if want_next else None, idx, val, n, r.diag, self.totals[k], k,
