@@ -123,6 +123,29 @@ int natinf_debug_ln_modulate(const void* x, int x_f16, const float* shift, const
  * outside the kind's contract. */
 int natinf_debug_softmax_rows(int kind, const float* S, void* P, int T, int64_t rows, natinf_stream_t stream);
 
+/* The glue kernels at the two ends of the DiT and SD3-MMDiT engines alone (tests/test_gpu_glue_kernels.py): the plans' own launchers on caller-supplied device
+ * buffers.  Nothing is allocated and nothing waits for the device; every refusal below is NATINF_EINVAL with nothing launched.
+ *
+ * natinf_debug_patch_embed: x[b*g*g + t][d] = sum_k w[d][k] patch(b, t)[k] + bias[d] + pos[t][d], k = (c, pi, qi) as Conv2d(C, D, 2, stride 2) flattens its
+ * weight.  z [B][C][2g][2g] fp32; w [D][C*4] fp32, the conv weight as a checkpoint stores it; wt: scratch of D*C*4 floats that receives its transpose [C*4][D]
+ * (k_transpose_f32, as the engines' load does), which the embedding kernel then reads; bias [D]; pos [g*g][D]; x [B*g*g][D] fp32, or IEEE half when x_f16.
+ * guard: NULL, or a status slot {uint32 max_bits, uint32 clamped} (NATINF_DIT_STREAM_GUARD above): the guarded kernel instances, which accumulate into the slot.
+ * Refused: a NULL z / w / wt / bias / pos / x; C outside 1..16; g outside 1..256; D outside 64..1536 or D % 64; B < 1; more than 65535 * 16 rows; x not aligned to
+ * its element; guard not 4-byte aligned.
+ * natinf_debug_dit_time_freq: emb [B][256] bf16 = [cos(t f_h) | sin(t f_h)], f_h = exp(-ln(1e4) h / 128), h = 0..127.  Refused: NULL t / emb, B outside 1..2^22.
+ * natinf_debug_dit_cond: cs[b][d] = bf16(SiLU(c0[b][d] + table[y[b]][d])); c0 [B][D] fp32, table [classes][D] fp32, y [B] int32 (device; not range-checked).
+ * Refused: a NULL pointer, D < 1, B < 1, B * D >= 2^31.
+ * natinf_debug_silu_bf16: cs[i] = bf16(SiLU(c[i])); natinf_debug_f32_to_bf16: dst[i] = bf16(src[i]), round to nearest even.  Refused: a NULL pointer, n < 1, n >= 2^31.
+ * natinf_debug_unpatchify: out[n][c][2 gh + pi][2 gw + qi] = tok[n*g*g + gh*g + gw][(2 pi + qi) * OC + c]; tok [n_images*g*g][4*OC] fp32, out [n_images][OC][2g][2g]
+ * fp32.  Refused: a NULL pointer, OC or g outside 1..4096, n_images < 1, 2^31 or more elements. */
+int natinf_debug_patch_embed(const float* z, const float* w, float* wt, const float* bias, const float* pos, void* x, int x_f16, uint32_t* guard,
+                             int C, int g, int D, int B, natinf_stream_t stream);
+int natinf_debug_dit_time_freq(const float* t, void* emb, int B, natinf_stream_t stream);
+int natinf_debug_dit_cond(const float* c0, const float* table, const int32_t* y, void* cs, int D, int B, natinf_stream_t stream);
+int natinf_debug_silu_bf16(const float* c, void* cs, int64_t n, natinf_stream_t stream);
+int natinf_debug_f32_to_bf16(const float* src, void* dst, int64_t n, natinf_stream_t stream);
+int natinf_debug_unpatchify(const float* tok, float* out, int OC, int g, int n_images, natinf_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

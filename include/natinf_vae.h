@@ -104,6 +104,18 @@ int natinf_vae_encode(natinf_vae_enc_t h, const float* images, float* moments, f
                       uint64_t seed, const int64_t* image_index, int64_t first_index, int64_t index_stride,
                       void* workspace, int64_t workspace_bytes, natinf_stream_t stream);
 
+/* The input passes of the two engines and the encoder's quant_conv alone (tests/test_gpu_glue_kernels.py): the plans' own launchers on caller-supplied device
+ * buffers.  Nothing is allocated and nothing waits for the device; every refusal is NATINF_EINVAL with nothing launched.
+ * natinf_debug_vae_latents: y bf16 [B][r+2][r+2][64] = post_quant_conv (1x1: W [C][C], bias [C]) of z fp32 [B][C][r][r] in the interior, +0 on the one-pixel
+ * border and in the channels >= C.  Refused: a NULL pointer, C outside 1..64, r outside 1..4096, B < 1, 2^31 or more output elements.
+ * natinf_debug_vae_images: y bf16 [B][R+2][R+2][64] = img fp32 [B][3][R][R] in channels 0..2 of the interior, +0 elsewhere.  Refused: a NULL pointer, R outside
+ * 1..16384, B < 1, 2^31 or more output elements, y not 16-byte aligned.
+ * natinf_debug_vae_quant: out[b][c][p] = bias[c] + sum_k W[c][k] m[b][k][p]; m, out fp32 [B][N][hw], W [N][N].  Refused: a NULL pointer, N outside 1..64 (2 *
+ * latent_ch of natinf_vae_enc_create), hw < 1, B < 1, 2^31 or more elements. */
+int natinf_debug_vae_latents(const float* z, const float* W, const float* bias, void* y, int C, int r, int B, natinf_stream_t stream);
+int natinf_debug_vae_images(const float* img, void* y, int R, int B, natinf_stream_t stream);
+int natinf_debug_vae_quant(const float* m, const float* W, const float* bias, float* out, int N, int hw, int B, natinf_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -152,6 +152,12 @@ SIGNATURES = {
     "natinf_dit_stream_status": (C.c_int, [_p, _p, _p, _p]),
     "natinf_debug_ln_modulate": (C.c_int, [_p, _i32, _p, _p, _i32, _p, _p, _p, _i32, _i64, _i32, C.POINTER(_i32), _p]),
     "natinf_debug_softmax_rows": (C.c_int, [_i32, _p, _p, _i32, _i64, _p]),
+    "natinf_debug_patch_embed": (C.c_int, [_p, _p, _p, _p, _p, _p, _i32, _p, _i32, _i32, _i32, _i32, _p]),
+    "natinf_debug_dit_time_freq": (C.c_int, [_p, _p, _i32, _p]),
+    "natinf_debug_dit_cond": (C.c_int, [_p, _p, _p, _p, _i32, _i32, _p]),
+    "natinf_debug_silu_bf16": (C.c_int, [_p, _p, _i64, _p]),
+    "natinf_debug_f32_to_bf16": (C.c_int, [_p, _p, _i64, _p]),
+    "natinf_debug_unpatchify": (C.c_int, [_p, _p, _i32, _i32, _i32, _p]),
     # include/natinf_mmdit.h
     "natinf_mmdit_create": (C.c_int, [C.POINTER(_p), _i32, _i32, _i32, _i32, _i32, _i32, _i32, _i32]),
     "natinf_mmdit_destroy": (C.c_int, [_p]),
@@ -204,6 +210,9 @@ SIGNATURES = {
     "natinf_vae_enc_load": (C.c_int, [_p, _p, _i64, _p, _i64, _p]),
     "natinf_vae_posterior_f32": (C.c_int, [_p, _p, _i64, _i32, _i64, _i32, _f32, _f32, C.c_uint64, _p, _i64, _i64, _p]),
     "natinf_vae_encode": (C.c_int, [_p, _p, _p, _p, _i32, _i32, _f32, _f32, C.c_uint64, _p, _i64, _i64, _p, _i64, _p]),
+    "natinf_debug_vae_latents": (C.c_int, [_p, _p, _p, _p, _i32, _i32, _i32, _p]),
+    "natinf_debug_vae_images": (C.c_int, [_p, _p, _i32, _i32, _p]),
+    "natinf_debug_vae_quant": (C.c_int, [_p, _p, _p, _p, _i32, _i32, _i32, _p]),
     # include/natinf_posterior.h
     "natinf_posterior_workspace_bytes": (C.c_int64, [_i32, _i32]),
     "natinf_posterior_samples": (C.c_int, [_p, _p, _f32, _f32, C.c_uint64, _p, _i64, _i64, _i32, _i32, _p, _p]),

@@ -12,7 +12,7 @@
 
 namespace ncsn {
 
-// dst[k][n] = src[n][k]
+// dst[k][n] = src[n][k]   (bytes checked through natinf_debug_patch_embed's scratch: tests/test_gpu_glue_kernels.py)
 __global__ void k_transpose_f32(const float* __restrict__ src, float* __restrict__ dst, int N, int K)
 {
     const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
@@ -26,6 +26,11 @@ namespace {
 
 inline int ilog2(int v) { int l = 0; while ((1 << l) < v) ++l; return l; }
 inline int64_t align_up(int64_t v, int64_t a) { return (v + a - 1) / a * a; }
+// src [rows][cols] -> dst [cols][rows]: a plan's load-time transpose (PlanBuilder::pack_f32_transposed) and natinf_debug_patch_embed (dit_engine.inc) launch it here
+inline void launch_transpose_f32(const float* src, float* dst, int rows, int cols, hipStream_t s) {
+    const int64_t n = (int64_t)rows * cols;
+    hipLaunchKernelGGL(k_transpose_f32, dim3(grid1d(n, 256, 1 << 30)), dim3(256), 0, s, src, dst, rows, cols);
+}
 
 // tensor reference inside the workspace: `off` is BYTES PER IMAGE (actual = off * B)
 // coff: channel offset inside a wider buffer; pad = 1: stored with a one-pixel zero border (3x3 GEMM inputs)
@@ -159,11 +164,7 @@ struct PlanBuilder {
     }
     int64_t pack_f32_transposed(int64_t src, int rows, int cols) {     // [rows][cols] -> [cols][rows]
         const int64_t dst = wres((int64_t)rows * cols * 4);
-        E.packs.push_back([=](const PackCtx& p) {
-            const int64_t n = (int64_t)rows * cols;
-            hipLaunchKernelGGL(k_transpose_f32, dim3(grid1d(n, 256, 1 << 30)), dim3(256), 0, p.stream, p.params + src,
-                               reinterpret_cast<float*>(p.packed + dst), rows, cols);
-        });
+        E.packs.push_back([=](const PackCtx& p) { launch_transpose_f32(p.params + src, reinterpret_cast<float*>(p.packed + dst), rows, cols, p.stream); });
         return dst;
     }
     void pack_f32_at(int64_t src, int64_t n, int64_t dst, int64_t src2 = -1) {      // src2: a second vector added to the first (the NCSN++ summed shortcut bias)

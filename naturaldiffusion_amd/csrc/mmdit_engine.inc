@@ -114,17 +114,17 @@ struct MMDitBuilder : TransformerBuilder {
             }
             const int64_t prow = (int64_t)c.B * Tx;
             launch_patch_embed(c.x, c.w<float>(w_pw), c.w<float>(w_pb), c.w<float>(w_pos), c.at<float>(x), C, gr, D, prow, s16, c.site(0), c.stream);
-            hipLaunchKernelGGL(k_dit_time_freq, dim3(grid1d((int64_t)c.B * 256, 256, 1 << 30)), dim3(256), 0, c.stream, c.labels, c.at<bf16>(tf), c.B);
+            launch_dit_time_freq(c.labels, c.at<bf16>(tf), c.B, c.stream);
             const int64_t np = (int64_t)c.B * Pd, nt = (int64_t)c.B * Tc * Jd;
-            hipLaunchKernelGGL(k_f32_to_bf16, dim3(grid1d(np, 256, 1 << 30)), dim3(256), 0, c.stream, eng->pooled, c.at<bf16>(pl), np);
-            hipLaunchKernelGGL(k_f32_to_bf16, dim3(grid1d(nt, 256, 1 << 30)), dim3(256), 0, c.stream, eng->text, c.at<bf16>(tx), nt);
+            launch_f32_to_bf16(eng->pooled, c.at<bf16>(pl), np, c.stream);
+            launch_f32_to_bf16(eng->text, c.at<bf16>(tx), nt, c.stream);
             launch_gemm(dense(c, c.at<bf16>(tf), 256, c.B, t1, D, ACT_SILU, c.at<bf16>(a1), OUT_BF16), c.stream);
             launch_gemm(dense(c, c.at<bf16>(a1), D, c.B, t2, D, ACT_NONE, c.at<float>(cf), OUT_F32), c.stream);
             launch_gemm(dense(c, c.at<bf16>(pl), Pd, c.B, x1, D, ACT_SILU, c.at<bf16>(a2), OUT_BF16), c.stream);
             GemmArgs g = dense(c, c.at<bf16>(a2), D, c.B, x2, D, ACT_NONE, c.at<float>(cf), OUT_F32);      // c = t_emb + pooled_emb
             g.resid_f32 = c.at<float>(cf); g.resid_f32_ld = D;
             launch_gemm(g, c.stream);
-            hipLaunchKernelGGL(k_silu_bf16, dim3(grid1d((int64_t)c.B * D, 256, 1 << 30)), dim3(256), 0, c.stream, c.at<float>(cf), c.at<bf16>(cs), (int64_t)c.B * D);
+            launch_silu_bf16(c.at<float>(cf), c.at<bf16>(cs), (int64_t)c.B * D, c.stream);
             launch_gemm(dense(c, c.at<bf16>(cs), D, c.B, Lin{w_mod, b_mod}, nmod, ACT_NONE, c.at<float>(mod), OUT_F32), c.stream);      // every adaLN linear at once
             launch_gemm(dense(c, c.at<bf16>(tx), Jd, c.B * Tc, ce, D, ACT_NONE, c.at<float>(e), OUT_F32), c.stream);   // context_embedder
         });
@@ -282,8 +282,7 @@ struct MMDitBuilder : TransformerBuilder {
         op(ln_mod(x, Tx, mo + D, mo, hx));
         op([=](const Ctx& c) {
             launch_gemm(dense(c, c.at<bf16>(hx), D, c.B * Tx, po, 4 * C, ACT_NONE, c.at<float>(tok), OUT_F32), c.stream);
-            const int64_t tot = (int64_t)c.B * C * 4 * Tx;
-            hipLaunchKernelGGL(k_unpatchify, dim3(grid1d(tot, 256, 1 << 30)), dim3(256), 0, c.stream, c.at<float>(tok), c.out, C, gr, tot);
+            launch_unpatchify(c.at<float>(tok), c.out, C, gr, c.B, c.stream);
         });
         finish();
     }

@@ -14,7 +14,31 @@ inline void launch_patch_embed(const float* z, const float* Wt, const float* bia
     else launch_patch_embed_as<false>(z, Wt, bias, pos, x, C, g, D, rows, x_f16, nullptr, s);
 }
 
-struct Lin { int64_t w, b; };                                      // bf16 [out][in], fp32 bias: offsets into the packed image
+// the glue kernels of transformer_rows.h with the grid a plan gives them: one thread per element, 256 per block.  The plans and the natinf_debug_* entries of
+// dit_engine.inc (tests/test_gpu_glue_kernels.py) launch them through these and through nothing else.
+inline void launch_dit_time_freq(const float* t, bf16* emb, int B, hipStream_t s)
+{
+    hipLaunchKernelGGL(k_dit_time_freq, dim3(grid1d((int64_t)B * 256, 256, 1 << 30)), dim3(256), 0, s, t, emb, B);
+}
+inline void launch_dit_cond(const float* c0, const float* table, const int32_t* y, bf16* cs, int D, int B, hipStream_t s)
+{
+    hipLaunchKernelGGL(k_dit_cond, dim3(grid1d((int64_t)B * D, 256, 1 << 30)), dim3(256), 0, s, c0, table, y, cs, D, B);
+}
+inline void launch_silu_bf16(const float* c, bf16* cs, int64_t n, hipStream_t s)
+{
+    hipLaunchKernelGGL(k_silu_bf16, dim3(grid1d(n, 256, 1 << 30)), dim3(256), 0, s, c, cs, n);
+}
+inline void launch_f32_to_bf16(const float* src, bf16* dst, int64_t n, hipStream_t s)
+{
+    hipLaunchKernelGGL(k_f32_to_bf16, dim3(grid1d(n, 256, 1 << 30)), dim3(256), 0, s, src, dst, n);
+}
+inline void launch_unpatchify(const float* tok, float* out, int OC, int g, int64_t n_images, hipStream_t s)       // tok [n_images * g * g][4 OC] -> out [n_images][OC][2g][2g]
+{
+    const int64_t tot = n_images * OC * (2 * g) * (2 * g);
+    hipLaunchKernelGGL(k_unpatchify, dim3(grid1d(tot, 256, 1 << 30)), dim3(256), 0, s, tok, out, OC, g, tot);
+}
+
+struct Lin { int64_t w, b; };                                     // bf16 [out][in], fp32 bias: offsets into the packed image
 struct Lin8 { int64_t w, s, b; };                                  // e4m3 bytes [out][in], per-output-channel scale, fp32 bias
 
 struct TransformerBuilder : PlanBuilder {

@@ -2,6 +2,9 @@
 // guarded: one template, its guarded instances live in stream_guard.hip), the LayerNorm-modulate family with its launcher, the conditioning / unpatchify / cast glue
 // and the 1,024-key row softmax.  Like the other kernel headers it may be included into an anonymous namespace (stream_guard.hip): it defines nothing with external
 // linkage, and the LayerNorm-modulate kernels and their launcher are templates, so a unit that launches none of them carries none of them.
+// Tested alone against fp64: the LayerNorm-modulate family and k_softmax_rows_1k by tests/test_gpu_row_kernels.py (cases: tests/row_kernel_cases.py); k_patch_embed (all four
+// instances), k_dit_time_freq, k_dit_cond, k_unpatchify, k_f32_to_bf16 and k_silu_bf16 by tests/test_gpu_glue_kernels.py (cases, radii and what each catches:
+// tests/glue_kernel_cases.py, tests/test_glue_kernels_host.py), through the natinf_debug_* entries of dit_engine.inc and the launchers of transformer_plan.h.
 #pragma once
 #include "gemm_dma.h"
 

@@ -10,6 +10,8 @@
 // The encoder (VaeEncBuilder) is the same blocks the other way: k_vae_images writes the zero-bordered 64-channel picture conv_in reads, the stride-2
 // convolutions run as k_inc_im2col + one GEMM (the `ddpm` plan's emit_downconv), conv_out leaves fp32 NCHW moments, k_vae_quant (vae_quant.hip) applies quant_conv,
 // and natinf_vae_encode ends with the posterior kernel of ni_step.hip.
+// Tested alone against fp64 (tests/test_gpu_glue_kernels.py; cases: tests/glue_kernel_cases.py): k_vae_latents, k_vae_images and k_vae_quant through natinf_debug_vae_latents /
+// _vae_images / _vae_quant at the end of this file; k_gn_fold by tests/test_gpu_gn_kernels.py, k_softmax_rows_wide by tests/test_gpu_row_kernels.py.
 #include "natinf_vae.h"
 #include "transformer_plan.h"      // the mid-block attention's q | k, V^T and output-projection launches are its recipes
 
@@ -55,6 +57,17 @@ __global__ __launch_bounds__(256) void k_vae_images(const float* __restrict__ im
     d[0] = v;
 #pragma unroll
     for (int k = 1; k < 8; ++k) d[k] = make_uint4(0u, 0u, 0u, 0u);
+}
+// the two input passes with the grid the plans give them (VaeBuilder / VaeEncBuilder and natinf_debug_vae_latents / natinf_debug_vae_images below)
+inline void launch_vae_latents(const float* z, const float* W, const float* bias, bf16* y, int C, int r, int B, hipStream_t s)
+{
+    const int64_t tot = (int64_t)B * (r + 2) * (r + 2) * 64;
+    hipLaunchKernelGGL(k_vae_latents, dim3(grid1d(tot, 256, 1 << 30)), dim3(256), 0, s, z, W, bias, y, C, r, tot);
+}
+inline void launch_vae_images(const float* img, bf16* y, int R, int B, hipStream_t s)
+{
+    const int64_t tot = (int64_t)B * (R + 2) * (R + 2);
+    hipLaunchKernelGGL(k_vae_images, dim3(grid1d(tot, 256, 1 << 30)), dim3(256), 0, s, img, y, R, tot);
 }
 // (k_fill_f32: ncsnpp_kernels.h)
 // partial GroupNorm tables P [B][tps][quads] (float2 = sum, sum of squares) -> [B][tps / fold][quads]; grid (tps / fold, B).
@@ -312,8 +325,7 @@ struct VaeBuilder : VaeBase {
         ident_sc = arena.alloc((int64_t)512 * 4); ident_sh = arena.alloc((int64_t)512 * 4);
         const int64_t isc = ident_sc, ish = ident_sh;
         op([=](const Ctx& c) {
-            const int64_t tot = (int64_t)c.B * (r + 2) * (r + 2) * 64;
-            hipLaunchKernelGGL(k_vae_latents, dim3(grid1d(tot, 256, 1 << 30)), dim3(256), 0, c.stream, c.x, c.w<float>(wq), c.w<float>(bq), c.act(z), Cl, r, tot);
+            launch_vae_latents(c.x, c.w<float>(wq), c.w<float>(bq), c.act(z), Cl, r, c.B, c.stream);
             const int64_t n = (int64_t)c.B * 512;
             hipLaunchKernelGGL(k_fill_f32, dim3(grid1d(n, 256, 1 << 30)), dim3(256), 0, c.stream, c.at<float>(isc), 1.0f, n);
             hipLaunchKernelGGL(k_fill_f32, dim3(grid1d(n, 256, 1 << 30)), dim3(256), 0, c.stream, c.at<float>(ish), 0.0f, n);
@@ -422,10 +434,7 @@ struct VaeEncBuilder : VaeBase {
         pack_conv3(p_iw, wi, 128, 3, 576);
         const int64_t bi = pack_f32(p_ib, 128);
         TRef z = new_act(R, 64, 1);
-        op([=](const Ctx& c) {
-            const int64_t tot = (int64_t)c.B * (R + 2) * (R + 2);
-            hipLaunchKernelGGL(k_vae_images, dim3(grid1d(tot, 256, 1 << 30)), dim3(256), 0, c.stream, c.x, c.act(z), R, tot);
-        });
+        op([=](const Ctx& c) { launch_vae_images(c.x, c.act(z), R, c.B, c.stream); });
         TRef x = new_act(R, 128);
         Part xp = conv(z, 64, 128, wi, 576, bi, x, nullptr, 0, nullptr), np;
         arena.release(z.off);
@@ -530,6 +539,26 @@ int natinf_debug_gn_fold(const float* P, int tps, int quads, int fold, int B, fl
     if ((reinterpret_cast<uintptr_t>(P) | reinterpret_cast<uintptr_t>(out)) % 8) return NATINF_EINVAL;
     hipLaunchKernelGGL(k_gn_fold, dim3((unsigned)(tps / fold), (unsigned)B), dim3(256), 0, (hipStream_t)stream, reinterpret_cast<const float2*>(P), tps, quads, fold,
                        reinterpret_cast<float2*>(out));
+    return hipGetLastError() == hipSuccess ? NATINF_OK : NATINF_ELAUNCH;
+}
+
+// The input passes and the encoder's quant_conv alone (include/natinf_vae.h; tests/test_gpu_glue_kernels.py): the plans' own launchers, so no kernel is instantiated
+// for these entries.
+int natinf_debug_vae_latents(const float* z, const float* W, const float* bias, void* y, int C, int r, int B, natinf_stream_t stream) {
+    if (!z || !W || !bias || !y || C < 1 || C > 64 || r < 1 || r > 4096 || B < 1 || (int64_t)B * (r + 2) * (r + 2) * 64 > INT32_MAX) return NATINF_EINVAL;
+    if (reinterpret_cast<uintptr_t>(y) % 2) return NATINF_EINVAL;
+    launch_vae_latents(z, W, bias, (bf16*)y, C, r, B, (hipStream_t)stream);
+    return hipGetLastError() == hipSuccess ? NATINF_OK : NATINF_ELAUNCH;
+}
+int natinf_debug_vae_images(const float* img, void* y, int R, int B, natinf_stream_t stream) {
+    if (!img || !y || R < 1 || R > 16384 || B < 1 || (int64_t)B * (R + 2) * (R + 2) * 64 > INT32_MAX) return NATINF_EINVAL;
+    if (reinterpret_cast<uintptr_t>(y) % 16) return NATINF_EINVAL;                  // a pixel's 128 bytes go out as eight 16-byte stores
+    launch_vae_images(img, (bf16*)y, R, B, (hipStream_t)stream);
+    return hipGetLastError() == hipSuccess ? NATINF_OK : NATINF_ELAUNCH;
+}
+int natinf_debug_vae_quant(const float* m, const float* W, const float* bias, float* out, int N, int hw, int B, natinf_stream_t stream) {
+    if (!m || !W || !bias || !out || N < 1 || N > 64 || hw < 1 || B < 1 || (int64_t)B * N * hw > INT32_MAX) return NATINF_EINVAL;      // N = 2 latent_ch <= 64 (natinf_vae_enc_create)
+    ncsn_vq::launch(m, W, bias, out, N, hw, (int64_t)B * N * hw, (void*)stream);
     return hipGetLastError() == hipSuccess ? NATINF_OK : NATINF_ELAUNCH;
 }
 

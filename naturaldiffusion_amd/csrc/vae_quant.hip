@@ -1,5 +1,5 @@
 // vae_quant.hip -- the AutoencoderKL encoder's quant_conv pass (vae_engine.inc, VaeEncBuilder): a translation unit of its own, next to ncsnpp.hip, whose
-// kernel count tests/test_build_isa.py caps.
+// kernel count tests/test_build_isa.py caps.  Tested alone against fp64 through natinf_debug_vae_quant (vae_engine.inc): tests/test_gpu_glue_kernels.py, N = 2 .. 64, hw = 1 / 63 / 64.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 

@@ -394,6 +394,53 @@ def test_gn_kernel_hooks_reject_bad_arguments():
         assert call(**bad) == -1, bad
 
 
+def test_glue_kernel_hooks_reject_bad_arguments():
+    """natinf_debug_patch_embed / _dit_time_freq / _dit_cond / _silu_bf16 / _f32_to_bf16 / _unpatchify (include/natinf_dit.h) and natinf_debug_vae_latents / _vae_images /
+    _vae_quant (include/natinf_vae.h): NATINF_EINVAL outside each stated contract, before anything is launched (there is no GPU here)."""
+    from naturaldiffusion_amd._lib import lib
+    d = 4096                                                # a non-NULL, 16-byte aligned dummy: never dereferenced by the argument check
+
+    def caller(fn, names, base):
+        return lambda **kw: fn(*[{**base, **kw}[n] for n in names])
+
+    names = ("z", "w", "wt", "bias", "pos", "x", "x_f16", "guard", "C", "g", "D", "B", "stream")
+    for x_f16 in (0, 1):
+        for guard in (None, d):
+            call = caller(lib.natinf_debug_patch_embed, names, dict(z=d, w=d, wt=d, bias=d, pos=d, x=d, x_f16=x_f16, guard=guard, C=4, g=3, D=320, B=3, stream=None))
+            for name in ("z", "w", "wt", "bias", "pos", "x"):
+                assert call(**{name: None}) == -1, name
+            for bad in (dict(C=0), dict(C=-4), dict(C=17), dict(C=64), dict(g=0), dict(g=-1), dict(g=257), dict(D=0), dict(D=-64), dict(D=32), dict(D=96), dict(D=330),
+                        dict(D=1600), dict(D=2048), dict(B=0), dict(B=-2), dict(g=256, B=17), dict(B=1 << 30), dict(x=d + 1), dict(guard=d + 2)):
+                assert call(**bad) == -1, bad
+            if not x_f16:
+                assert call(x=d + 2) == -1                                        # an fp32 stream is 4-byte aligned (a half stream 2-byte: d + 1 above)
+
+    call = caller(lib.natinf_debug_dit_time_freq, ("t", "emb", "B", "stream"), dict(t=d, emb=d, B=3, stream=None))
+    for bad in (dict(t=None), dict(emb=None), dict(B=0), dict(B=-1), dict(B=(1 << 22) + 1)):
+        assert call(**bad) == -1, bad
+    call = caller(lib.natinf_debug_dit_cond, ("c0", "table", "y", "cs", "D", "B", "stream"), dict(c0=d, table=d, y=d, cs=d, D=1152, B=3, stream=None))
+    for bad in (dict(c0=None), dict(table=None), dict(y=None), dict(cs=None), dict(D=0), dict(D=-64), dict(B=0), dict(B=-3), dict(D=1 << 16, B=1 << 15)):
+        assert call(**bad) == -1, bad
+    for fn in (lib.natinf_debug_silu_bf16, lib.natinf_debug_f32_to_bf16):
+        assert fn(None, d, 5, None) == -1 and fn(d, None, 5, None) == -1 and fn(d, d, 0, None) == -1 and fn(d, d, -7, None) == -1 and fn(d, d, 1 << 31, None) == -1
+    call = caller(lib.natinf_debug_unpatchify, ("tok", "out", "OC", "g", "n_images", "stream"), dict(tok=d, out=d, OC=8, g=16, n_images=2, stream=None))
+    for bad in (dict(tok=None), dict(out=None), dict(OC=0), dict(OC=-8), dict(OC=4097), dict(g=0), dict(g=-1), dict(g=4097), dict(n_images=0), dict(n_images=-2),
+                dict(OC=4096, g=4096), dict(n_images=1 << 22, g=16)):
+        assert call(**bad) == -1, bad
+
+    call = caller(lib.natinf_debug_vae_latents, ("z", "W", "bias", "y", "C", "r", "B", "stream"), dict(z=d, W=d, bias=d, y=d, C=4, r=8, B=2, stream=None))
+    for bad in (dict(z=None), dict(W=None), dict(bias=None), dict(y=None), dict(y=d + 1), dict(C=0), dict(C=-4), dict(C=65), dict(r=0), dict(r=-8), dict(r=4097), dict(B=0),
+                dict(B=-1), dict(r=4096, B=2)):
+        assert call(**bad) == -1, bad
+    call = caller(lib.natinf_debug_vae_images, ("img", "y", "R", "B", "stream"), dict(img=d, y=d, R=17, B=2, stream=None))
+    for bad in (dict(img=None), dict(y=None), dict(y=d + 8), dict(y=d + 2), dict(R=0), dict(R=-1), dict(R=16385), dict(B=0), dict(B=-2), dict(R=8192, B=1)):
+        assert call(**bad) == -1, bad
+    call = caller(lib.natinf_debug_vae_quant, ("m", "W", "bias", "out", "N", "hw", "B", "stream"), dict(m=d, W=d, bias=d, out=d, N=8, hw=63, B=2, stream=None))
+    for bad in (dict(m=None), dict(W=None), dict(bias=None), dict(out=None), dict(N=0), dict(N=-2), dict(N=65), dict(hw=0), dict(hw=-64), dict(B=0), dict(B=-1),
+                dict(N=64, hw=1 << 24, B=2)):
+        assert call(**bad) == -1, bad
+
+
 def test_validation_grid_is_one_row_of_eight(tmp_path):
     """reference ValidateNaturalInference.py:236: save_image(samples, path, nrow=8, ...): 8 images -> 1 x 8."""
     import torch
